@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """Headline benchmark: enhanced frames/s of the BAE/CAA forward hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 720p|lr180|128] [--precision fp32|fp16] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 720p|lr180|128] [--precision fp32|fp16] [--full]
+                    [--dump-outputs DIR] ...
 
 One "step" = one forward of the generator over one synthetic 7-frame clip per GPU (inputs resident in HBM).
+
+A plain run sets up, runs W warm-up steps, times exactly K steps, writes the last timed step's output with --dump-outputs DIR
+(the inputs and weights are seeded: the same arguments give the same inputs on every run), and prints the line.  Everything
+else -- per-kernel HIP-event timing and the rooflines, the dense-partition-map pass, the CPU baseline and parity check, and the
+secondary workloads below -- runs only with --full.
 
 N > 1: one process per GPU.  Started by the driver through torch.distributed.run (RANK / WORLD_SIZE in the env) the
 script is a rank; started plainly as `python bench.py --gpus N` it LAUNCHES the N ranks itself -- fresh child
@@ -15,7 +21,7 @@ tensors), a barrier + synchronize on both sides of the timed region, MAX over ra
 
 stdout carries exactly ONE strict-JSON line of at most 4 KB and nothing else (the driver keeps the last 8 KB of stdout; round 3's
 21 KB line was cut in half and never parsed): file descriptor 1 is pointed at stderr for the run -- RCCL and gloo print to
-stdout too -- and the line is written to the saved descriptor at the end.  At N = 1 with the default workload the other BASELINE.json workloads (7x3x128x128 fp32, 1 and
+stdout too -- and the line is written to the saved descriptor at the end.  With --full at N = 1 and the default workload the other BASELINE.json workloads (7x3x128x128 fp32, 1 and
 8 clips; 180x320 fp16 with and without the x4 heads; the opt-in precisions at 720p; the end-to-end loop) are measured in the same
 process after the headline, each with its own timed region, roofline and kernel-event mode; they go to `bench_secondary.json`
 beside this file (and to stderr), and the line carries only `north_star_128`, a compact summary of the 7x3x128x128 entries.
@@ -37,6 +43,9 @@ PEAK_F32_MFMA_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32,
 PEAK_F16_MFMA_TFLOPS = 2500.0     # MI355X_MICROARCH.md: dense fp16/bf16
 PEAK_HBM_GBS = 8000.0             # MI355X_MICROARCH.md: HBM3E spec (6.29 TB/s achievable)
 GEN_TYPE = 'IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par'
+DUMP_MAX_BYTES = 48 << 20         # --dump-outputs: an output up to this size is written whole, a larger one as a seeded sample
+DUMP_SAMPLE = 1 << 22             # elements of that sample (16 MB of float32)
+DUMP_SEED = 20251016
 
 
 def parse_args(argv=None):
@@ -56,9 +65,16 @@ def parse_args(argv=None):
     ap.add_argument('--clips', type=int, default=1,
                     help='clips per GPU per step (one batch; small frames run them concurrently, DESIGN.md section 4)')
     ap.add_argument('--graphs', action='store_true', help='replay each clip as one hipGraph (generator.use_graphs)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-events', action='store_true', help='skip per-kernel HIP-event timing')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the other BASELINE workloads after the headline')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the timed steps: per-kernel HIP-event timing and rooflines, the CPU baseline and parity check and, at '
+                         'the default workload on one GPU, the other BASELINE workloads (bench_secondary.json).  Without it a run '
+                         'only sets up, warms up, times the steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the generator output of the last timed step (rank 0) to DIR/output.npy '
+                         '(float32, whole) or, above %d MB, a fixed seeded sample of it to DIR/output_sample.npy' % (DUMP_MAX_BYTES >> 20))
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline and parity check')
+    ap.add_argument('--no-kernel-events', action='store_true', help='with --full: skip per-kernel HIP-event timing')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the other BASELINE workloads after the headline')
     ap.add_argument('--f16-mirrors', type=int, default=None, choices=[0, 1, 2],
                     help='fp16 path A/B: 0 no fp16 mirrors (r02 schedule), 1 frame slots + aligned key frame (default), 2 also the '
                          'running map inside a branch (PNP_OPT_F16_CHAIN_MIRRORS)')
@@ -69,7 +85,10 @@ def parse_args(argv=None):
     ap.add_argument('--tile-queue', type=int, default=None, choices=[0, 1],
                     help='split-fp16 path A/B: 0 = every block walks a static share of the tiles, 1 (default) = per-XCD tile queue '
                          '(PNP_OPT_TILE_QUEUE)')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -224,6 +243,24 @@ def make_inputs(seed, t, h, w, dev, n=1, crfs=None):
     clip = syn.make_clip(seed=seed, n=n, t=t, h=h, w=w, slices='IBBBP', qp_mode='qp', crf=crf[0] if n == 1 else list(crf),
                          block=8, par_classes=3)
     return clip, {k: torch.from_numpy(v).to(dev) for k, v in clip.items()}
+
+
+def dump_outputs(out, dirname):
+    """--dump-outputs: the generator output of the last timed step as float32 .npy in `dirname`.  Up to DUMP_MAX_BYTES it is written
+    whole (output.npy, the output's own shape); above that, DUMP_SAMPLE elements at fixed positions drawn from a seeded generator,
+    in increasing flat-index order (output_sample.npy): the same arguments give the same positions on every run and build."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    a = out.detach().float().cpu().numpy()
+    for name in ('output.npy', 'output_sample.npy'):          # a file of an earlier run with other arguments must not linger
+        p = os.path.join(dirname, name)
+        if os.path.exists(p):
+            os.remove(p)
+    if a.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(dirname, 'output.npy'), np.ascontiguousarray(a, dtype=np.float32))
+        return
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=DUMP_SAMPLE, replace=False))
+    np.save(os.path.join(dirname, 'output_sample.npy'), np.ascontiguousarray(a.reshape(-1)[idx], dtype=np.float32))
 
 
 def gpu_psnr(out, gt):
@@ -539,9 +576,10 @@ def timed_steps(step, steps, dist=None, cdev=None):
 
 
 def measure(dev, sd_np, cfg, *, workload, precision, vsr, clips, graphs, steps, warmup, T, rank=0, world=1,
-            kernel_events=True, dense_par=False, dist=None, cdev=None, crfs=None):
+            kernel_events=True, dense_par=False, dist=None, cdev=None, crfs=None, keep_output=False):
     """Build the model for (cfg, precision), make the clip, time `steps` forwards (barrier + synchronize on both sides,
-    MAX over ranks) and take the per-kernel HIP-event records.  Returns (result dict, model, device inputs)."""
+    MAX over ranks) and take the per-kernel HIP-event records.  Returns (result dict, model, device inputs); with `keep_output`
+    the result holds a copy of the last timed step's output as 'output' (taken before any later pass runs the model again)."""
     import torch
     h, w = WORKLOADS[workload]
     m = build_model(cfg, sd_np, dev, precision, graphs)
@@ -560,6 +598,7 @@ def measure(dev, sd_np, cfg, *, workload, precision, vsr, clips, graphs, steps, 
     if events_inside:
         m.profile(True)
     out, elapsed, elapsed_max = timed_steps(step, steps, dist, cdev)
+    kept = out.detach().clone() if keep_output else None
     ms_events_pass = None
     if kernel_events and not events_inside:
         m.profile(True)
@@ -594,6 +633,8 @@ def measure(dev, sd_np, cfg, *, workload, precision, vsr, clips, graphs, steps, 
                              else 'separate pass of the same steps after the timed region'),
            'ms_per_step_events_pass': ms_events_pass,
            'launches_per_frame': (sum(v['launches'] for v in prof.values()) / (steps * T * clips)) if prof else None}
+    if kept is not None:
+        res['output'] = kept
     if prof is not None:
         ptag = {'fp32': '', 'fp16': 'fp16_', 'f16x3': 'f16x3_'}[precision]
         tag = ptag if workload == '720p' and not vsr and cfg.get('deform', 'vos') == 'vos' \
@@ -667,10 +708,14 @@ def main(argv=None, measure_fn=None):
     T = args.frames
     headline = args.workload == '720p' and args.precision == 'fp32' and not args.vsr and args.deform == 'vos'
 
+    # a plain run is the headline figure alone: no per-kernel events, no dense-map pass, no CPU leg, no secondary workloads (--full)
+    kernel_events = args.full and not args.no_kernel_events
     r, m, a = measure_fn(dev, sd_np, cfg, workload=args.workload, precision=args.precision, vsr=args.vsr, clips=args.clips,
                       graphs=args.graphs, steps=args.steps, warmup=args.warmup, T=T, rank=rank, world=world,
-                      kernel_events=not args.no_kernel_events, dense_par=headline and world == 1,
-                      dist=dist if grouped else None, cdev=cdev)
+                      kernel_events=kernel_events, dense_par=kernel_events and headline and world == 1,
+                      dist=dist if grouped else None, cdev=cdev, keep_output=bool(args.dump_outputs) and rank == 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(r.pop('output'), args.dump_outputs)
 
     # per-rank metrics, gathered with one small collective (PSNR, frames/s): mmedit/apis/test.py:211-233
     mine = torch.tensor([r['psnr_rank'], r['frames_per_s_rank']], dtype=torch.float64, device=cdev)
@@ -706,7 +751,7 @@ def main(argv=None, measure_fn=None):
         for k in ('roofline', 'roofline_mv_warp', 'roofline_dcn'):
             if k in r:
                 res[k] = r[k]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cclip, ref, dt = cpu_baseline(sd_np, cfg, h, w)
             ca = {k: torch.from_numpy(v).to(dev) for k, v in cclip.items()}
             with torch.no_grad():
@@ -726,7 +771,7 @@ def main(argv=None, measure_fn=None):
             res['parity'] = {'sample': f'2x3x{h}x{w}', 'max_abs_diff_vs_cpu': float((got - ref).abs().max()),
                              'psnr_delta_db': cpu_ref.clip_psnr(got, gt) - cpu_ref.clip_psnr(ref, gt),
                              'gate': 1e-3}
-        elif world > 1 and not args.no_cpu_baseline:
+        elif world > 1 and args.full and not args.no_cpu_baseline:
             # an N > 1 line still carries the CPU leg: rank 0 alone times the oracle on the 128x128 clip of BASELINE
             # configs[0] AFTER the timed region (the other ranks wait in the final barrier below); ~5 s, never at the frame
             # size of the GPU workload (that sample is the N = 1 line's)
@@ -736,7 +781,7 @@ def main(argv=None, measure_fn=None):
         del m, a
         torch.cuda.empty_cache()
         full = None
-        if world == 1 and headline and not args.no_secondary and not args.no_kernel_events:
+        if world == 1 and headline and kernel_events and not args.no_secondary:
             # the other BASELINE workloads: measured after the headline, written beside this file and to stderr -- never on stdout
             try:
                 sec = secondary_workloads(dev, T, args.no_cpu_baseline)

@@ -120,10 +120,10 @@ def test_dist_test_driver_two_ranks_equals_one_rank():
 
 
 def test_bench_emits_the_contract_line():
-    """bench.py on a tiny workload: ONE JSON line with the driver's keys, the roofline / cpu_baseline / parity objects."""
+    """bench.py --full on a tiny workload: ONE JSON line with the driver's keys, the roofline / cpu_baseline / parity objects."""
     import json
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', '128', '--frames', '3',
-                          '--steps', '2', '--warmup', '1'], capture_output=True, text=True, timeout=900)
+                          '--steps', '2', '--warmup', '1', '--full'], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout + out.stderr
     d = bench_line(out.stdout)
     for k in ('roofline', 'cpu_baseline', 'parity'):
@@ -138,6 +138,34 @@ def test_bench_emits_the_contract_line():
     assert 'workload' in d['config'] and 'model' not in d['config']
 
 
+def test_plain_bench_run_is_the_headline_alone_and_dumps_the_last_timed_output(tmp_path):
+    """bench.py without --full: the line holds the timed steps' figures and none of the --full blocks, and --dump-outputs writes
+    what the last timed step computed: equal, bit for bit, to the same seeded clip through the same generator in this process."""
+    import importlib.util
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', '128', '--frames', '3', '--steps', '3',
+                          '--warmup', '1', '--dump-outputs', str(tmp_path / 'dump')], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout + out.stderr
+    d = bench_line(out.stdout)
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['dtype'] == 'f32' and d['unit'] == 'frames/s' and d['higher_is_better'] is True
+    assert d['value'] > 0 and abs(d['value'] - 3 * 3 / (d['ms_per_step'] * 3e-3)) < 1e-4 * d['value']
+    for k in ('roofline', 'roofline_mv_warp', 'cpu_baseline', 'parity', 'north_star_128', 'opt_in_720p', 'secondary_file'):
+        assert k not in d, k
+    assert d['kernel_events'] == 'none'
+    assert sorted(os.listdir(tmp_path / 'dump')) == ['output.npy']
+    got = np.load(tmp_path / 'dump' / 'output.npy')
+    assert got.dtype == np.float32 and got.shape == (1, 3, 3, 128, 128)
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    from pnp_vcve_amd import synthetic as syn
+    cfg = dict(syn.DEFAULT_GENERATOR_CFG, vsr=False)
+    m = bench.build_model(cfg, syn.make_state_dict(cfg, seed=2025), torch.device('cuda:0'), 'fp32')
+    _, a = bench.make_inputs(1000, 3, 128, 128, torch.device('cuda:0'))
+    with torch.no_grad():
+        ref = m(a['lq'], a['QPs'], a['slices'], a['mvs'], a['base_QPs'], a['partitions']).cpu().numpy()
+    assert np.array_equal(got, ref)
+
+
 def test_bench_gpus_2_launches_two_ranks_itself():
     """`python bench.py --gpus 2` (the driver's plain form, no torch.distributed environment) starts two ranks itself
     (tools/dist_test.sh:11-22's job), gathers per-rank metrics and prints ONE line with n_gpus == 2.  Both ranks share
@@ -146,7 +174,7 @@ def test_bench_gpus_2_launches_two_ranks_itself():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
     env['PNP_DIST_BACKEND'] = 'gloo'
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--workload', '128', '--frames', '3',
-                          '--steps', '2', '--warmup', '1'], capture_output=True, text=True, timeout=900, env=env)
+                          '--steps', '2', '--warmup', '1', '--full'], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout + out.stderr
     d = bench_line(out.stdout)
     assert d['n_gpus'] == 2 and d['config']['parallelism'] == 'clip-sharded replicas x2'
@@ -159,15 +187,15 @@ def test_bench_gpus_2_launches_two_ranks_itself():
 
 
 def test_bench_headline_line_is_short_and_the_secondary_workloads_go_to_a_side_file():
-    """the default (720p fp32) run: stdout is ONE strict-JSON line under 4 KB with roofline / cpu-free blocks (round 3's 21 KB line
+    """the default (720p fp32) workload with --full: stdout is ONE strict-JSON line under 4 KB with roofline / cpu-free blocks (round 3's 21 KB line
     was truncated by the driver and never parsed); the other BASELINE workloads are measured too but land in bench_secondary.json
     beside bench.py (kept short: 1 step, no CPU baseline)."""
     import json
     side = os.path.join(ROOT, 'bench_secondary.json')
     if os.path.exists(side):
         os.remove(side)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '1', '--warmup', '1', '--no-cpu-baseline'],
-                         capture_output=True, text=True, timeout=1200)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '1', '--warmup', '1', '--no-cpu-baseline',
+                          '--full'], capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stdout + out.stderr
     d = bench_line(out.stdout)
     assert d['metric'].startswith('enhanced frames/sec (1280x720') and d['dtype'] == 'f32'
@@ -250,10 +278,10 @@ def test_evaluate_refuses_a_batch_instead_of_scoring_sample_zero():
 
 @pytest.mark.parametrize('precision', ['fp32', 'fp16'])
 def test_bench_deform_basic_reports_the_dcn_roofline(precision):
-    """bench.py --deform basic: the modulated-deformable aligner is timed as its own kind and priced on 2240 B per pixel"""
+    """bench.py --deform basic --full: the modulated-deformable aligner is timed as its own kind and priced on 2240 B per pixel"""
     import json
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', '128', '--frames', '3', '--steps', '2',
-                          '--warmup', '1', '--deform', 'basic', '--precision', precision, '--no-cpu-baseline'],
+                          '--warmup', '1', '--deform', 'basic', '--precision', precision, '--no-cpu-baseline', '--full'],
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout + out.stderr
     d = bench_line(out.stdout)
@@ -375,7 +403,7 @@ def test_bench_gpus_8_launches_eight_ranks():
     env['PNP_DIST_BACKEND'] = 'gloo'
     env['OMP_NUM_THREADS'] = '4'
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--workload', '128', '--frames', '3',
-                          '--steps', '2', '--warmup', '1', '--no-kernel-events'], capture_output=True, text=True, timeout=1500,
+                          '--steps', '2', '--warmup', '1', '--no-kernel-events', '--full'], capture_output=True, text=True, timeout=1500,
                          env=env)
     assert out.returncode == 0, out.stdout + out.stderr
     d = bench_line(out.stdout)

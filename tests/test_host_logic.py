@@ -395,6 +395,36 @@ def test_bench_line_is_bounded_and_strict_json():
         bench.bounded_line(res)
 
 
+def test_bench_steps_and_full_options():
+    """--steps is the number of timed steps (at least one), --full is off unless asked for, --dump-outputs takes a directory"""
+    bench = _load_bench()
+    a = bench.parse_args(['--steps', '7', '--warmup', '0'])
+    assert a.steps == 7 and a.warmup == 0 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(['--full', '--dump-outputs', 'x'])
+    assert a.full is True and a.dump_outputs == 'x'
+    for bad in (['--steps', '0'], ['--warmup', '-1']):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_bench_dump_outputs_writes_float32_whole_or_as_a_fixed_sample(tmp_path):
+    """--dump-outputs: an output up to DUMP_MAX_BYTES is written whole; a larger one (a 720p clip is 77 MB) as DUMP_SAMPLE
+    elements at seeded positions, the same on every run, and a file of an earlier run does not linger beside it"""
+    bench = _load_bench()
+    small = torch.arange(2 * 3 * 8 * 8, dtype=torch.float32).reshape(1, 2, 3, 8, 8)
+    bench.dump_outputs(small, str(tmp_path))
+    got = np.load(tmp_path / 'output.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    big = torch.from_numpy(np.random.RandomState(3).rand(bench.DUMP_MAX_BYTES // 4 + 1).astype(np.float32))
+    bench.dump_outputs(big, str(tmp_path))
+    assert sorted(os.listdir(tmp_path)) == ['output_sample.npy']
+    s1 = np.load(tmp_path / 'output_sample.npy')
+    assert s1.dtype == np.float32 and s1.shape == (bench.DUMP_SAMPLE,) and s1.nbytes <= 64 << 20
+    assert np.isin(s1, big.numpy()).all()
+    bench.dump_outputs(big.clone(), str(tmp_path))
+    assert np.array_equal(np.load(tmp_path / 'output_sample.npy'), s1)
+
+
 BENCH_RANK = textwrap.dedent('''
     import importlib.util, os, sys, time
     spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(%r, 'bench.py'))
@@ -428,7 +458,7 @@ def test_bench_eight_rank_path_over_gloo_prints_one_bounded_line(tmp_path):
     port = 29900 + os.getpid() % 90
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=8', '--master-addr',
                           '127.0.0.1', '--master-port', str(port), str(script), '--gpus', '8', '--workload', '128', '--frames', '3',
-                          '--steps', '2', '--warmup', '1', '--no-kernel-events'], capture_output=True, text=True, timeout=600, env=env)
+                          '--steps', '2', '--warmup', '1', '--no-kernel-events', '--full'], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stdout + out.stderr
     d = bench_line(out.stdout)          # clean: bench.py points fd 1 at stderr, so even gloo's connection lines stay off stdout
     assert d['n_gpus'] == 8 and d['scaling'] == 'weak' and d['config']['parallelism'] == 'clip-sharded replicas x8'

@@ -4,7 +4,7 @@
 O=${1:-gpurun_out/power}; mkdir -p $O
 rocm-smi --showmaxpower --showclocks --showpower > $O/idle.txt 2>&1
 for mode in 1 0; do
-  python bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-secondary --winograd $mode > $O/bench_$mode.json 2> $O/bench_$mode.err &
+  python bench.py --steps 60 --warmup 5 --full --no-cpu-baseline --no-secondary --winograd $mode > $O/bench_$mode.json 2> $O/bench_$mode.err &
   BP=$!
   : > $O/smi_$mode.txt
   while kill -0 $BP 2>/dev/null; do

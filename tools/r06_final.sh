@@ -4,7 +4,7 @@
 O=gpurun_out/r06final; mkdir -p $O
 git rev-parse HEAD > $O/head.txt 2>/dev/null
 bash tools/profile_gpu.sh r06 > $O/profile.log 2>&1; head -20 gpurun_out/prof_r06/summary.txt | cut -c1-140
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_stderr.txt; cp bench_secondary.json $O/bench_secondary.json
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_line.json 2> $O/bench_stderr.txt; cp bench_secondary.json $O/bench_secondary.json
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r06final/bench_line.json').read().strip().split('\n')[-1])
