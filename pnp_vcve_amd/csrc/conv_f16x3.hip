@@ -379,16 +379,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_kernel(const X3Args a) {
             // x saturates at +-65504 as a WHOLE: the remainder is taken from the clamped value, so it is at most half an fp16 ulp
             // (<= 16) and its scaled form (<= 32768) needs no clamp of its own; in-range values are untouched
             char* d = k < ROWS ? l_main + k * XRSB : (S4 ? l_side6 : (k == ROWS ? l_side : l_side11));
-#ifdef X3_EXP_VERBATIM        /* upper bound of producer-split maps: the 16 bytes go to LDS as they are (wrong results) */
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
-            *reinterpret_cast<f32x2*>(d) = areg[k].xy;
-            *reinterpret_cast<f32x2*>(d + 128) = areg[k].zw;
-#else
             const f32x4 xc = clamp_h(areg[k]);
             const h4 hi = __builtin_convertvector(xc, h4);
             *reinterpret_cast<h4*>(d) = hi;
             *reinterpret_cast<h4*>(d + 128) = __builtin_convertvector((xc - __builtin_convertvector(hi, f32x4)) * X3_SCALE, h4);
-#endif
         }
 #pragma unroll
         for (int c = 0; c < 2; ++c)

@@ -57,41 +57,6 @@ constexpr int BG_B = PV_B + 256 * 48;         // 64 floats: bias * gamma
 constexpr int DUMP_B = BG_B + 256;            // 256 B per wave nobody reads: where the residual warm-up loads land (LDS-DMA: no destination register)
 constexpr int WINO_LDS = DUMP_B + 1024;       // 162048 of 163840
 constexpr unsigned OOBW = 0xFFFFFFF0u;
-#ifndef WINO_FOLD
-#define WINO_FOLD 1       // A/B switch: a wave-uniform partition plane folded into the B fragments instead of run as MFMAs
-#endif
-#ifndef WINO_JIT_ROWS
-#define WINO_JIT_ROWS 1   // A/B switch: the two patch rows a V row needs are read from the slab in the chunk that transforms them (32 transient
-#endif                    // registers) instead of living in four row arrays across the K loop and the epilogue (48-64 registers)
-#ifndef WINO_MS_FLAT
-#define WINO_MS_FLAT 0    // A/B switch (MS): 1 = no run-time `last source?` branch inside a chunk (descriptor / strides of the next segment as per-segment
-#endif                    // scalars, the RGB halo re-fetched by every segment); 0 = round 5's branches
-#ifndef WINO_MS_LAUNDER
-#define WINO_MS_LAUNDER 1 // A/B switch (MS): the thread id laundered per segment for the halo offsets (2: for every per-lane constant of the chunks)
-#endif
-#ifndef WINO_SEAM_CUT
-#define WINO_SEAM_CUT 2   // A/B switch: the rolling input transform stops at the tile seam -- V rows 0-2 of the next tile's first step are made behind
-#endif                    // the epilogue instead of in the tile's last three chunks (48 registers do not live across it).  1 = every single-source
-                          // kernel: 86.1 -> 72.8 frames/s (r06; r05 found the same: the allocator answers with 144-264 B of scratch); 2 = the branch
-                          // kernels only (default: 120 -> 56 B of scratch there, front half 414 -> 407 us); 0 = nowhere
-#ifndef WINO_LUMP
-#define WINO_LUMP 1       // A/B switch (non-branch kernels): the 8 float4 sums of a chunk's input transform in this many MFMA gaps.  8 = one sum per gap
-#endif                    // (round 5: lumped, the residual kernel spilled); r06, registers to spare: 8 / 4 / 2 / 1 gaps = 88.2 / 88.8 / 88.9 / 89.2 frames/s
-#ifndef WINO_QUAD_AHEAD
-#define WINO_QUAD_AHEAD 2   // A/B switch (conv3x3_wino_quad_kernel): B fragments requested this many steps ahead.  1 / 2 / 3 = 2076 / 2130 / 2040
-#endif                      // frames/s on 7x3x128x128 clips (3: the fourth fragment set lives in AGPRs, moved back and forth)
-#ifndef WINO_PK_FOLD
-#define WINO_PK_FOLD 0     // A/B switch (tile bodies): the folded plane's FMAs on the B fragments as v_pk_fma_f32 (8 instead of 16 per gap):
-#endif                    // bit-identical, 88.55 -> 88.15 frames/s (r06: fewer VALU cycles, denser MFMA issue, lower clock -- DESIGN.md 3.1)
-#ifndef WINO_RING_DMA
-#define WINO_RING_DMA 1   // A/B switch (plain / residual / fold-only kernels): the weight chunks arrive in the ring as LDS-DMA loads too -- no staging
-#endif                    // registers (16), no ring write, ONE counted wait per chunk placed a chunk and a half behind the request
-#ifndef WINO_HALO_DMA
-#define WINO_HALO_DMA 1   // A/B switch: the next tile's halo slabs arrive as LDS-DMA loads (no staging registers, no ds_write, no wait for the data in
-#endif                    // the instruction stream) instead of load -> register -> ds_write a chunk later
-#ifndef WINO_QUAD
-#define WINO_QUAD 1      // A/B switch of the quadrant units (conv3x3_wino_kernel's tail)
-#endif
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void* p, unsigned bytes) {
@@ -111,17 +76,6 @@ __device__ __forceinline__ void bstore4(__amdgpu_buffer_rsrc_t r, unsigned voff,
 }
 __device__ __forceinline__ void bstore1(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float v) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff, (int)soff, 0);
-}
-// b + c * w as two v_pk_fma_f32 (the same fused multiply-add per element as __builtin_elementwise_fma: bit-identical).  The unit is
-// compiled without packed fp32 ops (build_native.py), so this is inline asm: the compile step passes it through to the listing and the
-// assembler step of the build knows the instruction.  Half the vector-ALU instructions of the folded plane (WINO_PK_FOLD).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x4 pk_fma4(f32x2 c, f32x4 w, f32x4 b) {
-    f32x2 b01 = {b[0], b[1]}, b23 = {b[2], b[3]};
-    const f32x2 w01 = {w[0], w[1]}, w23 = {w[2], w[3]};
-    asm("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(b01) : "v"(c), "v"(w01));
-    asm("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(b23) : "v"(c), "v"(w23));
-    return f32x4{b01[0], b01[1], b23[0], b23[1]};
 }
 // Float4 sums written element by element.  As `a - b` on the vector type the four lanes stay one 128-bit value and the register
 // allocator needs an aligned quad for every intermediate of the rolling input transform; as four scalar ops they are independent
@@ -178,10 +132,13 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
     const int m = lane & 15, kq = lane >> 4;
     const int H = a.H, W = a.W;
     const int tiles_x = (W + 15) >> 4, ntiles = tiles_x * ((H + 15) >> 4);
-    // MS with the ring as LDS-DMA loads: no run-time `last source?` branch inside a chunk (every chunk's wait counts its own requests)
-    constexpr bool MSF = WINO_MS_FLAT || (MS && WINO_RING_DMA && WINO_HALO_DMA);
-    // the rolling input transform cut at the tile seam: 1 = every single-source kernel, 2 = the branch kernels only
-    constexpr bool SEAM = !MS && WINO_JIT_ROWS && (WINO_SEAM_CUT == 1 || (WINO_SEAM_CUT == 2 && PAR));
+    // MS with the ring as LDS-DMA loads: no run-time `last source?` branch inside a chunk (every chunk's wait counts its own requests).
+    // (MSF, the tile loop's last_seg and tqk, hreg[3] and the never-taken register branch of the MS weight requests only keep the
+    //  capture list of `chunk` as it was: without them no kernel computes anything else, but the register allocation of the MS and
+    //  gated kernels moves -- a change for a follow-up with a GPU A/B)
+    constexpr bool MSF = MS;
+    // the rolling input transform cut at the tile seam: the branch kernels only (see the end of the tile loop)
+    constexpr bool SEAM = PAR;
     if (a.gate) {      // (block-uniform: a scalar load)
         const int gv = __builtin_nontemporal_load(a.gate);
         if (((gv & a.gate_mask) != 0) != (a.gate_want != 0)) return;
@@ -327,14 +284,12 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
             // (64 FMAs per step) instead of running 64 more MFMAs per step.
             fold_next = -1;
             foldc_next = 0.f;
-            if (WINO_FOLD) {
 #pragma unroll
-                for (int j = 0; j < 3; ++j)
-                    if (need_next == (1 << j) && (uni >> j & 1)) {
-                        fold_next = j;
-                        foldc_next = 0.25f * uval[j];
-                    }
-            }
+            for (int j = 0; j < 3; ++j)
+                if (need_next == (1 << j) && (uni >> j & 1)) {
+                    fold_next = j;
+                    foldc_next = 0.25f * uval[j];
+                }
         }
     };
     // FO: plane and factor of the wave's quadrant of the tile at (y0, x0), from its first pixel (the frame passed the gate: the quadrant
@@ -484,11 +439,11 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
         const int nty0 = (ptile / tiles_x) * 16, ntx0 = (ptile % tiles_x) * 16;
         const unsigned nso = (unsigned)(nty0 * W + ntx0) * 256u;
         if constexpr (!MS) halo_offsets(tq, nty0, ntx0);
-        unsigned tq16 = (unsigned)tq * 16u;
+        const unsigned tq16 = (unsigned)tq * 16u;
         const int wave_s = __builtin_amdgcn_readfirstlane(tq >> 6);      // the wave's index as a scalar (LDS-DMA destinations go through M0)
-        int tqk = tq;            // the thread id the chunks derive their per-lane constants from (MS: laundered once more per segment)
-        // MS: per segment (= one 64-channel source): where its weight image starts, where the next segment's does, whether it is the
-        // tile's last one (then the next chunks are the next tile's RGB chunks), and the tile origin of the slabs it refills
+        int tqk = tq;            // the thread id the chunks derive their per-lane constants from
+        // MS: per segment (= one 64-channel source): where its weight image starts, descriptor, base, chunk and piece stride of the next
+        // segment's (after the tile's last source: the next tile's RGB chunks), and the tile origin of the slabs it refills
         unsigned u_so = 0, ref_so = nso, nx_base = 0, nx_cs = 16384, nx_ps = 4096;
         bool last_seg = true;
         __amdgpu_buffer_rsrc_t r_nx = r_u;
@@ -538,9 +493,9 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                 // first the fragments of the following position chunk (visible since the previous barrier)
 #pragma unroll
                 for (int n = 0; n < 4; ++n) bf[0][n] = lds4(((C + 1) & 3) * 16384 + bl + n * 1024);
-                // (WINO_JIT_ROWS: the patch centre of step S straight from slab S -- its refill starts in position chunk 1 of this step)
+                // (the patch centre of step S straight from slab S -- its refill starts in position chunk 1 of this step)
                 f32x4 xc[4];
-                if (WINO_JIT_ROWS && need != 0) {
+                if (need != 0) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) xc[q] = patch(s_c, 1 + (q >> 1), 1 + (q & 1));
                 }
@@ -554,7 +509,7 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         __builtin_amdgcn_sched_barrier(0);
-                        f32x4 ax = (WINO_JIT_ROWS ? xc[q] : (q == 0 ? d1[1] : (q == 1 ? d1[2] : (q == 2 ? d2[1] : d2[2])))) * pv[q];
+                        f32x4 ax = xc[q] * pv[q];
                         // (all four products in ONE gap: left alone each v_mul sits in front of its first MFMA, and a gap with any VALU
                         //  instruction costs ~20 cycles of matrix time before the 4 per instruction)
                         asm volatile("" : "+v"(ax));
@@ -587,16 +542,14 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                 //      scheduling barrier per gap (a 16x16x4 fp32 MFMA issues in a few cycles and executes for 32; left to itself hipcc
                 //      clusters the loads, the LDS traffic and the transform in front of and behind the MFMAs) --
                 //        gaps 0-3 of every position: the B fragments of the next position (across the chunk seam too)
-                //        gaps 4-7: the weight requests;  8-10: halo pieces requested a chunk ago -> LDS;  11-13: halo requests
-                //        gaps 36-43 (branch kernels: 16, 17): the rolling input transform;  20-27 (28-35): patch rows of step S + 1
-                //        gaps 52-55: the weight chunk requested at the top -> ring
-                using SN = I<(S + 1) & 3>;
+                //        gaps 4-7: the weight requests;  11-13: the next tile's halo pieces
+                //        gap 36 (branch kernels: 16, 17): the rolling input transform;  20-27 (8-15): the two patch rows it reads
+                //        gaps 52-55 (branch kernels): the weight chunk requested at the top -> ring
                 constexpr int NRING = NBR ? 3 : 4;
                 constexpr bool NEXT_IS_BR = PAR && PG == 3;      // the next chunk is a branch chunk: it reads its own fragments
                 constexpr int TR = PG == 0 ? 3 : PG - 1;         // the V row rewritten in this chunk (row 3 of step S, or row PG - 1 of S + 1)
-                constexpr bool RDMA = WINO_RING_DMA && WINO_HALO_DMA && !PAR;
                 constexpr bool XF = !(SEAM && S == 3 && PG >= 1);      // this chunk transforms a V row at all
-                // WINO_JIT_ROWS: V row TR = column transform of (patch row RA -/+ patch row RB): row 3 = d1 - d3 of step S (slab S is refilled from
+                // V row TR = column transform of (patch row RA -/+ patch row RB): row 3 = d1 - d3 of step S (slab S is refilled from
                 // position chunk 1 of step S on: still this tile's here), rows 0 / 1 / 2 = d0 - d2 / d1 + d2 / d2 - d1 of step S + 1.  Both rows are
                 // read in this chunk and dead behind the transform: no patch row lives across a chunk, the epilogue or the tile seam
                 using SR = I<PG == 0 ? S : ((S + 1) & 3)>;
@@ -621,7 +574,7 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                     }
                     if ((g & 15) < 4 && !(pj == 3 && NEXT_IS_BR)) {
                         // (MS, the tile's last chunk: the next one is an RGB chunk of the next tile, which reads its own fragments -- the read
-                        //  here is then of no use, and harmless; a run-time `if (last_seg)` per gap would cut the straight-line schedule)
+                        //  here is then of no use, and harmless; a run-time `last source?` test per gap would cut the straight-line schedule)
                         if (MSF || !(MS && C == 15 && pj == 3 && last_seg)) {
                             const unsigned nb = pj < 3 ? (C & 3) * 16384 + (pj + 1) * 4096 : ((C + 1) & 3) * 16384;
                             bf[(pj + 1) & 1][g & 3] = lds4(nb + bl + (g & 3) * 1024);
@@ -632,54 +585,44 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                         // which are one 4-KiB piece each.  Branch-free: descriptor, base, chunk and piece stride of "the next segment" are
                         // per-segment scalars (last source: the RGB image with piece stride 0 -- its one piece is fetched four times and lands
                         // in all four quarters of the ring slot, of which an RGB chunk reads the first)
-                        if (RDMA && g >= 4 && g < 8) {
+                        if (g >= 4 && g < 8) {
                             auto* dst = (__attribute__((address_space(3))) void*)(smem + (NC & 3) * 16384 + (g - 4) * 4096 + wave_s * 1024);
                             if (C < 13) __builtin_amdgcn_raw_ptr_buffer_load_lds(r_u, dst, 16, (int)tq16, (int)(u_so + (C + 3) * 16384 + (g - 4) * 4096), 0, 0);
                             else __builtin_amdgcn_raw_ptr_buffer_load_lds(r_nx, dst, 16, (int)tq16, (int)(nx_base + (C - 13) * nx_cs + (g - 4) * nx_ps), 0, 0);
-                        } else if (g >= 4 && g < 8) {
+                        } else if (g >= 4 && g < 8) {      // (never taken: see MSF)
                             if (C < 13) breg[g - 4] = bload4(r_u, tq16, u_so + (C + 3) * 16384 + (g - 4) * 4096);
                             else if (MSF) breg[g - 4] = bload4(r_nx, tq16, nx_base + (C - 13) * nx_cs + (g - 4) * nx_ps);
                             else if (!last_seg) breg[g - 4] = bload4(r_u, tq16, nx_base + (C - 13) * 16384 + (g - 4) * 4096);
                             else if (g == 4) breg[0] = bload4(r_urgb, tq16, (C - 13) * 4096);
                         }
-                    } else if (RDMA && g >= 4 && g < 8) {
+                    } else if (!PAR && g >= 4 && g < 8) {
                         // chunk C + 3 straight into its ring slot (the slot of chunk C - 1: every wave left it before the barrier at the top of
                         // this chunk), piece g - 4 of wave w = 64 lanes x 16 B at byte (g - 4) * 4096 + 1024 w
                         auto* dst = (__attribute__((address_space(3))) void*)(smem + (NC & 3) * 16384 + (g - 4) * 4096 + wave_s * 1024);
                         __builtin_amdgcn_raw_ptr_buffer_load_lds(r_u, dst, 16, (int)tq16, (NSTEP * 4 + NPG) * 16384 + (g - 4) * 4096, 0, 0);
-                    } else if (!RDMA && g >= 4 && g < 4 + NRING)
+                    } else if (PAR && g >= 4 && g < 4 + NRING)       // (the branch kernels stage their ring through registers)
                         breg[g - 4] = NBR ? bload4(r_up, tq16, NSTEP * 12288 + (g - 4) * 4096) : bload4(r_u, tq16, (NSTEP * 4 + NPG) * 16384 + (g - 4) * 4096);
                     if (S == 0 && PG == 1 && g == 7) bgv = *reinterpret_cast<const f32x4*>(smem + BG_B + (tqk & 15) * 16);
-                    if constexpr (WINO_HALO_DMA) {
-                        // The next tile's slab S (1296 float4) as LDS-DMA loads: pieces 0-2 in position chunk 1, pieces 3, 4 in chunk 2 -- every
-                        // wave has read its last patch rows of slab S in chunk 0, the barrier at the top of chunk 1 is behind -- each straight to
-                        // its place (piece i of wave w: 64 lanes x 16 B at element 256 i + 64 w).  No staging registers (12), no ds_write, and no
-                        // wait for HBM data in the instruction stream: the loads retire in order in front of the weight requests the ring
-                        // writes wait for, and the slab's first reader is five chunks away.  The sixth piece is 16 elements (1280 .. 1295): a
-                        // DMA load would write 240 lanes past the slab, so it stays load -> register -> ds_write (chunk 2 -> chunk 3).
-                        if ((PG == 1 || PG == 2) && g >= 11 && g < (PG == 1 ? 14 : 13)) {
-                            const int i = g - 11 + 3 * (PG - 1);
-                            auto* dst = (__attribute__((address_space(3))) void*)(smem + RING_B + S * SLAB_B + i * 4096 + wave_s * 1024);
-                            __builtin_amdgcn_raw_ptr_buffer_load_lds(r_src, dst, 16, (int)hoff[i], (int)(ref_so + S * 64), 0, 0);
-                        }
-                        if (PG == 2 && g == 13) hreg[0] = bload4(r_src, hoff[5], ref_so + S * 64);
-                        if (PG == 3 && g == 8) {
-                            int e = tqk + 256 * 5;
-                            e = e < NPX * 4 ? e : NPX * 4 - 1;
-                            *reinterpret_cast<f32x4*>(smem + RING_B + S * SLAB_B + e * 16) = hreg[0];
-                        }
-                    } else {
-                        if ((PG == 1 || PG == 2) && g >= 8 && g < 11) {        // (before this chunk's own halo requests reuse the registers)
-                            int e = tqk + 256 * (g - 8 + 3 * (PG - 1));
-                            e = e < NPX * 4 ? e : NPX * 4 - 1;
-                            *reinterpret_cast<f32x4*>(smem + RING_B + S * SLAB_B + e * 16) = hreg[g - 8];
-                        }
-                        if ((PG == 0 || PG == 1) && g >= 11 && g < 14) hreg[g - 11] = bload4(r_src, hoff[g - 11 + 3 * PG], ref_so + S * 64);
+                    // The next tile's slab S (1296 float4) as LDS-DMA loads: pieces 0-2 in position chunk 1, pieces 3, 4 in chunk 2 -- every
+                    // wave has read its last patch rows of slab S in chunk 0, the barrier at the top of chunk 1 is behind -- each straight to
+                    // its place (piece i of wave w: 64 lanes x 16 B at element 256 i + 64 w).  No staging registers (12), no ds_write, and no
+                    // wait for HBM data in the instruction stream: the loads retire in order in front of the weight requests the ring
+                    // writes wait for, and the slab's first reader is five chunks away.  The sixth piece is 16 elements (1280 .. 1295): a
+                    // DMA load would write 240 lanes past the slab, so it stays load -> register -> ds_write (chunk 2 -> chunk 3).
+                    if ((PG == 1 || PG == 2) && g >= 11 && g < (PG == 1 ? 14 : 13)) {
+                        const int i = g - 11 + 3 * (PG - 1);
+                        auto* dst = (__attribute__((address_space(3))) void*)(smem + RING_B + S * SLAB_B + i * 4096 + wave_s * 1024);
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(r_src, dst, 16, (int)hoff[i], (int)(ref_so + S * 64), 0, 0);
                     }
-                    // MS, last source: the next tile's RGB halo, requested in step 1 and stored a chunk later (this tile's RGB patch was read
-                    // before its first chunk)
-                    // (every segment does it: the same pixels again, but no run-time branch in the chunk and no value that lives across one)
-                    if (MS && S == 1 && PG == 0 && g == 14 && (MSF || last_seg)) rgb_dma(tqk, nty0, ntx0);
+                    if (PG == 2 && g == 13) hreg[0] = bload4(r_src, hoff[5], ref_so + S * 64);
+                    if (PG == 3 && g == 8) {
+                        int e = tqk + 256 * 5;
+                        e = e < NPX * 4 ? e : NPX * 4 - 1;
+                        *reinterpret_cast<f32x4*>(smem + RING_B + S * SLAB_B + e * 16) = hreg[0];
+                    }
+                    // MS: the next tile's RGB halo, requested in step 1 (this tile's RGB patch was read before its first chunk) -- by every
+                    // segment: the same pixels again, but no run-time branch in the chunk and no value that lives across one
+                    if (MS && S == 1 && PG == 0 && g == 14) rgb_dma(tqk, nty0, ntx0);
                     if (RES && S == 3 && PG == 0 && g == 16) {
                         // The residual map was last touched a whole launch ago: its lines come from HBM.  Touch this wave's 128 lines (8 rows x
                         // 8 pixels x 256 B) now, four chunks ahead of the epilogue, so that its 16-B loads find them in L2.  As LDS-DMA loads
@@ -700,10 +643,9 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                     // same source order makes hipcc keep `acc` and `V` in scratch MEMORY (private_seg_size 1616, ten times slower), and
                     // the pin costs the back half 8 %: they keep reads first, transform second, unpinned.
                     //   The branch kernels do the 32 adds in TWO gaps (16 + 16): a gap with any vector-ALU instruction in it costs ~9-20
-                    // cycles of matrix time before the 4 per instruction (tools/ubench/ub_valu_gap.hip; front half 427 -> 423 us).  The
-                    // plain kernels keep one float4 per gap: lumped, the residual kernel spills 22 instead of 13 registers (+3 %).
+                    // cycles of matrix time before the 4 per instruction (tools/ubench/ub_valu_gap.hip; front half 427 -> 423 us).
                     if constexpr (PAR) {
-                        if (XF && WINO_JIT_ROWS && g >= 8 && g < 16) {   // (beside the halo pieces: LDS reads cost the matrix pipe nothing)
+                        if (XF && g >= 8 && g < 16) {   // (beside the halo pieces: LDS reads cost the matrix pipe nothing)
                             const int c = g & 3;
                             if (g < 12) da[c] = patch(SR{}, RA, c);
                             else db[c] = patch(SR{}, RB, c);
@@ -711,8 +653,7 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                         if (XF && g == 16) {
 #pragma unroll
                             for (int c = 0; c < 4; ++c)
-                                tt[c] = WINO_JIT_ROWS ? (TR == 1 ? da[c] + db[c] : da[c] - db[c])
-                                                      : TR == 0 ? d0[c] - d2[c] : (TR == 1 ? d1[c] + d2[c] : (TR == 2 ? d2[c] - d1[c] : d1[c] - d3[c]));
+                                tt[c] = TR == 1 ? da[c] + db[c] : da[c] - db[c];
                         }
                         if (XF && g == 17) {
 #pragma unroll
@@ -721,38 +662,21 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                                 asm volatile("" : "+v"(V[4 * TR + c]));
                             }
                         }
-                        if (!WINO_JIT_ROWS && g >= 28 && g < 36) {                 // patch rows of step S + 1: rows 0, 2 | 1 | 3 | none
-                            const int c = (g - 28) & 3;
-                            if (PG == 0 && g < 32) d0[c] = patch(SN{}, 0, c);
-                            if (PG == 0 && g >= 32) d2[c] = patch(SN{}, 2, c);
-                            if (PG == 1 && g < 32) d1[c] = patch(SN{}, 1, c);
-                            if (PG == 2 && g < 32) d3[c] = patch(SN{}, 3, c);
-                        }
                     } else {
-                        if (XF && WINO_JIT_ROWS && g >= 20 && g < 28) {
+                        if (g >= 20 && g < 28) {
                             const int c = (g - 20) & 3;
                             if (g < 24) da[c] = patch(SR{}, RA, c);
                             else db[c] = patch(SR{}, RB, c);
                         }
-                        if (!WINO_JIT_ROWS && g >= 20 && g < 28) {                 // patch rows of step S + 1: rows 0, 2 | 1 | 3 | none
-                            const int c = (g - 20) & 3;
-                            if (PG == 0 && g < 24) d0[c] = patch(SN{}, 0, c);
-                            if (PG == 0 && g >= 24) d2[c] = patch(SN{}, 2, c);
-                            if (PG == 1 && g < 24) d1[c] = patch(SN{}, 1, c);
-                            if (PG == 2 && g < 24) d3[c] = patch(SN{}, 3, c);
-                        }
-                        // first the row combination, then the column combination: WINO_LUMP gaps in all (a gap that holds any vector-ALU
-                        // instruction costs ~9 cycles of matrix time before the 4 per instruction: 8 gaps 200 cycles per chunk, 2 gaps 146)
-                        constexpr int LPG = 8 / WINO_LUMP;       // float4 sums per gap
+                        // first the row combination, then the column combination: all eight float4 sums in ONE gap (a gap that holds any
+                        // vector-ALU instruction costs ~9 cycles of matrix time before the 4 per instruction; r06, with registers to spare:
+                        // 8 / 4 / 2 / 1 gaps = 88.2 / 88.8 / 88.9 / 89.2 frames/s -- round 5, at the register limit, spilled when lumped)
 #pragma unroll
                         for (int c = 0; c < 4; ++c)
-                            if (XF && g == 36 + c / LPG)
-                                tt[c] = WINO_JIT_ROWS ? (TR == 1 ? add4(da[c], db[c]) : sub4(da[c], db[c]))
-                                                      : TR == 0 ? sub4(d0[c], d2[c]) : (TR == 1 ? add4(d1[c], d2[c]) : (TR == 2 ? sub4(d2[c], d1[c]) : sub4(d1[c], d3[c])));
+                            if (g == 36) tt[c] = TR == 1 ? add4(da[c], db[c]) : sub4(da[c], db[c]);
 #pragma unroll
                         for (int c = 0; c < 4; ++c)
-                            if (XF && g == 36 + (4 + c) / LPG)
-                                V[4 * TR + c] = c == 0 ? sub4(tt[0], tt[2]) : (c == 1 ? add4(tt[1], tt[2]) : (c == 2 ? sub4(tt[2], tt[1]) : sub4(tt[1], tt[3])));
+                            if (g == 36) V[4 * TR + c] = c == 0 ? sub4(tt[0], tt[2]) : (c == 1 ? add4(tt[1], tt[2]) : (c == 2 ? sub4(tt[2], tt[1]) : sub4(tt[1], tt[3])));
                     }
                     if constexpr (FO) {
                         // the plane's 1x1 fragments of this step: requested in position row 0, parked (N tiles 0-2) / kept (3) in row 1
@@ -768,27 +692,19 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                         }
                         if ((PG == 1 || PG == 2) && (g == 15 || g == 31)) {
                             // positions (1,1) (1,2) | (2,1) (2,2) are next: their fragments (read a position ago) take the folded plane
+                            // (hand-written v_pk_fma_f32 instead, 8 instead of 16 per gap: bit-identical, but 88.55 -> 88.15 frames/s)
                             {
                                 const int pjn = (g + 1) >> 4;
                                 const float cs = ((PG == 1) == (pjn == 1)) ? foldc : -foldc;
-#if WINO_PK_FOLD
-                                const f32x2 c2 = {cs, cs};
-#pragma unroll
-                                for (int n = 0; n < 3; ++n) bf[pjn & 1][n] = pk_fma4(c2, wjt[n], bf[pjn & 1][n]);
-                                bf[pjn & 1][3] = pk_fma4(c2, wj3, bf[pjn & 1][3]);
-#else
                                 const f32x4 c4 = {cs, cs, cs, cs};
 #pragma unroll
                                 for (int n = 0; n < 3; ++n) bf[pjn & 1][n] = __builtin_elementwise_fma(c4, wjt[n], bf[pjn & 1][n]);
                                 bf[pjn & 1][3] = __builtin_elementwise_fma(c4, wj3, bf[pjn & 1][3]);
-#endif
                             }
                         }
                     }
-                    if (!RDMA && g >= 52 && g < 52 + NRING) {
-                        if (MSF || !(MS && C >= 13 && last_seg && g > 52)) *reinterpret_cast<f32x4*>(smem + (NC & 3) * 16384 + (g - 52) * 4096 + tq16) = breg[g - 52];
-                    }
-                    if (RDMA && g == 63) {
+                    if (PAR && g >= 52 && g < 52 + NRING) *reinterpret_cast<f32x4*>(smem + (NC & 3) * 16384 + (g - 52) * 4096 + tq16) = breg[g - 52];
+                    if (!PAR && g == 63) {
                         // The ONE wait of a chunk: everything requested BEFORE this chunk has landed -- i.e. the weight chunk C + 2 (requested a
                         // chunk ago, first read behind the barrier at the top of the next chunk) and every halo piece older than this chunk.
                         // vmcnt retires in order, so "at most the requests of THIS chunk outstanding" says exactly that: 4 weight pieces + the
@@ -796,7 +712,7 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                         // (The epilogue's stores in front of a tile's first chunk are not counted: that wait then covers them too, as the ring
                         //  write's wait did.)
                         // (MS: + the two pieces of the next tile's RGB halo)
-                        constexpr int NVM = 4 + (WINO_HALO_DMA ? (PG == 1 ? 3 : (PG == 2 ? 3 : 0)) : ((PG == 0 || PG == 1) ? 3 : 0))
+                        constexpr int NVM = 4 + ((PG == 1 || PG == 2) ? 3 : 0)
                                           + ((RES && S == 3 && PG == 0) ? 2 : 0) + ((FO && PG == 0) ? 4 : 0) + ((MS && S == 1 && PG == 0) ? 2 : 0);
                         wait_vm<NVM>();
                     }
@@ -859,8 +775,7 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
 #pragma unroll
                 for (int pj = 0; pj < 4; ++pj) br[pj] = lds4(PG * 16384 + (pj * 64 + (tq & 63)) * 16);
                 // three ahead: RGB chunk 3 (one piece), then the first source's chunks 0..2
-                constexpr bool RD = WINO_RING_DMA && WINO_HALO_DMA;
-                if constexpr (RD) {
+                {
                     // (the slot of the RGB chunk in front: every wave took its fragments out of it before the barrier above)
                     auto* dst = (__attribute__((address_space(3))) void*)(smem + ((PG + 3) & 3) * 16384 + wave_s * 1024);
                     if (PG == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(r_urgb, dst, 16, (int)tq16, 3 * 4096, 0, 0);
@@ -871,10 +786,6 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                             __builtin_amdgcn_raw_ptr_buffer_load_lds(r_u, di, 16, (int)tq16, (int)(a.u_off[0] + (PG - 1) * 16384 + i * 4096), 0, 0);
                         }
                     }
-                } else if (PG == 0) breg[0] = bload4(r_urgb, tq16, 3 * 4096);
-                else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) breg[i] = bload4(r_u, tq16, a.u_off[0] + (PG - 1) * 16384 + i * 4096);
                 }
 #pragma unroll
                 for (int pj = 0; pj < 4; ++pj)
@@ -888,11 +799,7 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
 #pragma unroll
                     for (int n = 0; n < 4; ++n) bf[0][n] = lds4(bl + n * 1024);
                 }
-                if constexpr (RD) wait_vm<(PG == 0 ? 1 : 4)>();       // what the chunks in front requested has landed (this chunk's own may fly)
-                else {
-#pragma unroll
-                    for (int i = 0; i < (PG == 0 ? 1 : 4); ++i) *reinterpret_cast<f32x4*>(smem + ((PG + 3) & 3) * 16384 + i * 4096 + tq16) = breg[i];
-                }
+                wait_vm<(PG == 0 ? 1 : 4)>();       // what the chunks in front requested has landed (this chunk's own may fly)
             };
             rgb_chunk(I<0>{});
             rgb_chunk(I<1>{});
@@ -903,21 +810,17 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
             for (int ks = 0; ks < nw; ++ks) {
                 last_seg = ks + 1 >= nw;
                 u_so = a.u_off[ks];
-                if (MSF) r_nx = rsrc_of(last_seg ? a.Urgb : a.ubase, last_seg ? 4u * 4096u : OOBW);
-                nx_base = (MSF && last_seg) ? 0u : a.u_off[last_seg ? 0 : ks + 1];
-                nx_cs = (MSF && last_seg) ? 4096u : 16384u;
-                nx_ps = (MSF && last_seg) ? 0u : 4096u;
+                r_nx = rsrc_of(last_seg ? a.Urgb : a.ubase, last_seg ? 4u * 4096u : OOBW);
+                nx_base = last_seg ? 0u : a.u_off[ks + 1];
+                nx_cs = last_seg ? 4096u : 16384u;
+                nx_ps = last_seg ? 0u : 4096u;
                 // the slabs this segment refills belong to the next source of this tile, or to the first source of the next tile
                 r_src = rsrc_of(reinterpret_cast<const char*>(a.srcs[last_seg ? 0 : ks + 1]) - ((long)W + 1) * 256, OOBW);
                 ref_so = last_seg ? nso : (unsigned)(ty0 * W + tx0) * 256u;
                 // (the thread id laundered per segment: the eighteen per-lane constants behind the six offsets are recomputed here instead
                 //  of living -- seven of them in scratch, each reload an s_waitcnt vmcnt(0) -- across the whole tile)
                 int tqs = tq;
-                if (WINO_MS_LAUNDER >= 1) asm volatile("" : "+v"(tqs));
-                if (WINO_MS_LAUNDER >= 2) {
-                    tqk = tqs;
-                    tq16 = (unsigned)tqs * 16u;
-                }
+                asm volatile("" : "+v"(tqs));
                 halo_offsets(tqs, last_seg ? nty0 : ty0, last_seg ? ntx0 : tx0);
                 step(I<0>{});
                 step(I<1>{});
@@ -1017,9 +920,11 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
         ty0 = nty0;
         tx0 = ntx0;
         if constexpr (SEAM) {
-            // V rows 0-2 of the next tile's first step (its slab 0 has been in place since this tile's step 1): twelve patch reads and 24
-            // float4 sums with no MFMA beside them -- the vector ALU is the matrix pipe, so only the LDS latency (a few hundred cycles per
-            // tile) is new -- in exchange for 48 registers that no longer live across the epilogue
+            // Branch kernels: the rolling input transform stops at the tile seam.  V rows 0-2 of the next tile's first step (its slab 0 has
+            // been in place since this tile's step 1): twelve patch reads and 24 float4 sums with no MFMA beside them -- the vector ALU is
+            // the matrix pipe, so only the LDS latency (a few hundred cycles per tile) is new -- in exchange for 48 registers that no longer
+            // live across the epilogue (r06: 120 -> 56 B of scratch, front half 414 -> 407 us).  Not in the single-source kernels without
+            // branches: 86.1 -> 72.8 frames/s there (r05 found the same: the allocator answers with 144-264 B of scratch)
             f32x4 e0[4], e1[4], e2[4];
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -1031,27 +936,17 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
             for (int i = 0; i < 3; ++i) {
                 f32x4 tr[4];
 #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    if constexpr (PAR) tr[c] = i == 0 ? e0[c] - e2[c] : (i == 1 ? e1[c] + e2[c] : e2[c] - e1[c]);
-                    else tr[c] = i == 0 ? sub4(e0[c], e2[c]) : (i == 1 ? add4(e1[c], e2[c]) : sub4(e2[c], e1[c]));
-                }
-                if constexpr (PAR) {
-                    V[4 * i + 0] = tr[0] - tr[2];
-                    V[4 * i + 1] = tr[1] + tr[2];
-                    V[4 * i + 2] = tr[2] - tr[1];
-                    V[4 * i + 3] = tr[1] - tr[3];
-                } else {
-                    V[4 * i + 0] = sub4(tr[0], tr[2]);
-                    V[4 * i + 1] = add4(tr[1], tr[2]);
-                    V[4 * i + 2] = sub4(tr[2], tr[1]);
-                    V[4 * i + 3] = sub4(tr[1], tr[3]);
-                }
+                for (int c = 0; c < 4; ++c) tr[c] = i == 0 ? e0[c] - e2[c] : (i == 1 ? e1[c] + e2[c] : e2[c] - e1[c]);
+                V[4 * i + 0] = tr[0] - tr[2];
+                V[4 * i + 1] = tr[1] + tr[2];
+                V[4 * i + 2] = tr[2] - tr[1];
+                V[4 * i + 3] = tr[1] - tr[3];
             }
         }
     }
     // (LDS-DMA loads of "the next tile's" first weight chunks may still be in flight behind the block's last tile: they must have landed
     //  before the block ends and its LDS goes to the next one)
-    if constexpr (WINO_RING_DMA && WINO_HALO_DMA && !PAR) wait_vm<0>();
+    if constexpr (!PAR) wait_vm<0>();
     // ---- quadrant unit (see the strip assignment): 8x8 pixels of tile qtile, wave w = output channels 16 w .. + 15.  Same arithmetic
     // in the same order as a whole tile -- per accumulator: branches, then the position's 4 k-steps, step by step; bias through the C
     // operand of position (1,1) -- so a pixel's value does not depend on which form computed it (bit for bit; tested).  Straight-line code:
@@ -1309,8 +1204,9 @@ __device__ __forceinline__ void wino_quad_body(const WinoArgs& a) {
     }
     const unsigned wq16 = (unsigned)lane * 16u + (unsigned)wave * 1024u;
     // B fragments of step s4 live in set s4 % QB, requested QA steps ahead (QA = 2: the first two steps' fragments are requested before
-    // the halo has landed)
-    constexpr int QA = WINO_QUAD_AHEAD, QB = QA + 1;
+    // the halo has landed).  1 / 2 / 3 ahead = 2076 / 2130 / 2040 frames/s on 7x3x128x128 clips (3: the fourth fragment set lives in
+    // AGPRs, moved back and forth)
+    constexpr int QA = 2, QB = QA + 1;
     f32x4 Bq[QB][16], Bp[QB][FO ? 1 : 3];
 #pragma unroll
     for (int s0 = 0; s0 < QA; ++s0) {
@@ -1361,18 +1257,16 @@ __device__ __forceinline__ void wino_quad_body(const WinoArgs& a) {
         if (a.par_flags) needq = __builtin_amdgcn_readfirstlane(nz_any);
         // exactly one plane live on the unit and constant there: folded into the B fragments of positions (1,1) (1,2) (2,1) (2,2), as in
         // the tile kernel (pv_finish there)
-        if (WINO_FOLD) {
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const float uv = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pq[j][0])));
-                const bool same = pq[j][0] == uv && -pq[j][1] == uv && -pq[j][2] == uv && pq[j][3] == uv;
-                if (nz_any == (1 << j) && __builtin_amdgcn_ballot_w64(!same) == 0) {
-                    foldq = j;
-                    foldcq = 0.25f * uv;
-                }
+        for (int j = 0; j < 3; ++j) {
+            const float uv = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pq[j][0])));
+            const bool same = pq[j][0] == uv && -pq[j][1] == uv && -pq[j][2] == uv && pq[j][3] == uv;
+            if (nz_any == (1 << j) && __builtin_amdgcn_ballot_w64(!same) == 0) {
+                foldq = j;
+                foldcq = 0.25f * uv;
             }
-            if (foldq >= 0) needq = 0;
         }
+        if (foldq >= 0) needq = 0;
     }
     const unsigned qo = (unsigned)((qy0 + 2 * kq) * W + qx0) * 256u + (unsigned)(wave * 16 + m) * 4u;
     float resq[16];
@@ -1831,7 +1725,7 @@ int launch_conv3x3_wino(const ConvArgs& a, hipStream_t stream) {
     w.W = a.W;
     w.act = a.act;
     w.dbg = a.dbg;
-    w.quad = WINO_QUAD;
+    w.quad = 1;
     const int ntiles = ((a.W + 15) / 16) * ((a.H + 15) / 16);
     if (a.wino_units && a.wwino) {                          // small frames: one block per quadrant unit
         const dim3 gq(4 * ntiles), bq(256);

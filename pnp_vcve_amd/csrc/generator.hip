@@ -698,9 +698,8 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
     // the input convs over wide sources likewise (180x320, 240 tiles, fp32: 561 frames/s direct, 707 with the direct input convs kept,
     // 712 with the multi-source tile kernel).  2 = the tile kernels at every size (tests)
     auto ntiles16 = [](int hh, int ww) { return (int64_t)((hh + 15) / 16) * ((ww + 15) / 16); };
-    auto wino_ok = [&](int hh, int ww) { return wopt == 2 || wopt == 1; };
+    const bool wino_on = wopt != 0;
     auto wino_units = [&](int hh, int ww) { return wopt == 1 && ntiles16(hh, ww) <= PNP_WINO_UNITS_MAX_TILES; };
-    auto wino_ms_ok = [&](int hh, int ww) { return wopt == 2 || wopt == 1; };
     // every 64-channel map that is only read as an MFMA A operand gets an fp16 copy from its producer
     const bool mirrors = f16_maps && g->opt[PNP_OPT_F16_MIRRORS] && c.deform == 0 && W.x16 != nullptr;
     // ... and, optionally, the running map x INSIDE a branch too (input conv and every block write x16 next to x, every front
@@ -935,8 +934,8 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
             int r = conv(in.bias(flat + B.in_bias).act(2).units(wino_units(h, w)).to(W.tmp0).also16(const_cast<void*>(x16)));
             if (r) return r;
             const float* x = W.tmp0;
-            const bool wino = wino_ok(h, w), un = wino_units(h, w);
-            if (wino && g->ndyn > 0) {      // this frame's Winograd images of the branch's expert-mixed convs, its channel gain folded in
+            const bool un = wino_units(h, w);
+            if (wino_on && g->ndyn > 0) {      // this frame's Winograd images of the branch's expert-mixed convs, its channel gain folded in
                 std::vector<const float*> ws;
                 std::vector<float*> wd;
                 for (int k = 0; k < c.num_blocks; ++k) {
@@ -964,9 +963,9 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
                 const float* b1 = c.one_layer ? flat + K.conv1_bias
                                               : W.mixb + ((int64_t)u * g->ndyn + K.dyn_conv1) * 64;
                 const float* g1 = c.one_layer ? nullptr : gam;
-                const float* u2 = !wino ? nullptr : (woqp ? packed + K.conv2_wino : W.wino + (int64_t)(2 * k) * PNP_WINO_IMG_FLOATS);
-                const float* u1 = !wino ? nullptr : (c.one_layer ? packed + K.conv1_wino : W.wino + (int64_t)(2 * k + 1) * PNP_WINO_IMG_FLOATS);
-                const float* up = !wino ? nullptr : packed + K.w1x1_wino;
+                const float* u2 = !wino_on ? nullptr : (woqp ? packed + K.conv2_wino : W.wino + (int64_t)(2 * k) * PNP_WINO_IMG_FLOATS);
+                const float* u1 = !wino_on ? nullptr : (c.one_layer ? packed + K.conv1_wino : W.wino + (int64_t)(2 * k + 1) * PNP_WINO_IMG_FLOATS);
+                const float* up = !wino_on ? nullptr : packed + K.w1x1_wino;
                 // the map between the two halves is read only as an MFMA A operand: an fp16 map on the fp16 path
                 const int o16 = f16_maps ? 1 : 0, s16 = f16_maps ? 2 : 0;
                 if (c.channel_first) {   // sr_backbone_utils.py:305-313
@@ -997,8 +996,7 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
         for (int i = t - 1; i >= 0; --i) {
             const BranchPk& B = g->br[0];
             ConvCall in(h, w, cfg_lr);
-            const bool wn = wino_ms_ok(h, w);
-            auto wi = [&](int64_t off) -> const float* { return wn ? packed + off : nullptr; };
+            auto wi = [&](int64_t off) -> const float* { return wino_on ? packed + off : nullptr; };
             in.source(W.lr4 + (int64_t)i * hw * 4, 4, packed + B.in_lr, wi(B.in_lr_wino));
             if (i < t - 1) {
                 int k = i + 1;
@@ -1019,8 +1017,7 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
         for (int i = 0; i < t; ++i) {
             const BranchPk& B = g->br[1];
             ConvCall in(h, w, cfg_lr);
-            const bool wn = wino_ms_ok(h, w);
-            auto wi = [&](int64_t off) -> const float* { return wn ? packed + off : nullptr; };
+            auto wi = [&](int64_t off) -> const float* { return wino_on ? packed + off : nullptr; };
             in.source(W.lr4 + (int64_t)i * hw * 4, 4, packed + B.in_lr, wi(B.in_lr_wino));
             if (i > 0) {
                 int k = i - 1;
@@ -1045,7 +1042,7 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
             const int o16 = f16_maps ? 1 : 0, s16 = f16_maps ? 2 : 0;
             if (!c.vsr) {   // :144-146
                 rc = conv(ConvCall(h, w, cfg_lr).source(feat, 64, packed + g->hr_img).mirror16(s16of(i)).bias(flat + g->hr_bias)
-                              .wino(wino_ok(h, w) ? packed + g->hr_wino : nullptr).units(wino_units(h, w)).act(2).to(W.tmp1).f16_map(o16));
+                              .wino(wino_on ? packed + g->hr_wino : nullptr).units(wino_units(h, w)).act(2).to(W.tmp1).f16_map(o16));
                 if (!rc)
                     rc = conv(ConvCall(h, w, CONV_CFG_RGB).source(W.tmp1, 64, packed + g->last_img).bias(packed + g->last_bias)
                                   .mode(2).rgb(lr_i, hw, packed + g->last_valu).to(out_i).f16_map(s16));
@@ -1060,7 +1057,7 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
                                   .bias(packed + g->up_bias[1], 64).act(2).mode(1, 4, IMG_WIDE).to(W.u2).f16_map(o16 | s16));
                 if (!rc)
                     rc = conv(ConvCall(4 * h, 4 * w, conv_pick_cfg(4 * h, 4 * w)).source(W.u2, 64, packed + g->hr_img)
-                                  .bias(flat + g->hr_bias).wino(wino_ok(4 * h, 4 * w) ? packed + g->hr_wino : nullptr).units(wino_units(4 * h, 4 * w)).act(2).to(W.u3)
+                                  .bias(flat + g->hr_bias).wino(wino_on ? packed + g->hr_wino : nullptr).units(wino_units(4 * h, 4 * w)).act(2).to(W.u3)
                                   .f16_map(o16 | s16));
                 if (!rc)
                     rc = conv(ConvCall(4 * h, 4 * w, CONV_CFG_RGB).source(W.u3, 64, packed + g->last_img)

@@ -12,9 +12,6 @@
 // reuse beyond what a 4-tap footprint shares through L1/L2.
 #include "warp.h"
 #include "f16_util.h"
-#ifndef WARP_RPT
-#define WARP_RPT 2
-#endif
 
 namespace {
 
@@ -208,7 +205,7 @@ int launch_mv_warp_nhwc(const float* feat, const float* fx, const float* fy, voi
                         hipStream_t stream, bool out_f16, bool nearest) {
     if (C % 4) return PNP_ERR_BAD_ARG;
     if (C == 64 && (long)H * W * 256 < (1L << 32)) {        // 32-bit byte offsets through buffer descriptors
-        constexpr int RPT = WARP_RPT;
+        constexpr int RPT = 2;
         auto k64 = out_f16 ? (nearest ? mv_warp_nhwc64_kernel<true, true, RPT> : mv_warp_nhwc64_kernel<true, false, RPT>)
                            : (nearest ? mv_warp_nhwc64_kernel<false, true, RPT> : mv_warp_nhwc64_kernel<false, false, RPT>);
         hipLaunchKernelGGL(k64, dim3((unsigned)((W + 15) / 16), (unsigned)((H + RPT - 1) / RPT)), dim3(256), 0, stream, feat, fx, fy, out,
