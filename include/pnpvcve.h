@@ -129,6 +129,20 @@ int pnp_generator_pack(const pnp_generator* g, const float* flat_dev, float* pac
 #define PNP_MAX_CONTEXTS 8
 int64_t pnp_generator_workspace_bytes(const pnp_generator* g, int t, int h, int w);
 
+/* Bounded-memory forward for long clips.  k bounds the 64-channel frame feature maps the two recurrent sweeps hold across branch
+ * runs (the per-frame slots of the workspace and their fp16 mirrors; per-launch scratch does not count).  0 (default) = unbounded:
+ * one map per frame, the schedule of earlier versions launch for launch; k >= t gives that schedule too.  0 < k < t: the backward
+ * sweep runs once as a checkpoint pass and the forward sweep recomputes each segment of backward features from its checkpoint
+ * just before it reads them -- the same kernels on the same values, so the output is bit-identical to the unbounded schedule.
+ * The workspace then holds k maps instead of t (the 16 B/pixel/frame RGB0 frames and the per-frame regions that do not scale with
+ * h*w stay per frame: DESIGN.md section 4).  The profiling counters count what runs, recomputed branch runs included.
+ * Set k BEFORE sizing: pnp_generator_workspace_bytes follows it and returns -1 when 0 < k < pnp_generator_min_resident(g, t),
+ * where pnp_generator_forward returns PNP_ERR_BAD_ARG.  pnp_generator_min_resident: the smallest k the scheme accepts for t
+ * frames with this configuration (about 2 * sqrt(2t); fewer without with_cat), -1 for t < 1.  Negative k: PNP_ERR_BAD_ARG. */
+int pnp_generator_set_max_resident(pnp_generator* g, int k);
+int pnp_generator_get_max_resident(const pnp_generator* g);
+int pnp_generator_min_resident(const pnp_generator* g, int t);
+
 /* generator.forward(lrs, QPs, slices, mvs, base_QPs, par_map)  iconvsr_ipb_par.py:44-149.
  *   lrs_dev (n,t,3,h,w)  mvs_dev (n,t,4,h,w)  par_dev (n,t,3,h,w)      NCHW, contiguous
  *   slices/qps/base_qps: HOST arrays of n*t floats (the (n,t,1,1,1) tensors, flattened);

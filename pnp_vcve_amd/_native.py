@@ -34,6 +34,9 @@ SIGNATURES = {
     'pnp_generator_packed_floats': (c_int64, [c_void_p]),
     'pnp_generator_pack': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     'pnp_generator_workspace_bytes': (c_int64, [c_void_p, c_int, c_int, c_int]),
+    'pnp_generator_set_max_resident': (c_int, [c_void_p, c_int]),
+    'pnp_generator_get_max_resident': (c_int, [c_void_p]),
+    'pnp_generator_min_resident': (c_int, [c_void_p, c_int]),
     'pnp_generator_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       POINTER(c_float), POINTER(c_float), POINTER(c_float),
                                       c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),

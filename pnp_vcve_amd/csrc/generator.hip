@@ -71,6 +71,7 @@ struct pnp_generator {
     pnp_generator_cfg cfg;
     int prec = PNP_PREC_F32;          // pnp_generator_set_precision
     int opt[PNP_OPT_COUNT] = {1, 1, 1, 1, 1, 1, 1, 0, 1, 1};   // pnp_generator_set_option (defaults: everything on but the chain mirrors; Winograd on large frames)
+    int max_resident = 0;             // pnp_generator_set_max_resident: bound on the frame feature maps held across steps (0 = one per frame)
     // optional per-launch HIP-event timing (pnp_generator_profile*): off by default
     mutable bool prof_on = false;
     mutable std::vector<hipEvent_t> prof_pool;
@@ -420,6 +421,133 @@ int64_t pnp_addr32_bytes_per_lr_pixel(int vsr, int deform) {
 // op-level entry points: the conv kernels address an NHWC64 fp32 map with 32-bit byte offsets
 bool op_map_fits(int h, int w) { return h >= 1 && w >= 1 && (int64_t)h * w * 256 < ((int64_t)1 << 32); }
 
+// ---- bounded-memory schedule (pnp_generator_set_max_resident)
+// With a bound k on the 64-channel frame maps held across branch runs (0 < k < t), the backward sweep runs once as a checkpoint
+// pass that keeps the first R frames' features (produced last, consumed first) and, at every boundary b of the segments
+// [R, R+L), [R+L, R+2L), ..., [.., t), the two maps the recompute of the segment ending at b reads: B[b] (with_cat) and B[first key >= b].
+// The forward sweep recomputes each segment's backward features from its checkpoint just before it consumes them.  Recomputed
+// frames: t - R.  Upper bound of the maps alive at any step (c = 2 with_cat, 1 without; nC = checkpoint boundaries):
+//   head of the checkpoint pass R + c*nC + 1, a segment of it c*nC + c + 1, a recomputed segment L + c + c*nC.
+int plan_need(int t, int with_cat, int R, int L) {
+    if (R >= t) return t;
+    const int c = with_cat ? 2 : 1;
+    const int nc = (t - R + L - 1) / L - 1;
+    int need = c * nc + c + 1;
+    if (R > 0 && R + c * nc + 1 > need) need = R + c * nc + 1;
+    if (L + c + c * nc > need) need = L + c + c * nc;
+    return need;
+}
+
+// the most resident frames (fewest recomputed) a bound of k maps allows: false if k is below the minimum.  k <= 0 or k >= t: R = t.
+bool plan_pick(int t, int with_cat, int k, int* R, int* L) {
+    if (k <= 0 || k >= t) {
+        *R = t;
+        *L = 0;
+        return true;
+    }
+    for (int r = k < t - 1 ? k : t - 1; r >= 0; --r)       // plan_need >= R + 1 and >= L + 1: both stay below k
+        for (int l = 1; l <= k && l <= t - r; ++l)
+            if (plan_need(t, with_cat, r, l) <= k) {
+                *R = r;
+                *L = l;
+                return true;
+            }
+    return false;
+}
+
+int plan_min_resident(int t, int with_cat) {
+    int R, L, k = 1;
+    while (!plan_pick(t, with_cat, k, &R, &L)) ++k;
+    return k;
+}
+
+bool bounded_mode(const pnp_generator* g, int t) { return g->max_resident > 0 && g->max_resident < t; }
+
+// One branch run of the clip schedule: the backward (sweep 0) or forward (sweep 1) branch of `frame`, and where its maps live.
+// out / key / nb / own: index of a 64-channel frame map in W.slots (and W.slots16); -1 = not read.  key_frame: the key frame it aligns.
+struct Step {
+    int sweep, frame, key_frame;
+    int out, key, nb, own;      // written map; aligned key-frame map; neighbour (with_cat: B[i+1] | F[i-1]); own backward feature (forward)
+};
+
+// The clip's branch runs in launch order.  Unbounded (k = 0 or k >= t): today's schedule, frame i in slot i.  Bounded: checkpoint
+// pass + recomputed segments, every map placed by a liveness scan on a free list of k slots.  Returns false if the scan ever needs
+// more than k slots (plan_need is an upper bound, so this does not happen; kept as a guard against a write past the workspace).
+bool make_schedule(const pnp_generator* g, int t, const std::vector<char>& key, std::vector<Step>& steps, int* recomputed) {
+    const int cat = g->cfg.with_cat;
+    steps.clear();
+    *recomputed = 0;
+    auto nk = [&](int i) { int k = i + 1; while (!key[k]) ++k; return k; };
+    auto pk = [&](int i) { int k = i - 1; while (!key[k]) --k; return k; };
+    if (!bounded_mode(g, t)) {
+        for (int i = t - 1; i >= 0; --i)
+            steps.push_back({0, i, i < t - 1 ? nk(i) : -1, i, i < t - 1 ? nk(i) : -1, (cat && i < t - 1) ? i + 1 : -1, -1});
+        for (int i = 0; i < t; ++i)
+            steps.push_back({1, i, i > 0 ? pk(i) : -1, i, i > 0 ? pk(i) : -1, (cat && i > 0) ? i - 1 : -1, i});
+        return true;
+    }
+    int R, L;
+    if (!plan_pick(t, cat, g->max_resident, &R, &L)) return false;
+    // 1) the steps with the INSTANCE (= producing step) each one reads
+    std::vector<int> bc(t, -1), br(t, -1), fw(t, -1);
+    for (int i = t - 1; i >= 0; --i) {
+        const int s = (int)steps.size();
+        steps.push_back({0, i, i < t - 1 ? nk(i) : -1, s, i < t - 1 ? bc[nk(i)] : -1, (cat && i < t - 1) ? bc[i + 1] : -1, -1});
+        bc[i] = s;
+    }
+    for (int i = 0; i < t; ++i) {
+        if (i >= R && (i - R) % L == 0) {          // entering segment [i, b): recompute b-1 .. i from the checkpoint of b
+            const int b = i + L < t ? i + L : t;
+            for (int j = b - 1; j >= i; --j) {
+                const int s = (int)steps.size();
+                const int kj = j < t - 1 ? nk(j) : -1;
+                steps.push_back({0, j, kj, s, kj < 0 ? -1 : (kj < b ? br[kj] : bc[kj]),
+                                 (cat && j < t - 1) ? (j + 1 < b ? br[j + 1] : bc[b]) : -1, -1});
+                br[j] = s;
+                ++*recomputed;
+            }
+        }
+        const int s = (int)steps.size();
+        steps.push_back({1, i, i > 0 ? pk(i) : -1, s, i > 0 ? fw[pk(i)] : -1, (cat && i > 0) ? fw[i - 1] : -1, i < R ? bc[i] : br[i]});
+        fw[i] = s;
+    }
+    // 2) last reader of every instance, 3) slots: a step frees what it read for the last time BEFORE its output takes a slot (every
+    // read of a step -- the alignment and the input conv -- is done before its last block writes the output)
+    const int ns = (int)steps.size();
+    std::vector<int> last(ns);
+    for (int s = 0; s < ns; ++s) {
+        last[s] = s;
+        for (int r : {steps[s].key, steps[s].nb, steps[s].own})
+            if (r >= 0 && s > last[r]) last[r] = s;
+    }
+    std::vector<int> slot(ns, -1), free_slots;
+    for (int k = g->max_resident - 1; k >= 0; --k) free_slots.push_back(k);
+    for (int s = 0; s < ns; ++s) {
+        Step& st = steps[s];
+        int* rd[3] = {&st.key, &st.nb, &st.own};
+        const int inst[3] = {st.key, st.nb, st.own};
+        for (int j = 0; j < 3; ++j) {
+            if (inst[j] < 0) continue;
+            if (slot[inst[j]] < 0) return false;
+            *rd[j] = slot[inst[j]];
+        }
+        for (int j = 0; j < 3; ++j)
+            if (inst[j] >= 0 && last[inst[j]] == s && slot[inst[j]] >= 0) {
+                free_slots.push_back(slot[inst[j]]);
+                slot[inst[j]] = -1;       // (read twice by one step: freed once)
+            }
+        if (free_slots.empty()) return false;
+        slot[s] = free_slots.back();
+        free_slots.pop_back();
+        st.out = slot[s];
+        if (last[s] == s) {
+            free_slots.push_back(slot[s]);
+            slot[s] = -1;
+        }
+    }
+    return true;
+}
+
 Workspace carve(const pnp_generator* g, char* base, int t, int h, int w) {
     Workspace W;
     int64_t off = 0;
@@ -429,8 +557,12 @@ Workspace carve(const pnp_generator* g, char* base, int t, int h, int w) {
         off = align_up(off + floats * 4, 256);
         return p;
     };
+    // frame maps: one per frame, or the bound's k (bounded schedule); the bounded schedule also binarises a sparse_val partition map
+    // per frame just before its branch runs instead of once per clip
+    const bool bounded = bounded_mode(g, t);
+    const int64_t nslots = bounded ? g->max_resident : t;
     W.lr4 = take(hw * 4 * t);
-    W.slots = take(hw * 64 * t);
+    W.slots = take(hw * 64 * nslots);
     W.kw = take(hw * 64);
     W.tmp0 = take(hw * 64);
     W.tmp1 = take(hw * 64);
@@ -447,7 +579,7 @@ Workspace carve(const pnp_generator* g, char* base, int t, int h, int w) {
     } else {
         W.flow4 = W.om = nullptr;
     }
-    W.parbin = g->cfg.sparse_val ? take(hw * 3 * t) : nullptr;
+    W.parbin = g->cfg.sparse_val ? take(hw * 3 * (bounded ? 1 : t)) : nullptr;
     W.ew = take((int64_t)t * g->cfg.num_experts);
     W.gamma = take((int64_t)t * 64);
     W.mixw = take((int64_t)t * g->ndyn * IMG_WIDE);
@@ -457,7 +589,7 @@ Workspace carve(const pnp_generator* g, char* base, int t, int h, int w) {
     W.wino = (g->prec == PNP_PREC_F32 && g->ndyn > 0) ? take((int64_t)2 * g->cfg.num_blocks * PNP_WINO_IMG_FLOATS) : nullptr;
     const bool mir = g->prec == PNP_PREC_F16 && g->cfg.deform == 0;      // sized whether or not PNP_OPT_F16_MIRRORS is on
     W.x16 = mir ? reinterpret_cast<uint16_t*>(take(hw * 32)) : nullptr;
-    W.slots16 = mir ? reinterpret_cast<uint16_t*>(take(hw * 32 * t)) : nullptr;
+    W.slots16 = mir ? reinterpret_cast<uint16_t*>(take(hw * 32 * nslots)) : nullptr;
     W.parany = reinterpret_cast<int*>(take(t));        // (not last: the harness shrinks the workspace and expects the last region to be touched)
     W.parflags = reinterpret_cast<int*>(take((int64_t)t * ((w + 15) / 16) * ((h + 7) / 8)));
     W.queue = g->prec == PNP_PREC_F16X3 ? reinterpret_cast<int*>(take(16)) : nullptr;
@@ -661,7 +793,20 @@ int pnp_generator_pack(const pnp_generator* g, const float* flat, float* packed,
 }
 
 int64_t pnp_generator_workspace_bytes(const pnp_generator* g, int t, int h, int w) {
+    int R, L;
+    if (bounded_mode(g, t) && !plan_pick(t, g->cfg.with_cat, g->max_resident, &R, &L)) return -1;    // bound below the minimum
     return carve(g, nullptr, t, h, w).bytes;
+}
+
+int pnp_generator_set_max_resident(pnp_generator* g, int k) {
+    if (!g || k < 0) return PNP_ERR_BAD_ARG;
+    g->max_resident = k;
+    return PNP_OK;
+}
+int pnp_generator_get_max_resident(const pnp_generator* g) { return g ? g->max_resident : -1; }
+int pnp_generator_min_resident(const pnp_generator* g, int t) {
+    if (!g || t < 1) return -1;
+    return plan_min_resident(t, g->cfg.with_cat);
 }
 
 }  // extern "C"
@@ -818,14 +963,24 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
         }
         rc = launch_pack_lr(lr_b, W.lr4, t, h, w, st);
         if (rc) return rc;
-        if (c.sparse_val && g->opt[PNP_OPT_SPARSE_EVAL]) {   // the reference's (eval-mode) sparse evaluation as a dense map (prep.hip)
+        // the reference's (eval-mode) sparse evaluation as a dense map (prep.hip): for the whole clip at once, or (bounded schedule)
+        // one frame at a time into a one-frame buffer, just before each branch run that reads it
+        const float* const par_in = par_b;
+        const bool sparse_now = c.sparse_val && g->opt[PNP_OPT_SPARSE_EVAL];
+        const bool sparse_per_frame = sparse_now && bounded_mode(g, t);
+        if (sparse_now && !sparse_per_frame) {
             rc = launch_par_sparse(par_b, W.parbin, t, h, w, st);
             if (rc) return rc;
             par_b = W.parbin;
         }
         // which 1x1 partition branches each 8x16 tile of each frame needs at all (32 front-half launches per frame use it)
         if (par_skip) {
-            rc = launch_par_tile_flags(par_b, hw, W.parflags, t, h, w, st);
+            const int64_t ntile = (int64_t)((w + 15) / 16) * ((h + 7) / 8);
+            for (int i = 0; sparse_per_frame && i < t && !rc; ++i) {
+                rc = launch_par_sparse(par_in + (int64_t)i * 3 * hw, W.parbin, 1, h, w, st);
+                if (!rc) rc = launch_par_tile_flags(W.parbin, hw, W.parflags + i * ntile, 1, h, w, st);
+            }
+            if (!sparse_per_frame) rc = launch_par_tile_flags(par_b, hw, W.parflags, t, h, w, st);
             if (rc) return rc;
             if (wopt >= 1) rc = launch_par_frame_any(W.parflags, W.parany, t, h, w, st);      // (for the I frames' gated front halves)
             if (rc) return rc;
@@ -917,10 +1072,11 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
         key[0] = key[t - 1] = 1;
 
         // input conv over the virtual concat `in` (sources already added), then the BAE blocks
-        auto run_branch = [&](int brid, int i, ConvCall in) -> int {
+        // (out: the frame map its last block writes, Step::out)
+        auto run_branch = [&](int brid, int i, int out, ConvCall in) -> int {
             const BranchPk& B = g->br[brid];
             const float* gam = (c.with_bias && c.with_se) ? W.gamma + (int64_t)i * 64 : nullptr;
-            const float* parp = par_b + (int64_t)i * 3 * hw;
+            const float* parp = sparse_per_frame ? W.parbin : par_b + (int64_t)i * 3 * hw;
             const int* pflags = par_skip ? W.parflags + (int64_t)i * ((w + 15) / 16) * ((h + 7) / 8) : nullptr;
             // the frame's partition word (launch_par_frame_any) gates the front halves on the device: fold-only kernel / branch kernel
             // (launch_conv3x3_wino); an I frame usually carries no record at all (its word is then 8: all quadrants zero)
@@ -928,7 +1084,7 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
             //  it has, in the flags and in the kernels alike)
             const int* pany = (par_skip && wopt >= 1) ? W.parany + i : nullptr;
             const int u = uidx[i];
-            float* slot = W.slots + (int64_t)i * fm;
+            float* slot = W.slots + (int64_t)out * fm;
             // fp16 mirrors: the input conv writes x16 next to x when it runs on the fp16 kernels at all (an RGB-only one does not)
             const void* x16 = (chain16 && in.nsrc > 1) ? W.x16 : nullptr;
             int r = conv(in.bias(flat + B.in_bias).act(2).units(wino_units(h, w)).to(W.tmp0).also16(const_cast<void*>(x16)));
@@ -952,7 +1108,7 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
             for (int k = 0; k < c.num_blocks; ++k) {
                 const BlockPk& K = B.blocks[k];
                 float* dst = (k == c.num_blocks - 1) ? slot : W.tmp0;
-                void* dst16 = !mirrors ? nullptr : (k == c.num_blocks - 1) ? (void*)(W.slots16 + (int64_t)i * fm)
+                void* dst16 = !mirrors ? nullptr : (k == c.num_blocks - 1) ? (void*)(W.slots16 + (int64_t)out * fm)
                                                                                  : (chain16 ? (void*)W.x16 : nullptr);
                 const bool woqp = c.blocktype == 1;      // conv2 a plain conv as well: no expert mix, no gain (sr_backbone_utils.py:366-384)
                 const float* w2 = woqp ? packed + K.conv2_img : W.mixw + ((int64_t)u * g->ndyn + K.dyn_conv2) * IMG_WIDE;
@@ -992,56 +1148,46 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
         // the neighbouring / own slots
         const void* kw16 = mirrors ? (const void*)W.kw : nullptr;
         auto s16of = [&](int i) -> const void* { return mirrors ? (const void*)(W.slots16 + (int64_t)i * fm) : nullptr; };
-        // ---- backward sweep (iconvsr_ipb_par.py:71-100)
-        for (int i = t - 1; i >= 0; --i) {
-            const BranchPk& B = g->br[0];
+        // ---- backward sweep (iconvsr_ipb_par.py:71-100), forward sweep + heads (:103-147); bounded: with recomputed segments
+        std::vector<Step> steps;
+        int recomputed = 0;
+        if (!make_schedule(g, t, key, steps, &recomputed)) return PNP_ERR_BAD_ARG;
+        auto slot_of = [&](int s) { return W.slots + (int64_t)s * fm; };
+        auto wi = [&](int64_t off) -> const float* { return wino_on ? packed + off : nullptr; };
+        for (const Step& sp : steps) {
+            const int i = sp.frame;
+            const BranchPk& B = g->br[sp.sweep];
             ConvCall in(h, w, cfg_lr);
-            auto wi = [&](int64_t off) -> const float* { return wino_on ? packed + off : nullptr; };
             in.source(W.lr4 + (int64_t)i * hw * 4, 4, packed + B.in_lr, wi(B.in_lr_wino));
-            if (i < t - 1) {
-                int k = i + 1;
-                while (!key[k]) ++k;
-                rc = align(W.slots + (int64_t)k * fm, mv_b + ((int64_t)i * 4 + 2) * hw, mv_b + ((int64_t)i * 4 + 3) * hw);
+            if (sp.key >= 0) {      // backward: the nearest key frame after i (flow planes 2, 3); forward: before i (planes 0, 1)
+                const int fp = sp.sweep == 0 ? 2 : 0;
+                rc = align(slot_of(sp.key), mv_b + ((int64_t)i * 4 + fp) * hw, mv_b + ((int64_t)i * 4 + fp + 1) * hw);
                 if (rc) return rc;
-                if (c.with_cat && c.align_key && k == i + 1) {     // neighbour == key frame: one source, summed weights
+                if (c.with_cat && c.align_key && sp.key_frame == (sp.sweep == 0 ? i + 1 : i - 1)) {     // neighbour == key frame: one source, summed weights
                     in.source(W.kw, 64, packed + B.in_wide01, wi(B.in_wide01_wino)).mirror16(kw16);
                 } else {
                     in.source(W.kw, 64, packed + B.in_wide[0], wi(B.in_wide_wino[0])).mirror16(kw16);
-                    if (c.with_cat) in.source(W.slots + (int64_t)(i + 1) * fm, 64, packed + B.in_wide[1], wi(B.in_wide_wino[1])).mirror16(s16of(i + 1));
+                    if (c.with_cat) in.source(slot_of(sp.nb), 64, packed + B.in_wide[1], wi(B.in_wide_wino[1])).mirror16(s16of(sp.nb));
                 }
             }
-            rc = run_branch(0, i, in);
-            if (rc) return rc;
-        }
-        // ---- forward sweep + heads (iconvsr_ipb_par.py:103-147)
-        for (int i = 0; i < t; ++i) {
-            const BranchPk& B = g->br[1];
-            ConvCall in(h, w, cfg_lr);
-            auto wi = [&](int64_t off) -> const float* { return wino_on ? packed + off : nullptr; };
-            in.source(W.lr4 + (int64_t)i * hw * 4, 4, packed + B.in_lr, wi(B.in_lr_wino));
-            if (i > 0) {
-                int k = i - 1;
-                while (!key[k]) --k;
-                rc = align(W.slots + (int64_t)k * fm, mv_b + ((int64_t)i * 4 + 0) * hw, mv_b + ((int64_t)i * 4 + 1) * hw);
+            if (sp.sweep == 1)      // backward feature of this frame
+                in.source(slot_of(sp.own), 64, packed + B.in_wide[B.n_wide - 1], wi(B.in_wide_wino[B.n_wide - 1])).mirror16(s16of(sp.own));
+            if (sparse_per_frame) {
+                rc = launch_par_sparse(par_in + (int64_t)i * 3 * hw, W.parbin, 1, h, w, st);
+                g->prof_last = nullptr;           // an untimed launch sits between two timed ones
                 if (rc) return rc;
-                if (c.with_cat && c.align_key && k == i - 1) {
-                    in.source(W.kw, 64, packed + B.in_wide01, wi(B.in_wide01_wino)).mirror16(kw16);
-                } else {
-                    in.source(W.kw, 64, packed + B.in_wide[0], wi(B.in_wide_wino[0])).mirror16(kw16);
-                    if (c.with_cat) in.source(W.slots + (int64_t)(i - 1) * fm, 64, packed + B.in_wide[1], wi(B.in_wide_wino[1])).mirror16(s16of(i - 1));
-                }
             }
-            in.source(W.slots + (int64_t)i * fm, 64, packed + B.in_wide[B.n_wide - 1], wi(B.in_wide_wino[B.n_wide - 1])).mirror16(s16of(i));   // backward feature of this frame
-            rc = run_branch(1, i, in);
+            rc = run_branch(sp.sweep, i, sp.out, in);
             if (rc) return rc;
+            if (sp.sweep == 0) continue;
 
-            const float* feat = W.slots + (int64_t)i * fm;
+            const float* feat = slot_of(sp.out);
             const float* lr_i = lr_b + (int64_t)i * 3 * hw;
             float* out_i = out_b + (int64_t)i * 3 * hw * os * os;
             // conv_hr's output feeds only conv_last: an fp16 map on the fp16 path
             const int o16 = f16_maps ? 1 : 0, s16 = f16_maps ? 2 : 0;
             if (!c.vsr) {   // :144-146
-                rc = conv(ConvCall(h, w, cfg_lr).source(feat, 64, packed + g->hr_img).mirror16(s16of(i)).bias(flat + g->hr_bias)
+                rc = conv(ConvCall(h, w, cfg_lr).source(feat, 64, packed + g->hr_img).mirror16(s16of(sp.out)).bias(flat + g->hr_bias)
                               .wino(wino_on ? packed + g->hr_wino : nullptr).units(wino_units(h, w)).act(2).to(W.tmp1).f16_map(o16));
                 if (!rc)
                     rc = conv(ConvCall(h, w, CONV_CFG_RGB).source(W.tmp1, 64, packed + g->last_img).bias(packed + g->last_bias)
@@ -1086,6 +1232,8 @@ int pnp_generator_forward(const pnp_generator* g, const float* flat, const float
     // stay below 4 GiB (2160p, or 720p -> 2880p with vsr, still fit)
     if (pnp_addr32_bytes_per_lr_pixel(g->cfg.vsr, g->cfg.deform) * (int64_t)h * w >= (int64_t)1 << 32)
         return PNP_ERR_UNSUPPORTED;
+    int plan_r, plan_l;
+    if (bounded_mode(g, t) && !plan_pick(t, g->cfg.with_cat, g->max_resident, &plan_r, &plan_l)) return PNP_ERR_BAD_ARG;
     const int64_t ctx_bytes = carve(g, nullptr, t, h, w).bytes;
     if (workspace_bytes < ctx_bytes || (reinterpret_cast<uintptr_t>(workspace) & 255)) return PNP_ERR_WORKSPACE;
     const int64_t hw = (int64_t)h * w;

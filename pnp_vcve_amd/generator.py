@@ -139,6 +139,36 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
     def get_option(self, option):
         return int(_native.lib().pnp_generator_get_option(self._handle, int(option)))
 
+    # ---------------------------------------------------------------- bounded memory for long clips
+    @property
+    def max_resident_features(self):
+        """None (default): one 64-channel feature map per frame, as in the reference.  An int k bounds the frame feature maps the two
+        sweeps hold (pnp_generator_set_max_resident): the forward sweep then recomputes segments of the backward features from
+        checkpoints -- bit-identical output, a workspace of k maps instead of t, at the cost of the recomputed frames.  k >= t (or
+        None) runs the unbounded schedule; a k below min_resident_features(t) raises ValueError at forward time."""
+        k = int(_native.lib().pnp_generator_get_max_resident(self._handle))
+        return None if k == 0 else k
+
+    @max_resident_features.setter
+    def max_resident_features(self, value):
+        if value is not None and (isinstance(value, bool) or not isinstance(value, int) or value < 1):
+            raise ValueError(f'max_resident_features must be None or a positive int, got {value!r}')
+        _native.check(_native.lib().pnp_generator_set_max_resident(self._handle, 0 if value is None else int(value)),
+                      'pnp_generator_set_max_resident')
+        self._workspace = {}
+        self._graphs = {}
+
+    def min_resident_features(self, t):
+        """The smallest max_resident_features the bounded schedule accepts for a clip of t frames (pnp_generator_min_resident)."""
+        if int(t) < 1:
+            raise ValueError(f't must be >= 1, got {t!r}')
+        return int(_native.lib().pnp_generator_min_resident(self._handle, int(t)))
+
+    def _check_resident(self, t):
+        k = self.max_resident_features
+        if k is not None and k < t and k < self.min_resident_features(t):
+            raise ValueError(f'max_resident_features={k} is below the minimum {self.min_resident_features(t)} for a clip of {t} frames')
+
     # ---------------------------------------------------------------- parameters
     def _register(self, dotted, param):
         mod = self
@@ -233,7 +263,7 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
 
     def _get_workspace(self, n, t, h, w, device):
         ctx = self._contexts(n, h, w)
-        k = (ctx, t, h, w, str(device))
+        k = (ctx, t, h, w, str(device), self.max_resident_features)
         ws = self._workspace.get(k)
         if ws is None:
             nbytes = int(_native.lib().pnp_generator_workspace_bytes(self._handle, t, h, w)) * ctx
@@ -253,6 +283,7 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         assert h >= 64 and w >= 64, (
             f'The height and width of inputs should be at least 64, but got {h} and {w}.')
         dev = lrs.device
+        self._check_resident(t)
         with torch.cuda.device(dev):
             self._ensure_packed(dev)
             lrs_c = lrs.detach().float().contiguous()
@@ -321,7 +352,7 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
     def _forward_graphed(self, lrs_c, mvs_c, par_c, side, out_shape):
         n, t, _, h, w = lrs_c.shape
         dev = lrs_c.device
-        key = (n, t, h, w, str(dev), side.numpy().tobytes(), self._packed.data_ptr(), self._packed_floats)
+        key = (n, t, h, w, str(dev), side.numpy().tobytes(), self._packed.data_ptr(), self._packed_floats, self.max_resident_features)
         ent = self._graphs.get(key)
         if ent is None:
             ctx = self._contexts(n, h, w)

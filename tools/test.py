@@ -41,6 +41,9 @@ def parse_args():
     p.add_argument('--clips-in-flight', type=int, default=2, choices=[1, 2],
                    help='2 (default): two clips of equal shape go through the generator as one batch, interleaved on two streams '
                         '(+5 % at 720p, bit-identical, a second workspace); 1: strictly one clip per forward like the reference')
+    p.add_argument('--max-resident-features', type=int, default=None, metavar='K',
+                   help='bound the frame feature maps the generator holds to K (long clips: the backward features are recomputed '
+                        'from checkpoints, bit-identical output, a workspace of K maps instead of one per frame); default unbounded')
     p.add_argument('--local_rank', type=int, default=0)
     a = p.parse_args()
     if 'LOCAL_RANK' not in os.environ:
@@ -85,6 +88,8 @@ def main():
         wrap_fp16_model(model)
     elif precision is not None:
         model.precision = precision
+    if args.max_resident_features is not None:
+        model.generator.max_resident_features = args.max_resident_features
     if args.save_path is not None:      # PNG encode off the critical path (pnp_vcve_amd/io_async.py)
         from pnp_vcve_amd.io_async import FrameWriter
         model.frame_writer = FrameWriter(max_workers=4)
