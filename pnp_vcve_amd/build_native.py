@@ -13,7 +13,9 @@ from . import isa_hazards
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'lib', 'libpnpvcve_hip.so')
-SOURCES = ['conv_mfma.hip', 'conv_persist.hip', 'conv_wino.hip', 'conv_wino_ms.hip', 'conv_f16.hip', 'conv_f16x3.hip', 'conv_last.hip', 'warp.hip', 'prep.hip', 'metrics.hip', 'raster.hip', 'dcn.hip', 'generator.hip']
+SOURCES = ['conv_mfma.hip', 'conv_persist.hip', 'conv_wino.hip', 'conv_wino_ms.hip', 'conv_f16.hip', 'conv_f16x3.hip', 'conv_last.hip', 'warp.hip', 'prep.hip', 'metrics.hip', 'raster.hip', 'dcn.hip', 'generator.hip', 'ops_abi.hip']
+# units of host code only (the stand-alone op wrappers): no kernel, so no code object in the library
+HOST_ONLY = ['ops_abi.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall']
 # per-source extras.  Rounds 3-5 met a signature three times -- wrong values whenever hipcc packed fp32 arithmetic into v_pk_*_f32
 # (dcn.hip r03, conv_f16x3.hip r04, conv_wino.hip r05; tools/repro/*_hazard.py, profiles/r0[345]_*hazard*) -- and fenced it off per

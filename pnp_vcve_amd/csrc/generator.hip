@@ -21,16 +21,13 @@
 
 #include "../../include/pnpvcve.h"
 #include "../../include/pnpvcve_debug.h"
+#include "abi_shared.h"
 #include "conv_mfma.h"
 #include "prep.h"
 #include "warp.h"
 #include "dcn.h"
 
 namespace {
-
-constexpr int64_t IMG_WIDE = 9 * 4096;   // floats: 9 chunks, 64 output channels
-constexpr int64_t IMG_CHUNK = 4096;      // 1 chunk, 64 output channels
-constexpr int64_t IMG_RGB = 9 * 2048;    // conv_last: 9 chunks, 32 (3 valid) output channels
 
 struct ParamInfo {
     std::string name;
@@ -94,13 +91,13 @@ struct pnp_generator {
     int64_t last_valu = -1;                                                 // packed: conv_last weights [9][64][4]
     int64_t up_img[2] = {-1, -1}, up_bias[2] = {-1, -1};                    // packed
     // deform = 'basic' | 'fvc' (iconvsr_mv.py:21-84): flat offsets of the aligner's parameters, packed images
-    int64_t f_dcn_w = -1, f_dcn_b = -1, f_off0_w = -1, f_off0_b = -1, f_off2_w = -1, f_off2_b = -1;
+    int64_t f_dcn_b = -1, f_off0_b = -1, f_off2_b = -1;
     int64_t dcn_img = -1, off0_flow_img = -1, off0_feat_img = -1, off2_img = -1, off2_bias = -1;
     int64_t p_w1 = -1, p_b1 = -1, p_w2 = -1, p_b2 = -1, p_v1 = -1, p_v2 = -1;  // flat
-    // flat offsets needed by pack()
-    int64_t f_in_w[2] = {-1, -1}, f_hr_w = -1, f_last_w = -1, f_last_b = -1, f_up_w[2] = {-1, -1},
-            f_up_b[2] = {-1, -1};
-    std::vector<int64_t> f_conv1_w[2], f_conv2_w[2], f_1x1_w[2];   // per block (1x1: 3 consecutive entries; conv2: 'drt_woqp' only)
+    // what pack() makes: every packed weight image with its flat tensor (build_layout), and the flat offsets of the few tensors
+    // it copies by hand
+    std::vector<WeightImage> images;
+    int64_t f_last_w = -1, f_last_b = -1, f_up_b[2] = {-1, -1};
 
     int64_t add_param(const std::string& name, std::vector<int64_t> shape) {
         ParamInfo p;
@@ -164,7 +161,14 @@ int build_layout(pnp_generator* g) {
             g->add_param(p + "conv2.bias", {E, 64});
             if (!c.one_layer) g->add_param(p + "conv1.bias", {E, 64});
         }
-    // 2) everything else
+    // 2) everything else.  A parameter that has packed images is recorded in g->images with how each one is made, here and nowhere
+    // else: pnp_generator_pack replays the records.
+    auto image = [&](int64_t src, int64_t dst, int cin_total, int ktaps, int kind, int cbase, int ntb = 2, int n_valid = 64) -> WeightImage& {
+        g->images.push_back(WeightImage{src, dst, cin_total, ktaps, kind, cbase, ntb, n_valid});
+        return g->images.back();
+    };
+    // grouped convs (num_group > 1) are packed as the dense conv they equal: zeros outside the diagonal blocks
+    const int gcin = c.num_group > 1 ? gc : 0;
     g->p_w1 = g->add_param("BasePredictor.BaseNet.0.weight", {64, 1});
     g->p_b1 = g->add_param("BasePredictor.BaseNet.0.bias", {64});
     g->p_w2 = g->add_param("BasePredictor.BaseNet.2.weight", {E, 64});
@@ -186,77 +190,108 @@ int build_layout(pnp_generator* g) {
         BranchPk& B = g->br[b];
         B.n_wide = (b == 0) ? (c.with_cat ? 2 : 1) : (c.with_cat ? 3 : 2);
         const int cin = 3 + 64 * B.n_wide;
-        g->f_in_w[b] = g->add_param(std::string(brn[b]) + ".input_conv.0.weight", {64, cin, 3, 3});
+        const int64_t in_w = g->add_param(std::string(brn[b]) + ".input_conv.0.weight", {64, cin, 3, 3});
         B.in_bias = g->add_param(std::string(brn[b]) + ".input_conv.0.bias", {64});
         B.in_lr = g->add_packed(IMG_CHUNK);
-        for (int s = 0; s < B.n_wide; ++s) B.in_wide[s] = g->add_packed(IMG_WIDE);
-        if (c.with_cat && c.align_key) B.in_wide01 = g->add_packed(IMG_WIDE);
-        g->f_conv1_w[b].assign(nb, -1);
-        g->f_conv2_w[b].assign(nb, -1);
-        g->f_1x1_w[b].assign(nb * 3, -1);
+        image(in_w, B.in_lr, cin, 9, PACK_RGB4, 0);
+        for (int s = 0; s < B.n_wide; ++s) {
+            B.in_wide[s] = g->add_packed(IMG_WIDE);
+            image(in_w, B.in_wide[s], cin, 9, PACK_WIDE, 3 + 64 * s);
+        }
+        if (c.with_cat && c.align_key) {
+            B.in_wide01 = g->add_packed(IMG_WIDE);
+            image(in_w, B.in_wide01, cin, 9, PACK_WIDE, 3).sum01 = true;
+        }
         for (int i = 0; i < nb; ++i) {
             const std::string p = std::string(brn[b]) + ".main." + std::to_string(i) + ".";
+            BlockPk& K = B.blocks[i];
             if (c.one_layer) {
-                g->f_conv1_w[b][i] = g->add_param(p + "conv1.weight", {64, gc, 3, 3});
-                B.blocks[i].conv1_bias = g->add_param(p + "conv1.bias", {64});
-                B.blocks[i].conv1_img = g->add_packed(IMG_WIDE);
+                const int64_t w1 = g->add_param(p + "conv1.weight", {64, gc, 3, 3});
+                K.conv1_bias = g->add_param(p + "conv1.bias", {64});
+                K.conv1_img = g->add_packed(IMG_WIDE);
+                image(w1, K.conv1_img, 64, 9, PACK_WIDE, 0).group_cin = gcin;
             }
             if (woqp) {
-                g->f_conv2_w[b][i] = g->add_param(p + "conv2.weight", {64, gc, 3, 3});
-                B.blocks[i].conv2_bias = g->add_param(p + "conv2.bias", {64});
-                B.blocks[i].conv2_img = g->add_packed(IMG_WIDE);
+                const int64_t w2 = g->add_param(p + "conv2.weight", {64, gc, 3, 3});
+                K.conv2_bias = g->add_param(p + "conv2.bias", {64});
+                K.conv2_img = g->add_packed(IMG_WIDE);
+                image(w2, K.conv2_img, 64, 9, PACK_WIDE, 0).group_cin = gcin;
             }
             static const char* k1[3] = {"conv16x16", "conv16x8", "conv8x8"};
-            for (int j = 0; j < 3; ++j) g->f_1x1_w[b][i * 3 + j] = g->add_param(p + k1[j] + ".weight", {64, gc, 1, 1});
-            B.blocks[i].w1x1 = g->add_packed(6 * IMG_CHUNK);      // conv16x16 / conv16x8 / conv8x8, then the same three x PNP_PAR_UNIT
+            int64_t w1x1[3];
+            for (int j = 0; j < 3; ++j) w1x1[j] = g->add_param(p + k1[j] + ".weight", {64, gc, 1, 1});
+            K.w1x1 = g->add_packed(6 * IMG_CHUNK);      // conv16x16 / conv16x8 / conv8x8, then the same three x PNP_PAR_UNIT
+            for (int j = 0; j < 6; ++j) {
+                WeightImage& r = image(w1x1[j % 3], K.w1x1 + j * IMG_CHUNK, 64, 1, PACK_1X1, 0);
+                r.group_cin = gcin;
+                if (j >= 3) r.scale = PNP_PAR_UNIT;
+            }
         }
     }
     if (c.deform != 0) {
-        g->f_dcn_w = g->add_param("deform_align.weight", {64, 64, 3, 3});
+        const int64_t dcn_w = g->add_param("deform_align.weight", {64, 64, 3, 3});
         g->f_dcn_b = g->add_param("deform_align.bias", {64});
-        g->f_off0_w = g->add_param("deform_align.conv_offset.0.weight", {64, 66, 3, 3});
+        const int64_t off0_w = g->add_param("deform_align.conv_offset.0.weight", {64, 66, 3, 3});
         g->f_off0_b = g->add_param("deform_align.conv_offset.0.bias", {64});
-        g->f_off2_w = g->add_param("deform_align.conv_offset.2.weight", {432, 64, 3, 3});
+        const int64_t off2_w = g->add_param("deform_align.conv_offset.2.weight", {432, 64, 3, 3});
         g->f_off2_b = g->add_param("deform_align.conv_offset.2.bias", {432});
         g->dcn_img = g->add_packed(IMG_WIDE);
         g->off0_flow_img = g->add_packed(IMG_CHUNK);
         g->off0_feat_img = g->add_packed(IMG_WIDE);
         g->off2_img = g->add_packed(7 * IMG_WIDE);
         g->off2_bias = g->add_packed(448);
+        image(dcn_w, g->dcn_img, 64, 9, PACK_WIDE, 0);
+        // conv_offset[0] over cat([ref, flow]) (iconvsr_mv.py:33,70): the 2 flow channels are concat channels 64,65
+        image(off0_w, g->off0_flow_img, 66, 9, PACK_RGB4, 64).cvalid = 2;
+        image(off0_w, g->off0_feat_img, 66, 9, PACK_WIDE, 0);
+        WeightImage& po = image(off2_w, g->off2_img, 64, 9, PACK_WIDE, 0);
+        po.co_mode = 1;            // 7 blocks of 64 permuted output channels (432 valid)
+        po.grid_y = 7;
+        po.dst_ystride = IMG_WIDE;
     }
     g->ones2 = g->add_packed(64);
-    g->f_hr_w = g->add_param("conv_hr.weight", {64, 64, 3, 3});
+    const int64_t hr_w = g->add_param("conv_hr.weight", {64, 64, 3, 3});
     g->hr_bias = g->add_param("conv_hr.bias", {64});
     g->hr_img = g->add_packed(IMG_WIDE);
+    image(hr_w, g->hr_img, 64, 9, PACK_WIDE, 0);
     g->f_last_w = g->add_param("conv_last.weight", {3, 64, 3, 3});
     g->f_last_b = g->add_param("conv_last.bias", {3});
     g->last_img = g->add_packed(IMG_RGB);
+    image(g->f_last_w, g->last_img, 64, 9, PACK_WIDE, 0, 1, 3);
     g->last_bias = g->add_packed(32);
     g->last_valu = g->add_packed(9 * 64 * 4);
     if (c.vsr) {
         for (int u = 0; u < 2; ++u) {
             const std::string p = "upsample" + std::to_string(u + 1) + ".upsample_conv.";
-            g->f_up_w[u] = g->add_param(p + "weight", {256, 64, 3, 3});
+            const int64_t up_w = g->add_param(p + "weight", {256, 64, 3, 3});
             g->f_up_b[u] = g->add_param(p + "bias", {256});
             g->up_img[u] = g->add_packed(4 * IMG_WIDE);
             g->up_bias[u] = g->add_packed(256);
+            WeightImage sub[4];
+            pixel_shuffle_images(up_w, g->up_img[u], sub);
+            g->images.insert(g->images.end(), sub, sub + 4);
         }
     }
     // Winograd images of the static 64 -> 64 convs and of the 1x1 branches (PNP_OPT_WINOGRAD; conv_wino.hip).  Appended last: no
     // earlier offset moves.  The dynamic convs get theirs per frame in the workspace (their channel gain is folded in).
+    auto wino_of = [&](int64_t img) {      // reserves the Winograd image of the 64 -> 64 image at packed offset img, in its record too
+        for (WeightImage& r : g->images)
+            if (r.dst == img) return r.wino = g->add_packed(PNP_WINO_IMG_FLOATS);
+        return int64_t(-1);
+    };
     for (int b = 0; b < 2; ++b) {
         BranchPk& B = g->br[b];
         B.in_lr_wino = g->add_packed(PNP_WINO_RGB_FLOATS);
-        for (int s = 0; s < B.n_wide; ++s) B.in_wide_wino[s] = g->add_packed(PNP_WINO_IMG_FLOATS);
-        if (B.in_wide01 >= 0) B.in_wide01_wino = g->add_packed(PNP_WINO_IMG_FLOATS);
+        for (int s = 0; s < B.n_wide; ++s) B.in_wide_wino[s] = wino_of(B.in_wide[s]);
+        if (B.in_wide01 >= 0) B.in_wide01_wino = wino_of(B.in_wide01);
     }
     for (int b = 0; b < 2; ++b)
         for (auto& K : g->br[b].blocks) {
-            if (K.conv1_img >= 0) K.conv1_wino = g->add_packed(PNP_WINO_IMG_FLOATS);
-            if (K.conv2_img >= 0) K.conv2_wino = g->add_packed(PNP_WINO_IMG_FLOATS);
+            if (K.conv1_img >= 0) K.conv1_wino = wino_of(K.conv1_img);
+            if (K.conv2_img >= 0) K.conv2_wino = wino_of(K.conv2_img);
             K.w1x1_wino = g->add_packed(PNP_WINO_PAR_FLOATS);
         }
-    g->hr_wino = g->add_packed(PNP_WINO_IMG_FLOATS);
+    g->hr_wino = wino_of(g->hr_img);
     return PNP_OK;
 }
 
@@ -276,28 +311,6 @@ __global__ void small_copy_kernel(const float* __restrict__ src, float* __restri
         const int r = pnp_dcn_ref_channel_impl(i);
         dst[i] = r >= 0 ? src[r] : 0.f;
     }
-}
-
-PackArgs plain_pack(const float* w, int cin_total, int ktaps, int kind, int cbase, int ntb, int n_valid, float* dst) {
-    PackArgs a;
-    memset(&a, 0, sizeof(a));
-    a.w = w;
-    a.ew = nullptr;
-    a.E = 1;
-    a.e_stride = 0;
-    a.cin_total = cin_total;
-    a.ktaps = ktaps;
-    a.co_mul = 1;
-    a.co_add = 0;
-    a.n_valid = n_valid;
-    a.co_mode = 0;
-    a.cvalid = 3;
-    a.kind = kind;
-    a.cbase = cbase;
-    a.ntb = ntb;
-    a.scale = 1.f;
-    a.dst = dst;
-    return a;
 }
 
 struct ProfScope {
@@ -417,9 +430,6 @@ int64_t pnp_addr32_bytes_per_lr_pixel(int vsr, int deform) {
     if (deform != 0 && b < 1792) b = 1792;
     return b;
 }
-
-// op-level entry points: the conv kernels address an NHWC64 fp32 map with 32-bit byte offsets
-bool op_map_fits(int h, int w) { return h >= 1 && w >= 1 && (int64_t)h * w * 256 < ((int64_t)1 << 32); }
 
 // ---- bounded-memory schedule (pnp_generator_set_max_resident)
 // With a bound k on the 64-channel frame maps held across branch runs (0 < k < t), the backward sweep runs once as a checkpoint
@@ -599,6 +609,19 @@ Workspace carve(const pnp_generator* g, char* base, int t, int h, int w) {
 
 }  // namespace
 
+int launch_fill(float* dst, float v, int n, hipStream_t stream) {
+    if (n < 0 || n > 64) return PNP_ERR_BAD_ARG;
+    hipLaunchKernelGGL(fill_kernel, dim3(1), dim3(64), 0, stream, dst, v, n);
+    return (int)hipGetLastError();
+}
+
+int launch_small_copy(const float* src, float* dst, int n_valid, int n_total, int mode, hipStream_t stream) {
+    if (n_total < 1 || mode < PNP_COPY_PAD || mode > PNP_COPY_DCN_CHANNELS) return PNP_ERR_BAD_ARG;
+    const int threads = n_total < 256 ? 64 : 256;
+    hipLaunchKernelGGL(small_copy_kernel, dim3((n_total + threads - 1) / threads), dim3(threads), 0, stream, src, dst, n_valid, n_total, mode);
+    return (int)hipGetLastError();
+}
+
 extern "C" {
 
 int pnp_abi_version(void) { return 5; }
@@ -665,109 +688,41 @@ int pnp_generator_pack(const pnp_generator* g, const float* flat, float* packed,
         const hipError_t e = hipMemsetAsync(packed, 0, (size_t)g->packed_floats * sizeof(float), st);
         if (e != hipSuccess) return (int)e;
     }
-    for (int b = 0; b < 2; ++b) {
-        const BranchPk& B = g->br[b];
-        const int cin = 3 + 64 * B.n_wide;
-        rc = launch_pack_weights(plain_pack(flat + g->f_in_w[b], cin, 9, PACK_RGB4, 0, 2, 64, packed + B.in_lr), 1, st);
+    for (const WeightImage& r : g->images) {
+        if (r.sum01) {       // the two "expert" weights (1, 1) its mixture reads
+            rc = launch_fill(packed + g->ones2, 1.0f, 2, st);
+            if (rc) return rc;
+        }
+        rc = pack_weight_image(r, flat, packed, packed + g->ones2, st);
         if (rc) return rc;
-        for (int s = 0; s < B.n_wide; ++s) {
-            rc = launch_pack_weights(
-                plain_pack(flat + g->f_in_w[b], cin, 9, PACK_WIDE, 3 + 64 * s, 2, 64, packed + B.in_wide[s]), 1, st);
-            if (rc) return rc;
-        }
-        if (B.in_wide01 >= 0) {       // the "expert" mechanism with weights (1, 1) over the two 64-channel input ranges
-            hipLaunchKernelGGL(fill_kernel, dim3(1), dim3(64), 0, st, packed + g->ones2, 1.0f, 2);
-            PackArgs a = plain_pack(flat + g->f_in_w[b], cin, 9, PACK_WIDE, 3, 2, 64, packed + B.in_wide01);
-            a.ew = packed + g->ones2;
-            a.E = 2;
-            a.e_stride = 64 * 9;
-            rc = launch_pack_weights(a, 1, st);
-            if (rc) return rc;
-        }
-        for (int i = 0; i < c.num_blocks; ++i) {
-            const BlockPk& K = B.blocks[i];
-            // grouped convs (num_group > 1) are packed as the dense conv they equal: zeros outside the diagonal blocks
-            const int gcin = c.num_group > 1 ? 64 / c.num_group : 0;
-            if (c.one_layer) {
-                PackArgs p1 = plain_pack(flat + g->f_conv1_w[b][i], 64, 9, PACK_WIDE, 0, 2, 64, packed + K.conv1_img);
-                p1.group_cin = gcin;
-                rc = launch_pack_weights(p1, 1, st);
-                if (rc) return rc;
-            }
-            if (c.blocktype == 1) {
-                PackArgs p2 = plain_pack(flat + g->f_conv2_w[b][i], 64, 9, PACK_WIDE, 0, 2, 64, packed + K.conv2_img);
-                p2.group_cin = gcin;
-                rc = launch_pack_weights(p2, 1, st);
-                if (rc) return rc;
-            }
-            for (int j = 0; j < 6; ++j) {
-                PackArgs pa = plain_pack(flat + g->f_1x1_w[b][i * 3 + j % 3], 64, 1, PACK_1X1, 0, 2, 64, packed + K.w1x1 + j * IMG_CHUNK);
-                pa.group_cin = gcin;
-                if (j >= 3) pa.scale = PNP_PAR_UNIT;
-                rc = launch_pack_weights(pa, 1, st);
-                if (rc) return rc;
-            }
-        }
     }
+    // what is not a weight image made by launch_pack_weights: three small bias copies and conv_last's vector-ALU layout
     if (c.deform != 0) {
-        rc = launch_pack_weights(plain_pack(flat + g->f_dcn_w, 64, 9, PACK_WIDE, 0, 2, 64, packed + g->dcn_img), 1, st);
+        rc = launch_small_copy(flat + g->f_off2_b, packed + g->off2_bias, 432, 448, PNP_COPY_DCN_CHANNELS, st);
         if (rc) return rc;
-        // conv_offset[0] over cat([ref, flow]) (iconvsr_mv.py:33,70): the 2 flow channels are concat channels 64,65
-        PackArgs pf = plain_pack(flat + g->f_off0_w, 66, 9, PACK_RGB4, 64, 2, 64, packed + g->off0_flow_img);
-        pf.cvalid = 2;
-        rc = launch_pack_weights(pf, 1, st);
-        if (rc) return rc;
-        rc = launch_pack_weights(plain_pack(flat + g->f_off0_w, 66, 9, PACK_WIDE, 0, 2, 64, packed + g->off0_feat_img), 1, st);
-        if (rc) return rc;
-        PackArgs po = plain_pack(flat + g->f_off2_w, 64, 9, PACK_WIDE, 0, 2, 64, packed + g->off2_img);
-        po.co_mode = 1;            // 7 blocks of 64 permuted output channels (432 valid)
-        po.w_ystride = 0;
-        po.dst_ystride = IMG_WIDE;
-        rc = launch_pack_weights(po, 7, st);
-        if (rc) return rc;
-        hipLaunchKernelGGL(small_copy_kernel, dim3(2), dim3(256), 0, st, flat + g->f_off2_b, packed + g->off2_bias, 432,
-                           448, 2);
     }
-    rc = launch_pack_weights(plain_pack(flat + g->f_hr_w, 64, 9, PACK_WIDE, 0, 2, 64, packed + g->hr_img), 1, st);
+    rc = launch_small_copy(flat + g->f_last_b, packed + g->last_bias, 3, 32, PNP_COPY_PAD, st);
     if (rc) return rc;
-    rc = launch_pack_weights(plain_pack(flat + g->f_last_w, 64, 9, PACK_WIDE, 0, 1, 3, packed + g->last_img), 1, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(small_copy_kernel, dim3(1), dim3(64), 0, st, flat + g->f_last_b, packed + g->last_bias, 3, 32, 0);
     rc = launch_pack_last_valu(flat + g->f_last_w, packed + g->last_valu, st);
     if (rc) return rc;
-    if (c.vsr) {
-        for (int u = 0; u < 2; ++u) {
-            for (int sub = 0; sub < 4; ++sub) {
-                PackArgs a = plain_pack(flat + g->f_up_w[u], 64, 9, PACK_WIDE, 0, 2, 64,
-                                        packed + g->up_img[u] + sub * IMG_WIDE);
-                a.co_mul = 4;      // F.pixel_shuffle(2): conv channel c*4 + (dy*2+dx) -> pixel (2y+dy, 2x+dx), channel c
-                a.co_add = sub;
-                rc = launch_pack_weights(a, 1, st);
-                if (rc) return rc;
-            }
-            hipLaunchKernelGGL(small_copy_kernel, dim3(1), dim3(256), 0, st, flat + g->f_up_b[u],
-                               packed + g->up_bias[u], 256, 256, 1);
-        }
+    for (int u = 0; c.vsr && u < 2; ++u) {
+        rc = launch_small_copy(flat + g->f_up_b[u], packed + g->up_bias[u], 256, 256, PNP_COPY_PIXEL_SHUFFLE_BIAS, st);
+        if (rc) return rc;
     }
     if (g->prec == PNP_PREC_F32) {   // Winograd images (only the fp32 path has a Winograd kernel)
-        std::vector<const float*> ws;
-        std::vector<float*> wd;
         for (int b = 0; b < 2; ++b) {
             const BranchPk& B = g->br[b];
             rc = launch_wino_rgb_image(packed + B.in_lr, packed + B.in_lr_wino, st);
             if (rc) return rc;
-            for (int s = 0; s < B.n_wide; ++s) { ws.push_back(packed + B.in_wide[s]); wd.push_back(packed + B.in_wide_wino[s]); }
-            if (B.in_wide01 >= 0) { ws.push_back(packed + B.in_wide01); wd.push_back(packed + B.in_wide01_wino); }
-        }
-        for (int b = 0; b < 2; ++b)
-            for (const auto& K : g->br[b].blocks) {
-                if (K.conv1_wino >= 0) { ws.push_back(packed + K.conv1_img); wd.push_back(packed + K.conv1_wino); }
-                if (K.conv2_wino >= 0) { ws.push_back(packed + K.conv2_img); wd.push_back(packed + K.conv2_wino); }
+            for (const BlockPk& K : B.blocks) {
                 rc = launch_wino_par_image(packed + K.w1x1, packed + K.w1x1_wino, st);
                 if (rc) return rc;
             }
-        ws.push_back(packed + g->hr_img);
-        wd.push_back(packed + g->hr_wino);
+        }
+        std::vector<const float*> ws;
+        std::vector<float*> wd;
+        for (const WeightImage& r : g->images)
+            if (r.wino >= 0) { ws.push_back(packed + r.dst); wd.push_back(packed + r.wino); }
         for (size_t i = 0; i < ws.size(); i += 16) {
             const int n = (int)(ws.size() - i < 16 ? ws.size() - i : 16);
             rc = launch_wino_images(ws.data() + i, wd.data() + i, n, nullptr, st);
@@ -959,7 +914,8 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
             // the last block of every launch leaves the queue zeroed; once per clip for a fresh workspace or a launch that was cut short.
             // A KERNEL, not hipMemsetAsync: as a memset node of a captured graph (generator.use_graphs) the 64 bytes came back as
             // pointer-like garbage from the second replay on (ROCm 7.2; tools/repro/graph_memset_node.py), i.e. endless ticket loops
-            hipLaunchKernelGGL(fill_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<float*>(W.queue), 0.0f, 16);
+            rc = launch_fill(reinterpret_cast<float*>(W.queue), 0.0f, 16, st);
+            if (rc) return rc;
         }
         rc = launch_pack_lr(lr_b, W.lr4, t, h, w, st);
         if (rc) return rc;
@@ -1027,25 +983,11 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
                 u = (int)ufirst.size();
                 ufirst.push_back(i);
                 const int gcm = 64 / c.num_group;
-                PackArgs a;
-                memset(&a, 0, sizeof(a));
-                a.w = flat + g->dyn_w;
+                PackArgs a = plain_pack(flat + g->dyn_w, 64, 9, PACK_WIDE, 0, 2, 64, W.mixw + (int64_t)u * g->ndyn * IMG_WIDE);
                 a.ew = W.ew + (int64_t)i * E;
                 a.E = E;
                 a.e_stride = 64 * gcm * 9;
-                a.cin_total = 64;
                 a.group_cin = c.num_group > 1 ? gcm : 0;
-                a.ktaps = 9;
-                a.co_mul = 1;
-                a.co_add = 0;
-                a.n_valid = 64;
-                a.co_mode = 0;
-                a.cvalid = 3;
-                a.kind = PACK_WIDE;
-                a.cbase = 0;
-                a.ntb = 2;
-                a.scale = 1.f;
-                a.dst = W.mixw + (int64_t)u * g->ndyn * IMG_WIDE;
                 a.w_ystride = (int64_t)E * 64 * gcm * 9;
                 a.dst_ystride = IMG_WIDE;
                 rc = launch_pack_weights(a, g->ndyn, st);
@@ -1309,474 +1251,6 @@ int pnp_generator_profile_read(pnp_generator* g, int kind, double* total_ms, int
     *launches = n;
     *work = wk;
     return PNP_OK;
-}
-
-// ------------------------------------------------------------------ single ops
-
-int pnp_flow_warp_nchw_f32(const float* x, const float* flow, float* out, int n, int c, int h, int w, void* st) {
-    if (n < 1 || c < 1 || h < 1 || w < 1) return PNP_ERR_BAD_ARG;
-    return launch_flow_warp_nchw(x, flow, out, n, c, h, w, (hipStream_t)st);
-}
-
-int pnp_flow_warp_nchw_mode_f32(const float* x, const float* flow, float* out, int n, int c, int h, int w, int mode, void* st) {
-    if (n < 1 || c < 1 || h < 1 || w < 1 || mode < 0 || mode > 1) return PNP_ERR_BAD_ARG;
-    return launch_flow_warp_nchw(x, flow, out, n, c, h, w, (hipStream_t)st, mode == 1);
-}
-
-int pnp_mv_warp_nhwc_mode_f32(const float* feat, const float* fx, const float* fy, float* out, int h, int w, int c, int mode,
-                              void* st) {
-    if (h < 1 || w < 1 || c < 4 || mode < 0 || mode > 1) return PNP_ERR_BAD_ARG;
-    return launch_mv_warp_nhwc(feat, fx, fy, out, h, w, c, (hipStream_t)st, false, mode == 1);
-}
-
-int pnp_mv_warp_nhwc_f32(const float* feat, const float* fx, const float* fy, float* out, int h, int w, int c,
-                         void* st) {
-    return launch_mv_warp_nhwc(feat, fx, fy, out, h, w, c, (hipStream_t)st);
-}
-
-int pnp_nchw_to_nhwc_f32(const float* in, float* out, int n, int c, int h, int w, void* st) {
-    return launch_nchw_to_nhwc(in, out, n, c, h, w, (hipStream_t)st);
-}
-
-int pnp_nhwc_to_nchw_f32(const float* in, float* out, int n, int c, int h, int w, void* st) {
-    return launch_nhwc_to_nchw(in, out, n, c, h, w, (hipStream_t)st);
-}
-
-int pnp_caa_predict_f32(const float* q_ew, const float* q_g, int count, int E, int softmax, const float* w1,
-                        const float* b1, const float* w2, const float* b2, const float* v1, const float* v2,
-                        float* ew, float* gamma, void* st) {
-    for (int t0 = 0; t0 < count; t0 += 32) {
-        CaaArgs a;
-        memset(&a, 0, sizeof(a));
-        a.count = (count - t0 < 32) ? count - t0 : 32;
-        for (int i = 0; i < a.count; ++i) {
-            a.q_ew[i] = q_ew[t0 + i];
-            a.q_g[i] = q_g[t0 + i];
-        }
-        a.t0 = t0;
-        a.E = E;
-        a.softmax = softmax;
-        a.with_se = (v1 && v2) ? 1 : 0;
-        a.w1 = w1;
-        a.b1 = b1;
-        a.w2 = w2;
-        a.b2 = b2;
-        a.v1 = v1;
-        a.v2 = v2;
-        a.ew = ew;
-        a.gamma = gamma;
-        const int rc = launch_caa_predict(a, (hipStream_t)st);
-        if (rc) return rc;
-    }
-    return PNP_OK;
-}
-
-int pnp_dcn_nhwc_f32(const float* x, const float* om, const float* fx, const float* fy, const float* w_packed,
-                     const float* bias, float* out, int h, int w, void* st) {
-    return pnp_dcn_nhwc_f32_ex(x, om, fx, fy, w_packed, bias, out, h, w, nullptr, st);
-}
-
-int pnp_dcn_f16_image_from_f32(const float* w_packed, void* dst, void* st) {
-    if (!w_packed || !dst) return PNP_ERR_BAD_ARG;
-    return launch_dcn_f16_image(w_packed, dst, (hipStream_t)st);
-}
-
-int pnp_dcn_nhwc_f16(const float* x, const float* om, const float* fx, const float* fy, const void* w_f16,
-                     const float* bias, float* out, int h, int w, void* st) {
-    if (h < 1 || w < 1 || !w_f16) return PNP_ERR_BAD_ARG;
-    DcnArgs d;
-    d.dbg = nullptr;
-    d.x = x;
-    d.om = om;
-    d.fx = fx;
-    d.fy = fy;
-    d.w = nullptr;
-    d.w16 = w_f16;
-    d.bias = bias;
-    d.out = out;
-    d.H = h;
-    d.W = w;
-    return launch_dcn(d, (hipStream_t)st);
-}
-
-int pnp_dcn_nhwc_f32_ex(const float* x, const float* om, const float* fx, const float* fy, const float* w_packed,
-                        const float* bias, float* out, int h, int w, void* trace, void* st) {
-    if (h < 1 || w < 1) return PNP_ERR_BAD_ARG;
-    DcnArgs d;
-    d.w16 = nullptr;
-    d.dbg = (unsigned long long*)trace;
-    d.x = x;
-    d.om = om;
-    d.fx = fx;
-    d.fy = fy;
-    d.w = w_packed;
-    d.bias = bias;
-    d.out = out;
-    d.H = h;
-    d.W = w;
-    return launch_dcn(d, (hipStream_t)st);
-}
-
-int pnp_dcn_ref_channel(int packed_channel) { return pnp_dcn_ref_channel_impl(packed_channel); }
-
-int pnp_dcn_trace_u64s(void) { return dcn_trace_u64s(); }
-
-int64_t pnp_packed_conv_floats(int csrc) { return csrc == 64 ? IMG_WIDE : IMG_CHUNK; }
-
-int pnp_pack_conv3x3_f32(const float* w, const float* ew, int E, int cout, int cin_total, int cbase, int csrc,
-                         float* dst, void* st) {
-    if (cout > 64 || (csrc != 64 && csrc != 3) || E < 1) return PNP_ERR_BAD_ARG;
-    PackArgs a = plain_pack(w, cin_total, 9, csrc == 64 ? PACK_WIDE : PACK_RGB4, cbase, 2, cout, dst);
-    a.E = E;
-    a.ew = ew;
-    a.e_stride = (long)cout * cin_total * 9;
-    if (E > 1 && !ew) return PNP_ERR_BAD_ARG;
-    return launch_pack_weights(a, 1, (hipStream_t)st);
-}
-
-int pnp_pack_conv1x1_f32(const float* w, float* dst, void* st) {
-    return launch_pack_weights(plain_pack(w, 64, 1, PACK_1X1, 0, 2, 64, dst), 1, (hipStream_t)st);
-}
-
-int64_t pnp_wino_image_floats(void) { return PNP_WINO_IMG_FLOATS; }
-int64_t pnp_wino_par_image_floats(void) { return PNP_WINO_PAR_FLOATS; }
-
-int64_t pnp_wino_rgb_image_floats(void) { return PNP_WINO_RGB_FLOATS; }
-
-int pnp_wino_rgb_image_from_packed_f32(const float* packed_rgb_chunk, float* dst, void* st) {
-    return launch_wino_rgb_image(packed_rgb_chunk, dst, (hipStream_t)st);
-}
-
-static int wino_ms_op(int nsrc, const float* const* srcs, const float* const* wino_w, const float* bias, int act, float* out,
-                      int h, int w, int units, void* st);
-
-int pnp_conv3x3_wino_ms_f32(int nsrc, const float* const* srcs, const float* const* wino_w, const float* bias, int act, float* out,
-                            int h, int w, void* st) {
-    return wino_ms_op(nsrc, srcs, wino_w, bias, act, out, h, w, 0, st);
-}
-
-int pnp_conv3x3_wino_ms_units_f32(int nsrc, const float* const* srcs, const float* const* wino_w, const float* bias, int act,
-                                  float* out, int h, int w, void* st) {
-    return wino_ms_op(nsrc, srcs, wino_w, bias, act, out, h, w, 1, st);
-}
-
-static int wino_ms_op(int nsrc, const float* const* srcs, const float* const* wino_w, const float* bias, int act, float* out,
-                      int h, int w, int units, void* st) {
-    if (nsrc < 2 || nsrc > 4 || !srcs || !wino_w || !out || act < 0 || act > 2) return PNP_ERR_BAD_ARG;
-    if (!op_map_fits(h, w)) return PNP_ERR_UNSUPPORTED;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nsrc = nsrc;
-    for (int s = 0; s < nsrc; ++s) {
-        if (!srcs[s] || !wino_w[s]) return PNP_ERR_BAD_ARG;
-        a.src[s] = srcs[s];
-        a.src_c[s] = s == 0 ? 4 : 64;
-        a.wwino_src[s] = wino_w[s];
-    }
-    a.wwino_rgb = wino_w[0];
-    a.bias = bias;
-    a.out = out;
-    a.H = h;
-    a.W = w;
-    a.act = act;
-    a.wino_units = units;
-    if (!conv_wino_ms_eligible(a, CONV_CFG_BIG, 1)) return PNP_ERR_UNSUPPORTED;
-    return launch_conv3x3_wino(a, (hipStream_t)st);
-}
-
-int pnp_wino_image_from_packed_f32(const float* packed_w, const float* gamma, float* dst, void* st) {
-    return launch_wino_images(&packed_w, &dst, 1, gamma, (hipStream_t)st);
-}
-
-int pnp_wino_par_image_from_packed_f32(const float* packed_w1x1, float* dst, void* st) {
-    return launch_wino_par_image(packed_w1x1, dst, (hipStream_t)st);
-}
-
-int pnp_conv3x3_wino_f32(const float* src, const float* wino_w, const float* bias, const float* gamma, const float* wino_w1x1,
-                         const float* par, const int* par_flags, const float* residual, int act, float* out, int h, int w,
-                         void* st) {
-    return pnp_conv3x3_wino_f32_ex(src, wino_w, bias, gamma, wino_w1x1, par, par_flags, residual, act, out, h, w, nullptr, st);
-}
-
-int pnp_conv3x3_wino_units_f32(const float* src, const float* wino_w, const float* bias, const float* gamma, const float* wino_w1x1,
-                               const float* par, const int* par_flags, const float* residual, int act, float* out, int h, int w,
-                               void* st) {
-    // (trace = this function's own address: the marker pnp_conv3x3_wino_f32_ex reads as "quadrant-unit kernel, no timeline")
-    return pnp_conv3x3_wino_f32_ex(src, wino_w, bias, gamma, wino_w1x1, par, par_flags, residual, act, out, h, w,
-                                   (void*)&pnp_conv3x3_wino_units_f32, st);
-}
-
-static const int* g_debug_wino_gate_word = nullptr;
-int pnp_debug_wino_gate_word(const int* gate_word_dev) {
-    g_debug_wino_gate_word = gate_word_dev;
-    return 0;
-}
-
-int pnp_conv3x3_wino_f32_ex(const float* src, const float* wino_w, const float* bias, const float* gamma, const float* wino_w1x1,
-                            const float* par, const int* par_flags, const float* residual, int act, float* out, int h, int w,
-                            void* trace, void* st) {
-    if (!src || !wino_w || !out || act < 0 || act > 2 || (wino_w1x1 && !par)) return PNP_ERR_BAD_ARG;
-    if (!op_map_fits(h, w)) return PNP_ERR_UNSUPPORTED;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nsrc = 1;
-    a.src[0] = src;
-    a.src_c[0] = 64;
-    a.wwino = wino_w;
-    a.wwino_par = wino_w1x1;
-    a.wpar = wino_w1x1;              // "has branches"; the direct-form image itself is not read on this path
-    a.par = wino_w1x1 ? par : nullptr;
-    a.par_flags = wino_w1x1 ? par_flags : nullptr;
-    a.par_any = (wino_w1x1 && par_flags) ? g_debug_wino_gate_word : nullptr;
-    a.par_plane = (long)h * w;
-    a.bias = bias;
-    a.gamma = gamma;
-    a.residual = residual;
-    a.out = out;
-    a.H = h;
-    a.W = w;
-    a.act = act;
-    if (trace == (void*)&pnp_conv3x3_wino_units_f32) a.wino_units = 1;
-    else a.dbg = (unsigned long long*)trace;
-    if (!conv_wino_eligible(a, CONV_CFG_BIG, 1)) return PNP_ERR_UNSUPPORTED;
-    return launch_conv3x3_wino(a, (hipStream_t)st);
-}
-
-int pnp_conv3x3_f32(int nsrc, const float* const* srcs, const int* src_channels, const float* const* packed_w,
-                    const float* bias, const float* gamma, const float* packed_w1x1, const float* par,
-                    const float* residual, int act, float* out, int h, int w, void* st) {
-    return pnp_conv3x3_f32_ex(nsrc, srcs, src_channels, packed_w, bias, gamma, packed_w1x1, par, residual, act, out, h, w,
-                              PNP_CONV_AUTO, nullptr, nullptr, st);
-}
-
-int pnp_conv3x3_f32_ex(int nsrc, const float* const* srcs, const int* src_channels, const float* const* packed_w,
-                       const float* bias, const float* gamma, const float* packed_w1x1, const float* par,
-                       const float* residual, int act, float* out, int h, int w, int variant, const int* par_flags,
-                       void* trace, void* st) {
-    if (nsrc < 1 || nsrc > 4) return PNP_ERR_BAD_ARG;
-    if (!op_map_fits(h, w)) return PNP_ERR_UNSUPPORTED;      // 32-bit byte offsets into a map
-    if (variant != PNP_CONV_AUTO && variant != PNP_CONV_TILE && variant != PNP_CONV_TILE_BIG) return PNP_ERR_BAD_ARG;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nsrc = nsrc;
-    for (int s = 0; s < nsrc; ++s) {
-        a.src[s] = srcs[s];
-        a.src_c[s] = src_channels[s];
-        a.wsrc[s] = packed_w[s];
-    }
-    a.wpar = packed_w1x1;
-    a.par = par;
-    a.par_plane = (long)h * w;
-    a.bias = bias;
-    a.gamma = gamma;
-    a.residual = residual;
-    a.out = out;
-    a.H = h;
-    a.W = w;
-    a.act = act;
-    a.out_mode = 0;
-    a.par_flags = par_flags;
-    a.dbg = (unsigned long long*)trace;
-    a.no_persist = variant != PNP_CONV_AUTO;
-    return launch_conv3x3(a, variant == PNP_CONV_TILE_BIG ? CONV_CFG_BIG : conv_pick_cfg(h, w), 1, (hipStream_t)st);
-}
-
-// ResidualBlockNoBNDynamic_drt.forward, channel_first / one_layer branch (sr_backbone_utils.py:305-313,329): two fused-conv
-// launches with the intermediate in caller scratch.
-int pnp_bae_block_f32(const float* x, const float* w2_packed, const float* b2, const float* gamma, const float* w1x1_packed,
-                      const float* par, const float* w1_packed, const float* b1, float* scratch, float* out, int h, int w,
-                      void* st) {
-    if (!x || !w2_packed || !w1_packed || !scratch || !out || h < 1 || w < 1) return PNP_ERR_BAD_ARG;
-    if ((w1x1_packed == nullptr) != (par == nullptr)) return PNP_ERR_BAD_ARG;
-    const float* src[1] = {x};
-    const int sc[1] = {64};
-    const float* wp[1] = {w2_packed};
-    int rc = pnp_conv3x3_f32(1, src, sc, wp, b2, gamma, w1x1_packed, par, nullptr, 1, scratch, h, w, st);
-    if (rc) return rc;
-    src[0] = scratch;
-    wp[0] = w1_packed;
-    return pnp_conv3x3_f32(1, src, sc, wp, b1, nullptr, nullptr, nullptr, x, 0, out, h, w, st);
-}
-
-// PixelShufflePack (common/upsample.py:40-51): conv3x3 64 -> 256 + F.pixel_shuffle(2), as 4 sub-pixel convs whose
-// output-channel order is permuted at pack time so that every sub-pixel is a contiguous 64-channel pixel row.
-int64_t pnp_packed_pixel_shuffle_floats(void) { return 4 * IMG_WIDE + 256; }
-
-int pnp_pack_pixel_shuffle_f32(const float* w, const float* b, float* dst, void* st_) {
-    hipStream_t st = (hipStream_t)st_;
-    if (!w || !b || !dst) return PNP_ERR_BAD_ARG;
-    for (int sub = 0; sub < 4; ++sub) {
-        PackArgs a = plain_pack(w, 64, 9, PACK_WIDE, 0, 2, 64, dst + sub * IMG_WIDE);
-        a.co_mul = 4;      // conv channel c*4 + (dy*2+dx) -> pixel (2y+dy, 2x+dx), channel c
-        a.co_add = sub;
-        const int rc = launch_pack_weights(a, 1, st);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(small_copy_kernel, dim3(1), dim3(256), 0, st, b, dst + 4 * IMG_WIDE, 256, 256, 1);
-    return (int)hipGetLastError();
-}
-
-int pnp_pixel_shuffle_conv_f32(const float* x, const float* packed, int act, float* out, int h, int w, void* st) {
-    if (!x || !packed || !out || h < 1 || w < 1 || act < 0 || act > 2) return PNP_ERR_BAD_ARG;
-    if ((int64_t)h * w * 4 * 256 >= (int64_t)1 << 32) return PNP_ERR_UNSUPPORTED;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nsrc = 1;
-    a.src[0] = x;
-    a.src_c[0] = 64;
-    a.wsrc[0] = packed;
-    a.w_ystride = IMG_WIDE;
-    a.bias = packed + 4 * IMG_WIDE;
-    a.bias_ystride = 64;
-    a.out = out;
-    a.H = h;
-    a.W = w;
-    a.act = act;
-    a.out_mode = 1;
-    return launch_conv3x3(a, conv_pick_cfg(h, w), 4, (hipStream_t)st);
-}
-
-int pnp_par_tile_flags_f32(const float* par, int* flags, int h, int w, void* st) {
-    if (!par || !flags || h < 1 || w < 1) return PNP_ERR_BAD_ARG;
-    return launch_par_tile_flags(par, (long)h * w, flags, 1, h, w, (hipStream_t)st);
-}
-
-int pnp_f16_image_from_f32(const float* packed_w, void* dst, int nchunks, void* st) {
-    if (!packed_w || !dst) return PNP_ERR_BAD_ARG;
-    return launch_f16_image(packed_w, dst, nchunks, 2, (hipStream_t)st);
-}
-
-int pnp_conv3x3_f16(int nsrc, const float* const* srcs, const int* src_channels, const void* const* packed_w_f16,
-                    const float* bias, const float* gamma, const void* packed_w1x1_f16, const float* par,
-                    const float* residual, int act, float* out, int h, int w, void* st) {
-    return pnp_conv3x3_f16_ex(nsrc, srcs, src_channels, packed_w_f16, bias, gamma, packed_w1x1_f16, par, residual, act, out,
-                              h, w, nullptr, st);
-}
-
-int pnp_conv3x3_f16_ex(int nsrc, const float* const* srcs, const int* src_channels, const void* const* packed_w_f16,
-                       const float* bias, const float* gamma, const void* packed_w1x1_f16, const float* par,
-                       const float* residual, int act, float* out, int h, int w, void* trace, void* st) {
-    if (nsrc < 1 || nsrc > 4) return PNP_ERR_BAD_ARG;
-    if (!op_map_fits(h, w)) return PNP_ERR_UNSUPPORTED;      // 32-bit byte offsets into a map
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nsrc = nsrc;
-    a.prec = 1;
-    for (int s = 0; s < nsrc; ++s) {
-        a.src[s] = srcs[s];
-        a.src_c[s] = src_channels[s];
-        a.wsrc_h[s] = packed_w_f16[s];
-    }
-    a.wpar_h = packed_w1x1_f16;
-    a.par = par;
-    a.par_plane = (long)h * w;
-    a.bias = bias;
-    a.gamma = gamma;
-    a.residual = residual;
-    a.out = out;
-    a.H = h;
-    a.W = w;
-    a.act = act;
-    a.out_mode = 0;
-    a.dbg = (unsigned long long*)trace;
-    if (a.wpar_h && (nsrc != 1 || !par)) return PNP_ERR_BAD_ARG;
-    if (!conv_f16_eligible(a, CONV_CFG_BIG, 1)) return PNP_ERR_UNSUPPORTED;
-    return launch_conv3x3_f16(a, 1, (hipStream_t)st);
-}
-
-int pnp_f16x3_image_from_f32(const float* packed_w, void* dst, int nchunks, void* st) {
-    if (!packed_w || !dst) return PNP_ERR_BAD_ARG;
-    return launch_f16x3_image(packed_w, dst, nchunks, (hipStream_t)st);
-}
-
-int pnp_conv3x3_f16x3(int nsrc, const float* const* srcs, const int* src_channels, const float* const* packed_w_f32,
-                      const void* const* packed_w_x3, const float* bias, const float* gamma, const void* packed_w1x1_x3,
-                      const float* par, const int* par_flags, const float* residual, int act, float* out, int h, int w, void* st) {
-    return pnp_conv3x3_f16x3_ex(nsrc, srcs, src_channels, packed_w_f32, packed_w_x3, bias, gamma, packed_w1x1_x3, par, par_flags,
-                                residual, act, out, h, w, 0, nullptr, nullptr, st);
-}
-
-int pnp_conv3x3_f16x3_ex(int nsrc, const float* const* srcs, const int* src_channels, const float* const* packed_w_f32,
-                         const void* const* packed_w_x3, const float* bias, const float* gamma, const void* packed_w1x1_x3,
-                         const float* par, const int* par_flags, const float* residual, int act, float* out, int h, int w,
-                         int w1x1_scaled, int* tile_queue, void* trace, void* st) {
-    if (nsrc < 1 || nsrc > 4 || !srcs || !src_channels || !packed_w_x3 || !out) return PNP_ERR_BAD_ARG;
-    if (!op_map_fits(h, w)) return PNP_ERR_UNSUPPORTED;      // 32-bit byte offsets into a map
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nsrc = nsrc;
-    a.prec = 2;
-    for (int s = 0; s < nsrc; ++s) {
-        a.src[s] = srcs[s];
-        a.src_c[s] = src_channels[s];
-        a.wsrc[s] = packed_w_f32 ? packed_w_f32[s] : nullptr;
-        a.wsrc_h[s] = packed_w_x3[s];
-        if (src_channels[s] == 4 && (s != 0 || !a.wsrc[s])) return PNP_ERR_BAD_ARG;    // the RGB frame: source 0, fp32 image
-    }
-    a.wpar_h = packed_w1x1_x3;
-    a.wpar_h_scaled = (packed_w1x1_x3 && w1x1_scaled) ? 1 : 0;
-    a.par = par;
-    a.par_flags = par_flags;
-    a.tile_queue = tile_queue;
-    // A queue that is not all zero on entry ends the blocks' walk early (tiles left unwritten, no error): zero it here instead of
-    // trusting the caller -- a launch aborted in mid-clip would leave it dirty for this entry point
-    if (tile_queue) hipLaunchKernelGGL(fill_kernel, dim3(1), dim3(64), 0, (hipStream_t)st, reinterpret_cast<float*>(tile_queue), 0.0f, 16);
-    a.par_plane = (long)h * w;
-    a.bias = bias;
-    a.gamma = gamma;
-    a.residual = residual;
-    a.out = out;
-    a.H = h;
-    a.W = w;
-    a.act = act;
-    a.out_mode = 0;
-    a.dbg = (unsigned long long*)trace;
-    if (a.wpar_h && (nsrc != 1 || !par)) return PNP_ERR_BAD_ARG;
-    if (!conv_f16x3_eligible(a, CONV_CFG_BIG, 1)) return PNP_ERR_UNSUPPORTED;
-    return launch_conv3x3_f16x3(a, conv_pick_cfg(h, w), (hipStream_t)st);
-}
-
-// pnpvcve_debug.h: the fp16-operand conv with explicit fp16 maps -- what pnp_generator_forward uses between its launches under
-// PNP_OPT_F16_MAPS / PNP_OPT_F16_MIRRORS -- so that tests can address every kernel variant through the ABI.
-int pnp_conv3x3_f16_maps(int nsrc, const void* const* srcs, const int* src_channels, int src_f16_mask,
-                         const void* const* packed_w_f16, const float* bias, const float* gamma, const void* packed_w1x1_f16,
-                         const float* par, const int* par_flags, const float* residual, int act, void* out, int out_f16,
-                         void* out16, int h, int w, int chain, void* trace, void* st) {
-    if (nsrc < 1 || nsrc > 4) return PNP_ERR_BAD_ARG;
-    if (!op_map_fits(h, w)) return PNP_ERR_UNSUPPORTED;      // 32-bit byte offsets into a map
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nsrc = nsrc;
-    a.prec = 1;
-    for (int s = 0; s < nsrc; ++s) {
-        a.src[s] = reinterpret_cast<const float*>(srcs[s]);
-        a.src_c[s] = src_channels[s];
-        a.wsrc_h[s] = packed_w_f16[s];
-    }
-    a.src_f16 = src_f16_mask;
-    a.out_f16 = out_f16 ? 1 : 0;
-    a.out16 = out16;
-    a.no_multi16 = chain ? 1 : 0;
-    a.wpar_h = packed_w1x1_f16;
-    a.par = par;
-    a.par_flags = par_flags;
-    a.par_plane = (long)h * w;
-    a.bias = bias;
-    a.gamma = gamma;
-    a.residual = residual;
-    a.out = reinterpret_cast<float*>(out);
-    a.H = h;
-    a.W = w;
-    a.act = act;
-    a.out_mode = 0;
-    a.dbg = (unsigned long long*)trace;
-    if (a.wpar_h && (nsrc != 1 || !par)) return PNP_ERR_BAD_ARG;
-    if (!conv_f16_eligible(a, CONV_CFG_BIG, 1)) return PNP_ERR_UNSUPPORTED;
-    return launch_conv3x3_f16(a, 1, (hipStream_t)st);
-}
-
-int pnp_mv_warp_nhwc_f16out(const float* feat, const float* fx, const float* fy, void* out16, int h, int w, int c, void* st) {
-    return launch_mv_warp_nhwc(feat, fx, fy, out16, h, w, c, (hipStream_t)st, true);
 }
 
 }  // extern "C"
