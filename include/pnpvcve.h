@@ -143,6 +143,23 @@ int pnp_generator_set_max_resident(pnp_generator* g, int k);
 int pnp_generator_get_max_resident(const pnp_generator* g);
 int pnp_generator_min_resident(const pnp_generator* g, int t);
 
+/* Row-band chains.  A branch is a chain of 3x3 convs, each reading the previous one's whole output, and every
+ * launch of the persistent tile kernels ends with a partial round and a drain during which most of the chip idles.  With the switch
+ * on, a chain runs as two: chain A on the caller's stream computes tile rows [0, a_n) of conv n, chain B on an internal stream rows
+ * [a_n, rows), with a_n = a_0 - n -- a region that shrinks by one tile row per conv never reads outside what its own chain wrote, and
+ * B's conv n waits (an event) only for A's conv n - 1.  The device then always holds a ready kernel that does not depend on the one
+ * whose tail is running.  Same kernels, same arithmetic per tile: the output is bit-identical to the one-launch schedule.
+ * This is the ONE statement of the rule: 0 = one launch per conv; 1 (default) = band chains where ALL of these hold -- PNP_PREC_F32,
+ * the Winograd tile kernels (PNP_OPT_WINOGRAD, a frame above PNP_WINO_UNITS_MAX_TILES tiles), one workspace context in flight
+ * (several clips on several streams fill each other's tails already), and enough tile rows that both regions stay non-empty
+ * over the whole chain (rows >= convs of the chain + 1: 720p and up); k >= 2 = as 1 with the first boundary a_0 = k instead of the
+ * centred (rows + convs - 1) / 2 (a tuning aid; a chain it leaves a region empty in takes one launch per conv).  Negative:
+ * PNP_ERR_BAD_ARG.  Stays on under pnp_generator_profile: a split conv counts as one launch, timed on the caller's stream
+ * (back to back with its neighbours: the chain's time per conv; the part on the internal stream overlaps the next conv and is not
+ * added, so a kind's total stays within wall time). */
+int pnp_generator_set_band_split(pnp_generator* g, int on);
+int pnp_generator_get_band_split(const pnp_generator* g);
+
 /* generator.forward(lrs, QPs, slices, mvs, base_QPs, par_map)  iconvsr_ipb_par.py:44-149.
  *   lrs_dev (n,t,3,h,w)  mvs_dev (n,t,4,h,w)  par_dev (n,t,3,h,w)      NCHW, contiguous
  *   slices/qps/base_qps: HOST arrays of n*t floats (the (n,t,1,1,1) tensors, flattened);

@@ -35,6 +35,18 @@ int pnp_conv3x3_wino_f32_ex(const float* src_dev, const float* wino_w_dev, const
  * body when bit 3 is set).  A device int; NULL = back to the ungated branch kernel.  Process-wide, not thread-safe: a tracing hook. */
 int pnp_debug_wino_gate_word(const int* gate_word_dev);
 
+/* The NEXT pnp_conv3x3_wino_f32 / _ex / pnp_conv3x3_wino_ms_f32 calls (tile kernels, not the quadrant-unit forms) compute the 16-pixel
+ * tile rows [row0, row0 + nrows) of the frame only and leave the rest of out_dev untouched -- one part of a row-band chain
+ * (pnp_generator_set_band_split).  nrows = 0: back to whole frames.  A range beyond the frame's ceil(h / 16) rows: the conv returns
+ * PNP_ERR_BAD_ARG.  Process-wide, not thread-safe: a test hook. */
+int pnp_debug_wino_tile_rows(int row0, int nrows);
+
+/* The row-band plan of pnp_generator_set_band_split as a pure function: for a chain of nconv convs on a frame of `rows` tile rows,
+ * writes the boundary row a_n of each conv (chain A: tile rows [0, a_n), chain B: [a_n, rows); a_n = a_0 - n) to bounds[0 .. nconv)
+ * and returns 1, or returns 0 (bounds untouched) when the frame has too few rows for both regions to stay non-empty: no split.
+ * a0 = 0: the centred trapezoid a_0 = (rows + nconv - 1) / 2; a0 > 0: that first boundary. */
+int pnp_band_plan(int rows, int nconv, int a0, int* bounds);
+
 /* The fp16-operand conv of pnpvcve.h with an optional timeline buffer (16 u64 per 4-wave group). */
 int pnp_conv3x3_f16_ex(int nsrc, const float* const* srcs_dev, const int* src_channels,
                        const void* const* packed_w_f16_dev, const float* bias_dev, const float* gamma_dev,

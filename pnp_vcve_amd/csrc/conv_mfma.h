@@ -3,6 +3,16 @@
 #pragma once
 #include "common.h"
 
+// One conv of a row-band chain (generator.hip run_branch) on the Winograd tile kernels: tile rows [0, row) run
+// on the caller's stream (chain A), tile rows [row, rows) on `side` (chain B).  `ready` is recorded on the caller's stream IN FRONT of
+// part A -- behind everything enqueued since the chain's previous conv -- and `side` waits for it before part B: part B reads the two
+// tile rows around `row` that chain A's previous conv wrote.  Nothing waits for part B here: the chain's owner joins `side` at its end.
+struct ConvBandSplit {
+    hipStream_t side;
+    hipEvent_t ready;
+    int row;
+};
+
 struct ConvArgs {
     const float* src[4];    // NHWC sources (virtual concat, never materialised)
     const float* wsrc[4];   // packed chunk images per source (9 chunks for C=64, 1 for C=4)
@@ -17,6 +27,9 @@ struct ConvArgs {
     const int* par_any;        // with wwino + wpar (tile kernel): the frame's partition word (launch_par_frame_any; bit 3 = every 8x8 quadrant of
                                // the frame is all zero or carries one constant plane).  The conv is then launched twice behind a device-side
                                // gate: the fold-only kernel (runs iff bit 3 is set) and the branch kernel (iff not); any frame size
+    int tile_row0, tile_rows;  // Winograd tile kernels: the launch covers 16-pixel tile rows [tile_row0, tile_row0 + tile_rows) only (its reads reach
+                               // one pixel row beyond on either side); tile_rows == 0: the whole frame
+    const ConvBandSplit* band; // Winograd tile kernels: run as the two launches of a row-band chain; nullptr (the op ABI, every other kernel): one launch
     int wino_units;            // with wwino: one block per 8x8 quadrant unit (conv3x3_wino_quad_kernel: frames too small to fill the chip with 16x16 tiles)
     const float* wvalu;     // conv_last only: [9][64][4] weights for the vector-ALU kernel (conv_last.hip), or nullptr
     const void* wsrc_h[4];  // prec == 1: fp16 twins of wsrc / wpar (conv_f16.hip); prec == 2: their split images (hi and lo

@@ -114,6 +114,8 @@ struct WinoArgs {
     const int* gate;        // nullptr, or one word (ConvArgs::par_any): the launch runs iff ((*gate & gate_mask) != 0) == (gate_want != 0)
     int gate_mask, gate_want;
     int quad;               // the tiles beyond an XCD band's whole rounds are worked on as four 8x8 quadrants by four blocks (see the kernel's tail)
+    int tile0, tcount;      // the launch works on tiles [tile0, tile0 + tcount) of the frame (row-major; whole tile rows: ConvArgs::tile_row0).
+                            // Only the strip walk knows: halo, edges, flags and the gate are the full frame's
 };
 
 // FO ("fold only"): the front half of a frame whose EVERY 8x8 quadrant is all zero or carries one constant partition plane (the gate
@@ -131,7 +133,7 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int m = lane & 15, kq = lane >> 4;
     const int H = a.H, W = a.W;
-    const int tiles_x = (W + 15) >> 4, ntiles = tiles_x * ((H + 15) >> 4);
+    const int tiles_x = (W + 15) >> 4;
     // MS with the ring as LDS-DMA loads: no run-time `last source?` branch inside a chunk (every chunk's wait counts its own requests).
     // (MSF, the tile loop's last_seg and tqk, hreg[3] and the never-taken register branch of the MS weight requests only keep the
     //  capture list of `chunk` as it was: without them no kernel computes anything else, but the register allocation of the MS and
@@ -144,12 +146,13 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
         if (((gv & a.gate_mask) != 0) != (a.gate_want != 0)) return;
     }
 
-    // ---- strip of tiles: XCD x owns a contiguous band, dealt round-robin to its resident blocks (neighbouring halos share its L2)
+    // ---- strip of tiles (the launch's range [tile0, tile0 + tcount); the whole frame unless the caller split it into row bands):
+    //      XCD x owns a contiguous band, dealt round-robin to its resident blocks (neighbouring halos share its L2)
     int tile, tstep, tend, qtile = -1, qquad = 0;
     if ((gridDim.x & 7) == 0) {
         const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-        const int bq = ntiles >> 3, br = ntiles & 7;
-        const int xbeg = xcd < br ? xcd * (bq + 1) : br * (bq + 1) + (xcd - br) * bq;
+        const int bq = a.tcount >> 3, br = a.tcount & 7;
+        const int xbeg = a.tile0 + (xcd < br ? xcd * (bq + 1) : br * (bq + 1) + (xcd - br) * bq);
         tend = xbeg + bq + (xcd < br ? 1 : 0);
         tile = xbeg + slot;
         tstep = gridDim.x >> 3;
@@ -165,9 +168,9 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
             }
         }
     } else {
-        tile = blockIdx.x;
+        tile = a.tile0 + blockIdx.x;
         tstep = gridDim.x;
-        tend = ntiles;
+        tend = a.tile0 + a.tcount;
     }
     if (tile >= tend) return;
 
@@ -1690,7 +1693,28 @@ bool conv_wino_eligible(const ConvArgs& a, int cfg, int grid_y) {
     return (long)a.H * a.W * 256 < ((long)1 << 32) - 65536;
 }
 
+static int launch_wino_rows(const ConvArgs& a, int row0, int nrows, hipStream_t stream);
+
+// A conv of a row-band chain (ConvBandSplit) becomes two launches of the same kernel over complementary tile rows; every tile is
+// computed exactly as in the one launch (which block walks it is all that changes), so the result is bit-identical.
 int launch_conv3x3_wino(const ConvArgs& a, hipStream_t stream) {
+    const int rows = (a.H + 15) / 16;
+    if (!a.band) {
+        if (a.tile_rows == 0) return launch_wino_rows(a, 0, rows, stream);
+        if (a.wino_units || a.tile_row0 < 0 || a.tile_rows < 0 || a.tile_row0 + a.tile_rows > rows) return PNP_ERR_BAD_ARG;
+        return launch_wino_rows(a, a.tile_row0, a.tile_rows, stream);
+    }
+    const ConvBandSplit& b = *a.band;
+    if (a.wino_units || a.tile_rows != 0 || b.row < 1 || b.row >= rows || !b.ready) return PNP_ERR_BAD_ARG;
+    hipError_t e = hipEventRecord(b.ready, stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(b.side, b.ready, 0);
+    if (e != hipSuccess) return (int)e;
+    int rc = launch_wino_rows(a, 0, b.row, stream);
+    if (rc) return rc;
+    return launch_wino_rows(a, b.row, rows - b.row, b.side);
+}
+
+static int launch_wino_rows(const ConvArgs& a, int row0, int nrows, hipStream_t stream) {
     static PnpPerDevice once;
     int cus = 256;
     const hipError_t attr_err = once.run([](int dev, int& g) {
@@ -1726,8 +1750,11 @@ int launch_conv3x3_wino(const ConvArgs& a, hipStream_t stream) {
     w.act = a.act;
     w.dbg = a.dbg;
     w.quad = 1;
-    const int ntiles = ((a.W + 15) / 16) * ((a.H + 15) / 16);
-    if (a.wino_units && a.wwino) {                          // small frames: one block per quadrant unit
+    const int tiles_x = (a.W + 15) / 16;
+    const int ntiles = tiles_x * nrows;                     // of this launch: whole tile rows of the frame
+    w.tile0 = tiles_x * row0;
+    w.tcount = ntiles;
+    if (a.wino_units && a.wwino) {                          // small frames: one block per quadrant unit (always the whole frame)
         const dim3 gq(4 * ntiles), bq(256);
         if (a.wpar && a.par_any) {
             w.gate = a.par_any;

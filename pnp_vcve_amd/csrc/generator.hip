@@ -14,6 +14,7 @@
 //   * mirror-extension detection (iconvsr.py:396-410) is skipped: for this class it only
 //     switches compute_flow (iconvsr_ipb.py:33-46) to an indexing that selects the same MV
 //     maps (flows_backward[-i] == mvs[:, i, 0:2]), so the output does not depend on it.
+#include <deque>
 #include <string>
 #include <vector>
 #include <cstring>
@@ -80,6 +81,13 @@ struct pnp_generator {
     mutable std::vector<hipStream_t> side_streams;
     mutable std::vector<hipEvent_t> join_events;
     mutable hipEvent_t fork_event = nullptr;
+    // row-band chains (pnp_generator_set_band_split): chain B's stream, one `ready` event per conv of a chain and the join event;
+    // made the first time a frame qualifies
+    int band_split = 1;
+    mutable hipStream_t band_stream = nullptr;
+    mutable std::vector<hipEvent_t> band_events;
+    mutable std::deque<ConvBandSplit> band_recs;     // the split of every chained conv of the latest forward (ConvArgs::band points here: the
+                                                     // recording launchers of the host-only scheduler tests read it back after the call)
     std::vector<ParamInfo> params;
     int64_t flat_floats = 0, packed_floats = 0;
     int ndyn = 0;
@@ -473,6 +481,31 @@ int plan_min_resident(int t, int with_cat) {
 
 bool bounded_mode(const pnp_generator* g, int t) { return g->max_resident > 0 && g->max_resident < t; }
 
+// ---- row-band chains (pnp_generator_set_band_split)
+// A chain of nconv 3x3 convs c_0 .. c_(nconv-1), each reading the previous one's output, on a frame of `rows` 16-pixel tile rows, run as
+// two chains with the boundary a_n = a_0 - n:  A (the caller's stream) computes tile rows [0, a_n) of c_n, B (the side stream) rows
+// [a_n, rows).  A 3x3 conv's output on pixel rows [p, q) reads pixel rows [p - 1, q + 1) of its input, and its residual / partition
+// planes at its own pixels.  With tile row r = pixel rows [16 r, 16 r + 16):
+//   * A's c_n reads input pixel rows <= 16 a_n, i.e. tile rows <= a_n = a_(n-1) - 1 < a_(n-1): all written by A's c_(n-1).  A never waits.
+//   * B's c_n reads input pixel rows >= 16 a_n - 1, i.e. tile rows >= a_n - 1: rows a_n - 1 and a_n are A's c_(n-1) (both < a_(n-1)), the
+//     rest B's own c_(n-1) (rows >= a_(n-1) = a_n + 1).  So B's c_n is enqueued behind an event recorded in front of A's c_n: it then
+//     follows A's c_(n-1) and all earlier ones, and B's c_(n-1) by stream order.
+//   * what runs unordered against B's c_n is A's c_m for m >= n.  Writes: A's c_m writes tile rows < a_m <= a_n, B's c_n rows >= a_n:
+//     disjoint, whichever buffers they are (the branch ping-pongs tmp0 -> tmp1 -> tmp0 and a back half writes over its own residual).
+//     A's writes against B's reads, m > n: A writes tile rows <= a_m - 1 <= a_n - 2, B reads tile rows >= a_n - 1.  m = n: the same conv,
+//     whose output is not its input.  B's writes against A's reads, m > n: A's c_m reads tile rows <= a_m <= a_n - 1, B's c_n writes
+//     rows >= a_n.  m = n: A reads the input, B writes the output.
+//   * B's c_n against A's c_m, m < n, is ordered by the event; the chain ends with A's stream waiting for B's.
+// Both regions non-empty over the whole chain: 1 <= a_(nconv-1) and a_0 <= rows - 1.  The centred trapezoid a_0 = (rows + nconv - 1) / 2
+// gives both chains the same number of tiles (+- a row); `a0` > 0 names another first boundary.
+bool band_plan(int rows, int nconv, int a0, int* first) {
+    if (rows < 1 || nconv < 1 || a0 < 0) return false;
+    const int a = a0 > 0 ? a0 : (rows + nconv - 1) / 2;
+    if (a - (nconv - 1) < 1 || a > rows - 1) return false;
+    *first = a;
+    return true;
+}
+
 // One branch run of the clip schedule: the backward (sweep 0) or forward (sweep 1) branch of `frame`, and where its maps live.
 // out / key / nb / own: index of a 64-channel frame map in W.slots (and W.slots16); -1 = not read.  key_frame: the key frame it aligns.
 struct Step {
@@ -646,6 +679,8 @@ void pnp_generator_destroy(pnp_generator* g) {
     for (hipEvent_t e : g->join_events) (void)hipEventDestroy(e);
     for (hipStream_t s : g->side_streams) (void)hipStreamDestroy(s);
     if (g->fork_event) (void)hipEventDestroy(g->fork_event);
+    for (hipEvent_t e : g->band_events) (void)hipEventDestroy(e);
+    if (g->band_stream) (void)hipStreamDestroy(g->band_stream);
     delete g;
 }
 
@@ -759,6 +794,18 @@ int pnp_generator_set_max_resident(pnp_generator* g, int k) {
     return PNP_OK;
 }
 int pnp_generator_get_max_resident(const pnp_generator* g) { return g ? g->max_resident : -1; }
+int pnp_generator_set_band_split(pnp_generator* g, int on) {
+    if (!g || on < 0) return PNP_ERR_BAD_ARG;
+    g->band_split = on;
+    return PNP_OK;
+}
+int pnp_generator_get_band_split(const pnp_generator* g) { return g ? g->band_split : -1; }
+int pnp_band_plan(int rows, int nconv, int a0, int* bounds) {
+    int first;
+    if (!bounds || nconv > 4096 || !band_plan(rows, nconv, a0, &first)) return 0;
+    for (int n = 0; n < nconv; ++n) bounds[n] = first - n;
+    return 1;
+}
 int pnp_generator_min_resident(const pnp_generator* g, int t) {
     if (!g || t < 1) return -1;
     return plan_min_resident(t, g->cfg.with_cat);
@@ -771,7 +818,7 @@ namespace {
 // One sample (clip) of the batch on one stream with one workspace context.
 int forward_sample(const pnp_generator* g, const float* flat, const float* packed, const float* lr_b, const float* mv_b,
                    const float* par_b, const float* sl, const float* qp, const float* bq, float* out_b,
-                   const Workspace& W, int t, int h, int w, hipStream_t st) {
+                   const Workspace& W, int t, int h, int w, hipStream_t st, bool alone) {
     const auto& c = g->cfg;
     const int64_t hw = (int64_t)h * w, fm = hw * 64;
     const int E = c.num_experts;
@@ -806,6 +853,50 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
     // half reads it).  Measured at 720p inside the pipeline (profiles/r03_fp16_*): the front half gains what the back half loses
     // to the extra 128 B per pixel it writes -- off by default, the frame slots keep their mirrors.
     const bool chain16 = mirrors && g->opt[PNP_OPT_F16_CHAIN_MIRRORS];
+    // ---- row-band chain in flight (band_plan): opened per branch run by the step loop, every conv goes through `conv` below
+    // `alone`: the only workspace context in flight (several clips on several streams fill each other's launch tails already)
+    const bool band_mode = alone && g->band_split != 0 && wopt != 0 && !wino_units(h, w);
+    struct {
+        bool open = false, forked = false;
+        int left = 0, n = 0, row = 0;       // convs still to come; convs split so far; the next conv's boundary row
+    } chain;
+    auto chain_open = [&](int nconv) -> int {
+        if (!band_mode) return PNP_OK;
+        // (the stream and the events are made the first time a frame qualifies: with the chain's first conv on another kernel it is
+        //  one conv shorter)
+        int first;
+        const int rows = (h + 15) / 16, a0 = g->band_split >= 2 ? g->band_split : 0;
+        if (!band_plan(rows, nconv, a0, &first) && !band_plan(rows, nconv - 1, a0, &first)) return PNP_OK;
+        if (!g->band_stream) {
+            const hipError_t e = hipStreamCreateWithFlags(&g->band_stream, hipStreamNonBlocking);
+            if (e != hipSuccess) return (int)e;
+        }
+        while ((int)g->band_events.size() < nconv + 1) {
+            hipEvent_t e;
+            const hipError_t err = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+            if (err != hipSuccess) return (int)err;
+            g->band_events.push_back(e);
+        }
+        chain.open = true;
+        chain.forked = false;
+        chain.left = nconv;
+        chain.n = 0;
+        return PNP_OK;
+    };
+    // the caller's stream waits for chain B: in front of whatever reads a whole map next (also on the way out of an error)
+    auto chain_close = [&]() -> int {
+        const bool join = chain.open && chain.forked;
+        chain.open = chain.forked = false;
+        if (!join) return PNP_OK;
+        hipError_t e = hipEventRecord(g->band_events.back(), g->band_stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(st, g->band_events.back(), 0);
+        g->prof_last = nullptr;
+        return (int)e;
+    };
+    struct ChainGuard {
+        decltype(chain_close)& close;
+        ~ChainGuard() { (void)close(); }
+    } chain_guard{chain_close};
     auto conv = [&](const ConvCall& q) -> int {
         ConvArgs a;
         memset(&a, 0, sizeof(a));
@@ -866,7 +957,30 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
         const double nreal = (q.mode_ == 2 || q.mode_ == 3) ? 3 : 64;   // RGB heads; mode 4 (DCN offsets) is 64 per blockIdx.y
         const int kind = (q.mode_ != 0) ? PNP_PROF_CONV_HEAD
                                         : (q.nsrc > 1 || q.sc[0] != 64) ? PNP_PROF_CONV_INPUT : PNP_PROF_CONV_BLOCK;
+        // (a conv of a row-band chain is timed like any other, on the caller's stream: back to back with its neighbours that is the
+        //  chain's time per conv.  Its part on the side stream shares the chip with the next conv's part A: timed as well and added,
+        //  a kind's total would exceed wall time, which bench.py's rooflines -- executed work over launch time -- rule out)
         ProfScope ps(g, st, kind, 2.0 * kreal * nreal * (double)q.H * q.W * q.gy_);
+        if (chain.open) {
+            // the tile kernels take a conv of the chain as two launches.  A conv on another kernel can only be the chain's first (the
+            // RGB-only input conv of a clip's last frame): it runs whole on the caller's stream in front of the first `ready` event,
+            // and the numbering starts behind it
+            const bool tiles = !a.wino_units && q.H == h && q.W == w && (conv_wino_eligible(a, q.cfg_, q.gy_) || conv_wino_ms_eligible(a, q.cfg_, q.gy_));
+            if (!tiles && chain.n > 0) return PNP_ERR_UNSUPPORTED;
+            if (tiles && chain.n == 0 && !band_plan((h + 15) / 16, chain.left, g->band_split >= 2 ? g->band_split : 0, &chain.row))
+                chain.open = false;          // too few tile rows for this chain: one launch per conv
+            --chain.left;
+            if (tiles && chain.open) {
+                g->band_recs.emplace_back();
+                ConvBandSplit& band = g->band_recs.back();
+                memset(&band, 0, sizeof(band));
+                band.side = g->band_stream;
+                band.ready = g->band_events[chain.n++];
+                band.row = chain.row--;
+                a.band = &band;
+                chain.forked = true;
+            }
+        }
         return launch_conv3x3(a, q.cfg_, q.gy_, st);
     };
 
@@ -1119,7 +1233,12 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
                 g->prof_last = nullptr;           // an untimed launch sits between two timed ones
                 if (rc) return rc;
             }
+            // the branch's convs as a row-band chain: input conv + two per block (+ conv_hr behind a forward branch at the frame's size)
+            const bool hr_in_chain = sp.sweep == 1 && !c.vsr;
+            rc = chain_open(1 + 2 * c.num_blocks + (hr_in_chain ? 1 : 0));
+            if (rc) return rc;
             rc = run_branch(sp.sweep, i, sp.out, in);
+            if (!rc && !hr_in_chain) rc = chain_close();
             if (rc) return rc;
             if (sp.sweep == 0) continue;
 
@@ -1131,6 +1250,7 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
             if (!c.vsr) {   // :144-146
                 rc = conv(ConvCall(h, w, cfg_lr).source(feat, 64, packed + g->hr_img).mirror16(s16of(sp.out)).bias(flat + g->hr_bias)
                               .wino(wino_on ? packed + g->hr_wino : nullptr).units(wino_units(h, w)).act(2).to(W.tmp1).f16_map(o16));
+                if (!rc) rc = chain_close();
                 if (!rc)
                     rc = conv(ConvCall(h, w, CONV_CFG_RGB).source(W.tmp1, 64, packed + g->last_img).bias(packed + g->last_bias)
                                   .mode(2).rgb(lr_i, hw, packed + g->last_valu).to(out_i).f16_map(s16));
@@ -1205,13 +1325,14 @@ int pnp_generator_forward(const pnp_generator* g, const float* flat, const float
         if (err != hipSuccess) return (int)err;
     }
     int rc = PNP_OK;
+    g->band_recs.clear();
     for (int b = 0; b < n && rc == PNP_OK; ++b) {
         const int k = b % nctx;
         const Workspace W = carve(g, (char*)workspace + (int64_t)k * ctx_bytes, t, h, w);
         rc = forward_sample(g, flat, packed, lrs + (int64_t)b * t * 3 * hw, mvs + (int64_t)b * t * 4 * hw,
                             par + (int64_t)b * t * 3 * hw, slices + (int64_t)b * t, qps + (int64_t)b * t,
                             base_qps + (int64_t)b * t, out + (int64_t)b * t * 3 * hw * os * os, W, t, h, w,
-                            nctx > 1 ? g->side_streams[k] : st);
+                            nctx > 1 ? g->side_streams[k] : st, nctx == 1);
     }
     if (nctx > 1) {      // join even after an error: the caller's stream must not run ahead of what was launched
         for (int k = 0; k < nctx; ++k) {

@@ -177,6 +177,14 @@ int pnp_wino_rgb_image_from_packed_f32(const float* packed_rgb_chunk, float* dst
 static int wino_ms_op(int nsrc, const float* const* srcs, const float* const* wino_w, const float* bias, int act, float* out,
                       int h, int w, int units, void* st);
 
+static int g_debug_wino_row0 = 0, g_debug_wino_rows = 0;
+int pnp_debug_wino_tile_rows(int row0, int nrows) {
+    if (row0 < 0 || nrows < 0) return PNP_ERR_BAD_ARG;
+    g_debug_wino_row0 = row0;
+    g_debug_wino_rows = nrows;
+    return 0;
+}
+
 int pnp_conv3x3_wino_ms_f32(int nsrc, const float* const* srcs, const float* const* wino_w, const float* bias, int act, float* out,
                             int h, int w, void* st) {
     return wino_ms_op(nsrc, srcs, wino_w, bias, act, out, h, w, 0, st);
@@ -199,6 +207,10 @@ static int wino_ms_op(int nsrc, const float* const* srcs, const float* const* wi
     }
     a.wwino_rgb = wino_w[0];
     a.wino_units = units;
+    if (!units) {
+        a.tile_row0 = g_debug_wino_row0;
+        a.tile_rows = g_debug_wino_rows;
+    }
     if (!conv_wino_ms_eligible(a, CONV_CFG_BIG, 1)) return PNP_ERR_UNSUPPORTED;
     return launch_conv3x3_wino(a, (hipStream_t)st);
 }
@@ -245,6 +257,10 @@ int pnp_conv3x3_wino_f32_ex(const float* src, const float* wino_w, const float* 
     a.wpar = wino_w1x1;              // "has branches"; the direct-form image itself is not read on this path
     a.par_any = (wino_w1x1 && par_flags) ? g_debug_wino_gate_word : nullptr;
     a.wino_units = units ? 1 : 0;
+    if (!units) {
+        a.tile_row0 = g_debug_wino_row0;
+        a.tile_rows = g_debug_wino_rows;
+    }
     if (!conv_wino_eligible(a, CONV_CFG_BIG, 1)) return PNP_ERR_UNSUPPORTED;
     return launch_conv3x3_wino(a, (hipStream_t)st);
 }

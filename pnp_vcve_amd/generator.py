@@ -158,6 +158,24 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         self._workspace = {}
         self._graphs = {}
 
+    # ---------------------------------------------------------------- row-band chains
+    @property
+    def band_split(self):
+        """1 (default): on frames that qualify (fp32, Winograd tile kernels, one clip in flight, 720p and up) every conv of a branch
+        runs as two launches over complementary tile-row bands on two streams, so that one band's launch tail is filled by the
+        other's next conv (pnp_generator_set_band_split, include/pnpvcve.h; bit-identical output).  0: one launch per conv.
+        k >= 2: as 1 with the chain's first boundary at tile row k (a tuning aid)."""
+        return int(_native.lib().pnp_generator_get_band_split(self._handle))
+
+    @band_split.setter
+    def band_split(self, value):
+        if isinstance(value, bool):
+            value = int(value)
+        if not isinstance(value, int) or value < 0:
+            raise ValueError(f'band_split must be an int >= 0, got {value!r}')
+        _native.check(_native.lib().pnp_generator_set_band_split(self._handle, value), 'pnp_generator_set_band_split')
+        self._graphs = {}
+
     def min_resident_features(self, t):
         """The smallest max_resident_features the bounded schedule accepts for a clip of t frames (pnp_generator_min_resident)."""
         if int(t) < 1:

@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory and the stream; every computatio
 runs in libpnpvcve_hip.so.  All functions require CUDA(HIP) fp32 contiguous tensors and
 raise otherwise -- there is deliberately no CPU path.
 """
+import contextlib
 import ctypes
 
 import torch
@@ -365,16 +366,20 @@ def wino_rgb_image(packed_rgb):
 
 
 @_on_device_of_first_tensor
-def conv3x3_wino_ms(srcs, wino_ws, bias=None, act=0, units=False):
+def conv3x3_wino_ms(srcs, wino_ws, bias=None, act=0, units=False, out=None):
     """The input conv on conv_wino.hip: srcs = [(h,w,4) frame, (h,w,64) maps ...], wino_ws = [wino_rgb_image(...), wino_image(...) ...];
-    the 64-channel sources' images must sit within 4 GiB of each other (slices of ONE tensor do)."""
+    the 64-channel sources' images must sit within 4 GiB of each other (slices of ONE tensor do).  out: an (h,w,64) tensor to write
+    into (inside wino_tile_rows() only the named tile rows of it are written)."""
     srcs = [_chk(x, 'src') for x in srcs]
     wino_ws = [_chk(x, 'wino_w') for x in wino_ws]
     h, w = srcs[0].shape[:2]
     n = len(srcs)
     if n != len(wino_ws) or srcs[0].shape[2] != 4 or any(x.shape != (h, w, 64) for x in srcs[1:]):
         raise ValueError('srcs must be [(h,w,4), (h,w,64) ...] with one Winograd image each')
-    out = torch.empty((h, w, 64), device=srcs[0].device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((h, w, 64), device=srcs[0].device, dtype=torch.float32)
+    elif _chk(out, 'out').shape != (h, w, 64) or not out.is_contiguous():
+        raise ValueError('out must be a contiguous (h, w, 64) tensor')
     sp = (ctypes.c_void_p * n)(*[x.data_ptr() for x in srcs])
     wp = (ctypes.c_void_p * n)(*[x.data_ptr() for x in wino_ws])
     fn = _native.lib().pnp_conv3x3_wino_ms_units_f32 if units else _native.lib().pnp_conv3x3_wino_ms_f32
@@ -383,11 +388,24 @@ def conv3x3_wino_ms(srcs, wino_ws, bias=None, act=0, units=False):
     return out
 
 
+@contextlib.contextmanager
+def wino_tile_rows(row0, nrows):
+    """Inside the block conv3x3_wino / conv3x3_wino_ms (tile kernels) compute the 16-pixel tile rows [row0, row0 + nrows) of the frame
+    only (pnp_debug_wino_tile_rows, include/pnpvcve_debug.h): one part of a row-band chain.  Process-wide: a test hook."""
+    _native.check(_native.lib().pnp_debug_wino_tile_rows(int(row0), int(nrows)), 'pnp_debug_wino_tile_rows')
+    try:
+        yield
+    finally:
+        _native.lib().pnp_debug_wino_tile_rows(0, 0)
+
+
 @_on_device_of_first_tensor
-def conv3x3_wino(x, wino_w, bias=None, gamma=None, wino_w1x1=None, par=None, par_flags=None, residual=None, act=0, trace=None, units=False):
+def conv3x3_wino(x, wino_w, bias=None, gamma=None, wino_w1x1=None, par=None, par_flags=None, residual=None, act=0, trace=None, units=False,
+                 out=None):
     """act(gamma * (conv3x3(x; W) + bias) + sum_j par_j * conv1x1_j(x)) + residual on conv_wino.hip; x (h,w,64) NHWC fp32,
     wino_w = wino_image(packed W, gamma) -- the SAME gamma -- and wino_w1x1 = wino_par_image(packed 1x1 images).  units=True: one block
-    per 8x8 quadrant unit (the small-frame form, pnp_conv3x3_wino_units_f32; same values)."""
+    per 8x8 quadrant unit (the small-frame form, pnp_conv3x3_wino_units_f32; same values).  out: an (h,w,64) tensor to write into (it
+    may be `residual` itself, as a block's back half runs; inside wino_tile_rows() only the named tile rows of it are written)."""
     x = _chk(x, 'x')
     h, w, c = x.shape
     if c != 64:
@@ -396,7 +414,10 @@ def conv3x3_wino(x, wino_w, bias=None, gamma=None, wino_w1x1=None, par=None, par
     if not isinstance(tag, str) and ((tag is None) != (gamma is None) or (gamma is not None and not torch.equal(tag, gamma))):
         raise ValueError('conv3x3_wino: `gamma` scales only the bias -- the conv term carries the gain wino_image() folded into wino_w; '
                          'pass the SAME gamma tensor to both (or none to both)')
-    out = torch.empty_like(x)
+    if out is None:
+        out = torch.empty_like(x)
+    elif _chk(out, 'out').shape != x.shape or not out.is_contiguous():
+        raise ValueError('out must be a contiguous tensor of the shape of x')
     opt = lambda t, n: _ptr(_chk(t, n)) if t is not None else None   # noqa: E731
     if par_flags is not None and (par_flags.dtype != torch.int32 or not par_flags.is_cuda):
         raise ValueError('par_flags must be a CUDA int32 tensor')
