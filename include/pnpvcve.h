@@ -171,6 +171,38 @@ int pnp_generator_forward(const pnp_generator* g, const float* flat_dev, const f
                           float* out_dev, void* workspace_dev, int64_t workspace_bytes,
                           int n, int t, int h, int w, void* stream);
 
+/* Byte frames and clips by pointer.  The same forward at the boundary a video pipeline has: the frames as the
+ * decoder's bytes, the output as display bytes, a batch as a HOST array of n clip descriptors (the clips live wherever they live:
+ * nothing is concatenated).  One lq_format and one out_mask per call.
+ *   PNP_FRAMES_U8_HWC: lq_dev (t,h,w,3) uint8 RGB; byte v stands for the fp32 value (float)v / 255.0f (IEEE division, one 256-entry
+ *   table), so the result is bit-identical to the fp32 forward on pnp_frames_from_rgb8 of the same bytes.
+ *   PNP_OUT_U8: out_u8_dev (t,H,W,3) = round_half_even(clamp(x,0,1) * 255) of the very fp32 value PNP_OUT_F32 stores, the arithmetic
+ *   of pnp_frames_to_rgb8; both bits: both buffers are written.  (H, W = h, w, or 4h, 4w with cfg.vsr.)
+ * No fp32 copy of a byte clip is made: the frames are unpacked straight into the conv source, and conv_last's vector-ALU kernel reads
+ * and writes the bytes itself; the kernels that keep an fp32 interface (PNP_PREC_F16, PNP_OPT_CONV_LAST_VALU = 0) go through ONE
+ * frame of fp32 planes in the workspace.  mvs_dev / par_dev as in pnp_generator_forward; slices / qps / base_qps: n*t host floats.
+ * Errors: those of pnp_generator_forward, and PNP_ERR_BAD_ARG for an unknown format, an out_mask of 0 or with bits beyond 3, a NULL
+ * pointer the format or mask requires, or a uint8 pointer that is not 4-byte aligned.  pnp_generator_forward is this call with
+ * descriptors made from its strides, PNP_FRAMES_F32_NCHW and PNP_OUT_F32: the same launches.
+ * pnp_generator_workspace_bytes_io: bytes of one context for that boundary (-1: unknown format / mask, or a bound below the minimum);
+ * with PNP_FRAMES_F32_NCHW and PNP_OUT_F32 it equals pnp_generator_workspace_bytes, otherwise it adds at most the one-frame buffers. */
+#define PNP_FRAMES_F32_NCHW 0 /* (t,3,h,w) fp32 */
+#define PNP_FRAMES_U8_HWC 1   /* (t,h,w,3) uint8 RGB */
+#define PNP_OUT_F32 1
+#define PNP_OUT_U8 2
+typedef struct pnp_clip_io {
+    const void* lq_dev;
+    const float* mvs_dev;
+    const float* par_dev;
+    float* out_f32_dev;        /* may be NULL when PNP_OUT_F32 is not in out_mask */
+    unsigned char* out_u8_dev; /* may be NULL when PNP_OUT_U8 is not in out_mask */
+} pnp_clip_io;
+int pnp_generator_forward_clips(const pnp_generator* g, const float* flat_dev, const float* packed_dev,
+                                const pnp_clip_io* clips_host, int n, int lq_format, int out_mask,
+                                const float* slices_host, const float* qps_host, const float* base_qps_host,
+                                void* workspace_dev, int64_t workspace_bytes, int t, int h, int w, void* stream);
+int64_t pnp_generator_workspace_bytes_io(const pnp_generator* g, int t, int h, int w, int lq_format, int out_mask);
+
 /* Optional per-launch timing with HIP events recorded on the caller's stream around every
  * kernel of pnp_generator_forward (measurement aid for bench.py; replaces the reference's
  * wall-clock print, mmedit/models/restorers/basicvsr.py:176-182).  Enable, run forwards,
@@ -326,6 +358,9 @@ int pnp_psnr_sse_f32(const float* a_dev, const float* b_dev, unsigned long long*
 /* tensor2img for the PNG write-back (mmedit/core/misc.py:51-71, basicvsr.py:205-231): frames (n,3,h,w) fp32 ->
  * out (n,h,w,3) uint8 RGB = round_half_even(clamp(x,0,1) * 255); a quarter of the D2H bytes of the fp32 frames. */
 int pnp_frames_to_rgb8(const float* frames_dev, unsigned char* out_dev, int nframes, int h, int w, void* stream);
+/* The inverse layout (RescaleToZeroOne + HWC -> CHW of a decoded frame): in (n,h,w,3) uint8 RGB -> out (n,3,h,w) fp32 planes, byte v
+ * -> (float)v / 255.0f by IEEE division (the table PNP_FRAMES_U8_HWC reads). */
+int pnp_frames_from_rgb8(const unsigned char* in_dev, float* out_dev, int nframes, int h, int w, void* stream);
 
 /* SSIM statistic (mmedit/core/evaluation/metrics.py:266-355: per channel, 11x11 Gaussian sigma 1.5, 'valid'
  * window, fp64, on the uint8-rounded frames).  Writes one partial sum of the SSIM map per 16x32 tile:

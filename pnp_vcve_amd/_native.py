@@ -20,6 +20,14 @@ class GeneratorCfg(ctypes.Structure):
         'blocktype')]
 
 
+class ClipIO(ctypes.Structure):
+    """pnp_clip_io: one clip of a pnp_generator_forward_clips batch (device addresses)"""
+    _fields_ = [(k, c_void_p) for k in ('lq_dev', 'mvs_dev', 'par_dev', 'out_f32_dev', 'out_u8_dev')]
+
+
+FRAMES_F32_NCHW, FRAMES_U8_HWC = 0, 1        # PNP_FRAMES_*
+OUT_F32, OUT_U8 = 1, 2                       # PNP_OUT_* (a mask)
+
 # name -> (restype, argtypes); every symbol include/pnpvcve.h declares
 SIGNATURES = {
     'pnp_abi_version': (c_int, []),
@@ -42,6 +50,10 @@ SIGNATURES = {
     'pnp_generator_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       POINTER(c_float), POINTER(c_float), POINTER(c_float),
                                       c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
+    'pnp_generator_forward_clips': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                            POINTER(c_float), POINTER(c_float), POINTER(c_float),
+                                            c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    'pnp_generator_workspace_bytes_io': (c_int64, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
     'pnp_generator_set_precision': (c_int, [c_void_p, c_int]),
     'pnp_generator_get_precision': (c_int, [c_void_p]),
     'pnp_generator_set_option': (c_int, [c_void_p, c_int, c_int]),
@@ -61,6 +73,7 @@ SIGNATURES = {
     'pnp_pack_conv3x3_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'pnp_pack_conv1x1_f32': (c_int, [c_void_p, c_void_p, c_void_p]),
     'pnp_frames_to_rgb8': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'pnp_frames_from_rgb8': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'pnp_psnr_sse_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'pnp_rasterise_side_info_f32': (c_int, [c_void_p, c_void_p, ctypes.c_long, POINTER(c_float), c_int, c_int, c_int,
                                             c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -6,10 +6,19 @@ from .datasets import collate
 from .dist import gather_clip_metrics, get_dist_info, shard_indices
 
 
-def _to_device(data, device):
+def _to_device(data, device, byte_frames=False):
     """Host -> device; when the clip carries raw decoder MV records (CompressedClipFolderDataset) the dense
-    motion / partition maps are painted on the GPU (pnp_rasterise_side_info_f32) instead of on the host."""
+    motion / partition maps are painted on the GPU (pnp_rasterise_side_info_f32) instead of on the host.
+    byte_frames: frames uploaded as uint8 stay what the decoder made -- `lq` is the (n,T,H,W,3) uint8 tensor itself, which the
+    generator reads directly (generator.forward's byte frames), and `gt` becomes fp32 planes in one kernel (ops.frames_from_rgb8:
+    the same 256 values as the loop below, bit for bit)."""
     out = {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in data.items()}
+    if byte_frames:
+        from .ops import frames_from_rgb8
+        if 'lq_u8' in out:
+            out['lq'] = out.pop('lq_u8')
+        if 'gt_u8' in out:
+            out['gt'] = frames_from_rgb8(out.pop('gt_u8'))
     for k in ('lq', 'gt'):
         if k + '_u8' in out:       # frames uploaded as uint8 (dataset.get_uint8): RescaleToZeroOne + FramesToTensor on the device.
             # The 256 possible values come from the host's own fp32 division (a device-side `x / 255.0` multiplies by a rounded
@@ -25,7 +34,8 @@ def _to_device(data, device):
     if 'mv_records' in out:
         from .ops import rasterise_side_info
         rec, rf = out.pop('mv_records'), out.pop('rec_frame')
-        t, h, w = out['lq'].shape[1], out['lq'].shape[-2], out['lq'].shape[-1]
+        t = out['lq'].shape[1]
+        h, w = out['lq'].shape[2:4] if out['lq'].dtype == torch.uint8 else out['lq'].shape[-2:]
         sl = [float(v) for v in data['slices'].reshape(-1)[:t]]
         mvs, par = rasterise_side_info(rec.float(), rf.int(), sl, h, w)
         out['mvs'], out['partitions'] = mvs.unsqueeze(0), par.unsqueeze(0)
@@ -39,10 +49,11 @@ class ClipPrefetcher:
     scatter -> forward -> evaluate, mmedit/apis/test.py:100-119); with whole 100-frame 720p clips the input
     of one clip is 3.7 GB (lq + mvs + partitions), i.e. ~60 ms of PCIe time that this hides."""
 
-    def __init__(self, dataset, indices, device, depth=1):
+    def __init__(self, dataset, indices, device, depth=1, byte_frames=False):
         import queue
         import threading
         self.dataset, self.indices, self.device = dataset, list(indices), torch.device(device)
+        self.byte_frames = bool(byte_frames)          # _to_device(byte_frames=...): lq stays the decoder's uint8 frames
         self.cuda = self.device.type == 'cuda'
         self.stream = torch.cuda.Stream(self.device) if self.cuda else None
         self.q = queue.Queue(maxsize=max(1, int(depth)))      # clips staged ahead of the consumer
@@ -57,12 +68,12 @@ class ClipPrefetcher:
                 if self.cuda:
                     data = {k: (v.pin_memory() if torch.is_tensor(v) else v) for k, v in data.items()}
                     with torch.cuda.stream(self.stream):
-                        dev = _to_device(data, self.device)
+                        dev = _to_device(data, self.device, self.byte_frames)
                         ev = torch.cuda.Event()
                         ev.record(self.stream)
                     self.q.put((dev, ev, data))           # keep the pinned host copies alive until consumed
                 else:
-                    self.q.put((_to_device(data, self.device), None, None))
+                    self.q.put((_to_device(data, self.device, self.byte_frames), None, None))
             self.q.put(None)
         except BaseException as e:                        # surface loader errors in the consumer
             self.q.put(e)
@@ -102,7 +113,8 @@ def _pairable(a, b):
                for k in GENERATOR_INPUTS)
 
 
-def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cuda', metrics=('PSNR', 'SSIM'), clips_in_flight=1):
+def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cuda', metrics=('PSNR', 'SSIM'), clips_in_flight=1,
+                   byte_frames=False):
     """Returns, on every rank, the ordered per-clip results [{'eval_result': {...}}, ...].
 
     clips_in_flight = 2: two clips of equal shape are enhanced by ONE generator call (a batch of two), which the generator runs
@@ -110,7 +122,12 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
     other's (+5 % at 720p, bit-identical to one clip at a time); metrics and image saving stay clip by
     clip (the reference evaluates with samples_per_gpu=1, mmedit/apis/test.py:100-119).  Costs a second workspace.
     `frames_per_s` of a PAIRED clip is the pair's throughput (frames of both clips over the pair's wall time), not the clip's own
-    forward time; an unpaired leftover clip (odd count, shape change, sparse_val model) reports its own."""
+    forward time; an unpaired leftover clip (odd count, shape change, sparse_val model) reports its own.
+
+    byte_frames (default off: the loop above, unchanged): the frames stay uint8 from the decoder to the generator, which also writes
+    the display bytes the PNG writer takes -- fp32 planes only when metrics are computed, uint8 frames only when images are saved,
+    both when both -- and a pair goes to the generator as two clips by pointer (generator.forward_clips) instead of a concatenated
+    batch.  Same PSNR / SSIM and the same PNG bytes."""
     import time
     model.eval()
     rank, world = get_dist_info()
@@ -122,16 +139,25 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
     # sr_backbone_utils.py:262-275; generator.py refuses n != 1): such a model keeps the clip-by-clip loop
     pairs = pairs and not getattr(model.generator, 'sparse_val', False)
 
+    byte_frames = bool(byte_frames) and dev.type == 'cuda' and hasattr(model, 'generator') and not getattr(model, 'psnr_only', False)
+    out_dtype = None
+    if byte_frames:
+        test_cfg = getattr(model, 'test_cfg', None)
+        want_f32 = bool(test_cfg is not None and test_cfg.get('metrics', None)) or not save_image
+        out_dtype = 'both' if (want_f32 and save_image) else (torch.float32 if want_f32 else torch.uint8)
+
     def finish(data, out=None, fps=None):
         with torch.no_grad():
             kw = {} if out is None else {'precomputed_output': out}
+            if byte_frames:
+                kw['out_dtype'] = out_dtype
             res = model(test_mode=True, save_image=save_image, save_path=save_path, **kw, **data)
         if fps is None:
             fps = data['lq'].shape[1] / model.last_forward_seconds if getattr(model, 'last_forward_seconds', None) else 0.0
         local.append([float(res['eval_result'].get(m, float('nan'))) for m in metrics] + [fps])
 
     held = None
-    for data in ClipPrefetcher(dataset, mine, device, depth=2 if pairs else 1):
+    for data in ClipPrefetcher(dataset, mine, device, depth=2 if pairs else 1, byte_frames=byte_frames):
         if not pairs:
             finish(data)
             continue
@@ -142,17 +168,26 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
             finish(held)
             held = data
             continue
-        both = [torch.cat([held[k], data[k]]) for k in GENERATOR_INPUTS]
-        with torch.no_grad():
-            torch.cuda.synchronize()
-            t0 = time.time()
-            out = model.generator(*both)
-            torch.cuda.synchronize()
-            dt = time.time() - t0
+        if byte_frames:         # the two clips where they are: no concatenation
+            with torch.no_grad():
+                torch.cuda.synchronize()
+                t0 = time.time()
+                outs = model.generator.forward_clips([tuple(c[k] for k in GENERATOR_INPUTS) for c in (held, data)], out_dtype=out_dtype)
+                torch.cuda.synchronize()
+                dt = time.time() - t0
+        else:
+            both = [torch.cat([held[k], data[k]]) for k in GENERATOR_INPUTS]
+            with torch.no_grad():
+                torch.cuda.synchronize()
+                t0 = time.time()
+                out = model.generator(*both)
+                torch.cuda.synchronize()
+                dt = time.time() - t0
+            outs = (out[0:1], out[1:2])
         model.last_forward_seconds = dt
         fps = (held['lq'].shape[1] + data['lq'].shape[1]) / dt
-        finish(held, out[0:1], fps)
-        finish(data, out[1:2], fps)
+        finish(held, outs[0], fps)
+        finish(data, outs[1], fps)
         held = None
     if held is not None:
         finish(held)

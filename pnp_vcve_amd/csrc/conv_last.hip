@@ -11,8 +11,11 @@
 //
 // Block = 128 threads = one 8x16 output tile; LDS 10 x 18 x 272 B = 48960 B -> 3 blocks per CU.
 #include "conv_mfma.h"
+#include "prep.h"
 
 namespace {
+
+__device__ const PnpU8Table k_u8_table = PnpU8Table();      // byte frames (IO = 1): 1 KiB, cache resident; 3 lookups per tap of the frame
 
 constexpr int TH = 8, TW = 16, PW = 18, PIX = (TH + 2) * PW, PSTR = 17;
 constexpr int LDS_BYTES = PIX * PSTR * 16;
@@ -23,7 +26,11 @@ constexpr int SIT = (PIX * 16 + 127) / 128;          // float4 halo loads per th
 // latency are the launch): 512 threads, thread group g = t >> 7 contracts input channels 16 g .. 16 g + 15 of every tap for pixel
 // t & 127 (the weights stay wave-uniform scalars), the four partial sums meet in LDS -- 16 -> 6 us per 128x128 frame; the
 // summation order differs from KS = 1 in the last bits (both are held to 2e-6 against the matrix-core form).
-template <int KS>
+// IO = 1 (launch_conv_last_io): the byte boundary.  The frame to add comes from a.lr_u8 (h,w,3 bytes through the table) when that is
+// set, and the sum goes to a.out as fp32 planes and / or to a.out_u8 as (H,W,3) bytes, whichever is set.  The contraction, the
+// bilinear expression and the sum are the IO = 0 text: the fp32 value is the same bit for bit, the byte is frames_to_rgb8_kernel's
+// arithmetic on it.  3 byte stores per pixel, 48 contiguous bytes per tile row.
+template <int KS, int IO = 0>
 __global__ __launch_bounds__(128 * KS) void conv_last_valu_kernel(const ConvArgs a, const float* __restrict__ wv) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     f32x4* sA = reinterpret_cast<f32x4*>(smem_raw);
@@ -59,7 +66,27 @@ __global__ __launch_bounds__(128 * KS) void conv_last_valu_kernel(const ConvArgs
     const int gy = ty0 + py, gx = tx0 + px;
     const bool inb = gy < H && gx < W;
     float base[3] = {0.f, 0.f, 0.f};
-    if (inb) {
+    if (IO && inb && a.lr_u8) {
+        if (a.out_mode == 2) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) base[c] = k_u8_table.v[a.lr_u8[((long)gy * W + gx) * 3 + c]];
+        } else {        // (the fp32 branch's coordinates and expression, the four taps read as bytes)
+            const int lh = H >> 2, lw = W >> 2;
+            float sy = (gy + 0.5f) * 0.25f - 0.5f, sx = (gx + 0.5f) * 0.25f - 0.5f;
+            sy = sy < 0.f ? 0.f : sy;
+            sx = sx < 0.f ? 0.f : sx;
+            const int y0 = (int)sy, x0 = (int)sx;
+            const int y1 = y0 + (y0 < lh - 1 ? 1 : 0), x1 = x0 + (x0 < lw - 1 ? 1 : 0);
+            const float ly = sy - y0, lx = sx - x0;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const unsigned char* p = a.lr_u8 + c;
+                const float v00 = k_u8_table.v[p[((long)y0 * lw + x0) * 3]], v01 = k_u8_table.v[p[((long)y0 * lw + x1) * 3]];
+                const float v10 = k_u8_table.v[p[((long)y1 * lw + x0) * 3]], v11 = k_u8_table.v[p[((long)y1 * lw + x1) * 3]];
+                base[c] = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+            }
+        }
+    } else if (inb) {
         if (a.out_mode == 2) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) base[c] = a.lr[c * a.lr_plane + (long)gy * W + gx];
@@ -133,7 +160,13 @@ __global__ __launch_bounds__(128 * KS) void conv_last_valu_kernel(const ConvArgs
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float u = fmaxf(v[c], 0.f) + neg_slope * fminf(v[c], 0.f);
-            a.out[c * plane + o] = u + base[c];
+            if constexpr (IO) {
+                const float x = u + base[c];
+                if (a.out) a.out[c * plane + o] = x;
+                if (a.out_u8) a.out_u8[o * 3 + c] = (unsigned char)rintf(fminf(fmaxf(x, 0.f), 1.f) * 255.0f);
+            } else {
+                a.out[c * plane + o] = u + base[c];
+            }
         }
     }
 }
@@ -154,14 +187,20 @@ int launch_pack_last_valu(const float* w_oihw, float* dst, hipStream_t stream) {
 }
 
 bool conv_last_valu_eligible(const ConvArgs& a, int cfg, int grid_y) {
-    return cfg == CONV_CFG_RGB && grid_y == 1 && a.wvalu && a.nsrc == 1 && a.src_c[0] == 64 &&
-           (a.out_mode == 2 || a.out_mode == 3) && a.lr && a.bias && !a.wpar && !a.residual && !a.gamma && !a.src_f16 &&
-           !a.out_f16;
+    return conv_last_valu_shape(a, cfg, grid_y, a.lr != nullptr);
 }
 
 int launch_conv_last_valu(const ConvArgs& a, hipStream_t stream) {
     const int tiles = ((a.W + TW - 1) / TW) * ((a.H + TH - 1) / TH);
     if (tiles < 768) hipLaunchKernelGGL(conv_last_valu_kernel<4>, dim3(tiles), dim3(512), LDS_BYTES, stream, a, a.wvalu);
     else hipLaunchKernelGGL(conv_last_valu_kernel<1>, dim3(tiles), dim3(128), LDS_BYTES, stream, a, a.wvalu);
+    return (int)hipGetLastError();
+}
+
+int launch_conv_last_io(const ConvArgs& a, hipStream_t stream) {
+    if (!conv_last_valu_shape(a, CONV_CFG_RGB, 1, a.lr || a.lr_u8) || (!a.out && !a.out_u8)) return PNP_ERR_UNSUPPORTED;
+    const int tiles = ((a.W + TW - 1) / TW) * ((a.H + TH - 1) / TH);
+    if (tiles < 768) hipLaunchKernelGGL((conv_last_valu_kernel<4, 1>), dim3(tiles), dim3(512), LDS_BYTES, stream, a, a.wvalu);
+    else hipLaunchKernelGGL((conv_last_valu_kernel<1, 1>), dim3(tiles), dim3(128), LDS_BYTES, stream, a, a.wvalu);
     return (int)hipGetLastError();
 }

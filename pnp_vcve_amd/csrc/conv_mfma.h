@@ -66,6 +66,10 @@ struct ConvArgs {
     int out_mode;           // 0 NHWC64 | 1 NHWC64 pixel-shuffle(2), sub-pixel = blockIdx.y
                             // 2 RGB NCHW + lr | 3 RGB NCHW + bilinear x4 upsample of lr (H/4 x W/4)
                             // 4 NHWC with out_cstride channels per pixel, channel block 64*blockIdx.y
+    // byte frames (launch_conv_last_io only; last, so that every other kernel's view of the struct is what it was):
+    const unsigned char* lr_u8;   // out_mode 2/3: the frame to add as (h,w,3) uint8 RGB, read through PnpU8Table INSTEAD of lr; or nullptr
+    unsigned char* out_u8;        // out_mode 2/3: (H,W,3) uint8 RGB = round_half_even(clamp(x,0,1) * 255) of the fp32 sum x, written next to
+                                  // `out` (or instead of it: out == nullptr); or nullptr
 };
 
 enum { CONV_CFG_BIG = 0,    // 8x16 pixel tile, 64 output channels per block
@@ -143,8 +147,17 @@ int launch_par_frame_any(const int* flags, int* any, int frames, int H, int W, h
 
 // conv_last on the vector ALUs (conv_last.hip): OIHW (3,64,3,3) -> [9][64][4]; 2304 floats
 int launch_pack_last_valu(const float* w_oihw, float* dst, hipStream_t stream);
+// which launches the vector-ALU conv_last takes, `has_frame`: the frame to add is there in the form the caller will read (a pure
+// function of the arguments: shared by conv_last.hip's two launchers and the host-only scheduler test build)
+static inline bool conv_last_valu_shape(const ConvArgs& a, int cfg, int grid_y, bool has_frame) {
+    return cfg == CONV_CFG_RGB && grid_y == 1 && a.wvalu && a.nsrc == 1 && a.src_c[0] == 64 && (a.out_mode == 2 || a.out_mode == 3) &&
+           has_frame && a.bias && !a.wpar && !a.residual && !a.gamma && !a.src_f16 && !a.out_f16;
+}
 bool conv_last_valu_eligible(const ConvArgs& a, int cfg, int grid_y);
 int launch_conv_last_valu(const ConvArgs& a, hipStream_t stream);
+// the same kernel with a byte boundary (ConvArgs::lr_u8 / out_u8): the frame read as bytes and / or the output written as bytes, the
+// fp32 sum and its order untouched.  PNP_ERR_UNSUPPORTED unless the launch is conv_last_valu_eligible apart from `lr`
+int launch_conv_last_io(const ConvArgs& a, hipStream_t stream);
 
 // Winograd F(2x2,3x3) variant of the single-source 64 -> 64 conv (conv_wino.hip): 2.25x fewer matrix FLOPs, fp32 arithmetic, results
 // within ~1e-6 (unit-scale data) of the direct kernels.  Weight images: src[i] = a packed direct-conv image (9 chunks), dst[i] = 16

@@ -27,6 +27,9 @@
 #include "prep.h"
 #include "warp.h"
 #include "dcn.h"
+#ifdef PNP_HOST_STUB
+#include "host_stub/io_stub.h"   // recording stand-ins for the byte-frame launchers (prep.h, conv_mfma.h) of the host-only scheduler tests
+#endif
 
 namespace {
 
@@ -406,6 +409,11 @@ struct ConvCall {
         wvalu_ = wvalu;
         return *this;
     }
+    // conv_last at a byte boundary (ConvArgs::lr_u8 / out_u8): the frame as (h,w,3) bytes instead of rgb()'s planes, the output as
+    // (H,W,3) bytes next to (or, with to(nullptr), instead of) the fp32 planes
+    const unsigned char* lr8_ = nullptr;
+    unsigned char* out8_ = nullptr;
+    ConvCall& rgb8(const unsigned char* lr8, unsigned char* out8) { lr8_ = lr8; out8_ = out8; return *this; }
     // fp16 path: 1 = the output is an fp16 map, 2 = the (single) source is one
     ConvCall& f16_map(int io16) { io16_ = io16; return *this; }
     // fp16 path with mirrors (PNP_OPT_F16_MIRRORS): the fp16 copy its producer wrote of the source added last (read INSTEAD of
@@ -426,6 +434,8 @@ struct Workspace {
     int* parflags;    // per frame, per 8x16 tile: which partition planes are nonzero there (ConvArgs::par_flags)
     float* wino;      // PNP_PREC_F32: Winograd images of one branch's dynamic convs for the frame in flight (2 per block; gain folded in)
     int* queue;       // PNP_PREC_F16X3: the split kernel's tile queue (ConvArgs::tile_queue), 16 ints, zero between launches
+    // byte frames on a last conv that keeps its fp32 interface (io_staged): ONE frame of fp32 planes each way, converted per frame
+    float *lr1, *out1;
     int64_t bytes;
 };
 
@@ -591,7 +601,12 @@ bool make_schedule(const pnp_generator* g, int t, const std::vector<char>& key, 
     return true;
 }
 
-Workspace carve(const pnp_generator* g, char* base, int t, int h, int w) {
+// Byte frames: conv_last's vector-ALU kernel reads and writes bytes itself (launch_conv_last_io).  The two other kernels that add the
+// frame -- the fp16 path's RGB body and the matrix-core conv under PNP_OPT_CONV_LAST_VALU = 0 -- keep their fp32 interface behind a
+// one-frame fp32 copy of the frame and / or of the output in the workspace.
+bool io_staged(const pnp_generator* g) { return g->prec == PNP_PREC_F16 || !g->opt[PNP_OPT_CONV_LAST_VALU]; }
+
+Workspace carve(const pnp_generator* g, char* base, int t, int h, int w, int lq_format = PNP_FRAMES_F32_NCHW, int out_mask = PNP_OUT_F32) {
     Workspace W;
     int64_t off = 0;
     const int64_t hw = (int64_t)h * w;
@@ -636,6 +651,10 @@ Workspace carve(const pnp_generator* g, char* base, int t, int h, int w) {
     W.parany = reinterpret_cast<int*>(take(t));        // (not last: the harness shrinks the workspace and expects the last region to be touched)
     W.parflags = reinterpret_cast<int*>(take((int64_t)t * ((w + 15) / 16) * ((h + 7) / 8)));
     W.queue = g->prec == PNP_PREC_F16X3 ? reinterpret_cast<int*>(take(16)) : nullptr;
+    // (behind everything else and only in the modes that need them: the fp32 boundary's layout and size are what they were)
+    const bool staged = io_staged(g);
+    W.lr1 = (staged && lq_format == PNP_FRAMES_U8_HWC) ? take(hw * 3) : nullptr;
+    W.out1 = (staged && out_mask == PNP_OUT_U8) ? take(hw * 3 * (g->cfg.vsr ? 16 : 1)) : nullptr;
     W.bytes = off;
     return W;
 }
@@ -816,10 +835,18 @@ int pnp_generator_min_resident(const pnp_generator* g, int t) {
 namespace {
 
 // One sample (clip) of the batch on one stream with one workspace context.
-int forward_sample(const pnp_generator* g, const float* flat, const float* packed, const float* lr_b, const float* mv_b,
-                   const float* par_b, const float* sl, const float* qp, const float* bq, float* out_b,
+int forward_sample(const pnp_generator* g, const float* flat, const float* packed, const pnp_clip_io& io, int lq_format, int out_mask,
+                   const float* sl, const float* qp, const float* bq,
                    const Workspace& W, int t, int h, int w, hipStream_t st, bool alone) {
     const auto& c = g->cfg;
+    // the clip's tensors: the frames as fp32 planes or as bytes, the output as fp32 planes and / or bytes
+    const float* const lr_b = lq_format == PNP_FRAMES_U8_HWC ? nullptr : static_cast<const float*>(io.lq_dev);
+    const unsigned char* const lq8 = lq_format == PNP_FRAMES_U8_HWC ? static_cast<const unsigned char*>(io.lq_dev) : nullptr;
+    float* const out_b = (out_mask & PNP_OUT_F32) ? io.out_f32_dev : nullptr;
+    unsigned char* const out8 = (out_mask & PNP_OUT_U8) ? io.out_u8_dev : nullptr;
+    const float* const mv_b = io.mvs_dev;
+    const float* par_b = io.par_dev;
+    const bool staged = (lq8 || out8) && io_staged(g);
     const int64_t hw = (int64_t)h * w, fm = hw * 64;
     const int E = c.num_experts;
     const int cfg_lr = conv_pick_cfg(h, w);
@@ -940,6 +967,8 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
         a.act = q.act_;
         a.out_mode = q.mode_;
         a.out_cstride = 448;
+        a.lr_u8 = q.lr8_;
+        a.out_u8 = q.out8_;
         a.out_f16 = q.io16_ & 1;          // io16: bit 0 the output is an fp16 map, bit 1 source 0 is one
         a.src_f16 = (q.io16_ & 2) ? 1 : 0;
         if (mirrors) {
@@ -981,6 +1010,7 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
                 chain.forked = true;
             }
         }
+        if (a.lr_u8 || a.out_u8) return launch_conv_last_io(a, st);      // (conv_last only, outside every chain)
         return launch_conv3x3(a, q.cfg_, q.gy_, st);
     };
 
@@ -1031,7 +1061,7 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
             rc = launch_fill(reinterpret_cast<float*>(W.queue), 0.0f, 16, st);
             if (rc) return rc;
         }
-        rc = launch_pack_lr(lr_b, W.lr4, t, h, w, st);
+        rc = lq8 ? launch_pack_lr_u8(lq8, W.lr4, t, h, w, st) : launch_pack_lr(lr_b, W.lr4, t, h, w, st);
         if (rc) return rc;
         // the reference's (eval-mode) sparse evaluation as a dense map (prep.hip): for the whole clip at once, or (bounded schedule)
         // one frame at a time into a one-frame buffer, just before each branch run that reads it
@@ -1243,17 +1273,39 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
             if (sp.sweep == 0) continue;
 
             const float* feat = slot_of(sp.out);
-            const float* lr_i = lr_b + (int64_t)i * 3 * hw;
-            float* out_i = out_b + (int64_t)i * 3 * hw * os * os;
+            const float* lr_i = lr_b ? lr_b + (int64_t)i * 3 * hw : nullptr;
+            float* out_i = out_b ? out_b + (int64_t)i * 3 * hw * os * os : nullptr;
+            const unsigned char* lr8_i = lq8 ? lq8 + (int64_t)i * 3 * hw : nullptr;
+            unsigned char* out8_i = out8 ? out8 + (int64_t)i * 3 * hw * os * os : nullptr;
+            // a last conv with an fp32 interface: this frame's bytes to planes in front of it, its planes to bytes behind it (untimed, like pack_lr)
+            auto stage_in = [&]() -> int {
+                if (!staged) return PNP_OK;
+                int r = PNP_OK;
+                if (lr8_i) {
+                    r = launch_frames_from_rgb8(lr8_i, W.lr1, 1, h, w, st);
+                    g->prof_last = nullptr;
+                    lr_i = W.lr1;
+                    lr8_i = nullptr;
+                }
+                if (out8_i && !out_i) out_i = W.out1;
+                return r;
+            };
+            auto stage_out = [&]() -> int {
+                if (!staged || !out8_i) return PNP_OK;
+                g->prof_last = nullptr;
+                return launch_frames_to_rgb8(out_i, out8_i, 1, h * os, w * os, st);
+            };
             // conv_hr's output feeds only conv_last: an fp16 map on the fp16 path
             const int o16 = f16_maps ? 1 : 0, s16 = f16_maps ? 2 : 0;
             if (!c.vsr) {   // :144-146
                 rc = conv(ConvCall(h, w, cfg_lr).source(feat, 64, packed + g->hr_img).mirror16(s16of(sp.out)).bias(flat + g->hr_bias)
                               .wino(wino_on ? packed + g->hr_wino : nullptr).units(wino_units(h, w)).act(2).to(W.tmp1).f16_map(o16));
                 if (!rc) rc = chain_close();
+                if (!rc) rc = stage_in();
                 if (!rc)
                     rc = conv(ConvCall(h, w, CONV_CFG_RGB).source(W.tmp1, 64, packed + g->last_img).bias(packed + g->last_bias)
-                                  .mode(2).rgb(lr_i, hw, packed + g->last_valu).to(out_i).f16_map(s16));
+                                  .mode(2).rgb(lr_i, hw, packed + g->last_valu).rgb8(lr8_i, staged ? nullptr : out8_i).to(out_i).f16_map(s16));
+                if (!rc) rc = stage_out();
                 if (rc) return rc;
             } else {        // :135-142: two PixelShufflePack(2) convs (4 sub-pixel weight images each), conv_hr, conv_last + x4 bilinear lr
                 // every map of the head is read by exactly one conv, as an MFMA A operand: fp16 maps all the way on the fp16 path
@@ -1267,9 +1319,11 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
                     rc = conv(ConvCall(4 * h, 4 * w, conv_pick_cfg(4 * h, 4 * w)).source(W.u2, 64, packed + g->hr_img)
                                   .bias(flat + g->hr_bias).wino(wino_on ? packed + g->hr_wino : nullptr).units(wino_units(4 * h, 4 * w)).act(2).to(W.u3)
                                   .f16_map(o16 | s16));
+                if (!rc) rc = stage_in();
                 if (!rc)
                     rc = conv(ConvCall(4 * h, 4 * w, CONV_CFG_RGB).source(W.u3, 64, packed + g->last_img)
-                                  .bias(packed + g->last_bias).mode(3).rgb(lr_i, hw, packed + g->last_valu).to(out_i).f16_map(s16));
+                                  .bias(packed + g->last_bias).mode(3).rgb(lr_i, hw, packed + g->last_valu).rgb8(lr8_i, staged ? nullptr : out8_i).to(out_i).f16_map(s16));
+                if (!rc) rc = stage_out();
                 if (rc) return rc;
             }
         }
@@ -1277,15 +1331,13 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
     return PNP_OK;
 }
 
-}  // namespace
+bool io_args_ok(int lq_format, int out_mask) {
+    return (lq_format == PNP_FRAMES_F32_NCHW || lq_format == PNP_FRAMES_U8_HWC) && out_mask >= 1 && out_mask <= (PNP_OUT_F32 | PNP_OUT_U8);
+}
 
-extern "C" {
-
-int pnp_generator_forward(const pnp_generator* g, const float* flat, const float* packed, const float* lrs,
-                          const float* mvs, const float* par, const float* slices, const float* qps,
-                          const float* base_qps, float* out, void* workspace, int64_t workspace_bytes, int n, int t,
-                          int h, int w, void* stream_) {
-    hipStream_t st = (hipStream_t)stream_;
+// What a forward refuses before it looks at a clip: batch and frame size, the bound, the workspace.  PNP_OK or the error.
+int forward_check(const pnp_generator* g, int n, int t, int h, int w, int lq_format, int out_mask, const void* workspace,
+                  int64_t workspace_bytes) {
     if (n < 1 || t < 1) return PNP_ERR_BAD_ARG;
     if (g->cfg.sparse_val && g->opt[PNP_OPT_SPARSE_EVAL] && n != 1) return PNP_ERR_UNSUPPORTED;   // sparse_conv reads feature[0] only (sr_backbone_utils.py:262-275)
     if (h < 64 || w < 64) return PNP_ERR_SIZE_ASSERT;
@@ -1296,10 +1348,18 @@ int pnp_generator_forward(const pnp_generator* g, const float* flat, const float
         return PNP_ERR_UNSUPPORTED;
     int plan_r, plan_l;
     if (bounded_mode(g, t) && !plan_pick(t, g->cfg.with_cat, g->max_resident, &plan_r, &plan_l)) return PNP_ERR_BAD_ARG;
-    const int64_t ctx_bytes = carve(g, nullptr, t, h, w).bytes;
+    const int64_t ctx_bytes = carve(g, nullptr, t, h, w, lq_format, out_mask).bytes;
     if (workspace_bytes < ctx_bytes || (reinterpret_cast<uintptr_t>(workspace) & 255)) return PNP_ERR_WORKSPACE;
-    const int64_t hw = (int64_t)h * w;
-    const int os = g->cfg.vsr ? 4 : 1;
+    return PNP_OK;
+}
+
+// The batch loop behind both entry points: n clips, each named by a descriptor, `lq_format` / `out_mask` for all of them.
+int forward_batch(const pnp_generator* g, const float* flat, const float* packed, const pnp_clip_io* clips, int n, int lq_format,
+                  int out_mask, const float* slices, const float* qps, const float* base_qps, void* workspace, int64_t workspace_bytes,
+                  int t, int h, int w, hipStream_t st) {
+    const int bad = forward_check(g, n, t, h, w, lq_format, out_mask, workspace, workspace_bytes);
+    if (bad) return bad;
+    const int64_t ctx_bytes = carve(g, nullptr, t, h, w, lq_format, out_mask).bytes;
     // Samples of a batch never interact.  With a workspace of k contexts they run k at a time on the library's side
     // streams (forked from / joined to the caller's stream with events): small frames leave most of the chip idle.
     int nctx = (int)(workspace_bytes / ctx_bytes);
@@ -1328,11 +1388,9 @@ int pnp_generator_forward(const pnp_generator* g, const float* flat, const float
     g->band_recs.clear();
     for (int b = 0; b < n && rc == PNP_OK; ++b) {
         const int k = b % nctx;
-        const Workspace W = carve(g, (char*)workspace + (int64_t)k * ctx_bytes, t, h, w);
-        rc = forward_sample(g, flat, packed, lrs + (int64_t)b * t * 3 * hw, mvs + (int64_t)b * t * 4 * hw,
-                            par + (int64_t)b * t * 3 * hw, slices + (int64_t)b * t, qps + (int64_t)b * t,
-                            base_qps + (int64_t)b * t, out + (int64_t)b * t * 3 * hw * os * os, W, t, h, w,
-                            nctx > 1 ? g->side_streams[k] : st, nctx == 1);
+        const Workspace W = carve(g, (char*)workspace + (int64_t)k * ctx_bytes, t, h, w, lq_format, out_mask);
+        rc = forward_sample(g, flat, packed, clips[b], lq_format, out_mask, slices + (int64_t)b * t,
+                            qps + (int64_t)b * t, base_qps + (int64_t)b * t, W, t, h, w, nctx > 1 ? g->side_streams[k] : st, nctx == 1);
     }
     if (nctx > 1) {      // join even after an error: the caller's stream must not run ahead of what was launched
         for (int k = 0; k < nctx; ++k) {
@@ -1342,6 +1400,50 @@ int pnp_generator_forward(const pnp_generator* g, const float* flat, const float
         }
     }
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t pnp_generator_workspace_bytes_io(const pnp_generator* g, int t, int h, int w, int lq_format, int out_mask) {
+    if (!g || !io_args_ok(lq_format, out_mask)) return -1;
+    int R, L;
+    if (bounded_mode(g, t) && !plan_pick(t, g->cfg.with_cat, g->max_resident, &R, &L)) return -1;
+    return carve(g, nullptr, t, h, w, lq_format, out_mask).bytes;
+}
+
+int pnp_generator_forward(const pnp_generator* g, const float* flat, const float* packed, const float* lrs,
+                          const float* mvs, const float* par, const float* slices, const float* qps,
+                          const float* base_qps, float* out, void* workspace, int64_t workspace_bytes, int n, int t,
+                          int h, int w, void* stream_) {
+    // (its own errors first, as ever: they are decided before a pointer of the batch is touched, and callers probe them with null buffers)
+    const int bad = forward_check(g, n, t, h, w, PNP_FRAMES_F32_NCHW, PNP_OUT_F32, workspace, workspace_bytes);
+    if (bad) return bad;
+    // n descriptors from the strides: sample b of every tensor
+    const int64_t hw = (int64_t)h * w, os = g->cfg.vsr ? 4 : 1;
+    std::vector<pnp_clip_io> clips(n);
+    for (int b = 0; b < n; ++b)
+        clips[b] = pnp_clip_io{lrs + (int64_t)b * t * 3 * hw, mvs + (int64_t)b * t * 4 * hw, par + (int64_t)b * t * 3 * hw,
+                               out + (int64_t)b * t * 3 * hw * os * os, nullptr};
+    return forward_batch(g, flat, packed, clips.data(), n, PNP_FRAMES_F32_NCHW, PNP_OUT_F32, slices, qps, base_qps, workspace, workspace_bytes,
+                         t, h, w, (hipStream_t)stream_);
+}
+
+int pnp_generator_forward_clips(const pnp_generator* g, const float* flat, const float* packed, const pnp_clip_io* clips, int n,
+                                int lq_format, int out_mask, const float* slices, const float* qps, const float* base_qps,
+                                void* workspace, int64_t workspace_bytes, int t, int h, int w, void* stream_) {
+    // what only this entry can get wrong, in front of everything else (no HIP call has been made)
+    if (!g || !clips || n < 1 || !io_args_ok(lq_format, out_mask)) return PNP_ERR_BAD_ARG;
+    for (int b = 0; b < n; ++b) {
+        const pnp_clip_io& c = clips[b];
+        if (!c.lq_dev || !c.mvs_dev || !c.par_dev) return PNP_ERR_BAD_ARG;
+        if ((out_mask & PNP_OUT_F32) && !c.out_f32_dev) return PNP_ERR_BAD_ARG;
+        if ((out_mask & PNP_OUT_U8) && (!c.out_u8_dev || (reinterpret_cast<uintptr_t>(c.out_u8_dev) & 3))) return PNP_ERR_BAD_ARG;
+        if (lq_format == PNP_FRAMES_U8_HWC && (reinterpret_cast<uintptr_t>(c.lq_dev) & 3)) return PNP_ERR_BAD_ARG;
+    }
+    return forward_batch(g, flat, packed, clips, n, lq_format, out_mask, slices, qps, base_qps, workspace, workspace_bytes, t, h, w,
+                         (hipStream_t)stream_);
 }
 
 int pnp_generator_profile(pnp_generator* g, int enable) {

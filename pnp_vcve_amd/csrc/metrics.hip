@@ -187,12 +187,43 @@ __global__ __launch_bounds__(256) void frames_to_rgb8_kernel(const float* __rest
         out[i * 3 + c] = (unsigned char)rintf(v);
     }
 }
+
+// The inverse layout: (frames,h,w,3) uint8 RGB -> (frames,3,h,w) fp32 planes, byte v -> float(v) / 255.0f through the table of
+// prep.h (what the loader's RescaleToZeroOne + HWC->CHW make of a decoded frame, bit for bit).
+__device__ const PnpU8Table k_u8_table = PnpU8Table();
+
+__global__ __launch_bounds__(256) void frames_from_rgb8_kernel(const unsigned char* __restrict__ in, float* __restrict__ out,
+                                                               long hw, long total) {
+    __shared__ float tab[256];
+    tab[threadIdx.x] = k_u8_table.v[threadIdx.x];
+    __syncthreads();
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;       // over frames * hw pixels
+    if (i >= total) return;
+    const long f = i / hw, p = i - f * hw;
+    float* d = out + f * 3 * hw + p;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d[c * hw] = tab[in[i * 3 + c]];
+}
 }  // namespace
+
+int launch_frames_to_rgb8(const float* frames, unsigned char* out, int nframes, int h, int w, hipStream_t stream) {
+    const long hw = (long)h * w, total = hw * nframes;
+    hipLaunchKernelGGL(frames_to_rgb8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, frames, out, hw, total);
+    return (int)hipGetLastError();
+}
+
+int launch_frames_from_rgb8(const unsigned char* in, float* out, int nframes, int h, int w, hipStream_t stream) {
+    const long hw = (long)h * w, total = hw * nframes;
+    hipLaunchKernelGGL(frames_from_rgb8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, in, out, hw, total);
+    return (int)hipGetLastError();
+}
 
 extern "C" int pnp_frames_to_rgb8(const float* frames, unsigned char* out, int nframes, int h, int w, void* stream) {
     if (nframes < 1 || h < 1 || w < 1 || !frames || !out) return PNP_ERR_BAD_ARG;
-    const long hw = (long)h * w, total = hw * nframes;
-    hipLaunchKernelGGL(frames_to_rgb8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       frames, out, hw, total);
-    return (int)hipGetLastError();
+    return launch_frames_to_rgb8(frames, out, nframes, h, w, (hipStream_t)stream);
+}
+
+extern "C" int pnp_frames_from_rgb8(const unsigned char* in, float* out, int nframes, int h, int w, void* stream) {
+    if (nframes < 1 || h < 1 || w < 1 || !in || !out) return PNP_ERR_BAD_ARG;
+    return launch_frames_from_rgb8(in, out, nframes, h, w, (hipStream_t)stream);
 }

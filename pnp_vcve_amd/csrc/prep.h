@@ -8,6 +8,20 @@
 int launch_zero_words(void* dst, long n_words, hipStream_t stream);
 // (T,3,H,W) NCHW frames -> (T,H,W,4) pixel-major, 4th channel zero
 int launch_pack_lr(const float* lrs, float* lr4, int T, int H, int W, hipStream_t stream);
+// Byte frames.  A decoder's byte v stands for the fp32 value float(v) / 255.0f by IEEE division: the 256 values,
+// evaluated by the compiler (round to nearest even, as numpy's float32 division).  A device-side multiply by a rounded 1/255 is not
+// bit-equal to it, so every kernel that reads a byte frame looks its value up here.
+struct PnpU8Table {
+    float v[256];
+    constexpr PnpU8Table() : v() {
+        for (int i = 0; i < 256; ++i) v[i] = (float)i / 255.0f;
+    }
+};
+// (T,H,W,3) uint8 RGB frames -> (T,H,W,4) pixel-major RGB0 fp32, 4th channel zero; lq 4-byte aligned.  3 B read + 16 B written per pixel
+int launch_pack_lr_u8(const unsigned char* lq, float* lr4, int T, int H, int W, hipStream_t stream);
+// (n,H,W,3) uint8 RGB <-> (n,3,H,W) fp32 planes (metrics.hip): the table one way, round_half_even(clamp(x,0,1) * 255) the other
+int launch_frames_from_rgb8(const unsigned char* in, float* out, int nframes, int H, int W, hipStream_t stream);
+int launch_frames_to_rgb8(const float* in, unsigned char* out, int nframes, int H, int W, hipStream_t stream);
 // (T,3,H,W) partition maps -> the dense equivalent of the reference's sparse_val evaluation (prep.hip)
 int launch_par_sparse(const float* par, float* out, int T, int H, int W, hipStream_t stream);
 // DCN conv_offset output channel order used by this build (dcn.hip): packed channel c' -> reference channel of

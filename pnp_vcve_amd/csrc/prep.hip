@@ -21,6 +21,30 @@ __global__ __launch_bounds__(256) void pack_lr_kernel(const float* __restrict__ 
     reinterpret_cast<f32x4*>(lr4)[i] = v;
 }
 
+// Byte frames: (T,H,W,3) uint8 RGB -> the (T,H,W,4) RGB0 conv source, every value through the table of prep.h (staged in LDS: the
+// lookups are per-lane gathers).  One thread = 4 pixels = three dword loads (12 B) and four 16-byte stores; h and w are multiples of
+// 4, so a frame is whole groups and a group never straddles two frames' bytes differently than it does two pixels'.
+__device__ const PnpU8Table k_u8_table = PnpU8Table();
+
+__global__ __launch_bounds__(256) void pack_lr_u8_kernel(const unsigned* __restrict__ lq, float* __restrict__ lr4, long groups) {
+    __shared__ float tab[256];
+    tab[threadIdx.x] = k_u8_table.v[threadIdx.x];
+    __syncthreads();
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= groups) return;
+    // little-endian bytes: a = r0 g0 b0 r1, b = g1 b1 r2 g2, c = b2 r3 g3 b3
+    const unsigned a = lq[3 * i], b = lq[3 * i + 1], c = lq[3 * i + 2];
+    f32x4* d = reinterpret_cast<f32x4*>(lr4) + 4 * i;
+    const f32x4 p0 = {tab[a & 255u], tab[(a >> 8) & 255u], tab[(a >> 16) & 255u], 0.f};
+    const f32x4 p1 = {tab[a >> 24], tab[b & 255u], tab[(b >> 8) & 255u], 0.f};
+    const f32x4 p2 = {tab[(b >> 16) & 255u], tab[b >> 24], tab[c & 255u], 0.f};
+    const f32x4 p3 = {tab[(c >> 8) & 255u], tab[(c >> 16) & 255u], tab[c >> 24], 0.f};
+    d[0] = p0;
+    d[1] = p1;
+    d[2] = p2;
+    d[3] = p3;
+}
+
 // sparse_val (eval): basicvsr_net.py:511-514 generate_indices(par_j) + sr_backbone_utils.py:294-302 sparse_conv:
 // the 1x1 branch j is evaluated where plane j is NONZERO (whatever its value), later planes overwrite earlier ones
 // (mask_roi_back assigns), and the result is divided by 255.  As a dense map: plane j = 1/255 where par_j != 0 and no
@@ -169,6 +193,15 @@ int launch_pack_lr(const float* lrs, float* lr4, int T, int H, int W, hipStream_
     const long hw = (long)H * W, total = hw * T;
     hipLaunchKernelGGL(pack_lr_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, lrs, lr4, hw,
                        total);
+    return (int)hipGetLastError();
+}
+
+int launch_pack_lr_u8(const unsigned char* lq, float* lr4, int T, int H, int W, hipStream_t stream) {
+    const long total = (long)H * W * T;
+    if (T < 1 || (total & 3) || (reinterpret_cast<uintptr_t>(lq) & 3)) return PNP_ERR_BAD_ARG;
+    const long groups = total / 4;
+    hipLaunchKernelGGL(pack_lr_u8_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, stream,
+                       reinterpret_cast<const unsigned*>(lq), lr4, groups);
     return (int)hipGetLastError();
 }
 

@@ -279,32 +279,63 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
     def _contexts(self, n, h, w):
         return min(n, self.LARGE_FRAME_CONTEXTS if h * w >= self.CONCURRENT_BELOW_PIXELS else self.MAX_CONTEXTS)
 
-    def _get_workspace(self, n, t, h, w, device):
+    def _workspace_bytes(self, t, h, w, fmt=_native.FRAMES_F32_NCHW, mask=_native.OUT_F32):
+        """bytes of one workspace context for a boundary (pnp_generator_workspace_bytes / _io: equal at the fp32 boundary)"""
+        L = _native.lib()
+        if (fmt, mask) == (_native.FRAMES_F32_NCHW, _native.OUT_F32):
+            return int(L.pnp_generator_workspace_bytes(self._handle, t, h, w))
+        return int(L.pnp_generator_workspace_bytes_io(self._handle, t, h, w, fmt, mask))
+
+    def _get_workspace(self, n, t, h, w, device, fmt=_native.FRAMES_F32_NCHW, mask=_native.OUT_F32):
         ctx = self._contexts(n, h, w)
-        k = (ctx, t, h, w, str(device), self.max_resident_features)
+        k = (ctx, t, h, w, str(device), self.max_resident_features, fmt, mask)
         ws = self._workspace.get(k)
         if ws is None:
-            nbytes = int(_native.lib().pnp_generator_workspace_bytes(self._handle, t, h, w)) * ctx
+            nbytes = self._workspace_bytes(t, h, w, fmt, mask) * ctx
             self._workspace.clear()        # keep one shape resident
             ws = torch.empty(nbytes, device=device, dtype=torch.uint8)
             self._workspace[k] = ws
         return ws
 
     # ---------------------------------------------------------------- forward
-    def forward(self, lrs, QPs=None, slices=None, mvs=None, base_QPs=None, par_map=None):
+    @staticmethod
+    def _out_mask(out_dtype):
+        if out_dtype is None or out_dtype == torch.float32:
+            return _native.OUT_F32
+        if out_dtype == torch.uint8:
+            return _native.OUT_U8
+        if isinstance(out_dtype, str) and out_dtype == 'both':
+            return _native.OUT_F32 | _native.OUT_U8
+        raise ValueError(f"out_dtype must be None, torch.float32, torch.uint8 or 'both', got {out_dtype!r}")
+
+    def forward(self, lrs, QPs=None, slices=None, mvs=None, base_QPs=None, par_map=None, out_dtype=None):
         """iconvsr_ipb_par.py:44-149.  lrs (n,t,3,h,w); QPs/slices/base_QPs (n,t,1,1,1);
-        mvs (n,t,4,h,w); par_map (n,t,3,h,w).  Returns (n,t,3,h,w) (x4 spatial when vsr)."""
+        mvs (n,t,4,h,w); par_map (n,t,3,h,w).  Returns (n,t,3,h,w) (x4 spatial when vsr).
+
+        Byte frames: a uint8 `lrs` is the decoder's layout (n,t,h,w,3), RGB, byte v standing for float32(v) / float32(255) -- the
+        result is bit-identical to forward(ops.frames_from_rgb8(lrs), ...), without the fp32 clip.  out_dtype: None / torch.float32
+        (the fp32 planes above) | torch.uint8 ((n,t,H,W,3) display bytes, ops.frames_to_rgb8's arithmetic on the same fp32 values) |
+        'both' (the pair (fp32, uint8))."""
         if not lrs.is_cuda:
             raise RuntimeError('PnP-VCVE generator: inputs must be CUDA/HIP tensors; this build has no CPU path '
                                '(the CPU restatement under oracle/ is test infrastructure only)')
-        n, t, c, h, w = lrs.size()
+        mask = self._out_mask(out_dtype)
+        byte_in = lrs.dtype == torch.uint8
+        if byte_in:
+            if lrs.dim() != 5 or lrs.shape[-1] != 3:
+                raise ValueError(f'uint8 frames must be (n,t,h,w,3) -- the decoder\'s HWC RGB layout -- got {tuple(lrs.shape)}')
+            n, t, h, w, c = lrs.size()
+        else:
+            n, t, c, h, w = lrs.size()
         assert h >= 64 and w >= 64, (
             f'The height and width of inputs should be at least 64, but got {h} and {w}.')
         dev = lrs.device
         self._check_resident(t)
         with torch.cuda.device(dev):
             self._ensure_packed(dev)
-            lrs_c = lrs.detach().float().contiguous()
+            lrs_c = lrs.detach().contiguous() if byte_in else lrs.detach().float().contiguous()
+            if byte_in and lrs_c.data_ptr() % 4:     # the library reads the bytes as dwords: a view at an odd storage offset is copied
+                lrs_c = lrs_c.clone()
             mvs_c = mvs.detach().float().contiguous()
             par_c = par_map.detach().float().contiguous()
             if mvs_c.shape != (n, t, 4, h, w) or par_c.shape != (n, t, 3, h, w):
@@ -332,9 +363,141 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
             side = torch.stack([slices.reshape(n, t).float(),
                                 QPs.reshape(n, t).float() if QPs is not None else zero,
                                 base_QPs.reshape(n, t).float() if base_QPs is not None else zero]).cpu().contiguous()
+            if byte_in or mask != _native.OUT_F32:
+                return self._forward_io(lrs_c, mvs_c, par_c, side, mask)
             # the PyTorch custom op over pnp_generator_forward (pnp_vcve_amd/torch_ops.py)
             out = torch.ops.pnpvcve.generator_forward(self._op_handle, lrs_c, mvs_c, par_c, side)
         return out
+
+    # ---------------------------------------------------------------- byte frames, clips by pointer
+    def _alloc_outs(self, n, t, h, w, mask, dev):
+        s = 4 if self.vsr else 1
+        f32 = torch.empty((n, t, 3, h * s, w * s), device=dev, dtype=torch.float32) if mask & _native.OUT_F32 else None
+        u8 = torch.empty((n, t, h * s, w * s, 3), device=dev, dtype=torch.uint8) if mask & _native.OUT_U8 else None
+        return f32, u8
+
+    @staticmethod
+    def _ret(f32, u8, mask):
+        return f32 if mask == _native.OUT_F32 else (u8 if mask == _native.OUT_U8 else (f32, u8))
+
+    def _forward_io(self, lrs_c, mvs_c, par_c, side, mask):
+        """forward() at a byte boundary: (n,...) batch tensors in, the outputs allocated as (n,...) tensors, every clip handed to
+        pnp_generator_forward_clips as a descriptor of its slices."""
+        byte_in = lrs_c.dtype == torch.uint8
+        n, t = lrs_c.shape[:2]
+        h, w = lrs_c.shape[2:4] if byte_in else lrs_c.shape[3:5]
+        dev = lrs_c.device
+        if self.use_graphs and not self._profiling:
+            return self._forward_graphed(lrs_c, mvs_c, par_c, side, None, mask)
+        f32, u8 = self._alloc_outs(n, t, h, w, mask, dev)
+        ws = self._get_workspace(n, t, h, w, dev, int(byte_in), mask)
+        self._launch_clips(list(lrs_c), list(mvs_c), list(par_c), side, list(f32) if f32 is not None else None,
+                           list(u8) if u8 is not None else None, ws, t, h, w)
+        return self._ret(f32, u8, mask)
+
+    def _launch_clips(self, lrs, mvs, par, side, outs_f32, outs_u8, ws, t, h, w):
+        """One pnp_generator_forward_clips call on torch's current stream: per-clip contiguous tensors, nothing concatenated."""
+        n = len(lrs)
+        byte_in = lrs[0].dtype == torch.uint8
+        mask = (_native.OUT_F32 if outs_f32 is not None else 0) | (_native.OUT_U8 if outs_u8 is not None else 0)
+        clips = (_native.ClipIO * n)()
+        for b in range(n):
+            clips[b] = _native.ClipIO(lrs[b].data_ptr(), mvs[b].data_ptr(), par[b].data_ptr(),
+                                      outs_f32[b].data_ptr() if outs_f32 is not None else None,
+                                      outs_u8[b].data_ptr() if outs_u8 is not None else None)
+        fp = ctypes.POINTER(ctypes.c_float)
+        base = side.data_ptr()
+        P = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
+        rc = _native.lib().pnp_generator_forward_clips(
+            self._handle, P(self._flat), P(self._packed), ctypes.cast(clips, ctypes.c_void_p), n,
+            _native.FRAMES_U8_HWC if byte_in else _native.FRAMES_F32_NCHW, mask, ctypes.cast(base, fp),
+            ctypes.cast(base + 4 * n * t, fp), ctypes.cast(base + 8 * n * t, fp), P(ws), ws.numel(), t, h, w,
+            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _native.check(rc, 'pnp_generator_forward_clips')
+
+    def forward_clips(self, clips, out_dtype=None):
+        """A batch as a sequence of clips, each where it lives: clips[i] = (lrs, QPs, slices, mvs, base_QPs, par_map) with the tensors
+        of forward() for n = 1 (or without the batch dimension).  All clips go to the library in ONE call as pointers -- nothing is
+        concatenated -- and run like a batch (large frames two at a time on two streams, small ones up to eight).  Returns a list of
+        per-clip outputs, each what forward(..., out_dtype) returns for that clip (with the batch dimension, n = 1).  The clips must
+        agree in shape and in the dtype class of lrs (uint8 or floating point): ValueError otherwise.  Not replayed from a graph
+        (use_graphs concerns forward()): a graph's static buffers would be the copies this call exists to avoid."""
+        mask = self._out_mask(out_dtype)
+        clips = list(clips)
+        if not clips:
+            raise ValueError('forward_clips needs at least one clip')
+        if self.sparse_val and not self.training and len(clips) != 1:
+            raise NotImplementedError('sparse_val=True evaluates one clip at a time: the reference reads feature[0] '
+                                      'only (sr_backbone_utils.py:262-275)')
+        lr_l, mv_l, par_l, sides = [], [], [], []
+        first = None
+        for lrs, QPs, slices, mvs, base_QPs, par_map in clips:
+            if not lrs.is_cuda:
+                raise RuntimeError('PnP-VCVE generator: inputs must be CUDA/HIP tensors; this build has no CPU path')
+            byte_in = lrs.dtype == torch.uint8
+            nd = 4 if lrs.dim() == 4 else 5
+            if lrs.dim() not in (4, 5) or (nd == 5 and lrs.shape[0] != 1):
+                raise ValueError(f'a clip of forward_clips is one sample: (t,...) or (1,t,...) tensors, got lrs {tuple(lrs.shape)}')
+            lrs = lrs.reshape(lrs.shape[-4:])
+            if byte_in and lrs.shape[-1] != 3:
+                raise ValueError(f'uint8 frames must be (t,h,w,3) -- the decoder\'s HWC RGB layout -- got {tuple(lrs.shape)}')
+            t, (h, w) = lrs.shape[0], (lrs.shape[1:3] if byte_in else lrs.shape[2:4])
+            sig = (byte_in, t, h, w, lrs.device)
+            if first is None:
+                first = sig
+            elif sig != first:
+                raise ValueError(f'the clips of one forward_clips call must agree in shape, device and in uint8 / float frames: '
+                                 f'{sig} against {first}')
+            assert h >= 64 and w >= 64, f'The height and width of inputs should be at least 64, but got {h} and {w}.'
+            if slices is None:
+                raise TypeError('slices (n,t,1,1,1) is required: it selects the key frames (iconvsr_ipb_par.py:60-62)')
+            if QPs is None and (self.with_bias or not self.use_base_qp):
+                raise TypeError('QPs is required by this configuration (iconvsr_ipb_par.py:45-48)')
+            if base_QPs is None and self.use_base_qp:
+                raise TypeError('base_QPs is required when use_base_qp=True (iconvsr_ipb_par.py:45)')
+            mvs_c = mvs.detach().float().reshape(mvs.shape[-4:]).contiguous()
+            par_c = par_map.detach().float().reshape(par_map.shape[-4:]).contiguous()
+            if mvs_c.shape != (t, 4, h, w) or par_c.shape != (t, 3, h, w):
+                raise ValueError(f'The spatial sizes of input ({(h, w)}) and flow/partition maps '
+                                 f'({tuple(mvs_c.shape)}, {tuple(par_c.shape)}) are not the same.')
+            lrs = lrs.detach().contiguous() if byte_in else lrs.detach().float().contiguous()
+            if byte_in and lrs.data_ptr() % 4:       # the library reads the bytes as dwords: a view at an odd storage offset is copied
+                lrs = lrs.clone()
+            lr_l.append(lrs)
+            mv_l.append(mvs_c)
+            par_l.append(par_c)
+            zero = torch.zeros(t, device=slices.device)
+            sides.append(torch.stack([slices.reshape(t).float(), QPs.reshape(t).float() if QPs is not None else zero,
+                                      base_QPs.reshape(t).float() if base_QPs is not None else zero]))
+        byte_in, t, h, w, dev = first
+        self._check_resident(t)
+        with torch.cuda.device(dev):
+            self._ensure_packed(dev)
+            if self.sparse_val:
+                sparse_now = 0 if self.training else 1
+                if self.get_option(_native.OPT_SPARSE_EVAL) != sparse_now:
+                    self.set_option(_native.OPT_SPARSE_EVAL, sparse_now)
+            side = torch.stack(sides, dim=1).cpu().contiguous()          # (3, n, t): ONE D2H copy
+            outs = torch.ops.pnpvcve.generator_forward_clips(self._op_handle, lr_l, mv_l, par_l, side, mask)
+        n = len(lr_l)
+        f32 = [o[None] for o in outs[:n]] if mask & _native.OUT_F32 else None
+        u8 = [o[None] for o in outs[-n:]] if mask & _native.OUT_U8 else None
+        return [self._ret(f32[i] if f32 else None, u8[i] if u8 else None, mask) for i in range(n)]
+
+    def _forward_clips_native(self, lrs, mvs, par, side, mask):
+        """Body of torch.ops.pnpvcve.generator_forward_clips: per-clip contiguous CUDA tensors + the (3, n, t) host side info ->
+        the fp32 outputs (mask & 1), then the uint8 ones (mask & 2), one freshly allocated tensor per clip."""
+        n = len(lrs)
+        byte_in = lrs[0].dtype == torch.uint8
+        t = lrs[0].shape[0]
+        h, w = lrs[0].shape[1:3] if byte_in else lrs[0].shape[2:4]
+        dev = lrs[0].device
+        with torch.cuda.device(dev):
+            f32 = [self._alloc_outs(1, t, h, w, _native.OUT_F32, dev)[0][0] for _ in range(n)] if mask & _native.OUT_F32 else None
+            u8 = [self._alloc_outs(1, t, h, w, _native.OUT_U8, dev)[1][0] for _ in range(n)] if mask & _native.OUT_U8 else None
+            ws = self._get_workspace(n, t, h, w, dev, int(byte_in), mask)
+            self._launch_clips(lrs, mvs, par, side, f32, u8, ws, t, h, w)
+        return (f32 or []) + (u8 or [])
 
     def _forward_native(self, lrs_c, mvs_c, par_c, side):
         """Body of torch.ops.pnpvcve.generator_forward: contiguous fp32 CUDA tensors + the (3, n, t) host side info."""
@@ -367,28 +530,42 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
     use_graphs = False
     MAX_GRAPHS = 8
 
-    def _forward_graphed(self, lrs_c, mvs_c, par_c, side, out_shape):
-        n, t, _, h, w = lrs_c.shape
+    def _forward_graphed(self, lrs_c, mvs_c, par_c, side, out_shape, mask=_native.OUT_F32):
+        """(a byte boundary -- uint8 lrs_c (n,t,h,w,3) and / or mask != OUT_F32 -- gets static buffers of the input's dtype and of the
+        outputs asked for, and a key with the format and the mask; out_shape is then unused)"""
+        byte_in = lrs_c.dtype == torch.uint8
+        io = byte_in or mask != _native.OUT_F32
+        n, t = lrs_c.shape[:2]
+        h, w = lrs_c.shape[2:4] if byte_in else lrs_c.shape[3:5]
         dev = lrs_c.device
         key = (n, t, h, w, str(dev), side.numpy().tobytes(), self._packed.data_ptr(), self._packed_floats, self.max_resident_features)
+        if io:
+            key = key + (int(byte_in), mask)
         ent = self._graphs.get(key)
         if ent is None:
             ctx = self._contexts(n, h, w)
-            nbytes = int(_native.lib().pnp_generator_workspace_bytes(self._handle, t, h, w)) * ctx
+            nbytes = self._workspace_bytes(t, h, w, int(byte_in), mask) * ctx
             ent = dict(lrs=torch.empty_like(lrs_c), mvs=torch.empty_like(mvs_c), par=torch.empty_like(par_c),
-                       out=torch.empty(out_shape, device=dev, dtype=torch.float32),
                        ws=torch.empty(nbytes, device=dev, dtype=torch.uint8), side=side.clone())
+            if io:
+                ent['out'], ent['out8'] = self._alloc_outs(n, t, h, w, mask, dev)
+                run = lambda: self._launch_clips(list(ent['lrs']), list(ent['mvs']), list(ent['par']), ent['side'],      # noqa: E731
+                                                 list(ent['out']) if ent['out'] is not None else None,
+                                                 list(ent['out8']) if ent['out8'] is not None else None, ent['ws'], t, h, w)
+            else:
+                ent['out'] = torch.empty(out_shape, device=dev, dtype=torch.float32)
+                run = lambda: self._launch(ent['lrs'], ent['mvs'], ent['par'], ent['side'], ent['out'], ent['ws'])      # noqa: E731
             for k, src in (('lrs', lrs_c), ('mvs', mvs_c), ('par', par_c)):
                 ent[k].copy_(src)
             cur = torch.cuda.current_stream()
             warm = torch.cuda.Stream()
             warm.wait_stream(cur)
             with torch.cuda.stream(warm):       # eager once: first-use attribute calls must not land in a capture
-                self._launch(ent['lrs'], ent['mvs'], ent['par'], ent['side'], ent['out'], ent['ws'])
+                run()
             cur.wait_stream(warm)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                self._launch(ent['lrs'], ent['mvs'], ent['par'], ent['side'], ent['out'], ent['ws'])
+                run()
             ent['graph'] = graph
             while len(self._graphs) >= self.MAX_GRAPHS:
                 self._graphs.pop(next(iter(self._graphs)))
@@ -397,6 +574,9 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
             for k, src in (('lrs', lrs_c), ('mvs', mvs_c), ('par', par_c)):
                 ent[k].copy_(src)
         ent['graph'].replay()
+        if io:
+            return self._ret(ent['out'].clone() if ent['out'] is not None else None,
+                             ent['out8'].clone() if ent['out8'] is not None else None, mask)
         return ent['out'].clone()
 
     # ---------------------------------------------------------------- measurement aid

@@ -15,7 +15,12 @@ import torch
 
 def frames_to_uint8_hwc(frames):
     """(T,3,H,W) or (3,H,W) float tensor in [0,1] (any device) -> uint8 (T,H,W,3) RGB on the host, with
-    tensor2img's arithmetic (mmedit/core/misc.py:51-71: clamp, * 255, round half to even)."""
+    tensor2img's arithmetic (mmedit/core/misc.py:51-71: clamp, * 255, round half to even).  A uint8 (T,H,W,3) or (H,W,3) tensor --
+    frames the generator already wrote as display bytes -- passes through."""
+    if frames.dtype == torch.uint8:
+        if frames.shape[-1] != 3 or frames.dim() not in (3, 4):
+            raise ValueError(f'uint8 frames must be (T,H,W,3) or (H,W,3) RGB, got {tuple(frames.shape)}')
+        return (frames.unsqueeze(0) if frames.dim() == 3 else frames).detach().cpu().contiguous().numpy()
     if frames.dim() == 3:
         frames = frames.unsqueeze(0)
     if frames.is_cuda:                       # HIP kernel (pnp_frames_to_rgb8), then a uint8 D2H copy

@@ -446,6 +446,28 @@ def frames_to_rgb8(frames):
 
 
 @_on_device_of_first_tensor
+def frames_from_rgb8(u8):
+    """(...,h,w,3) uint8 RGB CUDA frames -> (...,3,h,w) fp32 planes, byte v -> float32(v) / float32(255) (IEEE division; one table in
+    the library): what RescaleToZeroOne + HWC->CHW make of a decoded frame, bit for bit.  The inverse layout of frames_to_rgb8."""
+    if not isinstance(u8, torch.Tensor) or not u8.is_cuda:
+        raise RuntimeError('u8 must be a CUDA/HIP tensor: the PnP-VCVE hot path has no CPU fallback')
+    if u8.dtype != torch.uint8:
+        raise TypeError(f'u8 must be uint8, got {u8.dtype}')
+    if u8.dim() < 3 or u8.shape[-1] != 3:
+        raise ValueError('u8 must be (...,h,w,3) uint8 RGB')
+    u8 = u8.contiguous()
+    lead, (h, w) = tuple(u8.shape[:-3]), u8.shape[-3:-1]
+    n = 1
+    for d in lead:
+        n *= int(d)
+    out = torch.empty(lead + (3, h, w), device=u8.device, dtype=torch.float32)
+    if n:
+        _native.check(_native.lib().pnp_frames_from_rgb8(ctypes.c_void_p(u8.data_ptr()), _ptr(out), n, h, w, _stream()),
+                      'pnp_frames_from_rgb8')
+    return out
+
+
+@_on_device_of_first_tensor
 def psnr_frames(a, b, crop_border=0):
     """Per-frame PSNR with the reference's definition (uint8-rounded frames), computed on the GPU.
     a, b: (..., c, h, w) with any leading dims; returns a float64 CPU tensor of the leading shape."""

@@ -79,6 +79,8 @@ class BasicVSR(nn.Module):
         is_mirror_extended = False
         if lrs.size(1) % 2 == 0:
             lrs_1, lrs_2 = torch.chunk(lrs, 2, dim=1)
+            if lrs.dtype == torch.uint8:        # byte frames (n,t,h,w,3): the same test, exact on integers
+                return torch.equal(lrs_1, lrs_2.flip(1))
             if torch.norm(lrs_1 - lrs_2.flip(1)) == 0:
                 is_mirror_extended = True
         return is_mirror_extended
@@ -123,21 +125,32 @@ class BasicVSR(nn.Module):
         return eval_result
 
     def forward_test(self, lq, gt=None, QPs=None, slices=None, mvs=None, base_QPs=None, par_map=None, meta=None,
-                     save_image=False, save_path=None, iteration=None, precomputed_output=None):
+                     save_image=False, save_path=None, iteration=None, precomputed_output=None, out_dtype=None):
         """basicvsr.py:155-233.  `precomputed_output` (not in the reference): this clip's enhanced frames when the caller has
         already run the generator -- apis.multi_gpu_test does so for two clips at a time, which the generator interleaves on two
-        streams; evaluation and saving then proceed clip by clip exactly as below."""
+        streams; evaluation and saving then proceed clip by clip exactly as below.
+        Byte frames (not in the reference): `lq` may be the decoder's uint8 (n,t,h,w,3) frames, and `out_dtype` (generator.forward's)
+        asks the generator for the display bytes as well as / instead of the fp32 planes: metrics read the fp32 planes, the PNG
+        writer takes the bytes as they are."""
         if precomputed_output is not None:
             output = precomputed_output
         elif not self.psnr_only:
             with torch.no_grad():
                 torch.cuda.synchronize()
                 begin = time.time()
-                output = self.generator(lq, QPs, slices, mvs, base_QPs, par_map)
+                kw = {} if out_dtype is None else {'out_dtype': out_dtype}
+                output = self.generator(lq, QPs, slices, mvs, base_QPs, par_map, **kw)
                 torch.cuda.synchronize()
                 self.last_forward_seconds = time.time() - begin
         else:
             output = lq
+        output_u8 = None            # (n,t,H,W,3) display bytes from the generator, when asked for
+        if isinstance(output, tuple):
+            output, output_u8 = output
+        elif output.dtype == torch.uint8 and not self.psnr_only:
+            output_u8 = output
+            if (gt is not None and gt.ndim == 4) or (self.test_cfg is not None and self.test_cfg.get('metrics', None)):
+                raise ValueError("metrics and the centre-frame output read the fp32 planes: ask for out_dtype='both' or torch.float32")
         if gt is not None and gt.ndim == 4:
             t = output.size(1)
             if self.check_if_mirror_extended(lq):
@@ -148,7 +161,11 @@ class BasicVSR(nn.Module):
             assert gt is not None, 'evaluation with metrics must have gt images.'
             results = dict(eval_result=self.evaluate(output, gt))
         else:
-            results = dict(lq=lq.cpu(), output=output.cpu())
+            lq_planes = lq
+            if lq.dtype == torch.uint8 and lq.ndim == 5 and lq.is_cuda:       # byte frames: hand back the planes the caller knows
+                from .ops import frames_from_rgb8
+                lq_planes = frames_from_rgb8(lq)
+            results = dict(lq=lq_planes.cpu(), output=output.cpu())
             if gt is not None:
                 results['gt'] = gt.cpu()
         if save_image:
@@ -162,7 +179,7 @@ class BasicVSR(nn.Module):
             try:
                 if output.ndim == 5:
                     folder_name = meta[0]['key'].split('/')[0]
-                    rgb = frames_to_uint8_hwc(output[0])
+                    rgb = frames_to_uint8_hwc(output_u8[0] if output_u8 is not None else output[0])
                     for i in range(rgb.shape[0]):
                         name = f'{i:08d}.png' if iteration is None else f'{i:08d}-{iteration + 1:06d}.png'
                         writer.submit(osp.join(save_path, folder_name, name), rgb[i])

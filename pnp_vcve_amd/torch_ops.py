@@ -10,6 +10,10 @@ package).
     torch.ops.pnpvcve.mv_warp(feat_hwc, flow_x, flow_y)         iconvsr_mv.py:17-18 in the fused path's layout
     torch.ops.pnpvcve.psnr_sse(a, b, crop_border)               core/evaluation/metrics.py:200-215 statistic
     torch.ops.pnpvcve.generator_forward(handle, lrs, mvs, par, side)   iconvsr_ipb_par.py:44-149
+    torch.ops.pnpvcve.generator_forward_clips(handle, lrs[], mvs[], par[], side, out_mask)
+                                                                the same forward over clips given one by one (fp32 planes or uint8 HWC
+                                                                frames in; fp32 planes and / or uint8 HWC frames out, out_mask 1 | 2 | 3)
+    torch.ops.pnpvcve.frames_from_rgb8(u8)                      RescaleToZeroOne + HWC->CHW of decoded frames
 
     torch.ops.pnpvcve.conv3x3(srcs, packed_w, bias, gamma, packed_w1x1, par, residual, act)
                                                                 basicvsr_net.py:484, sr_backbone_utils.py:304-333 halves, iconvsr.py:365
@@ -83,6 +87,41 @@ def _(handle, lrs, mvs, par, side):
     s = 4 if (m is not None and m.vsr) else 1
     n, t, _, h, w = lrs.shape
     return lrs.new_empty((n, t, 3, h * s, w * s))
+
+
+@torch.library.custom_op('pnpvcve::frames_from_rgb8', mutates_args=())
+def frames_from_rgb8(u8: torch.Tensor) -> torch.Tensor:
+    return ops.frames_from_rgb8(u8)
+
+
+@frames_from_rgb8.register_fake
+def _(u8):
+    return u8.new_empty(tuple(u8.shape[:-3]) + (3,) + tuple(u8.shape[-3:-1]), dtype=torch.float32)
+
+
+@torch.library.custom_op('pnpvcve::generator_forward_clips', mutates_args=())
+def generator_forward_clips(handle: int, lrs: list[torch.Tensor], mvs: list[torch.Tensor], par: list[torch.Tensor],
+                            side: torch.Tensor, out_mask: int) -> list[torch.Tensor]:
+    """one clip per list entry: lrs[i] (t,3,h,w) fp32 or (t,h,w,3) uint8; -> per clip the fp32 planes (out_mask & 1), then the uint8
+    frames (out_mask & 2): len(lrs) tensors for out_mask 1 or 2, the fp32 ones followed by the uint8 ones for out_mask 3"""
+    m = _GENERATORS.get(handle)
+    if m is None:
+        raise RuntimeError(f'pnpvcve::generator_forward_clips: unknown generator handle {handle}')
+    return m._forward_clips_native(list(lrs), list(mvs), list(par), side, int(out_mask))
+
+
+@generator_forward_clips.register_fake
+def _(handle, lrs, mvs, par, side, out_mask):
+    m = _GENERATORS.get(handle)
+    s = 4 if (m is not None and m.vsr) else 1
+    outs = []
+    for bit, dt in ((1, torch.float32), (2, torch.uint8)):
+        for x in lrs:
+            if not out_mask & bit:
+                continue
+            t, (h, w) = x.shape[0], (x.shape[1:3] if x.dtype == torch.uint8 else x.shape[2:4])
+            outs.append(x.new_empty((t, 3, h * s, w * s) if bit == 1 else (t, h * s, w * s, 3), dtype=dt))
+    return outs
 
 
 @torch.library.custom_op('pnpvcve::conv3x3', mutates_args=())

@@ -44,6 +44,10 @@ def parse_args():
     p.add_argument('--max-resident-features', type=int, default=None, metavar='K',
                    help='bound the frame feature maps the generator holds to K (long clips: the backward features are recomputed '
                         'from checkpoints, bit-identical output, a workspace of K maps instead of one per frame); default unbounded')
+    p.add_argument('--byte-frames', action='store_true',
+                   help='keep the frames uint8 from the decoder into the generator and take its output as display bytes for the PNGs '
+                        '(fp32 planes only for the metrics); a pair of clips goes in by pointer instead of concatenated.  Same '
+                        'metrics and PNG bytes; default off')
     p.add_argument('--local_rank', type=int, default=0)
     a = p.parse_args()
     if 'LOCAL_RANK' not in os.environ:
@@ -95,7 +99,8 @@ def main():
         model.frame_writer = FrameWriter(max_workers=4)
     try:
         outputs = multi_gpu_test(model, dataset, save_image=args.save_path is not None, save_path=args.save_path,
-                                 device=dev, metrics=tuple(cfg.test_cfg['metrics']), clips_in_flight=args.clips_in_flight)
+                                 device=dev, metrics=tuple(cfg.test_cfg['metrics']), clips_in_flight=args.clips_in_flight,
+                                 byte_frames=args.byte_frames)
     finally:
         if getattr(model, 'frame_writer', None) is not None:
             model.frame_writer.close()
