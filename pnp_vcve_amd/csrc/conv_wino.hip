@@ -32,8 +32,9 @@
 //     added to position (0,0) / -(0,3) / -(3,0) / (3,3) reaches exactly output pixel (0,0) / (0,1) / (1,0) / (1,1) through A^T . A --
 //     as a fifth chunk per step whose A operand is par_j(pixel) * x(centre pixel).  A wave's quadrant is one 8x8 codec block, so on a one-hot
 //     map each wave runs ONE branch: which, it decides itself from the values it loaded (a zero plane adds exact zeros).
-//   * epilogue: Y = A^T M A in registers, + bias (* gamma), activation; one N tile at a time through 4 KiB of LDS per wave (the ring
-//     slot the tile's last chunk has just left) so that residual loads and stores move 16 B per lane (64-B channel runs per pixel).
+//   * epilogue: Y = A^T M A in registers, + bias (* gamma), activation.  The weight images put output channel co into column co >> 2
+//     of N tile co & 3, so a lane's four N tiles are four consecutive channels of one pixel: residual loads and stores move 16 B per
+//     lane straight from / to registers (a wave instruction covers four whole 256-B pixels), without an exchange through LDS.
 //   * quadrant units: the tiles beyond an XCD band's whole rounds are cut into four 8x8 units, one per block, the four waves splitting
 //     the output channels (the kernel's tail); conv3x3_wino_quad_kernel / _quad_ms_kernel run whole small frames that way.  Same
 //     arithmetic in the same order per accumulator: a pixel's value does not depend on the form that computed it.
@@ -205,9 +206,9 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
     const float act_lo = a.act == 0 ? 1.f : (a.act == 1 ? 0.f : 0.1f);
     // bias * gamma and the partition values live in LDS, not in registers: the K loop runs at the 256-VGPR limit, and a value
     // spilled to scratch comes back behind an s_waitcnt vmcnt(0) that also waits for every weight / halo request in flight
-    // (channel t = 16 n + m at float index 4 m + n: lane m reads its four N tiles' values as one float4)
-    if (t < 64) *reinterpret_cast<float*>(smem + BG_B + ((t & 15) * 4 + (t >> 4)) * 4) = (a.bias ? a.bias[t] : 0.f) * (a.gamma ? a.gamma[t] : 1.f);
-    // (accumulator register r of N tile nt is tile 4 kq + r -- C/D layout of the 16x16 MFMA -- channel 16 nt + m;
+    // (channel-linear: column m of N tile n is channel 4 m + n, so lane m reads its four N tiles' values as one float4)
+    if (t < 64) *reinterpret_cast<float*>(smem + BG_B + t * 4) = (a.bias ? a.bias[t] : 0.f) * (a.gamma ? a.gamma[t] : 1.f);
+    // (accumulator register r of N tile nt is tile 4 kq + r -- C/D layout of the 16x16 MFMA -- channel 4 m + nt;
     //  tile (ty', tx') = (2 wave + (kq >> 1), 4 (kq & 1) + r), pixel (a, b) of it: see the epilogue)
 
     f32x4 acc[16][4];
@@ -237,9 +238,6 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
             hoff[i] = inb ? (unsigned)(ry * W + rx) * 256u + (unsigned)quad * 16u : OOBW;
         }
     };
-    // partition values of the wave's pixels for the tile at (y0, x0), plane J: global -> LDS (signed), and whether the WAVE needs the
-    // branch at all.  One plane per call: the next tile's values are fetched plane by plane in the last three position chunks of a
-    // tile (all twelve at once, with their offsets, were what tipped the K loop into scratch spills)
     // partition values of the wave's pixels for the tile at (y0, x0): global -> registers (pv_request), then -> LDS, signed, with the
     // decision whether the WAVE needs each branch at all (pv_finish).  The next tile's values are requested at the top of the epilogue and
     // finished behind it: inside the K loop their twelve registers tipped the branch kernels into scratch spills, and a spill reload is
@@ -644,7 +642,8 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                     // LLVM's IR-level sinking moves the adds next to their first use, into the join block behind the next step's branches,
                     // where nothing overlaps them: 96 VALU instructions per branch chunk in the first PAR build).  Plain kernels: the
                     // same source order makes hipcc keep `acc` and `V` in scratch MEMORY (private_seg_size 1616, ten times slower), and
-                    // the pin costs the back half 8 %: they keep reads first, transform second, unpinned.
+                    // the pin costs the back half 8 %: they keep reads first, transform second, unpinned -- with ONE exception, below: the
+                    // three rows made in step 3 for the next tile (3 of a tile's 16 chunks), which without a pin leave the K loop altogether.
                     //   The branch kernels do the 32 adds in TWO gaps (16 + 16): a gap with any vector-ALU instruction in it costs ~9-20
                     // cycles of matrix time before the 4 per instruction (tools/ubench/ub_valu_gap.hip; front half 427 -> 423 us).
                     if constexpr (PAR) {
@@ -680,6 +679,12 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
 #pragma unroll
                         for (int c = 0; c < 4; ++c)
                             if (g == 36) V[4 * TR + c] = c == 0 ? sub4(tt[0], tt[2]) : (c == 1 ? add4(tt[1], tt[2]) : (c == 2 ? sub4(tt[2], tt[1]) : sub4(tt[1], tt[3])));
+                        // (the next tile's rows 0-2, made in step 3, pinned where they are computed: with no LDS exchange in the epilogue to hold
+                        //  them back the sums sink behind it, and their patch rows -- 24 quads -- wait there in scratch)
+                        if (S == 3 && PG >= 1 && g == 36) {
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) asm volatile("" : "+v"(V[4 * TR + c]));
+                        }
                     }
                     if constexpr (FO) {
                         // the plane's 1x1 fragments of this step: requested in position row 0, parked (N tiles 0-2) / kept (3) in row 1
@@ -841,12 +846,13 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
             dbg_k += dbg_b - dbg_a;
         }
 
-        // ---- epilogue: Y = A^T M A per (tile, channel) in the accumulator layout (+ bias (* gamma), activation), then one N tile at a
-        //      time through LDS -- the wave's 4 x 16 pixel strip x 16 channels = 4 KiB of ring slot 3, free now: the next tile's chunks
-        //      0..2 sit in slots 0..2 -- so that residual loads and stores are 16 B per lane (64-B channel runs per pixel)
+        // ---- epilogue: Y = A^T M A per (tile, channel) in the accumulator layout (+ bias (* gamma), activation).  Column m of N tile n is
+        //      channel 4 m + n, so the lane's four N tiles at one (pixel, register) are one 16-byte run of a pixel's channels: residual
+        //      loads and stores go 16 B per lane straight from / to registers (a wave instruction = four whole 256-B pixels), no
+        //      exchange through LDS.  No barrier here either: ring slot 3 is next written by chunk 0 of the next tile, behind that
+        //      chunk's own barrier, and the partition-value rows were last read before the barrier at the top of this tile's last chunk
         const unsigned so = (unsigned)(ty0 * W + tx0) * 256u;
         const bool partial = ty0 + 16 > H || tx0 + 16 > W;
-        lds_bar();                       // every wave has read its last fragments out of slot 3
         // (next = the block's quadrant unit: every wave fetches quadrant qquad's values)
         const int tqp = (!has_next && qtile >= 0) ? ((qquad << 6) | (tq & 63)) : tq;
         pv_request(tqp, nty0, ntx0);
@@ -858,24 +864,26 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
             int te = tq;
             asm volatile("" : "+v"(te));
             const int lq = te & 63, wq = te >> 6, kqq = lq >> 4, mq = lq & 15;
-            char* tr = smem + 3 * 16384 + wq * 4096;
-            // write side: accumulator register r of this lane is tile (row kq, column r) of the wave's 4x4 tiles; value (q = 2 a + b, r)
-            // is pixel (row 2 kq + a, column 2 r + b) of its 8x8 block, channel m
-            const unsigned wbase = (unsigned)((2 * kqq) * 8 * 64 + mq * 4);
-            // read side: float4 j of this lane = block pixel lp = 16 j + (lane >> 2) (row lp >> 3, column lp & 7), channels 4 (lane & 3) .. + 3
-            const unsigned rbase = (unsigned)((lq >> 2) * 64 + (lq & 3) * 16);
-            unsigned go[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = 8 * (wq >> 1) + 2 * j + (lq >> 5), col = 8 * (wq & 1) + ((lq >> 2) & 7);
-                go[j] = (unsigned)(row * W + col) * 256u + (unsigned)(lq & 3) * 16u;
-                if (PARTIAL) go[j] = (ty0 + row < H && tx0 + col < W) ? go[j] : OOBW;
-            }
-            f32x4 rs[4];
+            // accumulator register r of this lane is tile (row kq, column r) of the wave's 4x4 tiles; value (q = 2 a + b, r) is pixel
+            // (row 2 kq + a, column 2 r + b) of its 8x8 block, channels 4 m .. 4 m + 3 (N tiles 0..3).  Pixel row a goes into the scalar
+            // offset, the column into the immediate; a partial tile marks each pixel beyond the frame out of range
+            const int row = 8 * (wq >> 1) + 2 * kqq, col = 8 * (wq & 1);
+            const unsigned gb = (unsigned)(row * W + col) * 256u + (unsigned)mq * 16u;
+            auto voff = [&](int q, int r) -> unsigned {
+                const unsigned v = gb + (unsigned)(2 * r + (q & 1)) * 256u;
+                if (PARTIAL) return (ty0 + row + (q >> 1) < H && tx0 + col + 2 * r + (q & 1) < W) ? v : OOBW;
+                return v;
+            };
+            auto soff = [&](int q) -> unsigned { return so + (unsigned)((q >> 1) * W) * 256u; };
+            f32x4 rs[2][4];
             if (RES) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) rs[j] = bload4(r_res, go[j], so);
+                for (int r = 0; r < 4; ++r) rs[0][r] = bload4(r_res, voff(0, r), soff(0));
             }
+            // All 16 output quads live at once (64 registers; every accumulator read once).  An output row per pass halves that and
+            // reads position rows 1 and 2 twice: in the listings it buys nothing (plain / residual kernel 44 / 24 B of scratch with one
+            // pass, 28 / 24 B with two, but 132 instead of 24 accumulator moves in the plain kernel's K loop and 92 B in the gated one)
+            f32x4 o[4][4];                   // [q][r]: component n = N tile n
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
                 f32x4 w0[4], w1[4];
@@ -889,26 +897,29 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                 y[1] = w1[0] + w1[1] + w1[2];
                 y[2] = w0[1] - w0[2] - w0[3];
                 y[3] = w1[1] - w1[2] - w1[3];
+                // (the bias came in through the accumulator of position (1,1))
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    // (the bias came in through the accumulator of position (1,1))
+                for (int q = 0; q < 4; ++q)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) *reinterpret_cast<float*>(tr + wbase + ((q >> 1) * 8 + 2 * r + (q & 1)) * 64) = y[q][r];
+                    for (int r = 0; r < 4; ++r) o[q][r][n] = y[q][r];
+                // (one N tile's sums at a time: left alone the scheduler reads every accumulator first and the allocator answers with
+                //  23 accumulator quads parked in scratch during step 3 of the K loop)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (RES && q < 3) {          // requested one output row / column parity ahead
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) rs[(q + 1) & 1][r] = bload4(r_res, voff(q + 1, r), soff(q + 1));
                 }
-                f32x4 o[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = *reinterpret_cast<const f32x4*>(tr + rbase + j * 1024);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
+                for (int r = 0; r < 4; ++r) {
                     // none: max(v, 1 v) | relu: max(v, 0 v) | leaky-relu: max(v, 0.1 v).  The residual bodies take no activation (the
                     // reference adds the residual to a bare conv, sr_backbone_utils.py:313,329; launch_conv3x3_wino refuses anything else):
                     // 128 vector-ALU instructions per tile less where the matrix pipe stands idle
-                    if constexpr (!RES) o[j] = __builtin_elementwise_max(o[j], act_lo * o[j]);
-                    if (RES) {
-                        o[j] += rs[j];
-                        if (n < 3) rs[j] = bload4(r_res, go[j], so + (n + 1) * 64);       // requested one N tile ahead
-                    }
-                    bstore4(r_out, go[j], so + n * 64, o[j]);      // (the N tile's 64 B go into the scalar offset: go[j] may be the OOB marker)
+                    if constexpr (!RES) o[q][r] = __builtin_elementwise_max(o[q][r], act_lo * o[q][r]);
+                    if (RES) o[q][r] += rs[q & 1][r];
+                    bstore4(r_out, voff(q, r), soff(q), o[q][r]);      // (the pixel row goes into the scalar offset: the lane offset may be the OOB marker)
                 }
             }
         };
@@ -961,7 +972,7 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
             // (its tile's halo is in the slabs already: the last whole tile's K loop fetched it as "the next tile")
             if (a.dbg) dbg_q0 = __builtin_amdgcn_s_memtime();
             const int tyq = m >> 2, txq = m & 3;
-            const unsigned wq16 = (unsigned)lane * 16u + (unsigned)wave * 1024u;
+            const unsigned wq16 = (unsigned)(m & 3) * 1024u + (unsigned)(kq * 16 + 4 * wave + (m >> 2)) * 16u;
             const unsigned qb0 = RING_B + ((2 * (4 * (qquad >> 1) + tyq)) * HP + 4 * (qquad & 1) + txq) * 64 + kq * 16, qb1 = qb0 + 2 * SLAB_B;
             // B fragments of step 0 first (the first MFMAs wait for these only), then the residual values
             f32x4 Bq[2][16], Bp[2][3];
@@ -988,12 +999,14 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                         resq[q * 4 + r] = bload1(r_res, inq ? qo : OOBW, (unsigned)((q >> 1) * W + 2 * r + (q & 1)) * 256u);
                     }
             }
-            const float bgq = *reinterpret_cast<const float*>(smem + BG_B + (m * 4 + wave) * 4);
+            const float bgq = *reinterpret_cast<const float*>(smem + BG_B + (wave * 16 + m) * 4);
             if constexpr (PAR) {
 #pragma unroll
                 for (int n = 0; n < 1; ++n) acc[0][0] = acc[3][0] = acc[12][0] = acc[15][0] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
-            lds_bar();       // (the slabs are complete and every wave is out of the last epilogue; the requests above stay in flight)
+            // (the slabs are complete and every wave is out of the last epilogue, which has no barrier of its own: this one alone orders
+            //  the epilogue's pv_finish writes of quadrant qquad's rows against the unit's reads of them; the requests above stay in flight)
+            lds_bar();
             if (a.dbg) dbg_q1 = __builtin_amdgcn_s_memtime();
             // the partition values and the branch decision of this quadrant came through the tile pipeline (pv_request / pv_finish with
             // every wave on quadrant qquad)
@@ -1205,7 +1218,7 @@ __device__ __forceinline__ void wino_quad_body(const WinoArgs& a) {
             for (int j = 0; j < 3; ++j) praw[j][0] = a.par[(long)j * a.par_plane + (long)qy0 * W + qx0];      // (block-uniform)
         }
     }
-    const unsigned wq16 = (unsigned)lane * 16u + (unsigned)wave * 1024u;
+    const unsigned wq16 = (unsigned)(m & 3) * 1024u + (unsigned)(kq * 16 + 4 * wave + (m >> 2)) * 16u;
     // B fragments of step s4 live in set s4 % QB, requested QA steps ahead (QA = 2: the first two steps' fragments are requested before
     // the halo has landed).  1 / 2 / 3 ahead = 2076 / 2130 / 2040 frames/s on 7x3x128x128 clips (3: the fourth fragment set lives in
     // AGPRs, moved back and forth)
@@ -1449,10 +1462,11 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_quad_ms_kernel(const Wino
         *reinterpret_cast<f32x4*>(smem + 2 * HB + t * 16) = v;
     }
     const int tyq = m >> 2, txq = m & 3;
-    const unsigned wq16 = (unsigned)lane * 16u + (unsigned)wave * 1024u;
-    f32x4 Bq[2][16], Br[16];
+    const unsigned wq16 = (unsigned)(m & 3) * 1024u + (unsigned)(kq * 16 + 4 * wave + (m >> 2)) * 16u;
+    f32x4 Bq[2][16];
+    float Br[16];      // (the frame's image is channel-linear behind (position, k): the lane's own channel is one float)
 #pragma unroll
-    for (int p = 0; p < 16; ++p) Br[p] = bload4(r_urgb, (unsigned)lane * 16u, (unsigned)((p >> 2) * 4096 + (p & 3) * 1024));
+    for (int p = 0; p < 16; ++p) Br[p] = bload1(r_urgb, (unsigned)(kq * 64 + wave * 16 + m) * 4u, (unsigned)((p >> 2) * 4096 + (p & 3) * 1024));
 #pragma unroll
     for (int p = 0; p < 16; ++p) Bq[0][p] = bload4(r_u, wq16, a.u_off[0] + (unsigned)((p >> 2) * 16384 + (p & 3) * 4096));
     halo_store(0);
@@ -1482,8 +1496,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_quad_ms_kernel(const Wino
 #pragma unroll
         for (int p = 0; p < 16; ++p) {
             const f32x4 c0 = p == 5 ? f32x4{bgq, bgq, bgq, bgq} : f32x4{0.f, 0.f, 0.f, 0.f};
-            const float bw = wave == 0 ? Br[p][0] : (wave == 1 ? Br[p][1] : (wave == 2 ? Br[p][2] : Br[p][3]));
-            acc[p] = mfma16(Vr[p], bw, c0);
+            acc[p] = mfma16(Vr[p], Br[p], c0);
         }
     }
     for (int ks = 0; ks < a.nsrc; ++ks) {
@@ -1561,15 +1574,16 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_quad_ms_kernel(const Wino
 // U = G g G^T per (output channel, input channel), times gamma[co] when given (see launch_wino_images), from a packed direct-conv
 // B image (common.h: 9 chunks, chunk = tap; float index ((q * 2 + nt32) * 64 + h * 32 + n32) * 4 + j  <->  ci = 8 q + 4 h + j,
 // co = 32 nt32 + n32) into 16 chunks (chunk = 4 * (ci >> 4) + position row i; float index
-// ((pj * 4 + (co >> 4)) * 64 + ((ci >> 2) & 3) * 16 + (co & 15)) * 4 + (ci & 3)).  Computed in double, rounded once.
+// ((pj * 4 + (co & 3)) * 64 + ((ci >> 2) & 3) * 16 + (co >> 2)) * 4 + (ci & 3): output channel co is column co >> 2 of N tile co & 3,
+// so a lane's four N tiles are four consecutive channels -- the epilogue's 16-byte run).  Computed in double, rounded once.
 struct WinoImgArgs {
     const float* src[16];
     float* dst[16];
     const float* gamma;
 };
 __global__ __launch_bounds__(256) void wino_image_kernel(const WinoImgArgs a) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;          // [ci >> 4 | co >> 4 | (ci >> 2) & 3 | co & 15 | ci & 3]
-    const int ci = ((idx >> 10) & 3) * 16 + ((idx >> 6) & 3) * 4 + (idx & 3), co = ((idx >> 8) & 3) * 16 + ((idx >> 2) & 15);
+    const int idx = blockIdx.x * 256 + threadIdx.x;          // [ci >> 4 | co & 3 | (ci >> 2) & 3 | co >> 2 | ci & 3]
+    const int ci = ((idx >> 10) & 3) * 16 + ((idx >> 6) & 3) * 4 + (idx & 3), co = ((idx >> 2) & 15) * 4 + ((idx >> 8) & 3);
     const float* s = a.src[blockIdx.y];
     float* d = a.dst[blockIdx.y];
     double g[3][3];
@@ -1590,22 +1604,24 @@ __global__ __launch_bounds__(256) void wino_image_kernel(const WinoImgArgs a) {
         const double u[4] = {tmp[i][0], 0.5 * (tmp[i][0] + tmp[i][1] + tmp[i][2]), 0.5 * (tmp[i][0] - tmp[i][1] + tmp[i][2]), tmp[i][2]};
 #pragma unroll
         for (int pj = 0; pj < 4; ++pj)
-            d[((ci >> 4) * 4 + i) * 4096 + ((pj * 4 + (co >> 4)) * 64 + ((ci >> 2) & 3) * 16 + (co & 15)) * 4 + (ci & 3)] = (float)(u[pj] * gm);
+            d[((ci >> 4) * 4 + i) * 4096 + ((pj * 4 + (co & 3)) * 64 + ((ci >> 2) & 3) * 16 + (co >> 2)) * 4 + (ci & 3)] = (float)(u[pj] * gm);
     }
 }
 
 // the three 1x1 branch images (PACK_1X1 chunks, same float index as above with tap = branch) -> [step s][branch][N tile][lane][j]
+// (N tile co & 3, lane column co >> 2, as in the 3x3 images)
 __global__ __launch_bounds__(256) void wino_par_image_kernel(const float* __restrict__ src, float* __restrict__ dst) {
     const int idx = blockIdx.x * 256 + threadIdx.x;          // 3 * 4096
     const int br = idx >> 12, e = idx & 4095;
-    const int ci = ((e >> 10) & 3) * 16 + ((e >> 6) & 3) * 4 + (e & 3), co = ((e >> 8) & 3) * 16 + ((e >> 2) & 15);
+    const int ci = ((e >> 10) & 3) * 16 + ((e >> 6) & 3) * 4 + (e & 3), co = ((e >> 2) & 15) * 4 + ((e >> 8) & 3);
     const float v = src[br * 4096 + (((ci >> 3) * 2 + (co >> 5)) * 64 + ((ci >> 2) & 1) * 32 + (co & 31)) * 4 + (ci & 3)];
-    dst[(((ci >> 4) * 3 + br) * 4 + (co >> 4)) * 256 + (((ci >> 2) & 3) * 16 + (co & 15)) * 4 + (ci & 3)] = v;
+    dst[(((ci >> 4) * 3 + br) * 4 + (co & 3)) * 256 + (((ci >> 2) & 3) * 16 + (co >> 2)) * 4 + (ci & 3)] = v;
 }
 
 // the RGB frame's chunk (PACK_RGB4, common.h: float index ((q * 2 + nt32) * 64 + h * 32 + n32) * 4 + j  <->  tap 2 q + h, channel j,
 // co = 32 nt32 + n32) -> four position-row chunks of 1024 floats: float index (pj * 64 + kq * 16 + n16) * 4 + nt  <->  position
-// (i, pj), input channel kq (the MFMA's k index: one k-step covers R, G, B and the zero channel), co = 16 nt + n16
+// (i, pj), input channel kq (the MFMA's k index: one k-step covers R, G, B and the zero channel), co = 4 n16 + nt: channel-linear
+// behind (pj, kq)
 __global__ __launch_bounds__(256) void wino_rgb_image_kernel(const float* __restrict__ src, float* __restrict__ dst) {
     const int idx = blockIdx.x * 256 + threadIdx.x;          // 256 = 4 channels x 64 output channels
     const int c = idx >> 6, co = idx & 63;
@@ -1625,7 +1641,7 @@ __global__ __launch_bounds__(256) void wino_rgb_image_kernel(const float* __rest
     for (int i = 0; i < 4; ++i) {
         const double u[4] = {tmp[i][0], 0.5 * (tmp[i][0] + tmp[i][1] + tmp[i][2]), 0.5 * (tmp[i][0] - tmp[i][1] + tmp[i][2]), tmp[i][2]};
 #pragma unroll
-        for (int pj = 0; pj < 4; ++pj) dst[i * 1024 + (pj * 64 + c * 16 + (co & 15)) * 4 + (co >> 4)] = (float)u[pj];
+        for (int pj = 0; pj < 4; ++pj) dst[i * 1024 + (pj * 64 + c * 16) * 4 + co] = (float)u[pj];
     }
 }
 

@@ -644,7 +644,7 @@ Workspace carve(const pnp_generator* g, char* base, int t, int h, int w, int lq_
     W.mixb = take((int64_t)t * g->ndyn * 64);
     W.mixh = g->prec != PNP_PREC_F32 ? take((int64_t)t * g->ndyn * IMG_WIDE / (g->prec == PNP_PREC_F16X3 ? 1 : 2)) : nullptr;
     // (not the last region: the flags behind it are written by every forward, which is what the sanitizer harness's shrunken-workspace self-test trips over)
-    W.wino = (g->prec == PNP_PREC_F32 && g->ndyn > 0) ? take((int64_t)2 * g->cfg.num_blocks * PNP_WINO_IMG_FLOATS) : nullptr;
+    W.wino = (g->prec == PNP_PREC_F32 && g->ndyn > 0) ? take((int64_t)2 * 2 * g->cfg.num_blocks * PNP_WINO_IMG_FLOATS) : nullptr;      // two buffers: run s + 1's images are made while run s reads its own
     const bool mir = g->prec == PNP_PREC_F16 && g->cfg.deform == 0;      // sized whether or not PNP_OPT_F16_MIRRORS is on
     W.x16 = mir ? reinterpret_cast<uint16_t*>(take(hw * 32)) : nullptr;
     W.slots16 = mir ? reinterpret_cast<uint16_t*>(take(hw * 32 * nslots)) : nullptr;
@@ -1159,8 +1159,36 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
 
         // input conv over the virtual concat `in` (sources already added), then the BAE blocks
         // (out: the frame map its last block writes, Step::out)
-        auto run_branch = [&](int brid, int i, int out, ConvCall in) -> int {
+        // A branch run's Winograd images of its expert-mixed convs, this frame's channel gain folded in, into image buffer `buf` of W.wino.
+        // They depend on the clip prologue only (mixtures, gamma), not on any feature map, so the step loop issues run s + 1's in front
+        // of run s's chain (the first run's in front of the loop) into the buffer run s does not read: inside run_branch, between the
+        // input conv and the first block conv, the launch waited for CUs behind chain B's input-conv part and held chain A back.
+        // Buffer s & 1 is rewritten (for run s + 2) in front of run s + 1's chain, i.e. behind run s's join on the caller's stream.
+        auto wino_buf = [&](int buf) { return W.wino + (int64_t)buf * 2 * c.num_blocks * PNP_WINO_IMG_FLOATS; };
+        auto branch_images = [&](int brid, int i, int buf) -> int {
+            if (!(wino_on && g->ndyn > 0)) return 0;
             const BranchPk& B = g->br[brid];
+            const float* gam = (c.with_bias && c.with_se) ? W.gamma + (int64_t)i * 64 : nullptr;
+            const int u = uidx[i];
+            float* wb = wino_buf(buf);
+            std::vector<const float*> ws;
+            std::vector<float*> wd;
+            for (int k = 0; k < c.num_blocks; ++k) {
+                const BlockPk& K = B.blocks[k];
+                if (K.dyn_conv2 >= 0) { ws.push_back(W.mixw + ((int64_t)u * g->ndyn + K.dyn_conv2) * IMG_WIDE); wd.push_back(wb + (int64_t)(2 * k) * PNP_WINO_IMG_FLOATS); }
+                if (K.dyn_conv1 >= 0) { ws.push_back(W.mixw + ((int64_t)u * g->ndyn + K.dyn_conv1) * IMG_WIDE); wd.push_back(wb + (int64_t)(2 * k + 1) * PNP_WINO_IMG_FLOATS); }
+            }
+            for (size_t j = 0; j < ws.size(); j += 16) {
+                const int n = (int)(ws.size() - j < 16 ? ws.size() - j : 16);
+                const int r = launch_wino_images(ws.data() + j, wd.data() + j, n, gam, st);
+                if (r) return r;
+            }
+            g->prof_last = nullptr;           // an untimed launch sits between two timed ones
+            return 0;
+        };
+        auto run_branch = [&](int brid, int i, int out, int buf, ConvCall in) -> int {
+            const BranchPk& B = g->br[brid];
+            const float* wbuf = W.wino ? wino_buf(buf) : nullptr;
             const float* gam = (c.with_bias && c.with_se) ? W.gamma + (int64_t)i * 64 : nullptr;
             const float* parp = sparse_per_frame ? W.parbin : par_b + (int64_t)i * 3 * hw;
             const int* pflags = par_skip ? W.parflags + (int64_t)i * ((w + 15) / 16) * ((h + 7) / 8) : nullptr;
@@ -1177,20 +1205,6 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
             if (r) return r;
             const float* x = W.tmp0;
             const bool un = wino_units(h, w);
-            if (wino_on && g->ndyn > 0) {      // this frame's Winograd images of the branch's expert-mixed convs, its channel gain folded in
-                std::vector<const float*> ws;
-                std::vector<float*> wd;
-                for (int k = 0; k < c.num_blocks; ++k) {
-                    const BlockPk& K = B.blocks[k];
-                    if (K.dyn_conv2 >= 0) { ws.push_back(W.mixw + ((int64_t)u * g->ndyn + K.dyn_conv2) * IMG_WIDE); wd.push_back(W.wino + (int64_t)(2 * k) * PNP_WINO_IMG_FLOATS); }
-                    if (K.dyn_conv1 >= 0) { ws.push_back(W.mixw + ((int64_t)u * g->ndyn + K.dyn_conv1) * IMG_WIDE); wd.push_back(W.wino + (int64_t)(2 * k + 1) * PNP_WINO_IMG_FLOATS); }
-                }
-                for (size_t j = 0; j < ws.size(); j += 16) {
-                    const int n = (int)(ws.size() - j < 16 ? ws.size() - j : 16);
-                    r = launch_wino_images(ws.data() + j, wd.data() + j, n, gam, st);
-                    if (r) return r;
-                }
-            }
             for (int k = 0; k < c.num_blocks; ++k) {
                 const BlockPk& K = B.blocks[k];
                 float* dst = (k == c.num_blocks - 1) ? slot : W.tmp0;
@@ -1205,8 +1219,8 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
                 const float* b1 = c.one_layer ? flat + K.conv1_bias
                                               : W.mixb + ((int64_t)u * g->ndyn + K.dyn_conv1) * 64;
                 const float* g1 = c.one_layer ? nullptr : gam;
-                const float* u2 = !wino_on ? nullptr : (woqp ? packed + K.conv2_wino : W.wino + (int64_t)(2 * k) * PNP_WINO_IMG_FLOATS);
-                const float* u1 = !wino_on ? nullptr : (c.one_layer ? packed + K.conv1_wino : W.wino + (int64_t)(2 * k + 1) * PNP_WINO_IMG_FLOATS);
+                const float* u2 = !wino_on ? nullptr : (woqp ? packed + K.conv2_wino : wbuf + (int64_t)(2 * k) * PNP_WINO_IMG_FLOATS);
+                const float* u1 = !wino_on ? nullptr : (c.one_layer ? packed + K.conv1_wino : wbuf + (int64_t)(2 * k + 1) * PNP_WINO_IMG_FLOATS);
                 const float* up = !wino_on ? nullptr : packed + K.w1x1_wino;
                 // the map between the two halves is read only as an MFMA A operand: an fp16 map on the fp16 path
                 const int o16 = f16_maps ? 1 : 0, s16 = f16_maps ? 2 : 0;
@@ -1240,7 +1254,12 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
         if (!make_schedule(g, t, key, steps, &recomputed)) return PNP_ERR_BAD_ARG;
         auto slot_of = [&](int s) { return W.slots + (int64_t)s * fm; };
         auto wi = [&](int64_t off) -> const float* { return wino_on ? packed + off : nullptr; };
-        for (const Step& sp : steps) {
+        if (!steps.empty()) {
+            rc = branch_images(steps[0].sweep, steps[0].frame, 0);
+            if (rc) return rc;
+        }
+        for (size_t si = 0; si < steps.size(); ++si) {
+            const Step& sp = steps[si];
             const int i = sp.frame;
             const BranchPk& B = g->br[sp.sweep];
             ConvCall in(h, w, cfg_lr);
@@ -1265,9 +1284,14 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
             }
             // the branch's convs as a row-band chain: input conv + two per block (+ conv_hr behind a forward branch at the frame's size)
             const bool hr_in_chain = sp.sweep == 1 && !c.vsr;
+            // the next run's images first (recomputed runs of the bounded schedule are steps like any other): off this run's chains
+            if (si + 1 < steps.size()) {
+                rc = branch_images(steps[si + 1].sweep, steps[si + 1].frame, (int)((si + 1) & 1));
+                if (rc) return rc;
+            }
             rc = chain_open(1 + 2 * c.num_blocks + (hr_in_chain ? 1 : 0));
             if (rc) return rc;
-            rc = run_branch(sp.sweep, i, sp.out, in);
+            rc = run_branch(sp.sweep, i, sp.out, (int)(si & 1), in);
             if (!rc && !hr_in_chain) rc = chain_close();
             if (rc) return rc;
             if (sp.sweep == 0) continue;
