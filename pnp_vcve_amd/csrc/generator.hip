@@ -441,6 +441,9 @@ struct Workspace {
 
 int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
+// 8x16 tiles of a frame: one partition flag word each (Workspace::parflags, ConvArgs::par_flags)
+int64_t par_flag_tiles(int h, int w) { return (int64_t)((w + 15) / 16) * ((h + 7) / 8); }
+
 // Largest per-LR-pixel byte extent any kernel of the clip addresses with 32-bit offsets: a 64-channel fp32 map is
 // 256 B/pixel (x16 pixels behind the x4 heads); the DCN aligners' offset/mask map is 448 channels = 1792 B/pixel.
 int64_t pnp_addr32_bytes_per_lr_pixel(int vsr, int deform) {
@@ -649,7 +652,7 @@ Workspace carve(const pnp_generator* g, char* base, int t, int h, int w, int lq_
     W.x16 = mir ? reinterpret_cast<uint16_t*>(take(hw * 32)) : nullptr;
     W.slots16 = mir ? reinterpret_cast<uint16_t*>(take(hw * 32 * nslots)) : nullptr;
     W.parany = reinterpret_cast<int*>(take(t));        // (not last: the harness shrinks the workspace and expects the last region to be touched)
-    W.parflags = reinterpret_cast<int*>(take((int64_t)t * ((w + 15) / 16) * ((h + 7) / 8)));
+    W.parflags = reinterpret_cast<int*>(take(t * par_flag_tiles(h, w)));
     W.queue = g->prec == PNP_PREC_F16X3 ? reinterpret_cast<int*>(take(16)) : nullptr;
     // (behind everything else and only in the modes that need them: the fp32 boundary's layout and size are what they were)
     const bool staged = io_staged(g);
@@ -834,66 +837,29 @@ int pnp_generator_min_resident(const pnp_generator* g, int t) {
 
 namespace {
 
-// One sample (clip) of the batch on one stream with one workspace context.
-int forward_sample(const pnp_generator* g, const float* flat, const float* packed, const pnp_clip_io& io, int lq_format, int out_mask,
-                   const float* sl, const float* qp, const float* bq,
-                   const Workspace& W, int t, int h, int w, hipStream_t st, bool alone) {
-    const auto& c = g->cfg;
-    // the clip's tensors: the frames as fp32 planes or as bytes, the output as fp32 planes and / or bytes
-    const float* const lr_b = lq_format == PNP_FRAMES_U8_HWC ? nullptr : static_cast<const float*>(io.lq_dev);
-    const unsigned char* const lq8 = lq_format == PNP_FRAMES_U8_HWC ? static_cast<const unsigned char*>(io.lq_dev) : nullptr;
-    float* const out_b = (out_mask & PNP_OUT_F32) ? io.out_f32_dev : nullptr;
-    unsigned char* const out8 = (out_mask & PNP_OUT_U8) ? io.out_u8_dev : nullptr;
-    const float* const mv_b = io.mvs_dev;
-    const float* par_b = io.par_dev;
-    const bool staged = (lq8 || out8) && io_staged(g);
-    const int64_t hw = (int64_t)h * w, fm = hw * 64;
-    const int E = c.num_experts;
-    const int cfg_lr = conv_pick_cfg(h, w);
-    const int os = c.vsr ? 4 : 1;
-    int rc;
+// An untimed launch (or a wait) was issued: it sits between two timed ones, whose shared event (ProfScope) would time it too.
+void untimed(const pnp_generator* g) { g->prof_last = nullptr; }
 
-    // fp16 mirror of a weight image that lives in `packed` or in the per-clip expert mixtures
-    const int64_t n_mix = (int64_t)t * g->ndyn * IMG_WIDE;
-    auto twin = [&](const float* p) -> const void* {
-        if (g->prec == PNP_PREC_F32 || !p) return nullptr;
-        const int64_t halfs = g->prec == PNP_PREC_F16X3 ? 2 : 1;       // halfs of the twin per float of the image
-        if (p >= packed && p < packed + g->packed_floats)
-            return reinterpret_cast<const uint16_t*>(packed + g->packed_floats) + halfs * (p - packed);
-        if (p >= W.mixw && p < W.mixw + n_mix) return reinterpret_cast<const uint16_t*>(W.mixh) + halfs * (p - W.mixw);
-        return nullptr;
-    };
-    const bool f16_maps = g->prec == PNP_PREC_F16 && g->opt[PNP_OPT_F16_MAPS];
-    const bool par_skip = g->opt[PNP_OPT_PAR_SKIP] != 0;
-    // Winograd form of the single-source 64 -> 64 convs (fp32 path only): 1 = frames that fill the chip with 16x16 tiles, 2 = always
-    const int wopt = g->prec == PNP_PREC_F32 ? g->opt[PNP_OPT_WINOGRAD] : 0;
-    // 1: a frame of N 16x16 tiles takes the quadrant-unit kernel up to N = 128 (4 N blocks; 128x128: 12 us per conv against the direct
-    // kernel's 15 and the tile kernel's 26 on 64 of 256 CUs) and the persistent tile kernel above (240 tiles: 31 us against 48 direct);
-    // the input convs over wide sources likewise (180x320, 240 tiles, fp32: 561 frames/s direct, 707 with the direct input convs kept,
-    // 712 with the multi-source tile kernel).  2 = the tile kernels at every size (tests)
-    auto ntiles16 = [](int hh, int ww) { return (int64_t)((hh + 15) / 16) * ((ww + 15) / 16); };
-    const bool wino_on = wopt != 0;
-    auto wino_units = [&](int hh, int ww) { return wopt == 1 && ntiles16(hh, ww) <= PNP_WINO_UNITS_MAX_TILES; };
-    // every 64-channel map that is only read as an MFMA A operand gets an fp16 copy from its producer (DESIGN.md 3.4)
-    const bool mirrors = f16_maps && g->opt[PNP_OPT_F16_MIRRORS] && c.deform == 0 && W.x16 != nullptr;
-    // ... and, optionally, the running map x INSIDE a branch too (input conv and every block write x16 next to x, every front
-    // half reads it).  Measured at 720p inside the pipeline (profiles/r03_fp16_*): the front half gains what the back half loses
-    // to the extra 128 B per pixel it writes -- off by default, the frame slots keep their mirrors.
-    const bool chain16 = mirrors && g->opt[PNP_OPT_F16_CHAIN_MIRRORS];
-    // ---- row-band chain in flight (band_plan): opened per branch run by the step loop, every conv goes through `conv` below
-    // `alone`: the only workspace context in flight (several clips on several streams fill each other's launch tails already)
-    const bool band_mode = alone && g->band_split != 0 && wopt != 0 && !wino_units(h, w);
-    struct {
-        bool open = false, forked = false;
-        int left = 0, n = 0, row = 0;       // convs still to come; convs split so far; the next conv's boundary row
-    } chain;
-    auto chain_open = [&](int nconv) -> int {
-        if (!band_mode) return PNP_OK;
+// A row-band chain in flight (band_plan): ClipRun::step opens one per branch run, ClipRun::conv attaches every conv of the run.
+// The destructor joins: the caller's stream waits for chain B also on the way out of an error.
+struct BandChain {
+    const pnp_generator* g;
+    hipStream_t st;           // the caller's stream (chain A)
+    bool enabled;             // the clip qualifies at all (ClipRun's band_mode)
+    int rows;                 // 16-pixel tile rows of the frame
+    bool is_open = false, forked = false;
+    int left = 0, n = 0, row = 0;       // convs still to come; convs split so far; the next conv's boundary row
+
+    BandChain(const pnp_generator* g_, hipStream_t st_, bool enabled_, int h) : g(g_), st(st_), enabled(enabled_), rows((h + 15) / 16) {}
+    BandChain(const BandChain&) = delete;
+    ~BandChain() { (void)close(); }
+    int first_row() const { return g->band_split >= 2 ? g->band_split : 0; }      // pnp_generator_set_band_split: >= 2 names the first boundary
+    int open(int nconv) {
+        if (!enabled) return PNP_OK;
         // (the stream and the events are made the first time a frame qualifies: with the chain's first conv on another kernel it is
         //  one conv shorter)
         int first;
-        const int rows = (h + 15) / 16, a0 = g->band_split >= 2 ? g->band_split : 0;
-        if (!band_plan(rows, nconv, a0, &first) && !band_plan(rows, nconv - 1, a0, &first)) return PNP_OK;
+        if (!band_plan(rows, nconv, first_row(), &first) && !band_plan(rows, nconv - 1, first_row(), &first)) return PNP_OK;
         if (!g->band_stream) {
             const hipError_t e = hipStreamCreateWithFlags(&g->band_stream, hipStreamNonBlocking);
             if (e != hipSuccess) return (int)e;
@@ -904,40 +870,122 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
             if (err != hipSuccess) return (int)err;
             g->band_events.push_back(e);
         }
-        chain.open = true;
-        chain.forked = false;
-        chain.left = nconv;
-        chain.n = 0;
+        is_open = true, forked = false;
+        left = nconv, n = 0;
         return PNP_OK;
-    };
-    // the caller's stream waits for chain B: in front of whatever reads a whole map next (also on the way out of an error)
-    auto chain_close = [&]() -> int {
-        const bool join = chain.open && chain.forked;
-        chain.open = chain.forked = false;
+    }
+    // The next conv of the open chain.  tiles: it runs on the Winograd tile kernels at the frame's size, which take a conv of the chain as
+    // two launches.  A conv on another kernel can only be the chain's first (the RGB-only input conv of a clip's last frame): it runs
+    // whole on the caller's stream in front of the first `ready` event, and the numbering starts behind it
+    int attach(ConvArgs& a, bool tiles) {
+        if (!tiles && n > 0) return PNP_ERR_UNSUPPORTED;
+        if (tiles && n == 0 && !band_plan(rows, left, first_row(), &row)) is_open = false;          // too few tile rows for this chain: one launch per conv
+        --left;
+        if (!tiles || !is_open) return PNP_OK;
+        g->band_recs.emplace_back();
+        ConvBandSplit& band = g->band_recs.back();
+        memset(&band, 0, sizeof(band));
+        band.side = g->band_stream;
+        band.ready = g->band_events[n++];
+        band.row = row--;
+        a.band = &band;
+        forked = true;
+        return PNP_OK;
+    }
+    // the caller's stream waits for chain B: in front of whatever reads a whole map next
+    int close() {
+        const bool join = is_open && forked;
+        is_open = forked = false;
         if (!join) return PNP_OK;
         hipError_t e = hipEventRecord(g->band_events.back(), g->band_stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(st, g->band_events.back(), 0);
-        g->prof_last = nullptr;
+        untimed(g);
         return (int)e;
-    };
-    struct ChainGuard {
-        decltype(chain_close)& close;
-        ~ChainGuard() { (void)close(); }
-    } chain_guard{chain_close};
-    auto conv = [&](const ConvCall& q) -> int {
+    }
+};
+
+// One sample (clip) of the batch on one stream with one workspace context: what the run needs to know, and its launches phase by phase.
+struct ClipRun {
+    const pnp_generator* const g;
+    const pnp_generator_cfg& c;
+    const float *const flat, *const packed;
+    const Workspace W;
+    const int t, h, w;
+    const hipStream_t st;
+    // the clip's tensors: the frames as fp32 planes or as bytes, the output as fp32 planes and / or bytes
+    const float* const lr_b; const unsigned char* const lq8;
+    float* const out_b; unsigned char* const out8;
+    const float *const mv_b, *const par_in, *const sl, *const qp, *const bq;
+    const bool staged, alone;      // alone: the only workspace context in flight
+    const int64_t hw = (int64_t)h * w, fm = hw * 64;
+    const int E = c.num_experts, cfg_lr = conv_pick_cfg(h, w), os = c.vsr ? 4 : 1;
+    const bool f16_maps = g->prec == PNP_PREC_F16 && g->opt[PNP_OPT_F16_MAPS], par_skip = g->opt[PNP_OPT_PAR_SKIP] != 0;
+    // Winograd form of the single-source 64 -> 64 convs (fp32 path only): 1 = frames that fill the chip with 16x16 tiles, 2 = always
+    const int wopt = g->prec == PNP_PREC_F32 ? g->opt[PNP_OPT_WINOGRAD] : 0;
+    const bool wino_on = wopt != 0;
+    // every 64-channel map that is only read as an MFMA A operand gets an fp16 copy from its producer (DESIGN.md 3.4)
+    const bool mirrors = f16_maps && g->opt[PNP_OPT_F16_MIRRORS] && c.deform == 0 && W.x16 != nullptr;
+    // ... and, optionally, the running map x INSIDE a branch too (input conv and every block write x16 next to x, every front
+    // half reads it).  Measured at 720p inside the pipeline (profiles/r03_fp16_*): the front half gains what the back half loses
+    // to the extra 128 B per pixel it writes -- off by default, the frame slots keep their mirrors.
+    const bool chain16 = mirrors && g->opt[PNP_OPT_F16_CHAIN_MIRRORS];
+    // row-band chains: not with several clips on several streams, which fill each other's launch tails already
+    const bool band_mode = alone && g->band_split != 0 && wopt != 0 && !wino_units(h, w);
+    BandChain chain{g, st, band_mode, h};
+    // what the prologue leaves for the sweeps: the mixture of every frame, the key frames, the partition planes the block convs read
+    std::vector<int> uidx;
+    std::vector<char> key;
+    const float* par_b = par_in;
+    bool sparse_per_frame = false;
+
+    ClipRun(const pnp_generator* g_, const float* flat_, const float* packed_, const pnp_clip_io& io, int lq_format, int out_mask,
+            const float* sl_, const float* qp_, const float* bq_, const Workspace& W_, int t_, int h_, int w_, hipStream_t st_, bool alone_)
+        : g(g_), c(g_->cfg), flat(flat_), packed(packed_), W(W_), t(t_), h(h_), w(w_), st(st_),
+          lr_b(lq_format == PNP_FRAMES_U8_HWC ? nullptr : static_cast<const float*>(io.lq_dev)),
+          lq8(lq_format == PNP_FRAMES_U8_HWC ? static_cast<const unsigned char*>(io.lq_dev) : nullptr),
+          out_b((out_mask & PNP_OUT_F32) ? io.out_f32_dev : nullptr), out8((out_mask & PNP_OUT_U8) ? io.out_u8_dev : nullptr),
+          mv_b(io.mvs_dev), par_in(io.par_dev), sl(sl_), qp(qp_), bq(bq_), staged((lq8 || out8) && io_staged(g_)), alone(alone_) {}
+
+    // fp16 mirror of a weight image that lives in `packed` or in the per-clip expert mixtures
+    const void* twin(const float* p) const {
+        if (g->prec == PNP_PREC_F32 || !p) return nullptr;
+        const int64_t halfs = g->prec == PNP_PREC_F16X3 ? 2 : 1;       // halfs of the twin per float of the image
+        if (p >= packed && p < packed + g->packed_floats)
+            return reinterpret_cast<const uint16_t*>(packed + g->packed_floats) + halfs * (p - packed);
+        if (p >= W.mixw && p < W.mixw + (int64_t)t * g->ndyn * IMG_WIDE) return reinterpret_cast<const uint16_t*>(W.mixh) + halfs * (p - W.mixw);
+        return nullptr;
+    }
+    // wopt 1: a frame of N 16x16 tiles takes the quadrant-unit kernel up to N = 128 (4 N blocks; 128x128: 12 us per conv against the direct
+    // kernel's 15 and the tile kernel's 26 on 64 of 256 CUs) and the persistent tile kernel above (240 tiles: 31 us against 48 direct);
+    // the input convs over wide sources likewise (180x320, 240 tiles, fp32: 561 frames/s direct, 707 with the direct input convs kept,
+    // 712 with the multi-source tile kernel).  2 = the tile kernels at every size (tests)
+    static int64_t ntiles16(int hh, int ww) { return (int64_t)((hh + 15) / 16) * ((ww + 15) / 16); }
+    bool wino_units(int hh, int ww) const { return wopt == 1 && ntiles16(hh, ww) <= PNP_WINO_UNITS_MAX_TILES; }
+    const float* wi(int64_t off) const { return wino_on ? packed + off : nullptr; }      // a Winograd image in `packed`
+    // image buffer `buf` of W.wino: a branch run's Winograd images of its expert-mixed convs (branch_images)
+    float* wino_buf(int buf) const { return W.wino + (int64_t)buf * 2 * c.num_blocks * PNP_WINO_IMG_FLOATS; }
+    // expert-mixed conv `dyn` of mixture u: its weight image and its bias
+    float* mix_w(int u, int dyn) const { return W.mixw + ((int64_t)u * g->ndyn + dyn) * IMG_WIDE; }
+    float* mix_b(int u, int dyn) const { return W.mixb + ((int64_t)u * g->ndyn + dyn) * 64; }
+    const float* gam(int i) const { return (c.with_bias && c.with_se) ? W.gamma + (int64_t)i * 64 : nullptr; }      // frame i's channel gain
+    const float* routing() const { return c.use_base_qp ? bq : qp; }
+    float* slot_of(int s) const { return W.slots + (int64_t)s * fm; }
+    // fp16 mirror of a frame slot (sources of an input conv, conv_hr)
+    const void* s16of(int s) const { return mirrors ? (const void*)(W.slots16 + (int64_t)s * fm) : nullptr; }
+    // bounded schedule: frame i's sparse-equivalent partition map into the one-frame buffer
+    int sparse_frame(int i) const { return launch_par_sparse(par_in + (int64_t)i * 3 * hw, W.parbin, 1, h, w, st); }
+
+    // ConvCall -> ConvArgs: no side effect, no chain state
+    ConvArgs conv_args(const ConvCall& q) const {
         ConvArgs a;
         memset(&a, 0, sizeof(a));
         a.nsrc = q.nsrc;
         a.prec = g->prec;                 // PNP_PREC_* are ConvArgs::prec's values
         for (int s = 0; s < q.nsrc; ++s) {
-            a.src[s] = q.src[s];
-            a.src_c[s] = q.sc[s];
-            a.wsrc[s] = q.w[s];
-            a.wsrc_h[s] = twin(q.w[s]);
+            a.src[s] = q.src[s], a.src_c[s] = q.sc[s];
+            a.wsrc[s] = q.w[s], a.wsrc_h[s] = twin(q.w[s]);
         }
-        a.wpar = q.wpar_;
-        a.wwino = q.wino_;
-        a.wwino_par = q.wino_par_;
+        a.wpar = q.wpar_, a.wwino = q.wino_, a.wwino_par = q.wino_par_;
         if (q.nsrc >= 2 && q.sc[0] == 4 && q.wsrc_wino_[0]) {      // input conv with Winograd images on every member
             a.wwino_rgb = q.wsrc_wino_[0];
             for (int s = 1; s < q.nsrc; ++s) a.wwino_src[s] = q.wsrc_wino_[s];
@@ -946,29 +994,17 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
         a.par_any = (q.wino_ && q.wpar_) ? q.par_any_ : nullptr;       // (tile kernels and quadrant-unit kernels alike: one gated launch)
         a.wpar_h = twin(q.wpar_);
         a.wpar_h_scaled = (g->prec == PNP_PREC_F16X3 && a.wpar_h) ? 1 : 0;     // the packed buffer holds 3 + 3 branch images (build_layout)
-        a.par = q.par_;
-        a.par_flags = q.par_flags_;
+        a.par = q.par_, a.par_flags = q.par_flags_;
         a.tile_queue = (g->prec == PNP_PREC_F16X3 && g->opt[PNP_OPT_TILE_QUEUE]) ? W.queue : nullptr;
         a.par_plane = (long)q.H * q.W;
-        a.bias = q.bias_;
-        a.gamma = q.gamma_;
-        a.residual = q.residual_;
-        a.out = q.dst;
-        a.lr = q.lr_;
-        a.lr_plane = q.lr_plane_;
+        a.bias = q.bias_, a.gamma = q.gamma_, a.residual = q.residual_, a.out = q.dst;
+        a.lr = q.lr_, a.lr_plane = q.lr_plane_;
         a.wvalu = g->opt[PNP_OPT_CONV_LAST_VALU] ? q.wvalu_ : nullptr;
-        a.no_persist = g->opt[PNP_OPT_PERSIST] ? 0 : 1;
-        a.no_small16 = g->opt[PNP_OPT_SMALL_F16] ? 0 : 1;
-        a.no_multi16 = 0;
-        a.w_ystride = q.w_ystride_;
-        a.bias_ystride = q.bias_ystride_;
-        a.H = q.H;
-        a.W = q.W;
-        a.act = q.act_;
-        a.out_mode = q.mode_;
-        a.out_cstride = 448;
-        a.lr_u8 = q.lr8_;
-        a.out_u8 = q.out8_;
+        a.no_persist = g->opt[PNP_OPT_PERSIST] ? 0 : 1, a.no_small16 = g->opt[PNP_OPT_SMALL_F16] ? 0 : 1;
+        a.w_ystride = q.w_ystride_, a.bias_ystride = q.bias_ystride_;
+        a.H = q.H, a.W = q.W, a.act = q.act_;
+        a.out_mode = q.mode_, a.out_cstride = 448;
+        a.lr_u8 = q.lr8_, a.out_u8 = q.out8_;
         a.out_f16 = q.io16_ & 1;          // io16: bit 0 the output is an fp16 map, bit 1 source 0 is one
         a.src_f16 = (q.io16_ & 2) ? 1 : 0;
         if (mirrors) {
@@ -979,43 +1015,128 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
                 }
             a.out16 = q.out16_;
         }
-        // algorithmic FLOPs of this launch (reference channel counts, not padded ones)
+        return a;
+    }
+    // what ProfScope books a launch under: its kind, and its algorithmic FLOPs (reference channel counts, not padded ones)
+    static int conv_kind(const ConvCall& q) {
+        return (q.mode_ != 0) ? PNP_PROF_CONV_HEAD : (q.nsrc > 1 || q.sc[0] != 64) ? PNP_PROF_CONV_INPUT : PNP_PROF_CONV_BLOCK;
+    }
+    static double conv_work(const ConvCall& q) {
         double kreal = 0;
         for (int s = 0; s < q.nsrc; ++s) kreal += 9.0 * (q.sc[s] == 64 ? 64 : 3);
         if (q.wpar_) kreal += 3 * 64;
         const double nreal = (q.mode_ == 2 || q.mode_ == 3) ? 3 : 64;   // RGB heads; mode 4 (DCN offsets) is 64 per blockIdx.y
-        const int kind = (q.mode_ != 0) ? PNP_PROF_CONV_HEAD
-                                        : (q.nsrc > 1 || q.sc[0] != 64) ? PNP_PROF_CONV_INPUT : PNP_PROF_CONV_BLOCK;
+        return 2.0 * kreal * nreal * (double)q.H * q.W * q.gy_;
+    }
+    int conv(const ConvCall& q) {
+        ConvArgs a = conv_args(q);
         // (a conv of a row-band chain is timed like any other, on the caller's stream: back to back with its neighbours that is the
         //  chain's time per conv.  Its part on the side stream shares the chip with the next conv's part A: timed as well and added,
         //  a kind's total would exceed wall time, which bench.py's rooflines -- executed work over launch time -- rule out)
-        ProfScope ps(g, st, kind, 2.0 * kreal * nreal * (double)q.H * q.W * q.gy_);
-        if (chain.open) {
-            // the tile kernels take a conv of the chain as two launches.  A conv on another kernel can only be the chain's first (the
-            // RGB-only input conv of a clip's last frame): it runs whole on the caller's stream in front of the first `ready` event,
-            // and the numbering starts behind it
+        ProfScope ps(g, st, conv_kind(q), conv_work(q));
+        if (chain.is_open) {
             const bool tiles = !a.wino_units && q.H == h && q.W == w && (conv_wino_eligible(a, q.cfg_, q.gy_) || conv_wino_ms_eligible(a, q.cfg_, q.gy_));
-            if (!tiles && chain.n > 0) return PNP_ERR_UNSUPPORTED;
-            if (tiles && chain.n == 0 && !band_plan((h + 15) / 16, chain.left, g->band_split >= 2 ? g->band_split : 0, &chain.row))
-                chain.open = false;          // too few tile rows for this chain: one launch per conv
-            --chain.left;
-            if (tiles && chain.open) {
-                g->band_recs.emplace_back();
-                ConvBandSplit& band = g->band_recs.back();
-                memset(&band, 0, sizeof(band));
-                band.side = g->band_stream;
-                band.ready = g->band_events[chain.n++];
-                band.row = chain.row--;
-                a.band = &band;
-                chain.forked = true;
-            }
+            const int rc = chain.attach(a, tiles);
+            if (rc) return rc;
         }
         if (a.lr_u8 || a.out_u8) return launch_conv_last_io(a, st);      // (conv_last only, outside every chain)
         return launch_conv3x3(a, q.cfg_, q.gy_, st);
-    };
+    }
+
+    int fill_and_pack() {
+        untimed(g);           // untimed launches follow
+        if (W.queue) {
+            // the last block of every launch leaves the queue zeroed; once per clip for a fresh workspace or a launch that was cut short.
+            // A KERNEL, not hipMemsetAsync: as a memset node of a captured graph (generator.use_graphs) the 64 bytes came back as
+            // pointer-like garbage from the second replay on (ROCm 7.2; tools/repro/graph_memset_node.py), i.e. endless ticket loops
+            const int rc = launch_fill(reinterpret_cast<float*>(W.queue), 0.0f, 16, st);
+            if (rc) return rc;
+        }
+        return lq8 ? launch_pack_lr_u8(lq8, W.lr4, t, h, w, st) : launch_pack_lr(lr_b, W.lr4, t, h, w, st);
+    }
+    int partition_maps() {
+        // the reference's (eval-mode) sparse evaluation as a dense map (prep.hip): for the whole clip at once, or (bounded schedule)
+        // one frame at a time into a one-frame buffer, just before each branch run that reads it
+        const bool sparse_now = c.sparse_val && g->opt[PNP_OPT_SPARSE_EVAL];
+        sparse_per_frame = sparse_now && bounded_mode(g, t);
+        int rc = PNP_OK;
+        if (sparse_now && !sparse_per_frame) {
+            rc = launch_par_sparse(par_in, W.parbin, t, h, w, st);
+            if (rc) return rc;
+            par_b = W.parbin;
+        }
+        // which 1x1 partition branches each 8x16 tile of each frame needs at all (32 front-half launches per frame use it)
+        if (!par_skip) return PNP_OK;
+        for (int i = 0; sparse_per_frame && i < t && !rc; ++i) {
+            rc = sparse_frame(i);
+            if (!rc) rc = launch_par_tile_flags(W.parbin, hw, W.parflags + i * par_flag_tiles(h, w), 1, h, w, st);
+        }
+        if (!sparse_per_frame) rc = launch_par_tile_flags(par_b, hw, W.parflags, t, h, w, st);
+        if (rc) return rc;
+        if (wopt >= 1) rc = launch_par_frame_any(W.parflags, W.parany, t, h, w, st);      // (for the I frames' gated front halves)
+        return rc;
+    }
+    // CAA hyper-network (iconvsr_ipb_par.py:45-48)
+    int caa() {
+        for (int t0 = 0; t0 < t; t0 += 32) {
+            CaaArgs a;
+            memset(&a, 0, sizeof(a));
+            a.count = (t - t0 < 32) ? t - t0 : 32;
+            for (int i = 0; i < a.count; ++i) {
+                a.q_ew[i] = routing()[t0 + i];
+                a.q_g[i] = qp[t0 + i];
+            }
+            a.t0 = t0, a.E = E, a.softmax = c.expert_softmax;
+            a.with_se = (c.with_bias && c.with_se) ? 1 : 0;
+            a.w1 = flat + g->p_w1, a.b1 = flat + g->p_b1;
+            a.w2 = flat + g->p_w2, a.b2 = flat + g->p_b2;
+            a.v1 = a.with_se ? flat + g->p_v1 : nullptr;
+            a.v2 = a.with_se ? flat + g->p_v2 : nullptr;
+            a.ew = W.ew, a.gamma = W.gamma;
+            const int rc = launch_caa_predict(a, st);
+            if (rc) return rc;
+        }
+        return PNP_OK;
+    }
+    // mixture u of every expert-mixed conv, from frame i's expert attention (+ its fp16 twin)
+    int mix(int i, int u) {
+        const int gcm = 64 / c.num_group;
+        PackArgs a = plain_pack(flat + g->dyn_w, 64, 9, PACK_WIDE, 0, 2, 64, mix_w(u, 0));
+        a.ew = W.ew + (int64_t)i * E;
+        a.E = E;
+        a.e_stride = 64 * gcm * 9;
+        a.group_cin = c.num_group > 1 ? gcm : 0;
+        a.w_ystride = (int64_t)E * 64 * gcm * 9;
+        a.dst_ystride = IMG_WIDE;
+        int rc = launch_pack_weights(a, g->ndyn, st);
+        if (rc) return rc;
+        rc = launch_mix_bias(flat + g->dyn_b, a.ew, mix_b(u, 0), E, 64, g->ndyn, st);
+        if (rc) return rc;
+        uint16_t* const mixh = reinterpret_cast<uint16_t*>(W.mixh);
+        if (g->prec == PNP_PREC_F16) rc = launch_f16_image(a.dst, mixh + (a.dst - W.mixw), g->ndyn * 9, 2, st);
+        if (g->prec == PNP_PREC_F16X3) rc = launch_f16x3_image(a.dst, mixh + (a.dst - W.mixw) * 2, g->ndyn * 9, st);
+        return rc;
+    }
+    // expert mixing, once per distinct routing input
+    int mix_experts() {
+        const float* qe = routing();
+        uidx.resize(t);
+        std::vector<int> ufirst;
+        for (int i = 0; i < t; ++i) {
+            int u = 0;
+            while (u < (int)ufirst.size() && memcmp(&qe[ufirst[u]], &qe[i], sizeof(float)) != 0) ++u;
+            if (u == (int)ufirst.size()) {
+                ufirst.push_back(i);
+                const int rc = g->ndyn > 0 ? mix(i, u) : PNP_OK;      // ('drt_woqp': no expert-mixed conv at all)
+                if (rc) return rc;
+            }
+            uidx[i] = u;
+        }
+        return PNP_OK;
+    }
 
     // deform_align(feat, flow) -> W.kw  (iconvsr_ipb.py:19-24 dispatch; iconvsr_mv.py:12-84)
-    auto align = [&](const float* feat, const float* fxp, const float* fyp) -> int {
+    int align(const float* feat, const float* fxp, const float* fyp) {
         int r;
         if (c.deform == 0 || c.deform == 1) {   // 'vos', and the pre-warp of 'basic' (:69)
             ProfScope ps(g, st, PNP_PROF_WARP, (mirrors ? 392.0 : 520.0) * (double)hw);     // 8 flow + 256 gather + 256 | 128 write
@@ -1023,7 +1144,7 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
             if (r || c.deform == 0) return r;
         }
         r = launch_pack_flow4(fxp, fyp, W.flow4, h, w, st);
-        g->prof_last = nullptr;           // an untimed launch sits between two timed ones
+        untimed(g);
         if (r) return r;
         // conv_offset[0] + LeakyReLU over cat([ref_warped | ref_unwarped, flow])
         r = conv(ConvCall(h, w, cfg_lr).source(W.flow4, 4, packed + g->off0_flow_img)
@@ -1036,324 +1157,203 @@ int forward_sample(const pnp_generator* g, const float* flat, const float* packe
         if (r) return r;
         DcnArgs d;
         d.dbg = nullptr;
-        d.x = feat;
-        d.om = W.om;
+        d.x = feat, d.om = W.om, d.out = W.kw;
         d.fx = c.deform == 1 ? fxp : nullptr;
         d.fy = c.deform == 1 ? fyp : nullptr;
         d.w = packed + g->dcn_img;
         d.w16 = g->prec == PNP_PREC_F16 ? twin(packed + g->dcn_img) : nullptr;
         d.bias = flat + g->f_dcn_b;
-        d.out = W.kw;
-        d.H = h;
-        d.W = w;
+        d.H = h, d.W = w;
         ProfScope ps(g, st, PNP_PROF_DCN, 2240.0 * (double)hw);
         return launch_dcn(d, st);
-    };
+    }
 
-    {
-        const float* qe = c.use_base_qp ? bq : qp;
-
-        g->prof_last = nullptr;           // untimed launches follow
-        if (W.queue) {
-            // the last block of every launch leaves the queue zeroed; once per clip for a fresh workspace or a launch that was cut short.
-            // A KERNEL, not hipMemsetAsync: as a memset node of a captured graph (generator.use_graphs) the 64 bytes came back as
-            // pointer-like garbage from the second replay on (ROCm 7.2; tools/repro/graph_memset_node.py), i.e. endless ticket loops
-            rc = launch_fill(reinterpret_cast<float*>(W.queue), 0.0f, 16, st);
-            if (rc) return rc;
+    // A branch run's Winograd images of its expert-mixed convs, this frame's channel gain folded in, into image buffer `buf` of W.wino.
+    // They depend on the clip prologue only (mixtures, gamma), not on any feature map, so the step loop issues run s + 1's in front
+    // of run s's chain (the first run's in front of the loop) into the buffer run s does not read: inside run_branch, between the
+    // input conv and the first block conv, the launch waited for CUs behind chain B's input-conv part and held chain A back.
+    // Buffer s & 1 is rewritten (for run s + 2) in front of run s + 1's chain, i.e. behind run s's join on the caller's stream.
+    int branch_images(int brid, int i, int buf) {
+        if (!(wino_on && g->ndyn > 0)) return 0;
+        float* wb = wino_buf(buf);
+        std::vector<const float*> ws;
+        std::vector<float*> wd;
+        for (int k = 0; k < c.num_blocks; ++k) {
+            const BlockPk& K = g->br[brid].blocks[k];
+            if (K.dyn_conv2 >= 0) { ws.push_back(mix_w(uidx[i], K.dyn_conv2)); wd.push_back(wb + (int64_t)(2 * k) * PNP_WINO_IMG_FLOATS); }
+            if (K.dyn_conv1 >= 0) { ws.push_back(mix_w(uidx[i], K.dyn_conv1)); wd.push_back(wb + (int64_t)(2 * k + 1) * PNP_WINO_IMG_FLOATS); }
         }
-        rc = lq8 ? launch_pack_lr_u8(lq8, W.lr4, t, h, w, st) : launch_pack_lr(lr_b, W.lr4, t, h, w, st);
+        for (size_t j = 0; j < ws.size(); j += 16) {
+            const int n = (int)(ws.size() - j < 16 ? ws.size() - j : 16);
+            const int r = launch_wino_images(ws.data() + j, wd.data() + j, n, gam(i), st);
+            if (r) return r;
+        }
+        untimed(g);
+        return 0;
+    }
+
+    // input conv over the virtual concat `in` (sources already added), then the BAE blocks
+    // (out: the frame map its last block writes, Step::out)
+    int run_branch(int brid, int i, int out, int buf, ConvCall in) {
+        const BranchPk& B = g->br[brid];
+        const float* wbuf = W.wino ? wino_buf(buf) : nullptr;
+        const float* parp = sparse_per_frame ? W.parbin : par_b + (int64_t)i * 3 * hw;
+        const int* pflags = par_skip ? W.parflags + (int64_t)i * par_flag_tiles(h, w) : nullptr;
+        // the frame's partition word (launch_par_frame_any) gates the front halves on the device: fold-only kernel / branch kernel
+        // (launch_conv3x3_wino); an I frame usually carries no record at all (its word is then 8: all quadrants zero)
+        // (any frame size: a quadrant cut by the frame's edge -- 180x320 has a last row of them 4 pixels high -- counts with the pixels
+        //  it has, in the flags and in the kernels alike)
+        const int* pany = (par_skip && wopt >= 1) ? W.parany + i : nullptr;
+        const int u = uidx[i];
+        const bool un = wino_units(h, w);
+        // fp16 mirrors: the input conv writes x16 next to x when it runs on the fp16 kernels at all (an RGB-only one does not)
+        const void* x16 = (chain16 && in.nsrc > 1) ? W.x16 : nullptr;
+        int r = conv(in.bias(flat + B.in_bias).act(2).units(un).to(W.tmp0).also16(const_cast<void*>(x16)));
+        if (r) return r;
+        const float* x = W.tmp0;
+        const bool woqp = c.blocktype == 1;      // conv2 a plain conv as well: no expert mix, no gain (sr_backbone_utils.py:366-384)
+        // the map between the two halves is read only as an MFMA A operand: an fp16 map on the fp16 path
+        const int o16 = f16_maps ? 1 : 0, s16 = f16_maps ? 2 : 0;
+        for (int k = 0; k < c.num_blocks; ++k) {
+            const BlockPk& K = B.blocks[k];
+            const bool last = k == c.num_blocks - 1;
+            float* dst = last ? slot_of(out) : W.tmp0;
+            void* dst16 = !mirrors ? nullptr : last ? (void*)(W.slots16 + (int64_t)out * fm) : (chain16 ? (void*)W.x16 : nullptr);
+            const float* w2 = woqp ? packed + K.conv2_img : mix_w(u, K.dyn_conv2);
+            const float* b2 = woqp ? flat + K.conv2_bias : mix_b(u, K.dyn_conv2);
+            const float* g2 = woqp ? nullptr : gam(i);
+            const float* w1 = c.one_layer ? packed + K.conv1_img : mix_w(u, K.dyn_conv1);
+            const float* b1 = c.one_layer ? flat + K.conv1_bias : mix_b(u, K.dyn_conv1);
+            const float* g1 = c.one_layer ? nullptr : gam(i);
+            const float* u2 = !wino_on ? nullptr : (woqp ? packed + K.conv2_wino : wbuf + (int64_t)(2 * k) * PNP_WINO_IMG_FLOATS);
+            const float* u1 = !wino_on ? nullptr : (c.one_layer ? packed + K.conv1_wino : wbuf + (int64_t)(2 * k + 1) * PNP_WINO_IMG_FLOATS);
+            if (c.channel_first) {   // sr_backbone_utils.py:305-313
+                r = conv(ConvCall(h, w, cfg_lr).source(x, 64, w2).mirror16(x16).bias(b2).gamma(g2)
+                             .partition(packed + K.w1x1, parp, pflags).gate(pany).wino(u2, wi(K.w1x1_wino)).units(un).act(1).to(W.tmp1).f16_map(o16));
+                if (!r)
+                    r = conv(ConvCall(h, w, cfg_lr).source(W.tmp1, 64, w1).bias(b1).gamma(g1).wino(u1).units(un).residual(x).to(dst)
+                                 .f16_map(s16).also16(dst16));
+            } else {                 // sr_backbone_utils.py:314-327
+                r = conv(ConvCall(h, w, cfg_lr).source(x, 64, w1).mirror16(x16).bias(b1).gamma(g1).wino(u1).units(un).act(1).to(W.tmp1)
+                             .f16_map(o16));
+                if (!r)
+                    r = conv(ConvCall(h, w, cfg_lr).source(W.tmp1, 64, w2).bias(b2).gamma(g2)
+                                 .partition(packed + K.w1x1, parp, pflags).gate(pany).wino(u2, wi(K.w1x1_wino)).units(un).residual(x).to(dst).f16_map(s16).also16(dst16));
+            }
+            if (r) return r;
+            x = dst;
+            x16 = chain16 ? dst16 : nullptr;
+        }
+        return 0;
+    }
+
+    // reconstruction of a forward step's frame (iconvsr_ipb_par.py:135-146): [two PixelShufflePack(2) convs, 4 sub-pixel weight images
+    // each,] conv_hr, then conv_last + the (x4 bilinear) frame
+    int head(const Step& sp) {
+        const int i = sp.frame, H = h * os, Wd = w * os;
+        // every map of the head is read by exactly one conv, as an MFMA A operand: fp16 maps all the way on the fp16 path
+        // (the 720p map between the second pixel shuffle and conv_hr alone is 236 MB written + read per frame in fp32)
+        const int o16 = f16_maps ? 1 : 0, s16 = f16_maps ? 2 : 0;
+        const float* x = slot_of(sp.out);
+        const void* x16 = s16of(sp.out);
+        int rc = PNP_OK;
+        if (c.vsr) {
+            rc = conv(ConvCall(h, w, cfg_lr).source(x, 64, packed + g->up_img[0]).bias(packed + g->up_bias[0], 64)
+                          .act(2).mode(1, 4, IMG_WIDE).to(W.u1).f16_map(o16));
+            if (!rc)
+                rc = conv(ConvCall(2 * h, 2 * w, conv_pick_cfg(2 * h, 2 * w)).source(W.u1, 64, packed + g->up_img[1])
+                              .bias(packed + g->up_bias[1], 64).act(2).mode(1, 4, IMG_WIDE).to(W.u2).f16_map(o16 | s16));
+            if (rc) return rc;
+            x = W.u2;
+            x16 = nullptr;
+        }
+        float* const top = c.vsr ? W.u3 : W.tmp1;
+        rc = conv(ConvCall(H, Wd, conv_pick_cfg(H, Wd)).source(x, 64, packed + g->hr_img).mirror16(x16).bias(flat + g->hr_bias)
+                      .wino(wi(g->hr_wino)).units(wino_units(H, Wd)).act(2).to(top).f16_map(c.vsr ? o16 | s16 : o16));
+        if (!rc) rc = chain.close();      // (conv_hr at the frame's size is the last conv of a forward branch's chain)
         if (rc) return rc;
-        // the reference's (eval-mode) sparse evaluation as a dense map (prep.hip): for the whole clip at once, or (bounded schedule)
-        // one frame at a time into a one-frame buffer, just before each branch run that reads it
-        const float* const par_in = par_b;
-        const bool sparse_now = c.sparse_val && g->opt[PNP_OPT_SPARSE_EVAL];
-        const bool sparse_per_frame = sparse_now && bounded_mode(g, t);
-        if (sparse_now && !sparse_per_frame) {
-            rc = launch_par_sparse(par_b, W.parbin, t, h, w, st);
+        const float* lr_i = lr_b ? lr_b + (int64_t)i * 3 * hw : nullptr;
+        float* out_i = out_b ? out_b + (int64_t)i * 3 * hw * os * os : nullptr;
+        const unsigned char* lr8_i = lq8 ? lq8 + (int64_t)i * 3 * hw : nullptr;
+        unsigned char* const out8_i = out8 ? out8 + (int64_t)i * 3 * hw * os * os : nullptr;
+        // a last conv with an fp32 interface: this frame's bytes to planes in front of it, its planes to bytes behind it (untimed, like pack_lr)
+        if (staged && lr8_i) {
+            rc = launch_frames_from_rgb8(lr8_i, W.lr1, 1, h, w, st);
+            untimed(g);
             if (rc) return rc;
-            par_b = W.parbin;
+            lr_i = W.lr1;
+            lr8_i = nullptr;
         }
-        // which 1x1 partition branches each 8x16 tile of each frame needs at all (32 front-half launches per frame use it)
-        if (par_skip) {
-            const int64_t ntile = (int64_t)((w + 15) / 16) * ((h + 7) / 8);
-            for (int i = 0; sparse_per_frame && i < t && !rc; ++i) {
-                rc = launch_par_sparse(par_in + (int64_t)i * 3 * hw, W.parbin, 1, h, w, st);
-                if (!rc) rc = launch_par_tile_flags(W.parbin, hw, W.parflags + i * ntile, 1, h, w, st);
-            }
-            if (!sparse_per_frame) rc = launch_par_tile_flags(par_b, hw, W.parflags, t, h, w, st);
+        if (staged && out8_i && !out_i) out_i = W.out1;
+        rc = conv(ConvCall(H, Wd, CONV_CFG_RGB).source(top, 64, packed + g->last_img).bias(packed + g->last_bias)
+                      .mode(c.vsr ? 3 : 2).rgb(lr_i, hw, packed + g->last_valu).rgb8(lr8_i, staged ? nullptr : out8_i).to(out_i).f16_map(s16));
+        if (rc || !staged || !out8_i) return rc;
+        untimed(g);
+        return launch_frames_to_rgb8(out_i, out8_i, 1, H, Wd, st);
+    }
+
+    // one branch run of the schedule (recomputed runs of the bounded schedule are steps like any other) and, forward, the frame's head
+    int step(const std::vector<Step>& steps, size_t si) {
+        const Step& sp = steps[si];
+        const int i = sp.frame;
+        const BranchPk& B = g->br[sp.sweep];
+        ConvCall in(h, w, cfg_lr);
+        in.source(W.lr4 + (int64_t)i * hw * 4, 4, packed + B.in_lr, wi(B.in_lr_wino));
+        int rc;
+        if (sp.key >= 0) {      // backward: the nearest key frame after i (flow planes 2, 3); forward: before i (planes 0, 1)
+            const int fp = sp.sweep == 0 ? 2 : 0;
+            rc = align(slot_of(sp.key), mv_b + ((int64_t)i * 4 + fp) * hw, mv_b + ((int64_t)i * 4 + fp + 1) * hw);
             if (rc) return rc;
-            if (wopt >= 1) rc = launch_par_frame_any(W.parflags, W.parany, t, h, w, st);      // (for the I frames' gated front halves)
+            // fp16 mirrors of the sources: the aligned key frame (fp16 ONLY in this mode, written by the warp) and the neighbouring / own slots
+            const void* kw16 = mirrors ? (const void*)W.kw : nullptr;
+            if (c.with_cat && c.align_key && sp.key_frame == (sp.sweep == 0 ? i + 1 : i - 1)) {     // neighbour == key frame: one source, summed weights
+                in.source(W.kw, 64, packed + B.in_wide01, wi(B.in_wide01_wino)).mirror16(kw16);
+            } else {
+                in.source(W.kw, 64, packed + B.in_wide[0], wi(B.in_wide_wino[0])).mirror16(kw16);
+                if (c.with_cat) in.source(slot_of(sp.nb), 64, packed + B.in_wide[1], wi(B.in_wide_wino[1])).mirror16(s16of(sp.nb));
+            }
+        }
+        if (sp.sweep == 1)      // backward feature of this frame
+            in.source(slot_of(sp.own), 64, packed + B.in_wide[B.n_wide - 1], wi(B.in_wide_wino[B.n_wide - 1])).mirror16(s16of(sp.own));
+        if (sparse_per_frame) {
+            rc = sparse_frame(i);
+            untimed(g);
             if (rc) return rc;
         }
-        // ---- CAA hyper-network (iconvsr_ipb_par.py:45-48)
-        for (int t0 = 0; t0 < t; t0 += 32) {
-            CaaArgs a;
-            memset(&a, 0, sizeof(a));
-            a.count = (t - t0 < 32) ? t - t0 : 32;
-            for (int i = 0; i < a.count; ++i) {
-                a.q_ew[i] = qe[t0 + i];
-                a.q_g[i] = qp[t0 + i];
-            }
-            a.t0 = t0;
-            a.E = E;
-            a.softmax = c.expert_softmax;
-            a.with_se = (c.with_bias && c.with_se) ? 1 : 0;
-            a.w1 = flat + g->p_w1;
-            a.b1 = flat + g->p_b1;
-            a.w2 = flat + g->p_w2;
-            a.b2 = flat + g->p_b2;
-            a.v1 = a.with_se ? flat + g->p_v1 : nullptr;
-            a.v2 = a.with_se ? flat + g->p_v2 : nullptr;
-            a.ew = W.ew;
-            a.gamma = W.gamma;
-            rc = launch_caa_predict(a, st);
+        // the branch's convs as a row-band chain: input conv + two per block (+ conv_hr behind a forward branch at the frame's size)
+        const bool hr_in_chain = sp.sweep == 1 && !c.vsr;
+        // the next run's images first: off this run's chains
+        if (si + 1 < steps.size()) {
+            rc = branch_images(steps[si + 1].sweep, steps[si + 1].frame, (int)((si + 1) & 1));
             if (rc) return rc;
         }
-        // ---- expert mixing, once per distinct routing input
-        std::vector<int> uidx(t);
-        std::vector<int> ufirst;
-        for (int i = 0; i < t; ++i) {
-            int u = -1;
-            for (size_t k = 0; k < ufirst.size(); ++k)
-                if (memcmp(&qe[ufirst[k]], &qe[i], sizeof(float)) == 0) {
-                    u = (int)k;
-                    break;
-                }
-            if (u < 0 && g->ndyn == 0) {      // 'drt_woqp': no expert-mixed conv at all
-                u = (int)ufirst.size();
-                ufirst.push_back(i);
-            }
-            if (u < 0) {
-                u = (int)ufirst.size();
-                ufirst.push_back(i);
-                const int gcm = 64 / c.num_group;
-                PackArgs a = plain_pack(flat + g->dyn_w, 64, 9, PACK_WIDE, 0, 2, 64, W.mixw + (int64_t)u * g->ndyn * IMG_WIDE);
-                a.ew = W.ew + (int64_t)i * E;
-                a.E = E;
-                a.e_stride = 64 * gcm * 9;
-                a.group_cin = c.num_group > 1 ? gcm : 0;
-                a.w_ystride = (int64_t)E * 64 * gcm * 9;
-                a.dst_ystride = IMG_WIDE;
-                rc = launch_pack_weights(a, g->ndyn, st);
-                if (rc) return rc;
-                rc = launch_mix_bias(flat + g->dyn_b, W.ew + (int64_t)i * E, W.mixb + (int64_t)u * g->ndyn * 64, E, 64,
-                                     g->ndyn, st);
-                if (rc) return rc;
-                if (g->prec == PNP_PREC_F16) {
-                    rc = launch_f16_image(a.dst, reinterpret_cast<uint16_t*>(W.mixh) + (int64_t)u * g->ndyn * IMG_WIDE,
-                                          g->ndyn * 9, 2, st);
-                    if (rc) return rc;
-                }
-                if (g->prec == PNP_PREC_F16X3) {
-                    rc = launch_f16x3_image(a.dst, reinterpret_cast<uint16_t*>(W.mixh) + (int64_t)u * g->ndyn * IMG_WIDE * 2,
-                                            g->ndyn * 9, st);
-                    if (rc) return rc;
-                }
-            }
-            uidx[i] = u;
-        }
-        // ---- key frames (iconvsr_ipb_par.py:60-62)
-        std::vector<char> key(t);
+        rc = chain.open(1 + 2 * c.num_blocks + (hr_in_chain ? 1 : 0));
+        if (rc) return rc;
+        rc = run_branch(sp.sweep, i, sp.out, (int)(si & 1), in);
+        if (!rc && !hr_in_chain) rc = chain.close();
+        if (rc || sp.sweep == 0) return rc;
+        return head(sp);
+    }
+
+    int run() {
+        int rc = fill_and_pack();
+        if (!rc) rc = partition_maps();
+        if (!rc) rc = caa();
+        if (!rc) rc = mix_experts();
+        if (rc) return rc;
+        // key frames (iconvsr_ipb_par.py:60-62)
+        key.resize(t);
         for (int i = 0; i < t; ++i) key[i] = (sl[i] == 73.0f) || (sl[i] == 80.0f);
         key[0] = key[t - 1] = 1;
-
-        // input conv over the virtual concat `in` (sources already added), then the BAE blocks
-        // (out: the frame map its last block writes, Step::out)
-        // A branch run's Winograd images of its expert-mixed convs, this frame's channel gain folded in, into image buffer `buf` of W.wino.
-        // They depend on the clip prologue only (mixtures, gamma), not on any feature map, so the step loop issues run s + 1's in front
-        // of run s's chain (the first run's in front of the loop) into the buffer run s does not read: inside run_branch, between the
-        // input conv and the first block conv, the launch waited for CUs behind chain B's input-conv part and held chain A back.
-        // Buffer s & 1 is rewritten (for run s + 2) in front of run s + 1's chain, i.e. behind run s's join on the caller's stream.
-        auto wino_buf = [&](int buf) { return W.wino + (int64_t)buf * 2 * c.num_blocks * PNP_WINO_IMG_FLOATS; };
-        auto branch_images = [&](int brid, int i, int buf) -> int {
-            if (!(wino_on && g->ndyn > 0)) return 0;
-            const BranchPk& B = g->br[brid];
-            const float* gam = (c.with_bias && c.with_se) ? W.gamma + (int64_t)i * 64 : nullptr;
-            const int u = uidx[i];
-            float* wb = wino_buf(buf);
-            std::vector<const float*> ws;
-            std::vector<float*> wd;
-            for (int k = 0; k < c.num_blocks; ++k) {
-                const BlockPk& K = B.blocks[k];
-                if (K.dyn_conv2 >= 0) { ws.push_back(W.mixw + ((int64_t)u * g->ndyn + K.dyn_conv2) * IMG_WIDE); wd.push_back(wb + (int64_t)(2 * k) * PNP_WINO_IMG_FLOATS); }
-                if (K.dyn_conv1 >= 0) { ws.push_back(W.mixw + ((int64_t)u * g->ndyn + K.dyn_conv1) * IMG_WIDE); wd.push_back(wb + (int64_t)(2 * k + 1) * PNP_WINO_IMG_FLOATS); }
-            }
-            for (size_t j = 0; j < ws.size(); j += 16) {
-                const int n = (int)(ws.size() - j < 16 ? ws.size() - j : 16);
-                const int r = launch_wino_images(ws.data() + j, wd.data() + j, n, gam, st);
-                if (r) return r;
-            }
-            g->prof_last = nullptr;           // an untimed launch sits between two timed ones
-            return 0;
-        };
-        auto run_branch = [&](int brid, int i, int out, int buf, ConvCall in) -> int {
-            const BranchPk& B = g->br[brid];
-            const float* wbuf = W.wino ? wino_buf(buf) : nullptr;
-            const float* gam = (c.with_bias && c.with_se) ? W.gamma + (int64_t)i * 64 : nullptr;
-            const float* parp = sparse_per_frame ? W.parbin : par_b + (int64_t)i * 3 * hw;
-            const int* pflags = par_skip ? W.parflags + (int64_t)i * ((w + 15) / 16) * ((h + 7) / 8) : nullptr;
-            // the frame's partition word (launch_par_frame_any) gates the front halves on the device: fold-only kernel / branch kernel
-            // (launch_conv3x3_wino); an I frame usually carries no record at all (its word is then 8: all quadrants zero)
-            // (any frame size: a quadrant cut by the frame's edge -- 180x320 has a last row of them 4 pixels high -- counts with the pixels
-            //  it has, in the flags and in the kernels alike)
-            const int* pany = (par_skip && wopt >= 1) ? W.parany + i : nullptr;
-            const int u = uidx[i];
-            float* slot = W.slots + (int64_t)out * fm;
-            // fp16 mirrors: the input conv writes x16 next to x when it runs on the fp16 kernels at all (an RGB-only one does not)
-            const void* x16 = (chain16 && in.nsrc > 1) ? W.x16 : nullptr;
-            int r = conv(in.bias(flat + B.in_bias).act(2).units(wino_units(h, w)).to(W.tmp0).also16(const_cast<void*>(x16)));
-            if (r) return r;
-            const float* x = W.tmp0;
-            const bool un = wino_units(h, w);
-            for (int k = 0; k < c.num_blocks; ++k) {
-                const BlockPk& K = B.blocks[k];
-                float* dst = (k == c.num_blocks - 1) ? slot : W.tmp0;
-                void* dst16 = !mirrors ? nullptr : (k == c.num_blocks - 1) ? (void*)(W.slots16 + (int64_t)out * fm)
-                                                                                 : (chain16 ? (void*)W.x16 : nullptr);
-                const bool woqp = c.blocktype == 1;      // conv2 a plain conv as well: no expert mix, no gain (sr_backbone_utils.py:366-384)
-                const float* w2 = woqp ? packed + K.conv2_img : W.mixw + ((int64_t)u * g->ndyn + K.dyn_conv2) * IMG_WIDE;
-                const float* b2 = woqp ? flat + K.conv2_bias : W.mixb + ((int64_t)u * g->ndyn + K.dyn_conv2) * 64;
-                const float* g2 = woqp ? nullptr : gam;
-                const float* w1 = c.one_layer ? packed + K.conv1_img
-                                              : W.mixw + ((int64_t)u * g->ndyn + K.dyn_conv1) * IMG_WIDE;
-                const float* b1 = c.one_layer ? flat + K.conv1_bias
-                                              : W.mixb + ((int64_t)u * g->ndyn + K.dyn_conv1) * 64;
-                const float* g1 = c.one_layer ? nullptr : gam;
-                const float* u2 = !wino_on ? nullptr : (woqp ? packed + K.conv2_wino : wbuf + (int64_t)(2 * k) * PNP_WINO_IMG_FLOATS);
-                const float* u1 = !wino_on ? nullptr : (c.one_layer ? packed + K.conv1_wino : wbuf + (int64_t)(2 * k + 1) * PNP_WINO_IMG_FLOATS);
-                const float* up = !wino_on ? nullptr : packed + K.w1x1_wino;
-                // the map between the two halves is read only as an MFMA A operand: an fp16 map on the fp16 path
-                const int o16 = f16_maps ? 1 : 0, s16 = f16_maps ? 2 : 0;
-                if (c.channel_first) {   // sr_backbone_utils.py:305-313
-                    r = conv(ConvCall(h, w, cfg_lr).source(x, 64, w2).mirror16(x16).bias(b2).gamma(g2)
-                                 .partition(packed + K.w1x1, parp, pflags).gate(pany).wino(u2, up).units(un).act(1).to(W.tmp1).f16_map(o16));
-                    if (!r)
-                        r = conv(ConvCall(h, w, cfg_lr).source(W.tmp1, 64, w1).bias(b1).gamma(g1).wino(u1).units(un).residual(x).to(dst)
-                                     .f16_map(s16).also16(dst16));
-                } else {                 // sr_backbone_utils.py:314-327
-                    r = conv(ConvCall(h, w, cfg_lr).source(x, 64, w1).mirror16(x16).bias(b1).gamma(g1).wino(u1).units(un).act(1).to(W.tmp1)
-                                 .f16_map(o16));
-                    if (!r)
-                        r = conv(ConvCall(h, w, cfg_lr).source(W.tmp1, 64, w2).bias(b2).gamma(g2)
-                                     .partition(packed + K.w1x1, parp, pflags).gate(pany).wino(u2, up).units(un).residual(x).to(dst).f16_map(s16).also16(dst16));
-                }
-                if (r) return r;
-                x = dst;
-                x16 = chain16 ? dst16 : nullptr;
-            }
-            return 0;
-        };
-
-        // fp16 mirrors of the sources of an input conv: the aligned key frame (fp16 ONLY in this mode, written by the warp) and
-        // the neighbouring / own slots
-        const void* kw16 = mirrors ? (const void*)W.kw : nullptr;
-        auto s16of = [&](int i) -> const void* { return mirrors ? (const void*)(W.slots16 + (int64_t)i * fm) : nullptr; };
-        // ---- backward sweep (iconvsr_ipb_par.py:71-100), forward sweep + heads (:103-147); bounded: with recomputed segments
+        // backward sweep (iconvsr_ipb_par.py:71-100), forward sweep + heads (:103-147); bounded: with recomputed segments
         std::vector<Step> steps;
         int recomputed = 0;
         if (!make_schedule(g, t, key, steps, &recomputed)) return PNP_ERR_BAD_ARG;
-        auto slot_of = [&](int s) { return W.slots + (int64_t)s * fm; };
-        auto wi = [&](int64_t off) -> const float* { return wino_on ? packed + off : nullptr; };
-        if (!steps.empty()) {
-            rc = branch_images(steps[0].sweep, steps[0].frame, 0);
-            if (rc) return rc;
-        }
-        for (size_t si = 0; si < steps.size(); ++si) {
-            const Step& sp = steps[si];
-            const int i = sp.frame;
-            const BranchPk& B = g->br[sp.sweep];
-            ConvCall in(h, w, cfg_lr);
-            in.source(W.lr4 + (int64_t)i * hw * 4, 4, packed + B.in_lr, wi(B.in_lr_wino));
-            if (sp.key >= 0) {      // backward: the nearest key frame after i (flow planes 2, 3); forward: before i (planes 0, 1)
-                const int fp = sp.sweep == 0 ? 2 : 0;
-                rc = align(slot_of(sp.key), mv_b + ((int64_t)i * 4 + fp) * hw, mv_b + ((int64_t)i * 4 + fp + 1) * hw);
-                if (rc) return rc;
-                if (c.with_cat && c.align_key && sp.key_frame == (sp.sweep == 0 ? i + 1 : i - 1)) {     // neighbour == key frame: one source, summed weights
-                    in.source(W.kw, 64, packed + B.in_wide01, wi(B.in_wide01_wino)).mirror16(kw16);
-                } else {
-                    in.source(W.kw, 64, packed + B.in_wide[0], wi(B.in_wide_wino[0])).mirror16(kw16);
-                    if (c.with_cat) in.source(slot_of(sp.nb), 64, packed + B.in_wide[1], wi(B.in_wide_wino[1])).mirror16(s16of(sp.nb));
-                }
-            }
-            if (sp.sweep == 1)      // backward feature of this frame
-                in.source(slot_of(sp.own), 64, packed + B.in_wide[B.n_wide - 1], wi(B.in_wide_wino[B.n_wide - 1])).mirror16(s16of(sp.own));
-            if (sparse_per_frame) {
-                rc = launch_par_sparse(par_in + (int64_t)i * 3 * hw, W.parbin, 1, h, w, st);
-                g->prof_last = nullptr;           // an untimed launch sits between two timed ones
-                if (rc) return rc;
-            }
-            // the branch's convs as a row-band chain: input conv + two per block (+ conv_hr behind a forward branch at the frame's size)
-            const bool hr_in_chain = sp.sweep == 1 && !c.vsr;
-            // the next run's images first (recomputed runs of the bounded schedule are steps like any other): off this run's chains
-            if (si + 1 < steps.size()) {
-                rc = branch_images(steps[si + 1].sweep, steps[si + 1].frame, (int)((si + 1) & 1));
-                if (rc) return rc;
-            }
-            rc = chain_open(1 + 2 * c.num_blocks + (hr_in_chain ? 1 : 0));
-            if (rc) return rc;
-            rc = run_branch(sp.sweep, i, sp.out, (int)(si & 1), in);
-            if (!rc && !hr_in_chain) rc = chain_close();
-            if (rc) return rc;
-            if (sp.sweep == 0) continue;
-
-            const float* feat = slot_of(sp.out);
-            const float* lr_i = lr_b ? lr_b + (int64_t)i * 3 * hw : nullptr;
-            float* out_i = out_b ? out_b + (int64_t)i * 3 * hw * os * os : nullptr;
-            const unsigned char* lr8_i = lq8 ? lq8 + (int64_t)i * 3 * hw : nullptr;
-            unsigned char* out8_i = out8 ? out8 + (int64_t)i * 3 * hw * os * os : nullptr;
-            // a last conv with an fp32 interface: this frame's bytes to planes in front of it, its planes to bytes behind it (untimed, like pack_lr)
-            auto stage_in = [&]() -> int {
-                if (!staged) return PNP_OK;
-                int r = PNP_OK;
-                if (lr8_i) {
-                    r = launch_frames_from_rgb8(lr8_i, W.lr1, 1, h, w, st);
-                    g->prof_last = nullptr;
-                    lr_i = W.lr1;
-                    lr8_i = nullptr;
-                }
-                if (out8_i && !out_i) out_i = W.out1;
-                return r;
-            };
-            auto stage_out = [&]() -> int {
-                if (!staged || !out8_i) return PNP_OK;
-                g->prof_last = nullptr;
-                return launch_frames_to_rgb8(out_i, out8_i, 1, h * os, w * os, st);
-            };
-            // conv_hr's output feeds only conv_last: an fp16 map on the fp16 path
-            const int o16 = f16_maps ? 1 : 0, s16 = f16_maps ? 2 : 0;
-            if (!c.vsr) {   // :144-146
-                rc = conv(ConvCall(h, w, cfg_lr).source(feat, 64, packed + g->hr_img).mirror16(s16of(sp.out)).bias(flat + g->hr_bias)
-                              .wino(wino_on ? packed + g->hr_wino : nullptr).units(wino_units(h, w)).act(2).to(W.tmp1).f16_map(o16));
-                if (!rc) rc = chain_close();
-                if (!rc) rc = stage_in();
-                if (!rc)
-                    rc = conv(ConvCall(h, w, CONV_CFG_RGB).source(W.tmp1, 64, packed + g->last_img).bias(packed + g->last_bias)
-                                  .mode(2).rgb(lr_i, hw, packed + g->last_valu).rgb8(lr8_i, staged ? nullptr : out8_i).to(out_i).f16_map(s16));
-                if (!rc) rc = stage_out();
-                if (rc) return rc;
-            } else {        // :135-142: two PixelShufflePack(2) convs (4 sub-pixel weight images each), conv_hr, conv_last + x4 bilinear lr
-                // every map of the head is read by exactly one conv, as an MFMA A operand: fp16 maps all the way on the fp16 path
-                // (the 720p map between the second pixel shuffle and conv_hr alone is 236 MB written + read per frame in fp32)
-                rc = conv(ConvCall(h, w, cfg_lr).source(feat, 64, packed + g->up_img[0]).bias(packed + g->up_bias[0], 64)
-                              .act(2).mode(1, 4, IMG_WIDE).to(W.u1).f16_map(o16));
-                if (!rc)
-                    rc = conv(ConvCall(2 * h, 2 * w, conv_pick_cfg(2 * h, 2 * w)).source(W.u1, 64, packed + g->up_img[1])
-                                  .bias(packed + g->up_bias[1], 64).act(2).mode(1, 4, IMG_WIDE).to(W.u2).f16_map(o16 | s16));
-                if (!rc)
-                    rc = conv(ConvCall(4 * h, 4 * w, conv_pick_cfg(4 * h, 4 * w)).source(W.u2, 64, packed + g->hr_img)
-                                  .bias(flat + g->hr_bias).wino(wino_on ? packed + g->hr_wino : nullptr).units(wino_units(4 * h, 4 * w)).act(2).to(W.u3)
-                                  .f16_map(o16 | s16));
-                if (!rc) rc = stage_in();
-                if (!rc)
-                    rc = conv(ConvCall(4 * h, 4 * w, CONV_CFG_RGB).source(W.u3, 64, packed + g->last_img)
-                                  .bias(packed + g->last_bias).mode(3).rgb(lr_i, hw, packed + g->last_valu).rgb8(lr8_i, staged ? nullptr : out8_i).to(out_i).f16_map(s16));
-                if (!rc) rc = stage_out();
-                if (rc) return rc;
-            }
-        }
+        if (!steps.empty()) rc = branch_images(steps[0].sweep, steps[0].frame, 0);
+        for (size_t si = 0; si < steps.size() && !rc; ++si) rc = step(steps, si);
+        return rc;
     }
-    return PNP_OK;
-}
+};
 
 bool io_args_ok(int lq_format, int out_mask) {
     return (lq_format == PNP_FRAMES_F32_NCHW || lq_format == PNP_FRAMES_U8_HWC) && out_mask >= 1 && out_mask <= (PNP_OUT_F32 | PNP_OUT_U8);
@@ -1413,8 +1413,8 @@ int forward_batch(const pnp_generator* g, const float* flat, const float* packed
     for (int b = 0; b < n && rc == PNP_OK; ++b) {
         const int k = b % nctx;
         const Workspace W = carve(g, (char*)workspace + (int64_t)k * ctx_bytes, t, h, w, lq_format, out_mask);
-        rc = forward_sample(g, flat, packed, clips[b], lq_format, out_mask, slices + (int64_t)b * t,
-                            qps + (int64_t)b * t, base_qps + (int64_t)b * t, W, t, h, w, nctx > 1 ? g->side_streams[k] : st, nctx == 1);
+        rc = ClipRun(g, flat, packed, clips[b], lq_format, out_mask, slices + (int64_t)b * t, qps + (int64_t)b * t, base_qps + (int64_t)b * t,
+                     W, t, h, w, nctx > 1 ? g->side_streams[k] : st, nctx == 1).run();
     }
     if (nctx > 1) {      // join even after an error: the caller's stream must not run ahead of what was launched
         for (int k = 0; k < nctx; ++k) {

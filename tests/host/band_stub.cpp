@@ -29,6 +29,9 @@ int run_band(const BandScenario& sc) {
     mixes.clear();
     dcn_calls = 0;
     streams_created = events_created = 0;
+    regions.clear();
+    trace.clear();
+    pnp_stub_io_hook = trace_io;
     pnp_generator* g = nullptr;
     if (pnp_generator_create(&sc.cfg, &g)) return 2;
     pnp_generator_set_precision(g, sc.prec);
@@ -53,6 +56,13 @@ int run_band(const BandScenario& sc) {
     mark(lrs, nt * 3 * hw * 4);
     mark(mvs, nt * 4 * hw * 4);
     mark(par, nt * 3 * hw * 4);
+    region("flat", flat, (size_t)flat_n * 4);
+    region("packed", packed, (size_t)packed_n * 4);
+    region("ws", ws, (size_t)ws_bytes);
+    region("lrs", lrs, nt * 3 * hw * 4);
+    region("mvs", mvs, nt * 4 * hw * 4);
+    region("par", par, nt * 3 * hw * 4);
+    region("out", out, nt * 3 * hw * os * os * 4);
     std::vector<float> slices, qps, bqs;
     for (int b = 0; b < sc.n; ++b) {
         const std::vector<float> sl = pattern("IBBBP", t);
@@ -114,6 +124,7 @@ int run_band(const BandScenario& sc) {
     json_ints("streams_created_after_forward", streams_after);
     json_ints("band_events_created_after_forward", events_after);
     pnp_generator_destroy(g);
+    trace_dump(sc.name);
     printf("\"live_events_after_destroy\": %d, \"live_streams_after_destroy\": %d, \"errors\": [", live_events, live_streams);
     for (size_t i = 0; i < errors.size(); ++i) printf("%s\"%s\"", i ? ", " : "", errors[i].c_str());
     printf("]}\n");

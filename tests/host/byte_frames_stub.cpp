@@ -7,7 +7,8 @@
 // launchers of the byte boundary are recorded by csrc/host_stub/io_stub.h; the hook below gives them the same range bookkeeping the
 // other launchers have.  Two kinds of scenario, one JSON object each:
 //   * "same": an fp32 batch through pnp_generator_forward, then the same batch as descriptors through pnp_generator_forward_clips with
-//     (PNP_FRAMES_F32_NCHW, PNP_OUT_F32): the two launch lists must be identical, record for record;
+//     (PNP_FRAMES_F32_NCHW, PNP_OUT_F32): the two ordered traces (sched_stub.cpp: every HIP call and launch with every argument) must be
+//     identical, line for line;
 //   * "io": clips in separately allocated buffers of exactly the sizes the ABI names (ASan's red zones are the poisoned gaps between
 //     them), a format and an output mask: every read and write lies inside the owning clip's buffers, the pack launch reads exactly
 //     t*h*w*3 bytes, the last conv writes exactly H*W*3 bytes per frame, only the requested outputs are written and no launch is handed
@@ -21,6 +22,7 @@ using namespace stub;
 int n_pack = 0, n_from = 0, n_to = 0, n_last_io = 0;
 
 void io_hook(const PnpStubIoLaunch& r) {
+    trace_io(r);
     note_launch(r.stream);
     const size_t px = (size_t)r.frames * r.h * r.w;
     switch (r.kind) {
@@ -78,28 +80,6 @@ struct IoScenario {
     int prec, n, t, h, w, contexts, lq_format, out_mask, wino, last_valu, max_resident;
 };
 
-// everything a forward left in the logs, as one string per record
-std::vector<std::string> snapshot(const pnp_generator* g) {
-    std::vector<std::string> v;
-    for (int s : launch_streams) v.push_back("launch on " + std::to_string(s));
-    for (const ConvRec& c : convs) {
-        ConvArgs a = c.a;
-        const ConvBandSplit* b = a.band;
-        a.band = nullptr;
-        std::string s((const char*)&a, sizeof(a));
-        s += "|" + std::to_string(c.cfg) + "," + std::to_string(c.gy) + "," + std::to_string(c.stream) + "," + std::to_string(c.path);
-        if (b) s += "|band " + std::to_string(b->row) + "," + std::to_string(b->ready->id) + "," + std::to_string(b->side->id);
-        v.push_back(s);
-    }
-    for (const WarpRec& w : warps) v.push_back("warp " + std::to_string((uintptr_t)w.feat) + " " + std::to_string((uintptr_t)w.fx) + " " + std::to_string((uintptr_t)w.out) + (w.f16 ? " f16" : ""));
-    for (const MixRec& m : mixes) v.push_back("mix " + std::to_string((uintptr_t)m.dst) + " " + std::to_string(m.E) + " " + std::to_string(m.gy));
-    for (const Wait& w : waits) v.push_back("wait " + std::to_string(w.stream) + " " + std::to_string(w.event) + " " + std::to_string(w.event_recorded_on));
-    for (const auto& r : records) v.push_back("record " + std::to_string(r.first) + " " + std::to_string(r.second));
-    v.push_back("io launches " + std::to_string(pnp_stub_io_log.size()));
-    (void)g;
-    return v;
-}
-
 bool any_written(const void* p, size_t n) {
     const uintptr_t lo = (uintptr_t)p, hi = lo + n;
     for (const auto& iv : written)
@@ -120,6 +100,8 @@ void side_info(int n, int t, std::vector<float>& slices, std::vector<float>& qps
 
 int run_io(IoScenario sc) {
     reset();
+    regions.clear();
+    trace.clear();
     pnp_generator* g = nullptr;
     if (pnp_generator_create(&sc.cfg, &g)) return 2;
     pnp_generator_set_precision(g, sc.prec);
@@ -139,6 +121,9 @@ int run_io(IoScenario sc) {
     char* ws = nullptr;
     if (ws_bytes <= 0 || posix_memalign((void**)&ws, 256, (size_t)ws_bytes)) return 2;
     mark(flat, (size_t)flat_n * 4);
+    region("flat", flat, (size_t)flat_n * 4);
+    region("packed", packed, (size_t)packed_n * 4);
+    region("ws", ws, (size_t)ws_bytes);
     std::vector<float> slices, qps, bqs;
     side_info(n, t, slices, qps, bqs);
     pnp_stub_stream caller{0};
@@ -159,6 +144,10 @@ int run_io(IoScenario sc) {
         mark(lrs, (size_t)n * t * 3 * hw * 4);
         mark(mvs, (size_t)n * t * 4 * hw * 4);
         mark(par, (size_t)n * t * 3 * hw * 4);
+        region("lrs", lrs, (size_t)n * t * 3 * hw * 4);
+        region("mvs", mvs, (size_t)n * t * 4 * hw * 4);
+        region("par", par, (size_t)n * t * 3 * hw * 4);
+        region("out", out, (size_t)n * out_px * 4);
         const auto before = written;
         // (a first forward makes the handle's streams and events as it goes, and a chain's join event is "the last one made so far": the
         //  two forwards compared both run on a handle that has them all)
@@ -167,9 +156,10 @@ int run_io(IoScenario sc) {
         reset();
         errors = errs0;
         written = before;
+        const size_t ref_begin = trace.size();
         frc = pnp_generator_forward(g, flat, packed, lrs, mvs, par, slices.data(), qps.data(), bqs.data(), out, ws, ws_bytes, n, t, sc.h, sc.w, &caller);
         if (frc == 0 && !covered(out, (size_t)n * out_px * 4)) fail("pnp_generator_forward left part of the output unwritten");
-        const std::vector<std::string> ref = snapshot(g);
+        const std::vector<std::string> ref(trace.begin() + ref_begin, trace.end());
         const std::vector<std::string> errs = errors;
         reset();
         errors = errs;
@@ -180,14 +170,14 @@ int run_io(IoScenario sc) {
                                                     bqs.data(), ws, ws_bytes, t, sc.h, sc.w, &caller);
         if (crc != frc) fail("the two entry points return different codes");
         if (crc == 0 && !covered(out, (size_t)n * out_px * 4)) fail("pnp_generator_forward_clips left part of the output unwritten");
-        const std::vector<std::string> got = snapshot(g);
+        const std::vector<std::string> got(trace.begin() + ref_begin + ref.size(), trace.end());
         list_len = ref.size();
         same = ref.size() == got.size() ? 1 : 0;
         for (size_t i = 0; same == 1 && i < ref.size(); ++i)
             if (ref[i] != got[i]) {
                 same = 0;
                 first_diff = i;
-                if (getenv("PNP_STUB_SHOW_DIFF")) fprintf(stderr, "record %zu: [%s] against [%s]\n", i, ref[i].size() < 200 ? ref[i].c_str() : "(conv)", got[i].size() < 200 ? got[i].c_str() : "(conv)");
+                if (getenv("PNP_STUB_SHOW_DIFF")) fprintf(stderr, "line %zu: [%s] against [%s]\n", i, ref[i].c_str(), got[i].c_str());
             }
     } else {
         // every tensor of every clip its own heap block of exactly the size the ABI names; both output buffers exist whatever the mask asks for
@@ -201,6 +191,12 @@ int run_io(IoScenario sc) {
             mark(lq, lq_bytes);
             mark(mv, (size_t)t * 4 * hw * 4);
             mark(pr, (size_t)t * 3 * hw * 4);
+            const std::string cb = std::to_string(b);
+            region("lq" + cb, lq, lq_bytes);
+            region("mvs" + cb, mv, (size_t)t * 4 * hw * 4);
+            region("par" + cb, pr, (size_t)t * 3 * hw * 4);
+            region("out_f32_" + cb, of, out_px * 4);
+            region("out_u8_" + cb, o8, out_px);
             clips[b] = pnp_clip_io{lq, mv, pr, of, o8};
         }
         frc = pnp_generator_forward_clips(g, flat, packed, clips.data(), n, sc.lq_format, sc.out_mask, slices.data(), qps.data(), bqs.data(), ws,
@@ -255,6 +251,7 @@ int run_io(IoScenario sc) {
            (long long)(hw * 12), (long long)(hw * 12 * os * os), io_staged(g) ? 1 : 0, n_pack, n_from, n_to, n_last_io, rgb_heads, banded, n * t);
     json_ints("streams_used", streams_used);
     pnp_generator_destroy(g);
+    trace_dump(sc.name);
     printf("\"errors\": [");
     for (size_t i = 0; i < errors.size(); ++i) printf("%s\"%s\"", i ? ", " : "", errors[i].c_str());
     printf("]}\n");
@@ -278,7 +275,7 @@ int main(int argc, char** argv) {
     //   name                 kind    cfg  prec n  t   h    w   ctx fmt mask wino valu k
     const std::vector<IoScenario> all = {
         {"same_128_n3_ctx3", "same", d, 0, 3, 3, 128, 128, 3, F, 1, 1, 1, 0},
-        {"same_720_band", "same", d, 0, 1, 2, 720, 1280, 1, F, 1, 1, 1, 0},
+        {"same_720_band", "same", d, 0, 1, 3, 720, 1280, 1, F, 1, 1, 1, 0},
         {"same_128_bounded", "same", d, 0, 1, 9, 128, 128, 1, F, 1, 1, 1, -1},
         {"same_128_f16", "same", d, 1, 2, 3, 128, 128, 2, F, 1, 1, 1, 0},
         {"u8_128_n2_mask1", "io", d, 0, 2, 3, 128, 128, 2, U, 1, 1, 1, 0},

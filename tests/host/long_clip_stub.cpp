@@ -54,6 +54,9 @@ LcResult run_lc(const LcScenario& sc, int k) {
     convs.clear();
     mixes.clear();
     dcn_calls = 0;
+    regions.clear();
+    trace.clear();
+    pnp_stub_io_hook = trace_io;
     pnp_generator* g = nullptr;
     res.create_rc = pnp_generator_create(&sc.cfg, &g);
     if (res.create_rc) return res;
@@ -88,6 +91,13 @@ LcResult run_lc(const LcScenario& sc, int k) {
     mark(lrs, nt * 3 * hw * 4);
     mark(mvs, nt * 4 * hw * 4);
     mark(par, nt * 3 * hw * 4);
+    region("flat", flat, (size_t)flat_n * 4);
+    region("packed", packed, (size_t)packed_n * 4);
+    region("ws", ws, (size_t)ws_bytes);
+    region("lrs", lrs, nt * 3 * hw * 4);
+    region("mvs", mvs, nt * 4 * hw * 4);
+    region("par", par, nt * 3 * hw * 4);
+    region("out", out, nt * 3 * hw * os * os * 4);
     std::vector<float> slices, qps, bqs;
     for (int b = 0; b < sc.n; ++b) {
         const std::vector<float> sl = pattern(sc.pattern, t);
@@ -197,6 +207,7 @@ LcResult run_lc(const LcScenario& sc, int k) {
     // (deform = basic: the DCN offset convs run between an alignment and its input conv, outside any branch run, and read no frame map)
     if (wj != warps.size()) fail("an alignment whose result no input conv read");
     pnp_generator_destroy(g);
+    trace_dump(sc.name + "/k=" + std::to_string(k));
     res.errors = errors;
     free(flat);
     free(packed);

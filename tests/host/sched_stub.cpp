@@ -9,7 +9,9 @@
 //   * keeps a set of written ranges and refuses a read of bytes nothing has written (a schedule that consumes a map before its
 //     producer ran, e.g. an fp16 mirror that was never made);
 //   * records what the schedule did: which slot was aligned for which frame, which expert mixture each block conv used, how
-//     many mixtures / events / streams were created.
+//     many mixtures / events / streams were created;
+//   * appends one line per call to an ordered trace (stub::trace below; PNP_STUB_TRACE=<file> writes it out): two builds of the
+//     scheduler issue the same launches if and only if their traces are equal.
 // The scheduler itself is compiled UNCHANGED: this file #includes generator.hip.  The driver at the bottom runs the patterns
 // named on the command line and prints one JSON object per scenario.
 #include <algorithm>
@@ -22,6 +24,7 @@
 #include "../../pnp_vcve_amd/csrc/dcn.h"
 #include "../../pnp_vcve_amd/csrc/prep.h"
 #include "../../pnp_vcve_amd/csrc/warp.h"
+#include "../../pnp_vcve_amd/csrc/host_stub/io_stub.h"
 #ifndef __has_feature
 #define __has_feature(x) 0
 #endif
@@ -100,6 +103,72 @@ std::vector<int> launch_streams;               // stream id of every recorded la
 int sid(hipStream_t s) { return s ? s->id : 0; }
 void note_launch(hipStream_t s) { launch_streams.push_back(sid(s)); }
 
+// ---- the ordered trace: one line per HIP stand-in and per recording launcher, in call order, with the stream id and every argument.
+// A pointer is written as region+byte offset of a buffer the driver registered (`region`), `-` if null; scalars in full (floats as
+// hex floats).  Two schedulers that issue the same launches leave the same trace, whatever the allocator handed out.
+// PNP_STUB_TRACE=<file>: every driver writes each scenario's trace there under the scenario's name (`trace_dump`).
+struct Region { std::string name; uintptr_t lo, hi; };
+std::vector<Region> regions;
+std::vector<std::string> trace;
+void region(const std::string& name, const void* p, size_t n) { regions.push_back({name, (uintptr_t)p, (uintptr_t)p + n}); }
+std::string where(const void* p) {
+    if (!p) return "-";
+    for (const Region& r : regions)
+        if ((uintptr_t)p >= r.lo && (uintptr_t)p < r.hi) return r.name + "+" + std::to_string((uintptr_t)p - r.lo);
+    return "!pointer-into-no-registered-region";
+}
+struct Tr {          // one line, appended when it goes out of scope
+    std::string s;
+    explicit Tr(const char* name) : s(name) {}
+    Tr(const char* name, hipStream_t st) : s(name) { i("stream", sid(st)); }
+    ~Tr() { trace.push_back(s); }
+    Tr& raw(const std::string& k, const std::string& v) { s += " " + k + "=" + v; return *this; }
+    Tr& i(const std::string& k, long long v) { return raw(k, std::to_string(v)); }
+    Tr& p(const std::string& k, const void* v) { return raw(k, where(v)); }
+    Tr& f(const std::string& k, double v) {
+        char b[40];
+        snprintf(b, sizeof(b), "%a", v);
+        return raw(k, b);
+    }
+    Tr& ev(const std::string& k, hipEvent_t e) { return e ? i(k, e->id) : raw(k, "-"); }
+    Tr& st(const std::string& k, hipStream_t t) { return t ? i(k, t->id) : raw(k, "-"); }
+};
+void trace_conv(const char* name, const ConvArgs& a, int cfg, int gy, hipStream_t s) {
+    Tr t(name, s);
+    t.i("cfg", cfg).i("gy", gy).i("nsrc", a.nsrc);
+    for (int k = 0; k < 4; ++k) {
+        const std::string n = std::to_string(k);
+        t.p("src" + n, a.src[k]).p("wsrc" + n, a.wsrc[k]).i("src_c" + n, a.src_c[k]).p("wwino_src" + n, a.wwino_src[k]).p("wsrc_h" + n, a.wsrc_h[k]);
+    }
+    t.p("wpar", a.wpar).p("wwino", a.wwino).p("wwino_par", a.wwino_par).p("wwino_rgb", a.wwino_rgb).p("par_any", a.par_any);
+    t.i("tile_row0", a.tile_row0).i("tile_rows", a.tile_rows);
+    if (a.band) t.i("band.row", a.band->row).ev("band.ready", a.band->ready).st("band.side", a.band->side);
+    else t.raw("band", "-");
+    t.i("wino_units", a.wino_units).p("wvalu", a.wvalu).p("wpar_h", a.wpar_h).i("wpar_h_scaled", a.wpar_h_scaled).p("tile_queue", a.tile_queue);
+    t.i("prec", a.prec).i("src_f16", a.src_f16).i("out_f16", a.out_f16).p("out16", a.out16).i("no_multi16", a.no_multi16);
+    t.p("par", a.par).p("par_flags", a.par_flags).i("par_plane", a.par_plane).p("bias", a.bias).p("gamma", a.gamma).p("residual", a.residual);
+    t.p("out", a.out).p("lr", a.lr).i("lr_plane", a.lr_plane).i("w_ystride", a.w_ystride).i("bias_ystride", a.bias_ystride);
+    t.i("H", a.H).i("W", a.W).i("act", a.act).p("dbg", a.dbg).i("no_small16", a.no_small16).i("no_persist", a.no_persist);
+    t.i("out_cstride", a.out_cstride).i("out_mode", a.out_mode).p("lr_u8", a.lr_u8).p("out_u8", a.out_u8);
+}
+// the four launchers of the byte boundary (csrc/host_stub/io_stub.h): installed as, or called first by, pnp_stub_io_hook
+void trace_io(const PnpStubIoLaunch& r) {
+    static const char* const names[3] = {"launch_pack_lr_u8", "launch_frames_from_rgb8", "launch_frames_to_rgb8"};
+    if (r.kind == PNP_STUB_IO_CONV_LAST) return trace_conv("launch_conv_last_io", r.conv, CONV_CFG_RGB, 1, r.stream);
+    Tr(names[r.kind], r.stream).p("in", r.in).p("out", r.out).i("frames", r.frames).i("H", r.h).i("W", r.w);
+}
+void trace_dump(const std::string& scenario) {
+    static bool opened = false;
+    const char* path = getenv("PNP_STUB_TRACE");
+    if (!path) return;
+    FILE* fh = fopen(path, opened ? "a" : "w");
+    if (!fh) return fail(std::string("cannot write the trace to ") + path);
+    opened = true;
+    fprintf(fh, "== %s (%zu lines)\n", scenario.c_str(), trace.size());
+    for (const std::string& ln : trace) fprintf(fh, "%s\n", ln.c_str());
+    fclose(fh);
+}
+
 // ---- what the schedule did (filled by the launchers, interpreted by the driver, which knows the workspace layout)
 struct WarpRec { const void *feat, *fx, *out; bool f16; };
 struct ConvRec {
@@ -121,9 +190,11 @@ hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) {
     *e = new pnp_stub_event{stub::next_event++, -1};
     ++stub::live_events;
     ++stub::events_created;
+    stub::Tr("hipEventCreate").ev("event", *e);
     return hipSuccess;
 }
 hipError_t hipEventDestroy(hipEvent_t e) {
+    stub::Tr("hipEventDestroy").ev("event", e);
     delete e;
     --stub::live_events;
     return hipSuccess;
@@ -131,24 +202,29 @@ hipError_t hipEventDestroy(hipEvent_t e) {
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
     e->recorded_on = stub::sid(s);
     stub::records.push_back({e->id, stub::sid(s)});
+    stub::Tr("hipEventRecord", s).ev("event", e);
     return hipSuccess;
 }
 hipError_t hipEventSynchronize(hipEvent_t e) {
     if (e->recorded_on < 0) stub::fail("hipEventSynchronize on an event that was never recorded");
+    stub::Tr("hipEventSynchronize").ev("event", e);
     return hipSuccess;
 }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
     if (a->recorded_on < 0 || b->recorded_on < 0) stub::fail("hipEventElapsedTime on an unrecorded event");
     *ms = 1.0f;
+    stub::Tr("hipEventElapsedTime").ev("a", a).ev("b", b);
     return hipSuccess;
 }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
     *s = new pnp_stub_stream{stub::next_stream++};
     ++stub::live_streams;
     ++stub::streams_created;
+    stub::Tr("hipStreamCreate").st("made", *s);
     return hipSuccess;
 }
 hipError_t hipStreamDestroy(hipStream_t s) {
+    stub::Tr("hipStreamDestroy").st("destroyed", s);
     delete s;
     --stub::live_streams;
     return hipSuccess;
@@ -156,25 +232,44 @@ hipError_t hipStreamDestroy(hipStream_t s) {
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
     if (e->recorded_on < 0) stub::fail("hipStreamWaitEvent on an event that was never recorded");
     stub::waits.push_back({stub::sid(s), e->id, e->recorded_on});
+    stub::Tr("hipStreamWaitEvent", s).ev("event", e).i("recorded_on", e->recorded_on);
     return hipSuccess;
 }
 hipError_t hipMemsetAsync(void* dst, int, size_t bytes, hipStream_t s) {
     stub::cur = "hipMemsetAsync";
     stub::note_launch(s);
     stub::WR("memset destination", dst, bytes);
+    stub::Tr("hipMemsetAsync", s).p("dst", dst).i("bytes", (long long)bytes);
     return hipSuccess;
 }
-hipError_t hipGetLastError() { return hipSuccess; }
+hipError_t hipGetLastError() {
+    stub::Tr("hipGetLastError");
+    return hipSuccess;
+}
 hipError_t hipGetDevice(int* d) {
+    stub::Tr("hipGetDevice");
     *d = 0;
     return hipSuccess;
 }
-hipError_t hipFuncSetAttribute(const void*, int, int) { return hipSuccess; }
+hipError_t hipFuncSetAttribute(const void*, int attr, int value) {
+    stub::Tr("hipFuncSetAttribute").i("attr", attr).i("value", value);
+    return hipSuccess;
+}
 
 // the scheduler's own two little kernels (generator.hip): fill_kernel(dst, v, n), small_copy_kernel(src, dst, n_valid, n_total, mode)
-void pnp_stub_kernel_launch_impl(const char* name, dim3, dim3, hipStream_t s, const PnpStubArg* a, int n) {
+void pnp_stub_kernel_launch_impl(const char* name, dim3 grid, dim3 block, hipStream_t s, const PnpStubArg* a, int n) {
     stub::cur = name;
     stub::note_launch(s);
+    {
+        stub::Tr t(name, s);
+        t.i("grid", grid.x).i("grid.y", grid.y).i("grid.z", grid.z).i("block", block.x).i("block.y", block.y).i("block.z", block.z);
+        for (int k = 0; k < n; ++k) {
+            const std::string key = "arg" + std::to_string(k);
+            if (a[k].kind == 0) t.p(key, a[k].p);
+            else if (a[k].kind == 1) t.f(key, a[k].f);
+            else t.i(key, a[k].i);
+        }
+    }
     const std::string k(name);
     if (k == "fill_kernel" && n == 3) {
         stub::WR("fill destination", const_cast<void*>(a[0].p), (size_t)a[2].i * 4);
@@ -246,6 +341,7 @@ static void conv_touch(const ConvArgs& a, int cfg, int gy, int path) {
 int launch_conv3x3(const ConvArgs& a, int cfg, int gy, hipStream_t s) {
     stub::cur = "launch_conv3x3";
     stub::note_launch(s);
+    stub::trace_conv("launch_conv3x3", a, cfg, gy, s);
     if (a.nsrc < 1 || a.nsrc > 4) return PNP_ERR_BAD_ARG;
     const bool f16 = a.prec == 1 && conv_f16_eligible(a, cfg, gy);
     const bool x3 = a.prec == 2 && conv_f16x3_eligible(a, cfg, gy);
@@ -260,6 +356,7 @@ int launch_conv3x3(const ConvArgs& a, int cfg, int gy, hipStream_t s) {
 int launch_conv3x3_f16(const ConvArgs& a, int gy, hipStream_t s) {
     stub::cur = "launch_conv3x3_f16";
     stub::note_launch(s);
+    stub::trace_conv("launch_conv3x3_f16", a, CONV_CFG_BIG, gy, s);
     conv_touch(a, CONV_CFG_BIG, gy, 1);
     stub::convs.push_back({a, CONV_CFG_BIG, gy, stub::sid(s), 1});
     return 0;
@@ -267,6 +364,7 @@ int launch_conv3x3_f16(const ConvArgs& a, int gy, hipStream_t s) {
 int launch_conv3x3_f16x3(const ConvArgs& a, int cfg, hipStream_t s) {
     stub::cur = "launch_conv3x3_f16x3";
     stub::note_launch(s);
+    stub::trace_conv("launch_conv3x3_f16x3", a, cfg, 1, s);
     conv_touch(a, cfg, 1, 2);
     stub::convs.push_back({a, cfg, 1, stub::sid(s), 2});
     return 0;
@@ -274,6 +372,7 @@ int launch_conv3x3_f16x3(const ConvArgs& a, int cfg, hipStream_t s) {
 int launch_f16x3_image(const float* src, void* dst, int nchunks, hipStream_t s) {
     stub::cur = "launch_f16x3_image";
     stub::note_launch(s);
+    stub::Tr("launch_f16x3_image", s).p("src", src).p("dst", dst).i("nchunks", nchunks);
     const size_t n = (size_t)nchunks * pnp_chunk_floats(2);
     stub::RD("fp32 weight images", src, n * 4);
     stub::WR("split fp16 weight images", dst, n * 4);
@@ -282,6 +381,7 @@ int launch_f16x3_image(const float* src, void* dst, int nchunks, hipStream_t s) 
 int launch_f16_image(const float* src, void* dst, int nchunks, int ntb, hipStream_t s) {
     stub::cur = "launch_f16_image";
     stub::note_launch(s);
+    stub::Tr("launch_f16_image", s).p("src", src).p("dst", dst).i("nchunks", nchunks).i("ntb", ntb);
     const size_t n = (size_t)nchunks * pnp_chunk_floats(ntb);
     stub::RD("fp32 weight images", src, n * 4);
     stub::WR("fp16 weight images", dst, n * 2);
@@ -304,6 +404,7 @@ bool conv_wino_ms_eligible(const ConvArgs& a, int cfg, int grid_y) {    // conv_
 int launch_wino_rgb_image(const float* src, float* dst, hipStream_t s) {
     stub::cur = "launch_wino_rgb_image";
     stub::note_launch(s);
+    stub::Tr("launch_wino_rgb_image", s).p("src", src).p("dst", dst);
     stub::RD("the frame's packed weight chunk", src, 4096 * 4);
     stub::WR("the frame's Winograd weight image", dst, (size_t)PNP_WINO_RGB_FLOATS * 4);
     return 0;
@@ -311,6 +412,11 @@ int launch_wino_rgb_image(const float* src, float* dst, hipStream_t s) {
 int launch_wino_images(const float* const* src, float* const* dst, int n, const float* gamma, hipStream_t s) {
     stub::cur = "launch_wino_images";
     stub::note_launch(s);
+    {
+        stub::Tr t("launch_wino_images", s);
+        t.i("n", n).p("gamma", gamma);
+        for (int i = 0; i < n && i < 16; ++i) t.p("src" + std::to_string(i), src[i]).p("dst" + std::to_string(i), dst[i]);
+    }
     if (n < 1 || n > 16) return PNP_ERR_BAD_ARG;
     for (int i = 0; i < n; ++i) {
         stub::RD("a packed 3x3 weight image", src[i], 9 * 4096 * 4);
@@ -322,14 +428,19 @@ int launch_wino_images(const float* const* src, float* const* dst, int n, const 
 int launch_wino_par_image(const float* src, float* dst, hipStream_t s) {
     stub::cur = "launch_wino_par_image";
     stub::note_launch(s);
+    stub::Tr("launch_wino_par_image", s).p("src", src).p("dst", dst);
     stub::RD("the packed 1x1 weight images", src, 3 * 4096 * 4);
     stub::WR("the Winograd 1x1 weight image", dst, (size_t)PNP_WINO_PAR_FLOATS * 4);
     return 0;
 }
-int launch_conv3x3_wino(const ConvArgs&, hipStream_t) { return PNP_ERR_UNSUPPORTED; }      // only reached through launch_conv3x3
+int launch_conv3x3_wino(const ConvArgs& a, hipStream_t s) {      // only reached through launch_conv3x3
+    stub::trace_conv("launch_conv3x3_wino", a, CONV_CFG_BIG, 1, s);
+    return PNP_ERR_UNSUPPORTED;
+}
 int launch_par_tile_flags(const float* par, long plane, int* flags, int frames, int H, int W, hipStream_t s) {
     stub::cur = "launch_par_tile_flags";
     stub::note_launch(s);
+    stub::Tr("launch_par_tile_flags", s).p("par", par).i("plane", plane).p("flags", flags).i("frames", frames).i("H", H).i("W", W);
     stub::RD("partition maps", par, (size_t)frames * 3 * plane * 4);
     stub::WR("partition tile flags", flags, (size_t)frames * ((W + 15) / 16) * ((H + 7) / 8) * 4);
     return 0;
@@ -337,6 +448,7 @@ int launch_par_tile_flags(const float* par, long plane, int* flags, int frames, 
 int launch_par_frame_any(const int* flags, int* any, int frames, int H, int W, hipStream_t s) {
     stub::cur = "launch_par_frame_any";
     stub::note_launch(s);
+    stub::Tr("launch_par_frame_any", s).p("flags", flags).p("any", any).i("frames", frames).i("H", H).i("W", W);
     stub::RD("partition tile flags", flags, (size_t)frames * ((W + 15) / 16) * ((H + 7) / 8) * 4);
     stub::WR("per-frame partition-record words", any, (size_t)frames * 4);
     return 0;
@@ -344,13 +456,15 @@ int launch_par_frame_any(const int* flags, int* any, int frames, int H, int W, h
 int launch_pack_last_valu(const float* w, float* dst, hipStream_t s) {
     stub::cur = "launch_pack_last_valu";
     stub::note_launch(s);
+    stub::Tr("launch_pack_last_valu", s).p("w", w).p("dst", dst);
     stub::RD("conv_last.weight", w, 3 * 64 * 9 * 4);
     stub::WR("vector-ALU conv_last weights", dst, 9 * 64 * 4 * 4);
     return 0;
 }
-int launch_mv_warp_nhwc(const float* feat, const float* fx, const float* fy, void* out, int H, int W, int C, hipStream_t s, bool f16, bool) {
+int launch_mv_warp_nhwc(const float* feat, const float* fx, const float* fy, void* out, int H, int W, int C, hipStream_t s, bool f16, bool nearest) {
     stub::cur = "launch_mv_warp_nhwc";
     stub::note_launch(s);
+    stub::Tr("launch_mv_warp_nhwc", s).p("feat", feat).p("fx", fx).p("fy", fy).p("out", out).i("H", H).i("W", W).i("C", C).i("f16", f16).i("nearest", nearest);
     const size_t hw = (size_t)H * W;
     stub::RD("the key-frame feature", feat, hw * C * 4);
     stub::RD("flow plane x", fx, hw * 4);
@@ -359,9 +473,10 @@ int launch_mv_warp_nhwc(const float* feat, const float* fx, const float* fy, voi
     stub::warps.push_back({feat, fx, out, f16});
     return 0;
 }
-int launch_flow_warp_nchw(const float* x, const float* flow, float* out, int N, int C, int H, int W, hipStream_t s, bool) {
+int launch_flow_warp_nchw(const float* x, const float* flow, float* out, int N, int C, int H, int W, hipStream_t s, bool nearest) {
     stub::cur = "launch_flow_warp_nchw";
     stub::note_launch(s);
+    stub::Tr("launch_flow_warp_nchw", s).p("x", x).p("flow", flow).p("out", out).i("N", N).i("C", C).i("H", H).i("W", W).i("nearest", nearest);
     stub::RD("x", x, (size_t)N * C * H * W * 4);
     stub::RD("flow", flow, (size_t)N * H * W * 8);
     stub::WR("out", out, (size_t)N * C * H * W * 4);
@@ -370,6 +485,7 @@ int launch_flow_warp_nchw(const float* x, const float* flow, float* out, int N, 
 int launch_pack_lr(const float* lrs, float* lr4, int T, int H, int W, hipStream_t s) {
     stub::cur = "launch_pack_lr";
     stub::note_launch(s);
+    stub::Tr("launch_pack_lr", s).p("lrs", lrs).p("lr4", lr4).i("T", T).i("H", H).i("W", W);
     stub::RD("the low-quality frames", lrs, (size_t)T * 3 * H * W * 4);
     stub::WR("the packed RGB0 frames", lr4, (size_t)T * H * W * 16);
     return 0;
@@ -377,6 +493,7 @@ int launch_pack_lr(const float* lrs, float* lr4, int T, int H, int W, hipStream_
 int launch_par_sparse(const float* par, float* out, int T, int H, int W, hipStream_t s) {
     stub::cur = "launch_par_sparse";
     stub::note_launch(s);
+    stub::Tr("launch_par_sparse", s).p("par", par).p("out", out).i("T", T).i("H", H).i("W", W);
     stub::RD("partition maps", par, (size_t)T * 3 * H * W * 4);
     stub::WR("sparse-equivalent partition maps", out, (size_t)T * 3 * H * W * 4);
     return 0;
@@ -384,6 +501,7 @@ int launch_par_sparse(const float* par, float* out, int T, int H, int W, hipStre
 int launch_pack_flow4(const float* fx, const float* fy, float* out4, int H, int W, hipStream_t s) {
     stub::cur = "launch_pack_flow4";
     stub::note_launch(s);
+    stub::Tr("launch_pack_flow4", s).p("fx", fx).p("fy", fy).p("out4", out4).i("H", H).i("W", W);
     stub::RD("flow plane x", fx, (size_t)H * W * 4);
     stub::RD("flow plane y", fy, (size_t)H * W * 4);
     stub::WR("flow4", out4, (size_t)H * W * 16);
@@ -392,6 +510,7 @@ int launch_pack_flow4(const float* fx, const float* fy, float* out4, int H, int 
 int launch_nchw_to_nhwc(const float* in, float* out, int N, int C, int H, int W, hipStream_t s) {
     stub::cur = "launch_nchw_to_nhwc";
     stub::note_launch(s);
+    stub::Tr("launch_nchw_to_nhwc", s).p("in", in).p("out", out).i("N", N).i("C", C).i("H", H).i("W", W);
     stub::RD("in", in, (size_t)N * C * H * W * 4);
     stub::WR("out", out, (size_t)N * C * H * W * 4);
     return 0;
@@ -400,6 +519,10 @@ int launch_nhwc_to_nchw(const float* in, float* out, int N, int C, int H, int W,
 int launch_pack_weights(const PackArgs& a, int gy, hipStream_t s) {
     stub::cur = "launch_pack_weights";
     stub::note_launch(s);
+    stub::Tr("launch_pack_weights", s).i("gy", gy).p("w", a.w).p("ew", a.ew).i("E", a.E).i("e_stride", a.e_stride).i("cin_total", a.cin_total)
+        .i("ktaps", a.ktaps).i("group_cin", a.group_cin).i("co_mul", a.co_mul).i("co_add", a.co_add).i("n_valid", a.n_valid).i("co_mode", a.co_mode)
+        .i("cvalid", a.cvalid).i("kind", a.kind).i("cbase", a.cbase).i("ntb", a.ntb).f("scale", a.scale).p("dst", a.dst).i("w_ystride", a.w_ystride)
+        .i("dst_ystride", a.dst_ystride);
     const size_t co_max = a.co_mode == 1 ? 431 : (size_t)(a.n_valid - 1) * a.co_mul + a.co_add;
     const size_t rows = (co_max + 1) * (size_t)a.cin_total * a.ktaps;
     const size_t img = (a.kind == PACK_WIDE ? 9 : 1) * (size_t)a.ntb * 2048;
@@ -414,6 +537,7 @@ int launch_pack_weights(const PackArgs& a, int gy, hipStream_t s) {
 int launch_mix_bias(const float* b, const float* ew, float* out, int E, int C, int nconv, hipStream_t s) {
     stub::cur = "launch_mix_bias";
     stub::note_launch(s);
+    stub::Tr("launch_mix_bias", s).p("b", b).p("ew", ew).p("out", out).i("E", E).i("C", C).i("nconv", nconv);
     stub::RD("expert biases", b, (size_t)nconv * E * C * 4);
     stub::RD("expert attention", ew, (size_t)E * 4);
     stub::WR("mixed biases", out, (size_t)nconv * C * 4);
@@ -422,6 +546,12 @@ int launch_mix_bias(const float* b, const float* ew, float* out, int E, int C, i
 int launch_caa_predict(const CaaArgs& a, hipStream_t s) {
     stub::cur = "launch_caa_predict";
     stub::note_launch(s);
+    {
+        stub::Tr t("launch_caa_predict", s);
+        t.i("count", a.count).i("t0", a.t0).i("E", a.E).i("softmax", a.softmax).i("with_se", a.with_se).p("w1", a.w1).p("b1", a.b1).p("w2", a.w2)
+            .p("b2", a.b2).p("v1", a.v1).p("v2", a.v2).p("ew", a.ew).p("gamma", a.gamma);
+        for (int i = 0; i < 32; ++i) t.f("q_ew" + std::to_string(i), a.q_ew[i]).f("q_g" + std::to_string(i), a.q_g[i]);
+    }
     if (a.count < 1 || a.count > 32) stub::fail("caa: count out of range");
     stub::RD("BasePredictor.0.weight", a.w1, 64 * 4);
     stub::RD("BasePredictor.0.bias", a.b1, 64 * 4);
@@ -438,6 +568,8 @@ int launch_caa_predict(const CaaArgs& a, hipStream_t s) {
 int launch_dcn(const DcnArgs& a, hipStream_t s) {
     stub::cur = "launch_dcn";
     stub::note_launch(s);
+    stub::Tr("launch_dcn", s).p("x", a.x).p("om", a.om).p("fx", a.fx).p("fy", a.fy).p("w", a.w).p("w16", a.w16).p("bias", a.bias).p("out", a.out)
+        .i("H", a.H).i("W", a.W).p("dbg", a.dbg);
     const size_t hw = (size_t)a.H * a.W;
     stub::RD("the feature to sample", a.x, hw * 256);
     stub::RD("the offset/mask map", a.om, hw * 448 * 4);
@@ -454,6 +586,7 @@ int dcn_trace_u64s() { return 256 * 64; }
 int launch_dcn_f16_image(const float* w, void* dst, hipStream_t s) {
     stub::cur = "launch_dcn_f16_image";
     stub::note_launch(s);
+    stub::Tr("launch_dcn_f16_image", s).p("w", w).p("dst", dst);
     stub::RD("the DCN weight image", w, 9 * 4096 * 4);
     stub::WR("the fp16 DCN weight image", dst, 9 * 4096 * 2);
     return 0;
@@ -502,6 +635,9 @@ int run(const Scenario& sc) {
     mixes.clear();
     dcn_calls = 0;
     streams_created = events_created = 0;
+    regions.clear();
+    trace.clear();
+    pnp_stub_io_hook = trace_io;
     pnp_generator* g = nullptr;
     int rc = pnp_generator_create(&sc.cfg, &g);
     if (rc) {
@@ -532,6 +668,13 @@ int run(const Scenario& sc) {
     mark(lrs, (size_t)sc.n * sc.t * 3 * hw * 4);
     mark(mvs, (size_t)sc.n * sc.t * 4 * hw * 4);
     mark(par, (size_t)sc.n * sc.t * 3 * hw * 4);
+    region("flat", flat, (size_t)flat_n * 4);
+    region("packed", packed, (size_t)packed_n * 4);
+    region("ws", ws, (size_t)ws_bytes);
+    region("lrs", lrs, (size_t)sc.n * sc.t * 3 * hw * 4);
+    region("mvs", mvs, (size_t)sc.n * sc.t * 4 * hw * 4);
+    region("par", par, (size_t)sc.n * sc.t * 3 * hw * 4);
+    region("out", out, (size_t)sc.n * sc.t * 3 * hw * os * os * 4);
     pnp_stub_stream caller{0};
     rc = pnp_generator_pack(g, flat, packed, &caller);
     const size_t launches_pack = launch_streams.size();
@@ -645,6 +788,7 @@ int run(const Scenario& sc) {
     // every output byte of the call must have been written
     if (frc == 0 && !covered(out, (size_t)sc.n * sc.t * 3 * hw * os * os * 4)) fail("the output clip is not completely written");
     pnp_generator_destroy(g);
+    trace_dump(sc.name);
     printf("\"live_events_after_destroy\": %d, \"live_streams_after_destroy\": %d, \"errors\": [", live_events, live_streams);
     for (size_t i = 0; i < errors.size(); ++i) printf("%s\"%s\"", i ? ", " : "", errors[i].c_str());
     printf("]}\n");

@@ -65,6 +65,9 @@ int run_case(const Case& cs) {
     convs.clear();
     mixes.clear();
     img_events.clear();
+    regions.clear();
+    trace.clear();
+    pnp_stub_io_hook = trace_io;
     pnp_generator* g = nullptr;
     if (pnp_generator_create(&cs.cfg, &g)) return 2;
     pnp_generator_set_precision(g, PNP_PREC_F32);
@@ -86,6 +89,13 @@ int run_case(const Case& cs) {
     mark(lrs, nt * 3 * hw * 4);
     mark(mvs, nt * 4 * hw * 4);
     mark(par, nt * 3 * hw * 4);
+    region("flat", flat, (size_t)flat_n * 4);
+    region("packed", packed, (size_t)packed_n * 4);
+    region("ws", ws, (size_t)ws_bytes);
+    region("lrs", lrs, nt * 3 * hw * 4);
+    region("mvs", mvs, nt * 4 * hw * 4);
+    region("par", par, nt * 3 * hw * 4);
+    region("out", out, nt * 3 * hw * 4);
     std::vector<float> sl, qp, bq;
     for (int b = 0; b < cs.n; ++b) {
         const std::vector<float> p = pattern(cs.pat, cs.t);
@@ -153,6 +163,7 @@ int run_case(const Case& cs) {
         if (joins < forked) fail("run " + std::to_string(r) + ": its images are launched with " + std::to_string(forked - joins) + " chain(s) not joined");
     }
     pnp_generator_destroy(g);
+    trace_dump(cs.name);
     printf("{\"name\": \"%s\", \"pack_rc\": %d, \"forward_rc\": %d, \"bound_rc\": %d, \"runs\": %zu, \"image_launches\": %zu, \"image_reads\": %d, "
            "\"side_stream_convs\": %d, \"launches_into_buffer\": [%d, %d], \"errors\": [",
            cs.name, prc, frc, bound_rc, run_start.size(), img_events.size(), reads, side_convs, buffers_seen[0], buffers_seen[1]);
