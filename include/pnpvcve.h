@@ -24,6 +24,19 @@ extern "C" {
 #define PNP_ERR_WORKSPACE 1003
 #define PNP_ERR_SIZE_ASSERT 1004 /* reference: AssertionError, h/w < 64 (iconvsr_ipb_par.py:51) */
 #define PNP_ERR_SIZE_VALUE 1005  /* reference: ValueError from flow_warp.py:27-29 (h/w % 4 != 0) */
+/* any_size (this is the ONE statement of the rule).  0 (default): a frame whose height or width is no multiple of 4 is refused with
+ * PNP_ERR_SIZE_VALUE, as the reference refuses it (its spatial_padding pads lrs alone, iconvsr.py:371-394, and flow_warp.py:27-29 then
+ * raises).  1: such frames run -- the same formulas on the h x w grid as given, no padding and no crop: every conv zero-pads at the
+ * true frame edge, warps and partition planes are indexed on h x w, the output is (n,t,3,h,w) or (n,t,3,4h,4w) with cfg.vsr.  For h and
+ * w multiples of 4 the forward is the one of any_size = 0, launch for launch.  h, w >= 64 (PNP_ERR_SIZE_ASSERT) holds in both modes.
+ * With the switch on a byte clip (PNP_FRAMES_U8_HWC / PNP_OUT_U8) may start at any byte address -- clip b of a (n,t,h,w,3) batch
+ * does when t*h*w*3 is no multiple of 4 -- and cfg.deform = 'basic' | 'fvc' is refused with PNP_ERR_UNSUPPORTED at every size (the
+ * DCN aligners have not run on such frames).  Honoured by pnp_generator_forward, pnp_generator_forward_clips and the two workspace
+ * queries (which size any h x w; the refusals are the forward's).  The reference has no output at these sizes: the mode is pinned
+ * to the oracle's blocks (tests/any_size_ref.py).  Negative `on`: PNP_ERR_BAD_ARG; get: 0 / 1, -1 for NULL. */
+typedef struct pnp_generator pnp_generator; /* (pnp_generator_create below) */
+int pnp_generator_set_any_size(pnp_generator* g, int on);
+int pnp_generator_get_any_size(const pnp_generator* g);
 
 int pnp_abi_version(void); /* 5: PNP_OPT_WINOGRAD, pnp_wino_* / pnp_conv3x3_wino_f32.  4: pnp_generator_cfg grew num_group / flow_inter / blocktype (3: the never-implemented fused-block option / query of v2
                               removed, PNP_OPT_* renumbered, PNP_OPT_SPARSE_EVAL, PNP_OPT_F16_MIRRORS) */
@@ -53,8 +66,6 @@ typedef struct pnp_generator_cfg {
                        are plain convs, no expert mix and no gain; needs one_layer = 1 (with Dynamic_conv2d_se convs the
                        reference indexes a tensor with 'x' and raises) */
 } pnp_generator_cfg;
-
-typedef struct pnp_generator pnp_generator;
 
 int pnp_generator_create(const pnp_generator_cfg* cfg, pnp_generator** out);
 void pnp_generator_destroy(pnp_generator* g);

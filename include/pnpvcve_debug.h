@@ -41,6 +41,11 @@ int pnp_debug_wino_gate_word(const int* gate_word_dev);
  * PNP_ERR_BAD_ARG.  Process-wide, not thread-safe: a test hook. */
 int pnp_debug_wino_tile_rows(int row0, int nrows);
 
+/* The byte-frame unpacking in front of pnp_generator_forward_clips' convs, alone: lq_dev (t,h,w,3) uint8 -> lr4_dev (t,h,w,4) fp32
+ * RGB0, every byte through the table of pnp_frames_from_rgb8.  any_size = 0: the form for whole 12-byte groups on a 4-aligned address
+ * (PNP_ERR_BAD_ARG otherwise, before any launch); 1: the form pnp_generator_set_any_size adds, any address and any t*h*w. */
+int pnp_debug_pack_lr_u8(const unsigned char* lq_dev, float* lr4_dev, int t, int h, int w, int any_size, void* stream);
+
 /* The row-band plan of pnp_generator_set_band_split as a pure function: for a chain of nconv convs on a frame of `rows` tile rows,
  * writes the boundary row a_n of each conv (chain A: tile rows [0, a_n), chain B: [a_n, rows); a_n = a_0 - n) to bounds[0 .. nconv)
  * and returns 1, or returns 0 (bounds untouched) when the frame has too few rows for both regions to stay non-empty: no split.

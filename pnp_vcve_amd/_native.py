@@ -47,6 +47,8 @@ SIGNATURES = {
     'pnp_generator_set_band_split': (c_int, [c_void_p, c_int]),
     'pnp_generator_get_band_split': (c_int, [c_void_p]),
     'pnp_generator_min_resident': (c_int, [c_void_p, c_int]),
+    'pnp_generator_set_any_size': (c_int, [c_void_p, c_int]),
+    'pnp_generator_get_any_size': (c_int, [c_void_p]),
     'pnp_generator_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       POINTER(c_float), POINTER(c_float), POINTER(c_float),
                                       c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
@@ -129,6 +131,7 @@ DEBUG_SIGNATURES['pnp_dcn_nhwc_f32_ex'] = (c_int, [c_void_p, c_void_p, c_void_p,
 DEBUG_SIGNATURES['pnp_dcn_trace_u64s'] = (c_int, [])
 DEBUG_SIGNATURES['pnp_debug_wino_gate_word'] = (c_int, [c_void_p])
 DEBUG_SIGNATURES['pnp_debug_wino_tile_rows'] = (c_int, [c_int, c_int])
+DEBUG_SIGNATURES['pnp_debug_pack_lr_u8'] = (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
 DEBUG_SIGNATURES['pnp_band_plan'] = (c_int, [c_int, c_int, c_int, POINTER(c_int)])
 DEBUG_SIGNATURES['pnp_conv3x3_wino_f32_ex'] = (c_int, [c_void_p] * 8 + [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p])
 DEBUG_SIGNATURES['pnp_conv3x3_f16_maps'] = (c_int, [c_int, POINTER(c_void_p), POINTER(c_int), c_int, POINTER(c_void_p), c_void_p,

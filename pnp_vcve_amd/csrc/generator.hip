@@ -87,6 +87,7 @@ struct pnp_generator {
     // row-band chains (pnp_generator_set_band_split): chain B's stream, one `ready` event per conv of a chain and the join event;
     // made the first time a frame qualifies
     int band_split = 1;
+    int any_size = 0;                 // pnp_generator_set_any_size: frames whose height / width is no multiple of 4 run too
     mutable hipStream_t band_stream = nullptr;
     mutable std::vector<hipEvent_t> band_events;
     mutable std::deque<ConvBandSplit> band_recs;     // the split of every chained conv of the latest forward (ConvArgs::band points here: the
@@ -822,6 +823,12 @@ int pnp_generator_set_band_split(pnp_generator* g, int on) {
     return PNP_OK;
 }
 int pnp_generator_get_band_split(const pnp_generator* g) { return g ? g->band_split : -1; }
+int pnp_generator_set_any_size(pnp_generator* g, int on) {
+    if (!g || on < 0) return PNP_ERR_BAD_ARG;
+    g->any_size = on != 0;
+    return PNP_OK;
+}
+int pnp_generator_get_any_size(const pnp_generator* g) { return g ? g->any_size : -1; }
 int pnp_band_plan(int rows, int nconv, int a0, int* bounds) {
     int first;
     if (!bounds || nconv > 4096 || !band_plan(rows, nconv, a0, &first)) return 0;
@@ -1052,7 +1059,11 @@ struct ClipRun {
             const int rc = launch_fill(reinterpret_cast<float*>(W.queue), 0.0f, 16, st);
             if (rc) return rc;
         }
-        return lq8 ? launch_pack_lr_u8(lq8, W.lr4, t, h, w, st) : launch_pack_lr(lr_b, W.lr4, t, h, w, st);
+        if (!lq8) return launch_pack_lr(lr_b, W.lr4, t, h, w, st);
+        // any_size: a clip that is not whole 12-byte groups on a 4-aligned address takes the kernel with a head and a tail; every
+        // other clip the one it always took
+        const bool ragged = (((int64_t)t * hw) & 3) || (reinterpret_cast<uintptr_t>(lq8) & 3);
+        return (g->any_size && ragged) ? launch_pack_lr_u8_any(lq8, W.lr4, t, h, w, st) : launch_pack_lr_u8(lq8, W.lr4, t, h, w, st);
     }
     int partition_maps() {
         // the reference's (eval-mode) sparse evaluation as a dense map (prep.hip): for the whole clip at once, or (bounded schedule)
@@ -1365,7 +1376,8 @@ int forward_check(const pnp_generator* g, int n, int t, int h, int w, int lq_for
     if (n < 1 || t < 1) return PNP_ERR_BAD_ARG;
     if (g->cfg.sparse_val && g->opt[PNP_OPT_SPARSE_EVAL] && n != 1) return PNP_ERR_UNSUPPORTED;   // sparse_conv reads feature[0] only (sr_backbone_utils.py:262-275)
     if (h < 64 || w < 64) return PNP_ERR_SIZE_ASSERT;
-    if ((h % 4) || (w % 4)) return PNP_ERR_SIZE_VALUE;
+    if (!g->any_size && ((h % 4) || (w % 4))) return PNP_ERR_SIZE_VALUE;
+    if (g->any_size && g->cfg.deform != 0) return PNP_ERR_UNSUPPORTED;      // the DCN aligners have never run on a frame that is no multiple of 4
     // the kernels address a feature map with 32-bit byte offsets: the largest one (x16 pixels with the x4 heads) must
     // stay below 4 GiB (2160p, or 720p -> 2880p with vsr, still fit)
     if (pnp_addr32_bytes_per_lr_pixel(g->cfg.vsr, g->cfg.deform) * (int64_t)h * w >= (int64_t)1 << 32)
@@ -1463,8 +1475,10 @@ int pnp_generator_forward_clips(const pnp_generator* g, const float* flat, const
         const pnp_clip_io& c = clips[b];
         if (!c.lq_dev || !c.mvs_dev || !c.par_dev) return PNP_ERR_BAD_ARG;
         if ((out_mask & PNP_OUT_F32) && !c.out_f32_dev) return PNP_ERR_BAD_ARG;
-        if ((out_mask & PNP_OUT_U8) && (!c.out_u8_dev || (reinterpret_cast<uintptr_t>(c.out_u8_dev) & 3))) return PNP_ERR_BAD_ARG;
-        if (lq_format == PNP_FRAMES_U8_HWC && (reinterpret_cast<uintptr_t>(c.lq_dev) & 3)) return PNP_ERR_BAD_ARG;
+        // (any_size: a clip of t*h*w*3 bytes inside a batch starts at any byte address; the kernels then read and write bytes there)
+        const uintptr_t amask = g->any_size ? 0 : 3;
+        if ((out_mask & PNP_OUT_U8) && (!c.out_u8_dev || (reinterpret_cast<uintptr_t>(c.out_u8_dev) & amask))) return PNP_ERR_BAD_ARG;
+        if (lq_format == PNP_FRAMES_U8_HWC && (reinterpret_cast<uintptr_t>(c.lq_dev) & amask)) return PNP_ERR_BAD_ARG;
     }
     return forward_batch(g, flat, packed, clips, n, lq_format, out_mask, slices, qps, base_qps, workspace, workspace_bytes, t, h, w,
                          (hipStream_t)stream_);

@@ -1,5 +1,5 @@
 // Host-only stand-ins (-DPNP_HOST_STUB) for the launchers of the byte-frame boundary that the clip scheduler (csrc/generator.hip)
-// calls: launch_pack_lr_u8, launch_frames_from_rgb8, launch_frames_to_rgb8 (prep.h) and launch_conv_last_io (conv_mfma.h).
+// calls: launch_pack_lr_u8 (and its any_size form), launch_frames_from_rgb8, launch_frames_to_rgb8 (prep.h) and launch_conv_last_io (conv_mfma.h).
 //
 // The recording launchers of the scheduler's other kernels live in tests/host/sched_stub.cpp, which the earlier host tests include
 // unchanged; these four are defined here so that those tests keep compiling without knowing them (a forward at the fp32 boundary
@@ -36,6 +36,12 @@ inline int pnp_stub_io_record(const PnpStubIoLaunch& r) {
 inline int launch_pack_lr_u8(const unsigned char* lq, float* lr4, int T, int H, int W, hipStream_t stream) {
     if (T < 1 || (((long)H * W * T) & 3) || (reinterpret_cast<uintptr_t>(lq) & 3)) return PNP_ERR_BAD_ARG;       // prep.hip's own checks
     PnpStubIoLaunch r{PNP_STUB_IO_PACK_LR_U8, stream, lq, lr4, T, H, W, {}};
+    return pnp_stub_io_record(r);
+}
+
+inline int launch_pack_lr_u8_any(const unsigned char* lq, float* lr4, int T, int H, int W, hipStream_t stream) {
+    if (T < 1 || H < 1 || W < 1 || !lq || !lr4) return PNP_ERR_BAD_ARG;
+    PnpStubIoLaunch r{PNP_STUB_IO_PACK_LR_U8, stream, lq, lr4, T, H, W, {}};      // (the same ranges: t*h*w*3 bytes read, 16 B per pixel written)
     return pnp_stub_io_record(r);
 }
 

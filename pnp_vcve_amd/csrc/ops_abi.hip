@@ -40,6 +40,12 @@ ConvArgs op_conv_args(int nsrc, const float* const* srcs, const int* src_channel
 
 extern "C" {
 
+// the clip scheduler's byte-frame unpacking alone: any_size 0 = the aligned, whole-group form with its refusals, 1 = any address and count
+int pnp_debug_pack_lr_u8(const unsigned char* lq, float* lr4, int t, int h, int w, int any_size, void* st) {
+    if (!lq || !lr4 || t < 1 || h < 1 || w < 1) return PNP_ERR_BAD_ARG;
+    return any_size ? launch_pack_lr_u8_any(lq, lr4, t, h, w, (hipStream_t)st) : launch_pack_lr_u8(lq, lr4, t, h, w, (hipStream_t)st);
+}
+
 int pnp_flow_warp_nchw_f32(const float* x, const float* flow, float* out, int n, int c, int h, int w, void* st) {
     if (n < 1 || c < 1 || h < 1 || w < 1) return PNP_ERR_BAD_ARG;
     return launch_flow_warp_nchw(x, flow, out, n, c, h, w, (hipStream_t)st);

@@ -19,6 +19,8 @@ struct PnpU8Table {
 };
 // (T,H,W,3) uint8 RGB frames -> (T,H,W,4) pixel-major RGB0 fp32, 4th channel zero; lq 4-byte aligned.  3 B read + 16 B written per pixel
 int launch_pack_lr_u8(const unsigned char* lq, float* lr4, int T, int H, int W, hipStream_t stream);
+// the same at any byte address of lq and any pixel count (any_size): head and tail pixels byte by byte, the body as aligned 12-byte groups
+int launch_pack_lr_u8_any(const unsigned char* lq, float* lr4, int T, int H, int W, hipStream_t stream);
 // (n,H,W,3) uint8 RGB <-> (n,3,H,W) fp32 planes (metrics.hip): the table one way, round_half_even(clamp(x,0,1) * 255) the other
 int launch_frames_from_rgb8(const unsigned char* in, float* out, int nframes, int H, int W, hipStream_t stream);
 int launch_frames_to_rgb8(const float* in, unsigned char* out, int nframes, int H, int W, hipStream_t stream);

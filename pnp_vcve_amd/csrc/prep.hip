@@ -45,6 +45,40 @@ __global__ __launch_bounds__(256) void pack_lr_u8_kernel(const unsigned* __restr
     d[3] = p3;
 }
 
+// any_size (pnp_generator_set_any_size): the same unpacking for a clip at ANY byte address and with any pixel count.  Pixel p's bytes
+// start at lq + 3 p, so with a = lq & 3 the pixels p = a (mod 4) are the ones that start on a dword (3 a + a = 4 a): the `head` = a first
+// pixels and the (total - head) % 4 last ones are read byte by byte, and the body in between is whole 12-byte groups on aligned dwords
+// -- the three dword loads and the four stores of the kernel above, so no load needs realigning and none touches a byte outside
+// [lq, lq + 3 total).  lr4 is 16 B per pixel: every store stays aligned whatever `head` is.  Every value through the same table.
+__global__ __launch_bounds__(256) void pack_lr_u8_any_kernel(const unsigned char* __restrict__ lq, float* __restrict__ lr4, long total,
+                                                             int head, long groups) {
+    __shared__ float tab[256];
+    tab[threadIdx.x] = k_u8_table.v[threadIdx.x];
+    __syncthreads();
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    f32x4* const d4 = reinterpret_cast<f32x4*>(lr4);
+    if (i >= groups) {      // the up to 3 + 3 pixels outside the body: one thread each
+        const long j = i - groups;
+        const long p = j < head ? j : head + 4 * groups + (j - head);
+        if (p >= total) return;
+        const unsigned char* s = lq + 3 * p;
+        const f32x4 v = {tab[s[0]], tab[s[1]], tab[s[2]], 0.f};
+        d4[p] = v;
+        return;
+    }
+    const unsigned* q = reinterpret_cast<const unsigned*>(lq + 3 * head) + 3 * i;
+    const unsigned a = q[0], b = q[1], c = q[2];
+    f32x4* d = d4 + head + 4 * i;
+    const f32x4 p0 = {tab[a & 255u], tab[(a >> 8) & 255u], tab[(a >> 16) & 255u], 0.f};
+    const f32x4 p1 = {tab[a >> 24], tab[b & 255u], tab[(b >> 8) & 255u], 0.f};
+    const f32x4 p2 = {tab[(b >> 16) & 255u], tab[b >> 24], tab[c & 255u], 0.f};
+    const f32x4 p3 = {tab[(c >> 8) & 255u], tab[(c >> 16) & 255u], tab[c >> 24], 0.f};
+    d[0] = p0;
+    d[1] = p1;
+    d[2] = p2;
+    d[3] = p3;
+}
+
 // sparse_val (eval): basicvsr_net.py:511-514 generate_indices(par_j) + sr_backbone_utils.py:294-302 sparse_conv:
 // the 1x1 branch j is evaluated where plane j is NONZERO (whatever its value), later planes overwrite earlier ones
 // (mask_roi_back assigns), and the result is divided by 255.  As a dense map: plane j = 1/255 where par_j != 0 and no
@@ -202,6 +236,17 @@ int launch_pack_lr_u8(const unsigned char* lq, float* lr4, int T, int H, int W, 
     const long groups = total / 4;
     hipLaunchKernelGGL(pack_lr_u8_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, stream,
                        reinterpret_cast<const unsigned*>(lq), lr4, groups);
+    return (int)hipGetLastError();
+}
+
+int launch_pack_lr_u8_any(const unsigned char* lq, float* lr4, int T, int H, int W, hipStream_t stream) {
+    const long total = (long)H * W * T;
+    if (T < 1 || H < 1 || W < 1 || !lq || !lr4) return PNP_ERR_BAD_ARG;
+    const int a = (int)(reinterpret_cast<uintptr_t>(lq) & 3);
+    const int head = a < total ? a : (int)total;
+    const long groups = (total - head) / 4;
+    const long threads = groups + 6;        // the body, then one thread per possible head / tail pixel
+    hipLaunchKernelGGL(pack_lr_u8_any_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, lq, lr4, total, head, groups);
     return (int)hipGetLastError();
 }
 

@@ -34,7 +34,9 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
                  sparse_val=False, vsr=False, align_key=False,
                  # parents: iconvsr_ipb.py:16, iconvsr.py:346-351
                  with_cat=False, deform='vos', max_residue_magnitude=10, flow_inter='bilinear',
-                 keyframe_stride=5, padding=2):
+                 keyframe_stride=5, padding=2,
+                 # this build's own switch (no reference counterpart): see the any_size property
+                 any_size=False):
         super().__init__()
         if deform == 'stdf':
             raise TypeError('Not implemented yet')          # iconvsr_ipb.py:25-26
@@ -94,6 +96,8 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         self._profiling = False
         from . import torch_ops
         self._op_handle = torch_ops.register_generator(self)       # id under which torch.ops.pnpvcve finds this module
+        if any_size:
+            self.any_size = True
 
     # ---------------------------------------------------------------- precision
     @property
@@ -174,6 +178,21 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         if not isinstance(value, int) or value < 0:
             raise ValueError(f'band_split must be an int >= 0, got {value!r}')
         _native.check(_native.lib().pnp_generator_set_band_split(self._handle, value), 'pnp_generator_set_band_split')
+        self._graphs = {}
+
+    # ---------------------------------------------------------------- frames that are no multiple of 4
+    @property
+    def any_size(self):
+        """False (default): a frame whose height or width is no multiple of 4 raises ValueError, as the reference does (its
+        spatial_padding pads lrs alone and flow_warp then refuses the unpadded flow).  True: such frames run
+        (pnp_generator_set_any_size, include/pnpvcve.h) -- the same formulas on the h x w grid as given, no padding and no crop; the
+        output is (n,t,3,h,w), or (n,t,3,4h,4w) with vsr.  Multiples of 4 run exactly as with False.  h, w >= 64 holds either way;
+        deform='basic' | 'fvc' is refused with the switch on.  Also a constructor kwarg (model.generator.any_size=True in a config)."""
+        return bool(_native.lib().pnp_generator_get_any_size(self._handle))
+
+    @any_size.setter
+    def any_size(self, value):
+        _native.check(_native.lib().pnp_generator_set_any_size(self._handle, int(bool(value))), 'pnp_generator_set_any_size')
         self._graphs = {}
 
     def min_resident_features(self, t):
@@ -334,7 +353,8 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         with torch.cuda.device(dev):
             self._ensure_packed(dev)
             lrs_c = lrs.detach().contiguous() if byte_in else lrs.detach().float().contiguous()
-            if byte_in and lrs_c.data_ptr() % 4:     # the library reads the bytes as dwords: a view at an odd storage offset is copied
+            # the library reads the bytes as dwords: a view at an odd storage offset is copied (any_size reads a clip at any address)
+            if byte_in and lrs_c.data_ptr() % 4 and not self.any_size:
                 lrs_c = lrs_c.clone()
             mvs_c = mvs.detach().float().contiguous()
             par_c = par_map.detach().float().contiguous()
@@ -461,7 +481,8 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
                 raise ValueError(f'The spatial sizes of input ({(h, w)}) and flow/partition maps '
                                  f'({tuple(mvs_c.shape)}, {tuple(par_c.shape)}) are not the same.')
             lrs = lrs.detach().contiguous() if byte_in else lrs.detach().float().contiguous()
-            if byte_in and lrs.data_ptr() % 4:       # the library reads the bytes as dwords: a view at an odd storage offset is copied
+            # the library reads the bytes as dwords: a view at an odd storage offset is copied (any_size reads a clip at any address)
+            if byte_in and lrs.data_ptr() % 4 and not self.any_size:
                 lrs = lrs.clone()
             lr_l.append(lrs)
             mv_l.append(mvs_c)

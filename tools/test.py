@@ -48,6 +48,10 @@ def parse_args():
                    help='keep the frames uint8 from the decoder into the generator and take its output as display bytes for the PNGs '
                         '(fp32 planes only for the metrics); a pair of clips goes in by pointer instead of concatenated.  Same '
                         'metrics and PNG bytes; default off')
+    p.add_argument('--any-size', action='store_true',
+                   help='run frames whose height or width is no multiple of 4 (generator.any_size; the same as --cfg-options '
+                        'model.generator.any_size=True): the same formulas on the frame as given, no padding.  Default off: such '
+                        'frames raise ValueError, as in the reference')
     p.add_argument('--local_rank', type=int, default=0)
     a = p.parse_args()
     if 'LOCAL_RANK' not in os.environ:
@@ -94,6 +98,8 @@ def main():
         model.precision = precision
     if args.max_resident_features is not None:
         model.generator.max_resident_features = args.max_resident_features
+    if args.any_size:
+        model.generator.any_size = True
     if args.save_path is not None:      # PNG encode off the critical path (pnp_vcve_amd/io_async.py)
         from pnp_vcve_amd.io_async import FrameWriter
         model.frame_writer = FrameWriter(max_workers=4)
