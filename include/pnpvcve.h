@@ -381,6 +381,35 @@ int pnp_ssim_blocks(int h, int w, int crop_border);
 int pnp_ssim_partials_f32(const float* a_dev, const float* b_dev, double* partials_dev, int frames, int c, int h,
                           int w, int crop_border, void* stream);
 
+/* The same two statistics with a front end that does not care how a frame is stored, and an optional luma step (what
+ * BasicVSR.evaluate forwards as test_cfg.convert_to, mmedit/models/restorers/basicvsr.py:132-150, to psnr / ssim,
+ * mmedit/core/evaluation/metrics.py:200-206, 338-346).
+ *   a_format, b_format, each on its own: PNP_FRAMES_F32_NCHW, (frames,3,h,w) fp32, rounded to the byte tensor2img makes of it, or
+ *   PNP_FRAMES_U8_HWC, (frames,h,w,3) uint8 RGB, the byte as it is.  A byte clip may start at any byte address and h*w*3 need not
+ *   be a multiple of 4; no byte outside [p, p + frames*h*w*3) is read.  A U8_HWC clip gives, bit for bit, the statistic of
+ *   pnp_frames_from_rgb8 of it; with both formats F32_NCHW and PNP_COLOR_NONE the calls ARE pnp_psnr_sse_f32 / pnp_ssim_partials_f32.
+ *   color: PNP_COLOR_NONE, the three channels; PNP_COLOR_Y, the reference's mmcv.bgr2ycbcr(img / 255., y_only=True) * 255. of the
+ *   uint8 BGR image (arithmetic restated from mmcv's published source, mmcv/image/colorspace.py; mmcv is not vendored and parity
+ *   with an installed mmcv is unpinned): with x_c = (float)byte_c / 255.0f,
+ *       Y = (float)((((double)x_B * 24.966 + (double)x_G * 128.553) + (double)x_R * 65.481 + 16.0) / 255.0) * 255.0f,
+ *   every product and sum rounded on its own.  pnp_luma_from_frames writes that plane: frames of either format -> (frames,h,w) fp32.
+ * pnp_psnr_stat_io: PNP_COLOR_NONE: stat_dev (frames) uint64, the exact SSE over the 3 channels inside the crop, as
+ *   pnp_psnr_sse_f32.  PNP_COLOR_Y: stat_dev [frames][pnp_psnr_luma_blocks(h,w,crop)] doubles, one partial sum per block of
+ *   (double)d * d, d = Y_a - Y_b in fp32; the caller adds a frame's partials in index order (no floating-point atomics: the same
+ *   bits every run) and PSNR = 20 log10(255 / sqrt(sum / ((h - 2 crop)(w - 2 crop)))).
+ * pnp_ssim_partials_io: pnp_ssim_partials_f32's tiling, pnp_ssim_blocks and summation order; partials_dev [planes][blocks] with
+ *   planes = frames * 3 (PNP_COLOR_NONE) or frames (PNP_COLOR_Y, the window runs over the fp32 Y).
+ * PNP_ERR_BAD_ARG: c != 3 with a byte format or with PNP_COLOR_Y; an unknown format or color; 2 crop >= h or w; for SSIM a cropped
+ * frame smaller than 11x11; frames < 1, a negative crop or a NULL pointer. */
+#define PNP_COLOR_NONE 0
+#define PNP_COLOR_Y 1
+int pnp_psnr_luma_blocks(int h, int w, int crop_border);
+int pnp_psnr_stat_io(const void* a_dev, int a_format, const void* b_dev, int b_format, int color, void* stat_dev,
+                     int frames, int c, int h, int w, int crop_border, void* stream);
+int pnp_ssim_partials_io(const void* a_dev, int a_format, const void* b_dev, int b_format, int color,
+                         double* partials_dev, int frames, int c, int h, int w, int crop_border, void* stream);
+int pnp_luma_from_frames(const void* frames_dev, int format, float* out_dev, int nframes, int h, int w, void* stream);
+
 /* Modulated deformable 3x3 conv, 64 -> 64 channels, deform_groups 16 (mmcv.ops.modulated_deform_conv2d as
  * called at mmedit/models/backbones/sr_backbones/iconvsr_mv.py:38-41,81-84; semantics restated, mmcv is not
  * vendored).  x_dev (h,w,64) pixel-major; om_dev (h,w,448): conv_offset[2] output (pre-sigmoid masks) in the

@@ -27,6 +27,7 @@ class ClipIO(ctypes.Structure):
 
 FRAMES_F32_NCHW, FRAMES_U8_HWC = 0, 1        # PNP_FRAMES_*
 OUT_F32, OUT_U8 = 1, 2                       # PNP_OUT_* (a mask)
+COLOR_NONE, COLOR_Y = 0, 1                   # PNP_COLOR_* (the metrics' convert_to)
 
 # name -> (restype, argtypes); every symbol include/pnpvcve.h declares
 SIGNATURES = {
@@ -87,6 +88,10 @@ SIGNATURES = {
                                  c_void_p]),
     'pnp_ssim_blocks': (c_int, [c_int, c_int, c_int]),
     'pnp_ssim_partials_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'pnp_psnr_luma_blocks': (c_int, [c_int, c_int, c_int]),
+    'pnp_psnr_stat_io': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'pnp_ssim_partials_io': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'pnp_luma_from_frames': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     'pnp_conv3x3_f32': (c_int, [c_int, POINTER(c_void_p), POINTER(c_int), POINTER(c_void_p), c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     'pnp_bae_block_f32': (c_int, [c_void_p] * 10 + [c_int, c_int, c_void_p]),

@@ -6,19 +6,20 @@ from .datasets import collate
 from .dist import gather_clip_metrics, get_dist_info, shard_indices
 
 
-def _to_device(data, device, byte_frames=False):
+def _to_device(data, device, byte_frames=False, byte_metrics=False):
     """Host -> device; when the clip carries raw decoder MV records (CompressedClipFolderDataset) the dense
     motion / partition maps are painted on the GPU (pnp_rasterise_side_info_f32) instead of on the host.
     byte_frames: frames uploaded as uint8 stay what the decoder made -- `lq` is the (n,T,H,W,3) uint8 tensor itself, which the
     generator reads directly (generator.forward's byte frames), and `gt` becomes fp32 planes in one kernel (ops.frames_from_rgb8:
-    the same 256 values as the loop below, bit for bit)."""
+    the same 256 values as the loop below, bit for bit).
+    byte_metrics (with byte_frames): `gt` stays the (n,T,H,W,3) uint8 tensor too -- the device metrics read the bytes."""
     out = {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in data.items()}
     if byte_frames:
         from .ops import frames_from_rgb8
         if 'lq_u8' in out:
             out['lq'] = out.pop('lq_u8')
         if 'gt_u8' in out:
-            out['gt'] = frames_from_rgb8(out.pop('gt_u8'))
+            out['gt'] = out.pop('gt_u8') if byte_metrics else frames_from_rgb8(out.pop('gt_u8'))
     for k in ('lq', 'gt'):
         if k + '_u8' in out:       # frames uploaded as uint8 (dataset.get_uint8): RescaleToZeroOne + FramesToTensor on the device.
             # The 256 possible values come from the host's own fp32 division (a device-side `x / 255.0` multiplies by a rounded
@@ -49,11 +50,12 @@ class ClipPrefetcher:
     scatter -> forward -> evaluate, mmedit/apis/test.py:100-119); with whole 100-frame 720p clips the input
     of one clip is 3.7 GB (lq + mvs + partitions), i.e. ~60 ms of PCIe time that this hides."""
 
-    def __init__(self, dataset, indices, device, depth=1, byte_frames=False):
+    def __init__(self, dataset, indices, device, depth=1, byte_frames=False, byte_metrics=False):
         import queue
         import threading
         self.dataset, self.indices, self.device = dataset, list(indices), torch.device(device)
         self.byte_frames = bool(byte_frames)          # _to_device(byte_frames=...): lq stays the decoder's uint8 frames
+        self.byte_metrics = bool(byte_metrics)        # ... and so does gt
         self.cuda = self.device.type == 'cuda'
         self.stream = torch.cuda.Stream(self.device) if self.cuda else None
         self.q = queue.Queue(maxsize=max(1, int(depth)))      # clips staged ahead of the consumer
@@ -68,12 +70,12 @@ class ClipPrefetcher:
                 if self.cuda:
                     data = {k: (v.pin_memory() if torch.is_tensor(v) else v) for k, v in data.items()}
                     with torch.cuda.stream(self.stream):
-                        dev = _to_device(data, self.device, self.byte_frames)
+                        dev = _to_device(data, self.device, self.byte_frames, self.byte_metrics)
                         ev = torch.cuda.Event()
                         ev.record(self.stream)
                     self.q.put((dev, ev, data))           # keep the pinned host copies alive until consumed
                 else:
-                    self.q.put((_to_device(data, self.device, self.byte_frames), None, None))
+                    self.q.put((_to_device(data, self.device, self.byte_frames, self.byte_metrics), None, None))
             self.q.put(None)
         except BaseException as e:                        # surface loader errors in the consumer
             self.q.put(e)
@@ -114,7 +116,7 @@ def _pairable(a, b):
 
 
 def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cuda', metrics=('PSNR', 'SSIM'), clips_in_flight=1,
-                   byte_frames=False):
+                   byte_frames=False, byte_metrics=False):
     """Returns, on every rank, the ordered per-clip results [{'eval_result': {...}}, ...].
 
     clips_in_flight = 2: two clips of equal shape are enhanced by ONE generator call (a batch of two), which the generator runs
@@ -127,7 +129,12 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
     byte_frames (default off: the loop above, unchanged): the frames stay uint8 from the decoder to the generator, which also writes
     the display bytes the PNG writer takes -- fp32 planes only when metrics are computed, uint8 frames only when images are saved,
     both when both -- and a pair goes to the generator as two clips by pointer (generator.forward_clips) instead of a concatenated
-    batch.  Same PSNR / SSIM and the same PNG bytes."""
+    batch.  Same PSNR / SSIM and the same PNG bytes.
+
+    byte_metrics (default off; implies byte_frames): the metrics read bytes as well -- `gt` stays the decoder's uint8 frames, the
+    generator is asked for uint8 frames only, with or without save_image, and PSNR / SSIM are computed from the two byte clips
+    (ops.psnr_frames / ssim_frames: 6 B per pixel and frame instead of 24, and no fp32 copy of either clip).  The same values: the
+    metrics round the fp32 planes to exactly these bytes."""
     import time
     model.eval()
     rank, world = get_dist_info()
@@ -139,9 +146,12 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
     # sr_backbone_utils.py:262-275; generator.py refuses n != 1): such a model keeps the clip-by-clip loop
     pairs = pairs and not getattr(model.generator, 'sparse_val', False)
 
-    byte_frames = bool(byte_frames) and dev.type == 'cuda' and hasattr(model, 'generator') and not getattr(model, 'psnr_only', False)
+    byte_frames = (bool(byte_frames) or bool(byte_metrics)) and dev.type == 'cuda' and hasattr(model, 'generator') and not getattr(model, 'psnr_only', False)
+    byte_metrics = bool(byte_metrics) and byte_frames
     out_dtype = None
-    if byte_frames:
+    if byte_metrics:
+        out_dtype = torch.uint8
+    elif byte_frames:
         test_cfg = getattr(model, 'test_cfg', None)
         want_f32 = bool(test_cfg is not None and test_cfg.get('metrics', None)) or not save_image
         out_dtype = 'both' if (want_f32 and save_image) else (torch.float32 if want_f32 else torch.uint8)
@@ -157,7 +167,7 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
         local.append([float(res['eval_result'].get(m, float('nan'))) for m in metrics] + [fps])
 
     held = None
-    for data in ClipPrefetcher(dataset, mine, device, depth=2 if pairs else 1, byte_frames=byte_frames):
+    for data in ClipPrefetcher(dataset, mine, device, depth=2 if pairs else 1, byte_frames=byte_frames, byte_metrics=byte_metrics):
         if not pairs:
             finish(data)
             continue

@@ -227,3 +227,375 @@ extern "C" int pnp_frames_from_rgb8(const unsigned char* in, float* out, int nfr
     if (nframes < 1 || h < 1 || w < 1 || !in || !out) return PNP_ERR_BAD_ARG;
     return launch_frames_from_rgb8(in, out, nframes, h, w, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// The same statistics behind a front end that does not care how a frame is stored -- (frames,3,h,w) fp32 planes, rounded by to_u8, or
+// (frames,h,w,3) uint8 RGB, the byte as it is, each input on its own -- with an optional luma step between the byte and the statistic
+// (test_cfg.convert_to = 'y': basicvsr.py:132-150 -> metrics.py:200-206, 338-346).  The metric of two byte clips reads 6 B per pixel.
+//
+// Luma: the reference's mmcv.bgr2ycbcr(img / 255., y_only=True) * 255. on the uint8 BGR image.  mmcv is not available to this build:
+// the arithmetic is restated from its published source (mmcv/image/colorspace.py: np.dot(img, [24.966, 128.553, 65.481]) + 16.0 in
+// float64, / 255., back to float32), as SSIM's cv2.filter2D is above.  With x_c = (float)byte_c / 255.0f (PnpU8Table):
+//     Y = (float)((((double)x_B * 24.966 + (double)x_G * 128.553) + (double)x_R * 65.481 + 16.0) / 255.0) * 255.0f
+// The 3 x 256 fp64 products are evaluated by the compiler (each rounded once, IEEE) and staged in LDS; what is left on the device is
+// three fp64 additions, an fp64 division, the rounding to fp32 and one fp32 multiply, compiled with contraction off.
+namespace {
+
+struct PnpLumaTable {
+    double v[3][256];       // [R, G, B of the RGB frames = channels 2, 1, 0 of the reference's BGR image][byte]
+    constexpr PnpLumaTable() : v() {
+        for (int i = 0; i < 256; ++i) {
+            const float x = (float)i / 255.0f;
+            v[0][i] = (double)x * 65.481;
+            v[1][i] = (double)x * 128.553;
+            v[2][i] = (double)x * 24.966;
+        }
+    }
+};
+__device__ const PnpLumaTable k_luma_table = PnpLumaTable();
+
+// lt: 768 doubles of LDS; blocks of 256 threads
+__device__ __forceinline__ void stage_luma_table(double* lt) {
+    const double* src = &k_luma_table.v[0][0];
+    for (int i = threadIdx.x; i < 768; i += 256) lt[i] = src[i];
+    __syncthreads();
+}
+
+// px = R | G << 8 | B << 16.  Contraction is off in here: the closing fp32 product must be rounded before a caller subtracts two of
+// these (d = Y_a - Y_b would otherwise become fma(y_a, 255, -Y_b), which is not what the reference subtracts).
+__device__ __forceinline__ float luma_of(const double* lt, unsigned px) {
+#pragma clang fp contract(off)
+    const double y64 = (((lt[512 + (px >> 16)] + lt[256 + ((px >> 8) & 255u)]) + lt[px & 255u]) + 16.0) / 255.0;
+    return (float)y64 * 255.0f;
+}
+
+__device__ __forceinline__ unsigned px_of_f32(float r, float g, float b) {
+    return (unsigned)to_u8(r) | ((unsigned)to_u8(g) << 8) | ((unsigned)to_u8(b) << 16);
+}
+
+// One input of a metric: the clip's first frame and, for a byte clip, the bytes [lo, hi) that may be read.
+struct FrameSrc {
+    const void* p;
+    const unsigned char *lo, *hi;
+    int fmt;
+};
+
+// px[j] = the packed bytes of pixels p0 + j (j < npix <= 4; px[j] = 0 beyond) of `frame`; hw = h * w.
+// A byte frame: the 12 bytes of four pixels sit at ANY address (frames and cropped rows start anywhere), so they are read as the
+// aligned dwords that cover them and shifted into place -- 3 loads, 4 when the address is not a multiple of 4 -- where those dwords lie
+// inside the clip; the groups where they do not (the first of a misaligned clip, the last) and the short group at the end of a row
+// are read byte by byte (the head / body / tail split of pack_lr_u8_any_kernel, decided per group).
+__device__ __forceinline__ void load_px4(const FrameSrc& s, long frame, long hw, long p0, int npix, unsigned px[4]) {
+    if (s.fmt == PNP_FRAMES_U8_HWC) {
+        const unsigned char* q = static_cast<const unsigned char*>(s.p) + (frame * hw + p0) * 3;
+        const unsigned sh = (unsigned)(reinterpret_cast<uintptr_t>(q) & 3);
+        const unsigned char* q0 = q - sh;
+        if (npix == 4 && q0 >= s.lo && q0 + (sh ? 16 : 12) <= s.hi) {
+            const unsigned* d = reinterpret_cast<const unsigned*>(q0);
+            unsigned d0 = d[0], d1 = d[1], d2 = d[2];
+            if (sh) {
+                const unsigned d3 = d[3];
+                d0 = __builtin_amdgcn_alignbyte(d1, d0, sh);      // ({hi, lo} >> 8 sh), low dword
+                d1 = __builtin_amdgcn_alignbyte(d2, d1, sh);
+                d2 = __builtin_amdgcn_alignbyte(d3, d2, sh);
+            }
+            // little-endian bytes: d0 = r0 g0 b0 r1, d1 = g1 b1 r2 g2, d2 = b2 r3 g3 b3
+            px[0] = d0 & 0xffffffu;
+            px[1] = (d0 >> 24) | ((d1 & 0xffffu) << 8);
+            px[2] = (d1 >> 16) | ((d2 & 0xffu) << 16);
+            px[3] = d2 >> 8;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                px[j] = 0;
+                if (j < npix) px[j] = (unsigned)q[3 * j] | ((unsigned)q[3 * j + 1] << 8) | ((unsigned)q[3 * j + 2] << 16);
+            }
+        }
+        return;
+    }
+    const float* f = static_cast<const float*>(s.p) + frame * 3 * hw + p0;
+    float v[3][4];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float* fc = f + c * hw;
+        if (npix == 4 && (reinterpret_cast<uintptr_t>(fc) & 15) == 0) {
+            const f32x4 t = *reinterpret_cast<const f32x4*>(fc);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[c][j] = t[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[c][j] = j < npix ? fc[j] : 0.f;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) px[j] = j < npix ? px_of_f32(v[0][j], v[1][j], v[2][j]) : 0u;
+}
+
+// The pixels of a frame inside the crop as `rows` runs of `roww` consecutive pixels (crop 0: ONE run of h*w), each cut into groups of
+// four: group g -> its first pixel and how many of the four exist.
+struct PixelRuns {
+    long hw, roww, gpr, groups;     // gpr: groups per run
+    int W, crop, rows;
+    __host__ PixelRuns(int h, int w, int c) : hw((long)h * w), W(w), crop(c) {
+        rows = c ? h - 2 * c : 1;
+        roww = c ? w - 2 * c : hw;
+        gpr = (roww + 3) / 4;
+        groups = gpr * rows;
+    }
+    __device__ __forceinline__ long first(long g, int& npix) const {
+        const long r = rows == 1 ? 0 : g / gpr, gx = g - r * gpr;
+        const long left = roww - 4 * gx;
+        npix = left < 4 ? (int)left : 4;
+        return (crop + r) * W + crop + 4 * gx;
+    }
+};
+
+struct PsnrIoArgs {
+    FrameSrc a, b;
+    PixelRuns runs;
+    unsigned long long* sse;    // !Y: (frames), zeroed by the launcher
+    double* partial;            //  Y: [frames][gridDim.x]
+};
+
+// !Y: the exact integer SSE of the three channels, one integer atomic per wave like psnr_sse_kernel.  Y: d = Y_a - Y_b in fp32 as the
+// reference subtracts, (double)d * d (exact: 48 bits) summed in fp64 in a fixed order -- a thread's groups in index order, the wave
+// by shuffles, the block's four waves through four doubles of LDS -- and ONE partial per block, which the host adds in index order.
+template <bool Y>
+__global__ __launch_bounds__(256) void psnr_io_kernel(const PsnrIoArgs s) {
+    __shared__ double lt[Y ? 768 : 1];
+    __shared__ double red[4];
+    if (Y) stage_luma_table(lt);
+    const long frame = blockIdx.y;
+    unsigned long long acc = 0;
+    double accd = 0;
+    for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < s.runs.groups; g += (long)gridDim.x * 256) {
+        int npix;
+        const long p0 = s.runs.first(g, npix);
+        unsigned pa[4], pb[4];
+        load_px4(s.a, frame, s.runs.hw, p0, npix, pa);
+        load_px4(s.b, frame, s.runs.hw, p0, npix, pb);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= npix) continue;
+            if (Y) {
+                const float d = luma_of(lt, pa[j]) - luma_of(lt, pb[j]);
+                accd += (double)d * (double)d;
+            } else {
+                unsigned e = 0;
+#pragma unroll
+                for (int k = 0; k < 24; k += 8) {
+                    const int d = (int)((pa[j] >> k) & 255u) - (int)((pb[j] >> k) & 255u);
+                    e += (unsigned)(d * d);
+                }
+                acc += e;
+            }
+        }
+    }
+    if (Y) {
+        for (int off = 32; off > 0; off >>= 1) accd += __shfl_down(accd, off, 64);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = accd;
+        __syncthreads();
+        if (threadIdx.x == 0) s.partial[frame * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    } else {
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+        if ((threadIdx.x & 63) == 0 && acc) atomicAdd(&s.sse[frame], acc);
+    }
+}
+
+// frames of either format -> (frames, h, w) fp32 Y; four pixels per thread, one 16-byte store where the address allows
+__global__ __launch_bounds__(256) void luma_kernel(const FrameSrc src, float* __restrict__ out, long hw, long groups) {
+    __shared__ double lt[768];
+    stage_luma_table(lt);
+    const long frame = blockIdx.y;
+    for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < groups; g += (long)gridDim.x * 256) {
+        const long p0 = 4 * g, left = hw - p0;
+        const int npix = left < 4 ? (int)left : 4;
+        unsigned px[4];
+        load_px4(src, frame, hw, p0, npix, px);
+        float* o = out + frame * hw + p0;
+        if (npix == 4 && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
+            const f32x4 y = {luma_of(lt, px[0]), luma_of(lt, px[1]), luma_of(lt, px[2]), luma_of(lt, px[3])};
+            *reinterpret_cast<f32x4*>(o) = y;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < npix) o[j] = luma_of(lt, px[j]);
+        }
+    }
+}
+
+// ssim_kernel with a loader in front: the value of (plane, y, x) comes from either format and, with Y, through the luma step (one
+// plane per frame, the window runs over the fp32 Y).  Tiling, LDS layout and both passes are ssim_kernel's, statement for statement,
+// so a byte frame gives the partials of its fp32 planes bit for bit.
+struct SsimIoArgs {
+    double g[11];
+    FrameSrc a, b;
+    double* partial;       // [planes][blocks_per_plane]
+    int H, W, crop, oh, ow, tiles_x, blocks_per_plane;
+};
+
+template <bool Y>
+__device__ __forceinline__ float ssim_value(const FrameSrc& s, long frame, int ch, long hw, long pix, const double* lt) {
+    if (s.fmt == PNP_FRAMES_U8_HWC) {
+        const unsigned char* q = static_cast<const unsigned char*>(s.p) + (frame * hw + pix) * 3;
+        if (!Y) return (float)q[ch];
+        return luma_of(lt, (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16));
+    }
+    const float* f = static_cast<const float*>(s.p) + frame * 3 * hw + pix;
+    if (!Y) return (float)to_u8(f[ch * hw]);
+    return luma_of(lt, px_of_f32(f[0], f[hw], f[2 * hw]));
+}
+
+template <bool Y>
+__global__ __launch_bounds__(256) void ssim_io_kernel(const SsimIoArgs s) {
+    __shared__ float ta[26 * 42], tb[26 * 42];
+    __shared__ double hm[5][26 * 32];
+    __shared__ double red[4];
+    __shared__ double lt[Y ? 768 : 1];
+    if (Y) stage_luma_table(lt);
+    const int plane = blockIdx.y, blk = blockIdx.x, t = threadIdx.x;
+    const int ty0 = (blk / s.tiles_x) * 16, tx0 = (blk % s.tiles_x) * 32;        // in valid-map coordinates
+    const long frame = Y ? plane : plane / 3, hw = (long)s.H * s.W;
+    const int ch = Y ? 0 : plane % 3;
+    for (int i = t; i < 26 * 42; i += 256) {
+        const int r = i / 42, c = i - r * 42;
+        const int y = s.crop + ty0 + r, x = s.crop + tx0 + c;
+        float va = 0.f, vb = 0.f;
+        if (y < s.H - s.crop && x < s.W - s.crop) {
+            va = ssim_value<Y>(s.a, frame, ch, hw, (long)y * s.W + x, lt);
+            vb = ssim_value<Y>(s.b, frame, ch, hw, (long)y * s.W + x, lt);
+        }
+        ta[i] = va;
+        tb[i] = vb;
+    }
+    __syncthreads();
+    for (int i = t; i < 26 * 32; i += 256) {
+        const int r = i >> 5, c = i & 31;
+        double m1 = 0, m2 = 0, s11 = 0, s22 = 0, s12 = 0;
+#pragma unroll
+        for (int k = 0; k < 11; ++k) {
+            const double x = ta[r * 42 + c + k], y = tb[r * 42 + c + k], gk = s.g[k];
+            m1 += gk * x;
+            m2 += gk * y;
+            s11 += gk * x * x;
+            s22 += gk * y * y;
+            s12 += gk * x * y;
+        }
+        hm[0][i] = m1;
+        hm[1][i] = m2;
+        hm[2][i] = s11;
+        hm[3][i] = s22;
+        hm[4][i] = s12;
+    }
+    __syncthreads();
+    const double C1 = (0.01 * 255) * (0.01 * 255), C2 = (0.03 * 255) * (0.03 * 255);
+    double acc = 0;
+    for (int i = t; i < 16 * 32; i += 256) {
+        const int r = i >> 5, c = i & 31;
+        if (ty0 + r >= s.oh || tx0 + c >= s.ow) continue;
+        double v[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < 11; ++k)
+#pragma unroll
+            for (int q = 0; q < 5; ++q) v[q] += s.g[k] * hm[q][(r + k) * 32 + c];
+        const double mu1 = v[0], mu2 = v[1];
+        const double sg1 = v[2] - mu1 * mu1, sg2 = v[3] - mu2 * mu2, sg12 = v[4] - mu1 * mu2;
+        acc += ((2 * mu1 * mu2 + C1) * (2 * sg12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (sg1 + sg2 + C2));
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((t & 63) == 0) red[t >> 6] = acc;
+    __syncthreads();
+    if (t == 0) s.partial[(long)plane * s.blocks_per_plane + blk] = red[0] + red[1] + red[2] + red[3];
+}
+
+bool known_format(int f) { return f == PNP_FRAMES_F32_NCHW || f == PNP_FRAMES_U8_HWC; }
+
+FrameSrc frame_src(const void* p, int fmt, int frames, int h, int w) {
+    FrameSrc s;
+    s.p = p;
+    s.fmt = fmt;
+    s.lo = static_cast<const unsigned char*>(p);
+    s.hi = s.lo + (fmt == PNP_FRAMES_U8_HWC ? (long)frames * h * w * 3 : 0);
+    return s;
+}
+
+// what every io entry refuses before it looks at its statistic
+bool io_args_ok(const void* a, int fa, const void* b, int fb, int color, const void* out, int frames, int c, int h, int w, int crop) {
+    if (!a || !b || !out || !known_format(fa) || !known_format(fb) || (color != PNP_COLOR_NONE && color != PNP_COLOR_Y)) return false;
+    if (frames < 1 || c < 1 || h < 1 || w < 1 || crop < 0 || 2 * crop >= h || 2 * crop >= w) return false;
+    const bool planes_only = fa == PNP_FRAMES_F32_NCHW && fb == PNP_FRAMES_F32_NCHW && color == PNP_COLOR_NONE;
+    return c == 3 || planes_only;
+}
+
+// blocks per frame of the pixel-group kernels: about four groups (16 pixels) a thread, so that staging the table is paid seldom
+int pixel_group_blocks(long groups) {
+    long bx = (groups + 1023) / 1024;
+    return (int)(bx < 1 ? 1 : (bx > 512 ? 512 : bx));
+}
+
+}  // namespace
+
+extern "C" int pnp_psnr_luma_blocks(int h, int w, int crop_border) {
+    if (h < 1 || w < 1 || crop_border < 0 || 2 * crop_border >= h || 2 * crop_border >= w) return 0;
+    return pixel_group_blocks(PixelRuns(h, w, crop_border).groups);
+}
+
+extern "C" int pnp_psnr_stat_io(const void* a, int a_format, const void* b, int b_format, int color, void* stat, int frames, int c,
+                                int h, int w, int crop_border, void* stream) {
+    if (!io_args_ok(a, a_format, b, b_format, color, stat, frames, c, h, w, crop_border)) return PNP_ERR_BAD_ARG;
+    if (a_format == PNP_FRAMES_F32_NCHW && b_format == PNP_FRAMES_F32_NCHW && color == PNP_COLOR_NONE)
+        return pnp_psnr_sse_f32(static_cast<const float*>(a), static_cast<const float*>(b), static_cast<unsigned long long*>(stat), frames, c,
+                                h, w, crop_border, stream);
+    hipStream_t st = (hipStream_t)stream;
+    PsnrIoArgs s = {frame_src(a, a_format, frames, h, w), frame_src(b, b_format, frames, h, w), PixelRuns(h, w, crop_border), nullptr, nullptr};
+    const int bx = pixel_group_blocks(s.runs.groups);
+    if (color == PNP_COLOR_Y) {
+        s.partial = static_cast<double*>(stat);
+        hipLaunchKernelGGL((psnr_io_kernel<true>), dim3(bx, frames), dim3(256), 0, st, s);
+    } else {
+        s.sse = static_cast<unsigned long long*>(stat);
+        const int ze = launch_zero_words(s.sse, 2L * frames, st);
+        if (ze != PNP_OK) return ze;
+        hipLaunchKernelGGL((psnr_io_kernel<false>), dim3(bx, frames), dim3(256), 0, st, s);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int pnp_ssim_partials_io(const void* a, int a_format, const void* b, int b_format, int color, double* partials, int frames,
+                                    int c, int h, int w, int crop_border, void* stream) {
+    if (!io_args_ok(a, a_format, b, b_format, color, partials, frames, c, h, w, crop_border)) return PNP_ERR_BAD_ARG;
+    const int nb = pnp_ssim_blocks(h, w, crop_border);
+    if (nb < 1) return PNP_ERR_BAD_ARG;
+    if (a_format == PNP_FRAMES_F32_NCHW && b_format == PNP_FRAMES_F32_NCHW && color == PNP_COLOR_NONE)
+        return pnp_ssim_partials_f32(static_cast<const float*>(a), static_cast<const float*>(b), partials, frames, c, h, w, crop_border, stream);
+    SsimIoArgs s;
+    double sum = 0;
+    for (int i = 0; i < 11; ++i) {                       // cv2.getGaussianKernel(11, 1.5)
+        s.g[i] = exp(-((i - 5.0) * (i - 5.0)) / (2 * 1.5 * 1.5));
+        sum += s.g[i];
+    }
+    for (int i = 0; i < 11; ++i) s.g[i] /= sum;
+    s.a = frame_src(a, a_format, frames, h, w);
+    s.b = frame_src(b, b_format, frames, h, w);
+    s.partial = partials;
+    s.H = h;
+    s.W = w;
+    s.crop = crop_border;
+    s.oh = h - 2 * crop_border - 10;
+    s.ow = w - 2 * crop_border - 10;
+    s.tiles_x = (s.ow + 31) / 32;
+    s.blocks_per_plane = nb;
+    if (color == PNP_COLOR_Y)
+        hipLaunchKernelGGL((ssim_io_kernel<true>), dim3(nb, frames), dim3(256), 0, (hipStream_t)stream, s);
+    else
+        hipLaunchKernelGGL((ssim_io_kernel<false>), dim3(nb, frames * 3), dim3(256), 0, (hipStream_t)stream, s);
+    return (int)hipGetLastError();
+}
+
+extern "C" int pnp_luma_from_frames(const void* frames_dev, int format, float* out, int nframes, int h, int w, void* stream) {
+    if (!frames_dev || !out || !known_format(format) || nframes < 1 || h < 1 || w < 1) return PNP_ERR_BAD_ARG;
+    const long hw = (long)h * w, groups = (hw + 3) / 4;
+    hipLaunchKernelGGL(luma_kernel, dim3(pixel_group_blocks(groups), nframes), dim3(256), 0, (hipStream_t)stream,
+                       frame_src(frames_dev, format, nframes, h, w), out, hw, groups);
+    return (int)hipGetLastError();
+}

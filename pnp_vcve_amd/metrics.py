@@ -11,6 +11,11 @@ Reference quirk kept: with crop_border != 0 the reference slices `img[cb:-cb, cb
 (metrics.py:343-345), which turns an HWC image into (H', W', 1, 3); its channel loop then runs once
 over `img[..., 0]`, i.e. SSIM is computed on channel 0 (B of the BGR image) only.  PSNR is a mean over
 all elements and is unaffected.  The shipped configs use crop_border=0.
+
+convert_to='y' (metrics.py:200-203, 338-343): `mmcv.bgr2ycbcr(img / 255., y_only=True) * 255.` on the float32 BGR image.  mmcv is
+not available here; its arithmetic is restated from its published source (mmcv/image/colorspace.py: bgr2ycbcr with y_only and
+_convert_input_type_range / _convert_output_type_range for a float32 image) in `bgr2y`; parity with an installed mmcv is unpinned,
+like cv2's above.
 """
 import numpy as np
 import torch
@@ -33,13 +38,32 @@ def tensor2img(tensor, out_type=np.uint8, min_max=(0, 1)):
     return img.astype(out_type)
 
 
+BGR2Y = [24.966, 128.553, 65.481]       # mmcv's bgr2ycbcr(y_only=True): 219 * (0.114, 0.587, 0.299), the BT.601 luma of B, G, R
+
+
+def bgr2y(img):
+    """mmcv.bgr2ycbcr(img, y_only=True) for a float32 (H,W,3) BGR image in [0,1] -> float32 (H,W) Y in [16/255, 235/255]: the dot
+    product and the offset in float64 (np.dot with a list of Python floats), / 255., back to the input's float32."""
+    out_img = np.dot(img, BGR2Y) + 16.0
+    out_img /= 255.
+    return out_img.astype(np.float32)
+
+
+def _is_y(convert_to, quote_end):
+    if isinstance(convert_to, str) and convert_to.lower() == 'y':
+        return True
+    if convert_to is not None:
+        raise ValueError('Wrong color model. Supported values are "Y" and None' + quote_end)
+    return False
+
+
 def psnr(img1, img2, crop_border=0, input_order='HWC', convert_to=None):
     assert img1.shape == img2.shape, f'Image shapes are different: {img1.shape}, {img2.shape}.'
-    if convert_to is not None:
-        raise NotImplementedError('convert_to is not used by the shipped configs')
     if input_order == 'CHW':
         img1, img2 = img1.transpose(1, 2, 0), img2.transpose(1, 2, 0)
     a, b = img1.astype(np.float32), img2.astype(np.float32)
+    if _is_y(convert_to, '.'):                   # metrics.py:201-206
+        a, b = bgr2y(a / 255.) * 255., bgr2y(b / 255.) * 255.
     if crop_border != 0:
         a = a[crop_border:-crop_border, crop_border:-crop_border, None]
         b = b[crop_border:-crop_border, crop_border:-crop_border, None]
@@ -77,10 +101,11 @@ def _ssim_channel(a, b):
 
 def ssim(img1, img2, crop_border=0, input_order='HWC', convert_to=None):
     assert img1.shape == img2.shape, f'Image shapes are different: {img1.shape}, {img2.shape}.'
-    if convert_to is not None:
-        raise NotImplementedError('convert_to is not used by the shipped configs')
     if input_order == 'CHW':
         img1, img2 = img1.transpose(1, 2, 0), img2.transpose(1, 2, 0)
+    if _is_y(convert_to, ''):                    # metrics.py:338-346: one channel, the float32 Y
+        img1, img2 = img1.astype(np.float32), img2.astype(np.float32)
+        img1, img2 = bgr2y(img1 / 255.) * 255., bgr2y(img2 / 255.) * 255.
     if img1.ndim == 2:
         img1, img2 = img1[..., None], img2[..., None]
     if crop_border != 0:       # metrics.py:343-350: the `None` index leaves only channel 0 in the loop (see module docstring)

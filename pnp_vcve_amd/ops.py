@@ -1,8 +1,8 @@
 """Tensor-level wrappers over the C ABI (device pointers + the current HIP stream).
 
 PyTorch is plumbing here: it owns device memory and the stream; every computation
-runs in libpnpvcve_hip.so.  All functions require CUDA(HIP) fp32 contiguous tensors and
-raise otherwise -- there is deliberately no CPU path.
+runs in libpnpvcve_hip.so.  All functions require CUDA(HIP) fp32 contiguous tensors (the frame converters and the metrics also take
+uint8 frames) and raise otherwise -- there is deliberately no CPU path.
 """
 import contextlib
 import ctypes
@@ -467,23 +467,85 @@ def frames_from_rgb8(u8):
     return out
 
 
-@_on_device_of_first_tensor
-def psnr_frames(a, b, crop_border=0):
-    """Per-frame PSNR with the reference's definition (uint8-rounded frames), computed on the GPU.
-    a, b: (..., c, h, w) with any leading dims; returns a float64 CPU tensor of the leading shape."""
-    a, b = _chk(a, 'a'), _chk(b, 'b')
-    if a.shape != b.shape:
+def _metric_frames(t, name):
+    """One input of a device metric: fp32 (...,c,h,w) planes or uint8 (...,h,w,3) RGB bytes -> (contiguous tensor, PNP_FRAMES_*
+    format, leading shape, c, h, w)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f'{name} must be a CUDA/HIP tensor: the PnP-VCVE hot path has no CPU fallback')
+    if t.dtype == torch.uint8:
+        if t.dim() < 3 or t.shape[-1] != 3:
+            raise ValueError(f'{name}: uint8 frames must be (...,h,w,3) RGB')
+        h, w = t.shape[-3:-1]
+        return t.contiguous(), _native.FRAMES_U8_HWC, tuple(t.shape[:-3]), 3, int(h), int(w)
+    if t.dtype != torch.float32:
+        raise TypeError(f'{name} must be float32 planes or uint8 RGB frames, got {t.dtype}')
+    if t.dim() < 3:
+        raise ValueError(f'{name}: fp32 frames must be (...,c,h,w)')
+    c, h, w = t.shape[-3:]
+    return t.contiguous(), _native.FRAMES_F32_NCHW, tuple(t.shape[:-3]), int(c), int(h), int(w)
+
+
+def _metric_pair(a, b, convert_to):
+    """-> (a, a_format, b, b_format, PNP_COLOR_*, leading shape, frames, c, h, w) of two clips that show the same frames"""
+    if isinstance(convert_to, str) and convert_to.lower() == 'y':
+        color = _native.COLOR_Y
+    elif convert_to is None:
+        color = _native.COLOR_NONE
+    else:
+        raise ValueError('Wrong color model. Supported values are "Y" and None.')
+    a, fa, lead_a, ca, ha, wa = _metric_frames(a, 'a')
+    b, fb, lead_b, cb, hb, wb = _metric_frames(b, 'b')
+    if (lead_a, ca, ha, wa) != (lead_b, cb, hb, wb):
         raise AssertionError(f'Image shapes are different: {tuple(a.shape)}, {tuple(b.shape)}.')
-    c, h, w = a.shape[-3:]
-    frames = a.numel() // (c * h * w)
-    sse = torch.empty(frames, dtype=torch.int64, device=a.device)
-    _native.check(_native.lib().pnp_psnr_sse_f32(_ptr(a), _ptr(b), _ptr(sse), frames, c, h, w, int(crop_border),
-                                                 _stream()), 'pnp_psnr_sse_f32')
-    n = c * (h - 2 * crop_border) * (w - 2 * crop_border)
-    mse = sse.cpu().double() / n
+    if a.device != b.device:
+        raise RuntimeError('a and b must be on the same device')
+    frames = 1
+    for d in lead_a:
+        frames *= d
+    return a, fa, b, fb, color, lead_a, frames, ca, ha, wa
+
+
+@_on_device_of_first_tensor
+def luma_frames(x):
+    """fp32 (...,3,h,w) planes (rounded to bytes as tensor2img does) or uint8 (...,h,w,3) RGB frames -> fp32 (...,h,w) CUDA tensor of
+    the reference's Y, mmcv.bgr2ycbcr(img / 255., y_only=True) * 255. of the uint8 BGR image, bit for bit (pnp_luma_from_frames)."""
+    x, fmt, lead, c, h, w = _metric_frames(x, 'x')
+    if c != 3:
+        raise ValueError('x must have 3 channels')
+    frames = 1
+    for d in lead:
+        frames *= d
+    out = torch.empty(lead + (h, w), device=x.device, dtype=torch.float32)
+    if frames:
+        _native.check(_native.lib().pnp_luma_from_frames(_ptr(x), fmt, _ptr(out), frames, h, w, _stream()), 'pnp_luma_from_frames')
+    return out
+
+
+@_on_device_of_first_tensor
+def psnr_frames(a, b, crop_border=0, convert_to=None):
+    """Per-frame PSNR with the reference's definition (uint8-rounded frames), computed on the GPU.
+    a, b, each on its own: fp32 (..., c, h, w) planes or uint8 (..., h, w, 3) RGB frames, any leading dims; convert_to None | 'y' / 'Y'
+    (the Y of the BGR image, metrics.py:201-203).  Returns a float64 CPU tensor of the leading shape."""
+    a, fa, b, fb, color, lead, frames, c, h, w = _metric_pair(a, b, convert_to)
+    crop_border = int(crop_border)
+    L = _native.lib()
+    if color == _native.COLOR_Y:
+        nb = int(L.pnp_psnr_luma_blocks(h, w, crop_border))
+        stat = torch.empty((frames, max(nb, 1)), dtype=torch.float64, device=a.device)
+    else:
+        stat = torch.empty(frames, dtype=torch.int64, device=a.device)
+    _native.check(L.pnp_psnr_stat_io(_ptr(a), fa, _ptr(b), fb, color, _ptr(stat), frames, c, h, w, crop_border, _stream()),
+                  'pnp_psnr_stat_io')
+    if color == _native.COLOR_Y:
+        n = (h - 2 * crop_border) * (w - 2 * crop_border)
+        sse = torch.from_numpy(stat.cpu().numpy().cumsum(axis=1)[:, -1].copy())      # a frame's partials added in index order
+    else:
+        n = c * (h - 2 * crop_border) * (w - 2 * crop_border)
+        sse = stat.cpu().double()
+    mse = sse / n
     out = 20.0 * torch.log10(255.0 / mse.sqrt())
     out[mse == 0] = float('inf')
-    return out.reshape(a.shape[:-3])
+    return out.reshape(lead)
 
 
 @_on_device_of_first_tensor
@@ -538,28 +600,27 @@ def modulated_deform_conv_nhwc(x, offset, mask_logits, weight, bias, flow=None, 
 
 
 @_on_device_of_first_tensor
-def ssim_frames(a, b, crop_border=0):
+def ssim_frames(a, b, crop_border=0, convert_to=None):
     """Per-frame SSIM with the reference's definition (metrics.py:266-355), computed on the GPU in fp64.
-    a, b: (..., c, h, w); returns a float64 CPU tensor of the leading shape."""
-    a, b = _chk(a, 'a'), _chk(b, 'b')
-    if a.shape != b.shape:
-        raise AssertionError(f'Image shapes are different: {tuple(a.shape)}, {tuple(b.shape)}.')
-    c, h, w = a.shape[-3:]
-    frames = a.numel() // (c * h * w)
+    a, b, each on its own: fp32 (..., c, h, w) planes or uint8 (..., h, w, 3) RGB frames; convert_to None | 'y' / 'Y' (one channel, the
+    fp32 Y of the BGR image, metrics.py:338-343).  Returns a float64 CPU tensor of the leading shape."""
+    a, fa, b, fb, color, lead, frames, c, h, w = _metric_pair(a, b, convert_to)
+    crop_border = int(crop_border)
     L = _native.lib()
-    nb = int(L.pnp_ssim_blocks(h, w, int(crop_border)))
+    nb = int(L.pnp_ssim_blocks(h, w, crop_border))
     if nb < 1:
         raise ValueError('frames are smaller than the 11x11 SSIM window')
-    part = torch.empty((frames * c, nb), dtype=torch.float64, device=a.device)
-    _native.check(L.pnp_ssim_partials_f32(_ptr(a), _ptr(b), _ptr(part), frames, c, h, w, int(crop_border), _stream()),
-                  'pnp_ssim_partials_f32')
+    planes = 1 if color == _native.COLOR_Y else c
+    part = torch.empty((frames * planes, nb), dtype=torch.float64, device=a.device)
+    _native.check(L.pnp_ssim_partials_io(_ptr(a), fa, _ptr(b), fb, color, _ptr(part), frames, c, h, w, crop_border, _stream()),
+                  'pnp_ssim_partials_io')
     n = (h - 2 * crop_border - 10) * (w - 2 * crop_border - 10)
-    per_plane = (part.sum(dim=1) / n).reshape(frames, c)
-    if crop_border != 0 and c == 3:
+    per_plane = (part.sum(dim=1) / n).reshape(frames, planes)
+    if crop_border != 0 and planes == 3:
         # reference quirk (metrics.py:343-350, see pnp_vcve_amd/metrics.py): with a crop only channel 0 of the BGR image,
         # i.e. the B plane of these RGB frames, enters the SSIM mean
         per_plane = per_plane[:, 2:3]
-    return per_plane.mean(dim=1).cpu().reshape(a.shape[:-3])
+    return per_plane.mean(dim=1).cpu().reshape(lead)
 
 
 @_on_device_of_first_tensor

@@ -101,16 +101,26 @@ class BasicVSR(nn.Module):
             # the reference evaluates with samples_per_gpu=1 (configs/*: test_dataloader); with n > 1 its tensor2img
             # would compare make_grid mosaics of the batch.  Refuse loudly instead of scoring sample 0 only.
             raise ValueError(f'evaluate() expects one clip per call (samples_per_gpu=1), got a batch of {output.size(0)}')
+        # byte clips (1,t,h,w,3) uint8 count as 5-D clips; the device path serves convert_to None and 'y' / 'Y' and reads either
+        # layout as it is (ops.psnr_frames / ssim_frames): two byte clips cost 6 B per pixel, no fp32 copy of either
+        on_device = output.is_cuda and output.ndim == 5 and (convert_to is None or (isinstance(convert_to, str) and convert_to.lower() == 'y'))
+        if (output.dtype == torch.uint8 or gt.dtype == torch.uint8) and not on_device:
+            raise ValueError('uint8 frames are evaluated on the device: a (1,t,h,w,3) clip on the GPU and convert_to None or "Y"')
+
+        def frames_of(x):      # one clip without its batch dimension, on the output's device, in a dtype the kernels read
+            x = x[0].to(output.device)
+            return x if x.dtype == torch.uint8 else x.float()
+
         for metric in self.test_cfg['metrics']:
-            if metric == 'PSNR' and convert_to is None and output.is_cuda and output.ndim == 5:
-                # on-device statistic (pnp_psnr_sse_f32): 8 bytes per frame cross PCIe instead of the frames
+            if metric == 'PSNR' and on_device:
+                # on-device statistic (pnp_psnr_stat_io): 8 bytes per frame (or per block, for Y) cross PCIe instead of the frames
                 from .ops import psnr_frames
-                per_frame = psnr_frames(output[0].float(), gt[0].float().to(output.device), crop_border)
+                per_frame = psnr_frames(frames_of(output), frames_of(gt), crop_border, convert_to)
                 eval_result[metric] = float(per_frame.mean())
                 continue
-            if metric == 'SSIM' and convert_to is None and output.is_cuda and output.ndim == 5:
-                from .ops import ssim_frames           # pnp_ssim_partials_f32 (fp64 on the GPU)
-                per_frame = ssim_frames(output[0].float(), gt[0].float().to(output.device), crop_border)
+            if metric == 'SSIM' and on_device:
+                from .ops import ssim_frames           # pnp_ssim_partials_io (fp64 on the GPU)
+                per_frame = ssim_frames(frames_of(output), frames_of(gt), crop_border, convert_to)
                 eval_result[metric] = float(per_frame.mean())
                 continue
             if output.ndim == 5:
@@ -130,8 +140,9 @@ class BasicVSR(nn.Module):
         already run the generator -- apis.multi_gpu_test does so for two clips at a time, which the generator interleaves on two
         streams; evaluation and saving then proceed clip by clip exactly as below.
         Byte frames (not in the reference): `lq` may be the decoder's uint8 (n,t,h,w,3) frames, and `out_dtype` (generator.forward's)
-        asks the generator for the display bytes as well as / instead of the fp32 planes: metrics read the fp32 planes, the PNG
-        writer takes the bytes as they are."""
+        asks the generator for the display bytes as well as / instead of the fp32 planes: the PNG writer takes the bytes as they
+        are, and so do the metrics when the bytes are all there is (`gt` may then be a uint8 (n,t,h,w,3) clip too); only the
+        centre-frame case (a 4-D `gt`) still needs the fp32 planes."""
         if precomputed_output is not None:
             output = precomputed_output
         elif not self.psnr_only:
@@ -149,8 +160,8 @@ class BasicVSR(nn.Module):
             output, output_u8 = output
         elif output.dtype == torch.uint8 and not self.psnr_only:
             output_u8 = output
-            if (gt is not None and gt.ndim == 4) or (self.test_cfg is not None and self.test_cfg.get('metrics', None)):
-                raise ValueError("metrics and the centre-frame output read the fp32 planes: ask for out_dtype='both' or torch.float32")
+            if gt is not None and gt.ndim == 4:
+                raise ValueError("the centre-frame output reads the fp32 planes: ask for out_dtype='both' or torch.float32")
         if gt is not None and gt.ndim == 4:
             t = output.size(1)
             if self.check_if_mirror_extended(lq):

@@ -2,7 +2,8 @@
 """The end-to-end loop of bench.py (pipeline_e2e) by itself, a few repetitions: where does the forward inside the loop lose against the
 same two-clip forward in the bench?   [GPU_MAX_HW_QUEUES=8] python tools/e2e_probe.py [--reps 3]
 --byte-frames: the same tree, model and warm-up through apis.multi_gpu_test(byte_frames=True) -- what `tools/test.py --byte-frames`
-runs: uint8 frames into the generator, display bytes out of it, a pair of clips by pointer; --loop: that loop with the switch off."""
+runs: uint8 frames into the generator, display bytes out of it, a pair of clips by pointer; --loop: that loop with the switch off;
+--byte-metrics: that loop with byte_metrics=True (`tools/test.py --byte-metrics`: uint8 output only, PSNR / SSIM from the two byte clips)."""
 import argparse
 import os
 import sys
@@ -17,6 +18,7 @@ ap.add_argument('--reps', type=int, default=3)
 ap.add_argument('--workers', type=int, default=16)
 ap.add_argument('--prewarm', action='store_true', help='fill the caching allocators (device + pinned host) before the first pass')
 ap.add_argument('--byte-frames', action='store_true', help='the tools/test.py loop with --byte-frames (apis.multi_gpu_test)')
+ap.add_argument('--byte-metrics', action='store_true', help='the tools/test.py loop with --byte-metrics (apis.multi_gpu_test)')
 ap.add_argument('--loop', action='store_true', help='the tools/test.py loop (apis.multi_gpu_test) with byte frames off: the same harness as --byte-frames')
 args = ap.parse_args()
 dev = torch.device('cuda:0')
@@ -28,7 +30,7 @@ if args.prewarm:
     del x, y
 
 
-def loop_e2e(dev, T, byte_frames, clips=10, workers=16):
+def loop_e2e(dev, T, byte_frames, clips=10, workers=16, byte_metrics=False):
     """bench.pipeline_e2e's tree, model, warm-up clip and timed window (loader start to the last PNG on disk) around apis.multi_gpu_test"""
     import shutil
     import tempfile
@@ -67,12 +69,13 @@ def loop_e2e(dev, T, byte_frames, clips=10, workers=16):
         out_dir = os.path.join(root, 'out')
         with FrameWriter(max_workers=workers) as writer:
             model.frame_writer = writer
-            multi_gpu_test(model, Tail(ds, 0, 1), save_image=True, save_path=out_dir, device=dev, clips_in_flight=2, byte_frames=byte_frames)
+            multi_gpu_test(model, Tail(ds, 0, 1), save_image=True, save_path=out_dir, device=dev, clips_in_flight=2, byte_frames=byte_frames,
+                           byte_metrics=byte_metrics)
             torch.cuda.synchronize()
             writer.drain()
             t0 = time.perf_counter()
             res = multi_gpu_test(model, Tail(ds, 1, clips), save_image=True, save_path=out_dir, device=dev, clips_in_flight=2,
-                                 byte_frames=byte_frames)
+                                 byte_frames=byte_frames, byte_metrics=byte_metrics)
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             writer.drain()
@@ -86,10 +89,10 @@ def loop_e2e(dev, T, byte_frames, clips=10, workers=16):
 
 
 for r in range(args.reps):
-    if args.byte_frames or args.loop:
-        e = loop_e2e(dev, 7, args.byte_frames, workers=args.workers)
+    if args.byte_frames or args.byte_metrics or args.loop:
+        e = loop_e2e(dev, 7, args.byte_frames, workers=args.workers, byte_metrics=args.byte_metrics)
         print('rep %d [%s]: %.1f frames/s  total %.3f s  forward %.3f s (%.1f frames/s inside the forward)  drain %.3f  PSNR %.6f'
-              % (r, 'byte frames' if args.byte_frames else 'loop', e['value'], e['seconds_total'], e['seconds_generator_forward'],
+              % (r, 'byte metrics' if args.byte_metrics else ('byte frames' if args.byte_frames else 'loop'), e['value'], e['seconds_total'], e['seconds_generator_forward'],
                  e['frames'] / e['seconds_generator_forward'], e['seconds_png_drain_after_last_clip'], e['psnr']), flush=True)
         continue
     e = bench.pipeline_e2e(dev, 7, workers=args.workers)

@@ -48,6 +48,10 @@ def parse_args():
                    help='keep the frames uint8 from the decoder into the generator and take its output as display bytes for the PNGs '
                         '(fp32 planes only for the metrics); a pair of clips goes in by pointer instead of concatenated.  Same '
                         'metrics and PNG bytes; default off')
+    p.add_argument('--byte-metrics', action='store_true',
+                   help='implies --byte-frames; PSNR / SSIM read bytes too: the ground truth stays uint8 on the device and the generator '
+                        'writes display bytes only, with or without --save-path (6 B per pixel into the metrics instead of 24).  Same '
+                        'metrics; default off')
     p.add_argument('--any-size', action='store_true',
                    help='run frames whose height or width is no multiple of 4 (generator.any_size; the same as --cfg-options '
                         'model.generator.any_size=True): the same formulas on the frame as given, no padding.  Default off: such '
@@ -106,7 +110,7 @@ def main():
     try:
         outputs = multi_gpu_test(model, dataset, save_image=args.save_path is not None, save_path=args.save_path,
                                  device=dev, metrics=tuple(cfg.test_cfg['metrics']), clips_in_flight=args.clips_in_flight,
-                                 byte_frames=args.byte_frames)
+                                 byte_frames=args.byte_frames or args.byte_metrics, byte_metrics=args.byte_metrics)
     finally:
         if getattr(model, 'frame_writer', None) is not None:
             model.frame_writer.close()
