@@ -214,6 +214,64 @@ int pnp_generator_forward_clips(const pnp_generator* g, const float* flat_dev, c
                                 void* workspace_dev, int64_t workspace_bytes, int t, int h, int w, void* stream);
 int64_t pnp_generator_workspace_bytes_io(const pnp_generator* g, int t, int h, int w, int lq_format, int out_mask);
 
+/* Y'CbCr 4:2:0 boundary: the same forward on the planes a decoder writes (NV12 / NV21 / I420, 8 bit) and, on
+ * request, writing planes an encoder or a display takes -- 1.5 B per pixel and frame each way, no RGB bytes and no fp32 copy of a clip
+ * in between, ONE rounding (on the way out).  The reference has no such path (its loaders read PNGs): the mode is pinned to the
+ * arithmetic below, which tests/yuv_ref.py restates in numpy.  This is the ONE statement of it.
+ *   Standards: Kr, Kb = 0.299, 0.114 (BT.601) | 0.2126, 0.0722 (BT.709), Kg = 1 - Kr - Kb; limited range sy = 219, sc = 224,
+ *   yoff = 16; full range sy = sc = 255, yoff = 0.  Every constant named below is evaluated in double from Kr and Kb and rounded to
+ *   fp32 ONCE; every product and sum after that is an fp32 operation rounded on its own (no fused multiply-add).
+ *   Bytes -> RGB (fp32, not rounded to 8 bits): y = cy * float(Y - yoff), u = float(Cb - 128), v = float(Cr - 128) with cy = 1 / sy,
+ *   crv = 2 (1 - Kr) / sc, cbu = 2 (1 - Kb) / sc, cgu = 2 Kb (1 - Kb) / (Kg sc), cgv = 2 Kr (1 - Kr) / (Kg sc);
+ *       R = y + crv * v,   G = (y - cgu * u) - cgv * v,   B = y + cbu * u,   each then min(max(x, 0), 1).
+ *   Chroma is REPLICATED: pixel (yy, xx) reads the chroma sample (yy >> 1, xx >> 1).
+ *   RGB -> bytes: r, g, b clamped to [0, 1]; yl = (Kr * r + Kg * g) + Kb * b; Y = clamp(rint(float(yoff) + sy * yl), 0, 255), rint
+ *   rounding half to even; per pixel pb = (b - yl) * (0.5 / (1 - Kb)), pr = (r - yl) * (0.5 / (1 - Kr)); the chroma sample of a 2x2
+ *   block is the BOX MEAN ((p00 + p01) + (p10 + p11)) * 0.25 (rows top then bottom, columns left then right) and
+ *   Cb = clamp(rint(128 + sc * mean_pb), 0, 255), Cr likewise.  Box-down and replicate-up are consistent (centre siting); other
+ *   sitings and filters, 10 bit, 4:2:2 and 4:4:4 are not offered.  Limited-range white (235,128,128) gives 0.99999994, not 1.
+ * A plane pointer may sit at ANY byte address and a pitch may be any value that holds a row, odd ones too.  No byte outside
+ * [plane, plane + rows * pitch) of a plane is read or written, and inside it the bytes of a row beyond the frame's width are never
+ * written.  Planes and pitches that are 4-byte aligned take a faster form of the unpacking (same values).
+ * pnp_generator_forward_clips_yuv: pnp_generator_forward_clips with the frames as planes; out_mask is any non-empty set of
+ * PNP_OUT_F32 | PNP_OUT_U8 | PNP_OUT_YUV420, each output the one its own call would write: the result is bit-identical to the fp32
+ * forward on pnp_frames_from_yuv420 of the planes, and the PNP_OUT_YUV420 bytes are pnp_frames_to_yuv420 of the fp32 output.
+ * Errors, decided on the host before any HIP call: PNP_ERR_BAD_ARG for an unknown standard, a mask of 0 or beyond 7, a NULL plane or
+ * output the mask needs, c_step not 1 or 2, a pitch below the row's bytes, or odd h or w; then the forward's own, in their order
+ * (with pnp_generator_set_any_size every even h, w >= 64 runs).
+ * pnp_generator_workspace_bytes_yuv: bytes of one context (-1: mask, or a bound below the minimum): pnp_generator_workspace_bytes
+ * plus ONE frame of fp32 planes (12 h w bytes, 256-aligned) in front of a last conv that keeps its fp32 interface (PNP_PREC_F16,
+ * PNP_OPT_CONV_LAST_VALU = 0), plus ONE output frame of fp32 planes (12 H W) where bytes or planes are made of an fp32 frame the
+ * caller did not ask for (PNP_OUT_YUV420 without PNP_OUT_F32; PNP_OUT_U8 without it on such a last conv). */
+#define PNP_YUV_BT601_LIMITED 0
+#define PNP_YUV_BT601_FULL 1
+#define PNP_YUV_BT709_LIMITED 2
+#define PNP_YUV_BT709_FULL 3
+#define PNP_OUT_YUV420 4
+typedef struct pnp_yuv420_planes {      /* t frames of h x w, 8 bit, 4:2:0 */
+    unsigned char *y, *cb, *cr;         /* first frame's planes; NV12: cr == cb + 1, c_step 2; NV21: cb == cr + 1; I420: c_step 1 */
+    int64_t y_pitch, c_pitch;           /* bytes between rows (>= w, >= c_step * w/2); any value, odd ones too */
+    int64_t y_frame, c_frame;           /* bytes between frames of the Y plane / of the chroma planes */
+    int c_step;                         /* 1 | 2: bytes between chroma samples of a row */
+} pnp_yuv420_planes;
+typedef struct pnp_clip_yuv {
+    pnp_yuv420_planes lq;               /* read only */
+    const float *mvs_dev, *par_dev;     /* as in pnp_clip_io */
+    float* out_f32_dev;                 /* PNP_OUT_F32 */
+    unsigned char* out_u8_dev;          /* PNP_OUT_U8 */
+    pnp_yuv420_planes out_yuv;          /* PNP_OUT_YUV420: H x W = h x w, or 4h x 4w with cfg.vsr */
+} pnp_clip_yuv;
+int pnp_generator_forward_clips_yuv(const pnp_generator* g, const float* flat_dev, const float* packed_dev,
+                                    const pnp_clip_yuv* clips_host, int n, int yuv_standard, int out_mask,
+                                    const float* slices_host, const float* qps_host, const float* base_qps_host,
+                                    void* workspace_dev, int64_t workspace_bytes, int t, int h, int w, void* stream);
+int64_t pnp_generator_workspace_bytes_yuv(const pnp_generator* g, int t, int h, int w, int out_mask);
+/* The two conversions alone, n frames: in_host_desc / out_host_desc are HOST structs of device addresses; planes_dev (n,3,h,w) fp32. */
+int pnp_frames_from_yuv420(const pnp_yuv420_planes* in_host_desc, int yuv_standard, float* out_planes_dev, int n, int h, int w,
+                           void* stream);
+int pnp_frames_to_yuv420(const float* planes_dev, const pnp_yuv420_planes* out_host_desc, int yuv_standard, int n, int h, int w,
+                         void* stream);
+
 /* Optional per-launch timing with HIP events recorded on the caller's stream around every
  * kernel of pnp_generator_forward (measurement aid for bench.py; replaces the reference's
  * wall-clock print, mmedit/models/restorers/basicvsr.py:176-182).  Enable, run forwards,

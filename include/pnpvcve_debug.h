@@ -46,6 +46,12 @@ int pnp_debug_wino_tile_rows(int row0, int nrows);
  * (PNP_ERR_BAD_ARG otherwise, before any launch); 1: the form pnp_generator_set_any_size adds, any address and any t*h*w. */
 int pnp_debug_pack_lr_u8(const unsigned char* lq_dev, float* lr4_dev, int t, int h, int w, int any_size, void* stream);
 
+/* The 4:2:0 unpacking in front of pnp_generator_forward_clips_yuv's convs, alone: t frames of planes -> lr4_dev (t,h,w,4) fp32 RGB0,
+ * the values of pnp_frames_from_yuv420.  general = 0: the form the forward picks (the aligned one where planes and pitches are 4-byte
+ * aligned and w is a multiple of 4); 1: the byte-load form whatever the alignment.  Same values either way. */
+int pnp_debug_pack_lr_yuv420(const pnp_yuv420_planes* in_host_desc, int yuv_standard, float* lr4_dev, int t, int h, int w,
+                             int general, void* stream);
+
 /* The row-band plan of pnp_generator_set_band_split as a pure function: for a chain of nconv convs on a frame of `rows` tile rows,
  * writes the boundary row a_n of each conv (chain A: tile rows [0, a_n), chain B: [a_n, rows); a_n = a_0 - n) to bounds[0 .. nconv)
  * and returns 1, or returns 0 (bounds untouched) when the frame has too few rows for both regions to stay non-empty: no split.

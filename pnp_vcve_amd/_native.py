@@ -25,8 +25,21 @@ class ClipIO(ctypes.Structure):
     _fields_ = [(k, c_void_p) for k in ('lq_dev', 'mvs_dev', 'par_dev', 'out_f32_dev', 'out_u8_dev')]
 
 
+class Yuv420Planes(ctypes.Structure):
+    """pnp_yuv420_planes: t frames of 8-bit 4:2:0 planes (device addresses, byte strides)"""
+    _fields_ = [('y', c_void_p), ('cb', c_void_p), ('cr', c_void_p), ('y_pitch', c_int64), ('c_pitch', c_int64), ('y_frame', c_int64),
+                ('c_frame', c_int64), ('c_step', c_int)]
+
+
+class ClipYuv(ctypes.Structure):
+    """pnp_clip_yuv: one clip of a pnp_generator_forward_clips_yuv batch"""
+    _fields_ = [('lq', Yuv420Planes), ('mvs_dev', c_void_p), ('par_dev', c_void_p), ('out_f32_dev', c_void_p), ('out_u8_dev', c_void_p),
+                ('out_yuv', Yuv420Planes)]
+
+
 FRAMES_F32_NCHW, FRAMES_U8_HWC = 0, 1        # PNP_FRAMES_*
-OUT_F32, OUT_U8 = 1, 2                       # PNP_OUT_* (a mask)
+OUT_F32, OUT_U8, OUT_YUV420 = 1, 2, 4        # PNP_OUT_* (a mask; OUT_YUV420 on pnp_generator_forward_clips_yuv only)
+YUV_STANDARDS = {'bt601-limited': 0, 'bt601-full': 1, 'bt709-limited': 2, 'bt709-full': 3}      # PNP_YUV_*
 COLOR_NONE, COLOR_Y = 0, 1                   # PNP_COLOR_* (the metrics' convert_to)
 
 # name -> (restype, argtypes); every symbol include/pnpvcve.h declares
@@ -57,6 +70,12 @@ SIGNATURES = {
                                             POINTER(c_float), POINTER(c_float), POINTER(c_float),
                                             c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     'pnp_generator_workspace_bytes_io': (c_int64, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
+    'pnp_generator_forward_clips_yuv': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                                POINTER(c_float), POINTER(c_float), POINTER(c_float),
+                                                c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    'pnp_generator_workspace_bytes_yuv': (c_int64, [c_void_p, c_int, c_int, c_int, c_int]),
+    'pnp_frames_from_yuv420': (c_int, [POINTER(Yuv420Planes), c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'pnp_frames_to_yuv420': (c_int, [c_void_p, POINTER(Yuv420Planes), c_int, c_int, c_int, c_int, c_void_p]),
     'pnp_generator_set_precision': (c_int, [c_void_p, c_int]),
     'pnp_generator_get_precision': (c_int, [c_void_p]),
     'pnp_generator_set_option': (c_int, [c_void_p, c_int, c_int]),
@@ -137,6 +156,7 @@ DEBUG_SIGNATURES['pnp_dcn_trace_u64s'] = (c_int, [])
 DEBUG_SIGNATURES['pnp_debug_wino_gate_word'] = (c_int, [c_void_p])
 DEBUG_SIGNATURES['pnp_debug_wino_tile_rows'] = (c_int, [c_int, c_int])
 DEBUG_SIGNATURES['pnp_debug_pack_lr_u8'] = (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
+DEBUG_SIGNATURES['pnp_debug_pack_lr_yuv420'] = (c_int, [POINTER(Yuv420Planes), c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
 DEBUG_SIGNATURES['pnp_band_plan'] = (c_int, [c_int, c_int, c_int, POINTER(c_int)])
 DEBUG_SIGNATURES['pnp_conv3x3_wino_f32_ex'] = (c_int, [c_void_p] * 8 + [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p])
 DEBUG_SIGNATURES['pnp_conv3x3_f16_maps'] = (c_int, [c_int, POINTER(c_void_p), POINTER(c_int), c_int, POINTER(c_void_p), c_void_p,

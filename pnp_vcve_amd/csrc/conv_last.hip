@@ -30,6 +30,7 @@ constexpr int SIT = (PIX * 16 + 127) / 128;          // float4 halo loads per th
 // set, and the sum goes to a.out as fp32 planes and / or to a.out_u8 as (H,W,3) bytes, whichever is set.  The contraction, the
 // bilinear expression and the sum are the IO = 0 text: the fp32 value is the same bit for bit, the byte is frames_to_rgb8_kernel's
 // arithmetic on it.  3 byte stores per pixel, 48 contiguous bytes per tile row.
+// IO = 2: as IO = 1 on the output side; the frame to add is a.lr_rgb0, the (h,w,4) fp32 RGB0 frame a 4:2:0 clip was unpacked into.
 template <int KS, int IO = 0>
 __global__ __launch_bounds__(128 * KS) void conv_last_valu_kernel(const ConvArgs a, const float* __restrict__ wv) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -66,6 +67,27 @@ __global__ __launch_bounds__(128 * KS) void conv_last_valu_kernel(const ConvArgs
     const int gy = ty0 + py, gx = tx0 + px;
     const bool inb = gy < H && gx < W;
     float base[3] = {0.f, 0.f, 0.f};
+    if constexpr (IO == 2) {        // the frame as the (h,w,4) RGB0 conv source: the fp32 branch's coordinates and expression, pixel stride 4
+        if (inb && a.out_mode == 2) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(a.lr_rgb0 + ((long)gy * W + gx) * 4);
+            base[0] = v[0], base[1] = v[1], base[2] = v[2];
+        } else if (inb) {
+            const int lh = H >> 2, lw = W >> 2;
+            float sy = (gy + 0.5f) * 0.25f - 0.5f, sx = (gx + 0.5f) * 0.25f - 0.5f;
+            sy = sy < 0.f ? 0.f : sy;
+            sx = sx < 0.f ? 0.f : sx;
+            const int y0 = (int)sy, x0 = (int)sx;
+            const int y1 = y0 + (y0 < lh - 1 ? 1 : 0), x1 = x0 + (x0 < lw - 1 ? 1 : 0);
+            const float ly = sy - y0, lx = sx - x0;
+            const f32x4* p = reinterpret_cast<const f32x4*>(a.lr_rgb0);
+            const f32x4 q00 = p[(long)y0 * lw + x0], q01 = p[(long)y0 * lw + x1], q10 = p[(long)y1 * lw + x0], q11 = p[(long)y1 * lw + x1];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float v00 = q00[c], v01 = q01[c], v10 = q10[c], v11 = q11[c];
+                base[c] = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+            }
+        }
+    } else
     if (IO && inb && a.lr_u8) {
         if (a.out_mode == 2) {
 #pragma unroll
@@ -198,8 +220,13 @@ int launch_conv_last_valu(const ConvArgs& a, hipStream_t stream) {
 }
 
 int launch_conv_last_io(const ConvArgs& a, hipStream_t stream) {
-    if (!conv_last_valu_shape(a, CONV_CFG_RGB, 1, a.lr || a.lr_u8) || (!a.out && !a.out_u8)) return PNP_ERR_UNSUPPORTED;
+    if (!conv_last_valu_shape(a, CONV_CFG_RGB, 1, a.lr || a.lr_u8 || a.lr_rgb0) || (!a.out && !a.out_u8)) return PNP_ERR_UNSUPPORTED;
     const int tiles = ((a.W + TW - 1) / TW) * ((a.H + TH - 1) / TH);
+    if (a.lr_rgb0) {
+        if (tiles < 768) hipLaunchKernelGGL((conv_last_valu_kernel<4, 2>), dim3(tiles), dim3(512), LDS_BYTES, stream, a, a.wvalu);
+        else hipLaunchKernelGGL((conv_last_valu_kernel<1, 2>), dim3(tiles), dim3(128), LDS_BYTES, stream, a, a.wvalu);
+        return (int)hipGetLastError();
+    }
     if (tiles < 768) hipLaunchKernelGGL((conv_last_valu_kernel<4, 1>), dim3(tiles), dim3(512), LDS_BYTES, stream, a, a.wvalu);
     else hipLaunchKernelGGL((conv_last_valu_kernel<1, 1>), dim3(tiles), dim3(128), LDS_BYTES, stream, a, a.wvalu);
     return (int)hipGetLastError();

@@ -70,6 +70,9 @@ struct ConvArgs {
     const unsigned char* lr_u8;   // out_mode 2/3: the frame to add as (h,w,3) uint8 RGB, read through PnpU8Table INSTEAD of lr; or nullptr
     unsigned char* out_u8;        // out_mode 2/3: (H,W,3) uint8 RGB = round_half_even(clamp(x,0,1) * 255) of the fp32 sum x, written next to
                                   // `out` (or instead of it: out == nullptr); or nullptr
+    // 4:2:0 frames (launch_conv_last_io only; behind the byte fields for the same reason):
+    const float* lr_rgb0;         // out_mode 2/3: the frame to add as (h,w,4) fp32 RGB0, the conv source the pack launch wrote into the workspace
+                                  // (pixel stride 4), read INSTEAD of lr / lr_u8; or nullptr
 };
 
 enum { CONV_CFG_BIG = 0,    // 8x16 pixel tile, 64 output channels per block

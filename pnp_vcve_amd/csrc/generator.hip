@@ -27,8 +27,10 @@
 #include "prep.h"
 #include "warp.h"
 #include "dcn.h"
+#include "yuv.h"
 #ifdef PNP_HOST_STUB
 #include "host_stub/io_stub.h"   // recording stand-ins for the byte-frame launchers (prep.h, conv_mfma.h) of the host-only scheduler tests
+#include "host_stub/yuv_stub.h"  // ... and for the 4:2:0 launchers (yuv.h)
 #endif
 
 namespace {
@@ -415,6 +417,9 @@ struct ConvCall {
     const unsigned char* lr8_ = nullptr;
     unsigned char* out8_ = nullptr;
     ConvCall& rgb8(const unsigned char* lr8, unsigned char* out8) { lr8_ = lr8; out8_ = out8; return *this; }
+    // conv_last behind a 4:2:0 clip (ConvArgs::lr_rgb0): the frame as the (h,w,4) RGB0 conv source in the workspace
+    const float* lr0_ = nullptr;
+    ConvCall& rgb0(const float* lr0) { lr0_ = lr0; return *this; }
     // fp16 path: 1 = the output is an fp16 map, 2 = the (single) source is one
     ConvCall& f16_map(int io16) { io16_ = io16; return *this; }
     // fp16 path with mirrors (PNP_OPT_F16_MIRRORS): the fp16 copy its producer wrote of the source added last (read INSTEAD of
@@ -610,6 +615,12 @@ bool make_schedule(const pnp_generator* g, int t, const std::vector<char>& key, 
 // one-frame fp32 copy of the frame and / or of the output in the workspace.
 bool io_staged(const pnp_generator* g) { return g->prec == PNP_PREC_F16 || !g->opt[PNP_OPT_CONV_LAST_VALU]; }
 
+// 4:2:0 frames (pnp_generator_forward_clips_yuv): a frame format of the scheduler only -- the public entry for formats refuses it -- and
+// one more bit of the output mask.  The unpacked frame in the workspace is what conv_last adds (ConvArgs::lr_rgb0); the kernels with an
+// fp32 interface get the one-frame planes of the byte boundary.  Output planes are made per frame from the fp32 output frame: the
+// caller's where PNP_OUT_F32 is asked for, the one-frame buffer otherwise.
+constexpr int FRAMES_YUV420 = 2;
+
 Workspace carve(const pnp_generator* g, char* base, int t, int h, int w, int lq_format = PNP_FRAMES_F32_NCHW, int out_mask = PNP_OUT_F32) {
     Workspace W;
     int64_t off = 0;
@@ -657,8 +668,9 @@ Workspace carve(const pnp_generator* g, char* base, int t, int h, int w, int lq_
     W.queue = g->prec == PNP_PREC_F16X3 ? reinterpret_cast<int*>(take(16)) : nullptr;
     // (behind everything else and only in the modes that need them: the fp32 boundary's layout and size are what they were)
     const bool staged = io_staged(g);
-    W.lr1 = (staged && lq_format == PNP_FRAMES_U8_HWC) ? take(hw * 3) : nullptr;
-    W.out1 = (staged && out_mask == PNP_OUT_U8) ? take(hw * 3 * (g->cfg.vsr ? 16 : 1)) : nullptr;
+    W.lr1 = (staged && (lq_format == PNP_FRAMES_U8_HWC || lq_format == FRAMES_YUV420)) ? take(hw * 3) : nullptr;
+    const bool out1 = !(out_mask & PNP_OUT_F32) && ((staged && (out_mask & PNP_OUT_U8)) || (out_mask & PNP_OUT_YUV420));
+    W.out1 = out1 ? take(hw * 3 * (g->cfg.vsr ? 16 : 1)) : nullptr;
     W.bytes = off;
     return W;
 }
@@ -923,6 +935,9 @@ struct ClipRun {
     const float* const lr_b; const unsigned char* const lq8;
     float* const out_b; unsigned char* const out8;
     const float *const mv_b, *const par_in, *const sl, *const qp, *const bq;
+    // ... or the frames and / or one more output as 4:2:0 planes (nullptr: not), with the standard's constants
+    const pnp_yuv420_planes *const lqy, *const outy;
+    YuvCoef yk{};
     const bool staged, alone;      // alone: the only workspace context in flight
     const int64_t hw = (int64_t)h * w, fm = hw * 64;
     const int E = c.num_experts, cfg_lr = conv_pick_cfg(h, w), os = c.vsr ? 4 : 1;
@@ -946,12 +961,16 @@ struct ClipRun {
     bool sparse_per_frame = false;
 
     ClipRun(const pnp_generator* g_, const float* flat_, const float* packed_, const pnp_clip_io& io, int lq_format, int out_mask,
-            const float* sl_, const float* qp_, const float* bq_, const Workspace& W_, int t_, int h_, int w_, hipStream_t st_, bool alone_)
+            const float* sl_, const float* qp_, const float* bq_, const Workspace& W_, int t_, int h_, int w_, hipStream_t st_, bool alone_,
+            const pnp_clip_yuv* yuv = nullptr, int yuv_standard = 0)
         : g(g_), c(g_->cfg), flat(flat_), packed(packed_), W(W_), t(t_), h(h_), w(w_), st(st_),
-          lr_b(lq_format == PNP_FRAMES_U8_HWC ? nullptr : static_cast<const float*>(io.lq_dev)),
+          lr_b(lq_format == PNP_FRAMES_F32_NCHW ? static_cast<const float*>(io.lq_dev) : nullptr),
           lq8(lq_format == PNP_FRAMES_U8_HWC ? static_cast<const unsigned char*>(io.lq_dev) : nullptr),
           out_b((out_mask & PNP_OUT_F32) ? io.out_f32_dev : nullptr), out8((out_mask & PNP_OUT_U8) ? io.out_u8_dev : nullptr),
-          mv_b(io.mvs_dev), par_in(io.par_dev), sl(sl_), qp(qp_), bq(bq_), staged((lq8 || out8) && io_staged(g_)), alone(alone_) {}
+          mv_b(io.mvs_dev), par_in(io.par_dev), sl(sl_), qp(qp_), bq(bq_), lqy(yuv ? &yuv->lq : nullptr),
+          outy((yuv && (out_mask & PNP_OUT_YUV420)) ? &yuv->out_yuv : nullptr), staged((lq8 || out8 || lqy) && io_staged(g_)), alone(alone_) {
+        if (yuv) (void)yuv_coef(yuv_standard, &yk);
+    }
 
     // fp16 mirror of a weight image that lives in `packed` or in the per-clip expert mixtures
     const void* twin(const float* p) const {
@@ -1012,6 +1031,7 @@ struct ClipRun {
         a.H = q.H, a.W = q.W, a.act = q.act_;
         a.out_mode = q.mode_, a.out_cstride = 448;
         a.lr_u8 = q.lr8_, a.out_u8 = q.out8_;
+        a.lr_rgb0 = q.lr0_;
         a.out_f16 = q.io16_ & 1;          // io16: bit 0 the output is an fp16 map, bit 1 source 0 is one
         a.src_f16 = (q.io16_ & 2) ? 1 : 0;
         if (mirrors) {
@@ -1046,7 +1066,7 @@ struct ClipRun {
             const int rc = chain.attach(a, tiles);
             if (rc) return rc;
         }
-        if (a.lr_u8 || a.out_u8) return launch_conv_last_io(a, st);      // (conv_last only, outside every chain)
+        if (a.lr_u8 || a.out_u8 || a.lr_rgb0) return launch_conv_last_io(a, st);      // (conv_last only, outside every chain)
         return launch_conv3x3(a, q.cfg_, q.gy_, st);
     }
 
@@ -1059,6 +1079,7 @@ struct ClipRun {
             const int rc = launch_fill(reinterpret_cast<float*>(W.queue), 0.0f, 16, st);
             if (rc) return rc;
         }
+        if (lqy) return launch_pack_lr_yuv420(*lqy, yk, W.lr4, t, h, w, false, st);
         if (!lq8) return launch_pack_lr(lr_b, W.lr4, t, h, w, st);
         // any_size: a clip that is not whole 12-byte groups on a 4-aligned address takes the kernel with a head and a tail; every
         // other clip the one it always took
@@ -1295,12 +1316,28 @@ struct ClipRun {
             lr_i = W.lr1;
             lr8_i = nullptr;
         }
-        if (staged && out8_i && !out_i) out_i = W.out1;
+        // a 4:2:0 clip: the frame conv_last adds is the RGB0 frame the pack launch left in the workspace, or (fp32 interface) its planes
+        const float* lr0_i = nullptr;
+        if (lqy && staged) {
+            rc = launch_frames_from_yuv420(yuv_frame(*lqy, i), yk, W.lr1, 1, h, w, st);
+            untimed(g);
+            if (rc) return rc;
+            lr_i = W.lr1;
+        } else if (lqy) {
+            lr0_i = W.lr4 + (int64_t)i * hw * 4;
+        }
+        if (((staged && out8_i) || outy) && !out_i) out_i = W.out1;
         rc = conv(ConvCall(H, Wd, CONV_CFG_RGB).source(top, 64, packed + g->last_img).bias(packed + g->last_bias)
-                      .mode(c.vsr ? 3 : 2).rgb(lr_i, hw, packed + g->last_valu).rgb8(lr8_i, staged ? nullptr : out8_i).to(out_i).f16_map(s16));
-        if (rc || !staged || !out8_i) return rc;
+                      .mode(c.vsr ? 3 : 2).rgb(lr_i, hw, packed + g->last_valu).rgb8(lr8_i, staged ? nullptr : out8_i).rgb0(lr0_i).to(out_i).f16_map(s16));
+        if (rc) return rc;
+        if (staged && out8_i) {
+            untimed(g);
+            rc = launch_frames_to_rgb8(out_i, out8_i, 1, H, Wd, st);
+            if (rc) return rc;
+        }
+        if (!outy) return rc;
         untimed(g);
-        return launch_frames_to_rgb8(out_i, out8_i, 1, H, Wd, st);
+        return launch_frames_to_yuv420(out_i, yuv_frame(*outy, i), yk, 1, H, Wd, st);
     }
 
     // one branch run of the schedule (recomputed runs of the bounded schedule are steps like any other) and, forward, the frame's head
@@ -1392,7 +1429,7 @@ int forward_check(const pnp_generator* g, int n, int t, int h, int w, int lq_for
 // The batch loop behind both entry points: n clips, each named by a descriptor, `lq_format` / `out_mask` for all of them.
 int forward_batch(const pnp_generator* g, const float* flat, const float* packed, const pnp_clip_io* clips, int n, int lq_format,
                   int out_mask, const float* slices, const float* qps, const float* base_qps, void* workspace, int64_t workspace_bytes,
-                  int t, int h, int w, hipStream_t st) {
+                  int t, int h, int w, hipStream_t st, const pnp_clip_yuv* yclips = nullptr, int yuv_standard = 0) {
     const int bad = forward_check(g, n, t, h, w, lq_format, out_mask, workspace, workspace_bytes);
     if (bad) return bad;
     const int64_t ctx_bytes = carve(g, nullptr, t, h, w, lq_format, out_mask).bytes;
@@ -1425,8 +1462,10 @@ int forward_batch(const pnp_generator* g, const float* flat, const float* packed
     for (int b = 0; b < n && rc == PNP_OK; ++b) {
         const int k = b % nctx;
         const Workspace W = carve(g, (char*)workspace + (int64_t)k * ctx_bytes, t, h, w, lq_format, out_mask);
-        rc = ClipRun(g, flat, packed, clips[b], lq_format, out_mask, slices + (int64_t)b * t, qps + (int64_t)b * t, base_qps + (int64_t)b * t,
-                     W, t, h, w, nctx > 1 ? g->side_streams[k] : st, nctx == 1).run();
+        // (a 4:2:0 batch comes as its own descriptors: the pointers the two kinds share, then the planes)
+        const pnp_clip_io io = yclips ? pnp_clip_io{nullptr, yclips[b].mvs_dev, yclips[b].par_dev, yclips[b].out_f32_dev, yclips[b].out_u8_dev} : clips[b];
+        rc = ClipRun(g, flat, packed, io, lq_format, out_mask, slices + (int64_t)b * t, qps + (int64_t)b * t, base_qps + (int64_t)b * t,
+                     W, t, h, w, nctx > 1 ? g->side_streams[k] : st, nctx == 1, yclips ? yclips + b : nullptr, yuv_standard).run();
     }
     if (nctx > 1) {      // join even after an error: the caller's stream must not run ahead of what was launched
         for (int k = 0; k < nctx; ++k) {
@@ -1482,6 +1521,33 @@ int pnp_generator_forward_clips(const pnp_generator* g, const float* flat, const
     }
     return forward_batch(g, flat, packed, clips, n, lq_format, out_mask, slices, qps, base_qps, workspace, workspace_bytes, t, h, w,
                          (hipStream_t)stream_);
+}
+
+int64_t pnp_generator_workspace_bytes_yuv(const pnp_generator* g, int t, int h, int w, int out_mask) {
+    if (!g || out_mask < 1 || out_mask > (PNP_OUT_F32 | PNP_OUT_U8 | PNP_OUT_YUV420)) return -1;
+    int R, L;
+    if (bounded_mode(g, t) && !plan_pick(t, g->cfg.with_cat, g->max_resident, &R, &L)) return -1;
+    return carve(g, nullptr, t, h, w, FRAMES_YUV420, out_mask).bytes;
+}
+
+int pnp_generator_forward_clips_yuv(const pnp_generator* g, const float* flat, const float* packed, const pnp_clip_yuv* clips, int n,
+                                    int yuv_standard, int out_mask, const float* slices, const float* qps, const float* base_qps,
+                                    void* workspace, int64_t workspace_bytes, int t, int h, int w, void* stream_) {
+    // what only this entry can get wrong, in front of everything else (no HIP call has been made)
+    YuvCoef k;
+    if (!g || !clips || n < 1 || !yuv_coef(yuv_standard, &k) || out_mask < 1 || out_mask > (PNP_OUT_F32 | PNP_OUT_U8 | PNP_OUT_YUV420)) return PNP_ERR_BAD_ARG;
+    if (h < 2 || w < 2 || (h & 1) || (w & 1)) return PNP_ERR_BAD_ARG;
+    const int os = g->cfg.vsr ? 4 : 1;
+    for (int b = 0; b < n; ++b) {
+        const pnp_clip_yuv& c = clips[b];
+        if (!yuv_planes_ok(c.lq, w) || !c.mvs_dev || !c.par_dev) return PNP_ERR_BAD_ARG;
+        if ((out_mask & PNP_OUT_F32) && !c.out_f32_dev) return PNP_ERR_BAD_ARG;
+        const uintptr_t amask = g->any_size ? 0 : 3;      // (the byte output's rule of pnp_generator_forward_clips)
+        if ((out_mask & PNP_OUT_U8) && (!c.out_u8_dev || (reinterpret_cast<uintptr_t>(c.out_u8_dev) & amask))) return PNP_ERR_BAD_ARG;
+        if ((out_mask & PNP_OUT_YUV420) && !yuv_planes_ok(c.out_yuv, w * os)) return PNP_ERR_BAD_ARG;
+    }
+    return forward_batch(g, flat, packed, nullptr, n, FRAMES_YUV420, out_mask, slices, qps, base_qps, workspace, workspace_bytes, t, h, w,
+                         (hipStream_t)stream_, clips, yuv_standard);
 }
 
 int pnp_generator_profile(pnp_generator* g, int enable) {

@@ -56,7 +56,7 @@ inline int launch_frames_to_rgb8(const float* in, unsigned char* out, int nframe
 }
 
 inline int launch_conv_last_io(const ConvArgs& a, hipStream_t stream) {
-    if (!conv_last_valu_shape(a, CONV_CFG_RGB, 1, a.lr || a.lr_u8) || (!a.out && !a.out_u8)) return PNP_ERR_UNSUPPORTED;      // conv_last.hip's rule
+    if (!conv_last_valu_shape(a, CONV_CFG_RGB, 1, a.lr || a.lr_u8 || a.lr_rgb0) || (!a.out && !a.out_u8)) return PNP_ERR_UNSUPPORTED;      // conv_last.hip's rule
     PnpStubIoLaunch r{PNP_STUB_IO_CONV_LAST, stream, nullptr, nullptr, 1, a.H, a.W, a};
     return pnp_stub_io_record(r);
 }

@@ -13,7 +13,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import _native
+from . import _native, ops
 from .registry import BACKBONES
 
 _DEFORM = {'vos': 0, 'basic': 1, 'fvc': 2}
@@ -303,6 +303,8 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         L = _native.lib()
         if (fmt, mask) == (_native.FRAMES_F32_NCHW, _native.OUT_F32):
             return int(L.pnp_generator_workspace_bytes(self._handle, t, h, w))
+        if fmt == 'yuv':        # the 4:2:0 boundary (pnp_generator_forward_clips_yuv)
+            return int(L.pnp_generator_workspace_bytes_yuv(self._handle, t, h, w, mask))
         return int(L.pnp_generator_workspace_bytes_io(self._handle, t, h, w, fmt, mask))
 
     def _get_workspace(self, n, t, h, w, device, fmt=_native.FRAMES_F32_NCHW, mask=_native.OUT_F32):
@@ -327,14 +329,22 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
             return _native.OUT_F32 | _native.OUT_U8
         raise ValueError(f"out_dtype must be None, torch.float32, torch.uint8 or 'both', got {out_dtype!r}")
 
-    def forward(self, lrs, QPs=None, slices=None, mvs=None, base_QPs=None, par_map=None, out_dtype=None):
+    def forward(self, lrs, QPs=None, slices=None, mvs=None, base_QPs=None, par_map=None, out_dtype=None, yuv_standard='bt601-limited'):
         """iconvsr_ipb_par.py:44-149.  lrs (n,t,3,h,w); QPs/slices/base_QPs (n,t,1,1,1);
         mvs (n,t,4,h,w); par_map (n,t,3,h,w).  Returns (n,t,3,h,w) (x4 spatial when vsr).
 
         Byte frames: a uint8 `lrs` is the decoder's layout (n,t,h,w,3), RGB, byte v standing for float32(v) / float32(255) -- the
         result is bit-identical to forward(ops.frames_from_rgb8(lrs), ...), without the fp32 clip.  out_dtype: None / torch.float32
         (the fp32 planes above) | torch.uint8 ((n,t,H,W,3) display bytes, ops.frames_to_rgb8's arithmetic on the same fp32 values) |
-        'both' (the pair (fp32, uint8))."""
+        'both' (the pair (fp32, uint8)).
+
+        4:2:0 frames: an ops.Yuv420Frames `lrs` is the decoder's planes where they lie (NV12 / NV21 / I420 views, any pitch) in the
+        colour standard `yuv_standard` ('bt601-limited' | 'bt601-full' | 'bt709-limited' | 'bt709-full') -- bit-identical to
+        forward(ops.frames_from_yuv420(lrs, yuv_standard), ...), without the fp32 clip.  out_dtype then also takes 'nv12' / 'i420'
+        (a packed uint8 (n,t,3H/2,W) buffer, ops.frames_to_yuv420's arithmetic on the same fp32 values) and a tuple or list of
+        dtypes (several outputs, returned as a tuple in that order)."""
+        if isinstance(lrs, ops.Yuv420Frames):
+            return self._forward_yuv(lrs, QPs, slices, mvs, base_QPs, par_map, out_dtype, yuv_standard)
         if not lrs.is_cuda:
             raise RuntimeError('PnP-VCVE generator: inputs must be CUDA/HIP tensors; this build has no CPU path '
                                '(the CPU restatement under oracle/ is test infrastructure only)')
@@ -435,15 +445,19 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         _native.check(rc, 'pnp_generator_forward_clips')
 
-    def forward_clips(self, clips, out_dtype=None):
+    def forward_clips(self, clips, out_dtype=None, yuv_standard='bt601-limited'):
         """A batch as a sequence of clips, each where it lives: clips[i] = (lrs, QPs, slices, mvs, base_QPs, par_map) with the tensors
         of forward() for n = 1 (or without the batch dimension).  All clips go to the library in ONE call as pointers -- nothing is
         concatenated -- and run like a batch (large frames two at a time on two streams, small ones up to eight).  Returns a list of
         per-clip outputs, each what forward(..., out_dtype) returns for that clip (with the batch dimension, n = 1).  The clips must
         agree in shape and in the dtype class of lrs (uint8 or floating point): ValueError otherwise.  Not replayed from a graph
-        (use_graphs concerns forward()): a graph's static buffers would be the copies this call exists to avoid."""
-        mask = self._out_mask(out_dtype)
+        (use_graphs concerns forward()): a graph's static buffers would be the copies this call exists to avoid.
+        Clips whose lrs are ops.Yuv420Frames (each clip's planes in allocations of their own) take yuv_standard and the out_dtype
+        values of forward()'s 4:2:0 boundary."""
         clips = list(clips)
+        if clips and isinstance(clips[0][0], ops.Yuv420Frames):
+            return self._forward_clips_yuv(clips, out_dtype, yuv_standard)
+        mask = self._out_mask(out_dtype)
         if not clips:
             raise ValueError('forward_clips needs at least one clip')
         if self.sparse_val and not self.training and len(clips) != 1:
@@ -519,6 +533,211 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
             ws = self._get_workspace(n, t, h, w, dev, int(byte_in), mask)
             self._launch_clips(lrs, mvs, par, side, f32, u8, ws, t, h, w)
         return (f32 or []) + (u8 or [])
+
+    # ---------------------------------------------------------------- 4:2:0 frames (pnp_generator_forward_clips_yuv)
+    @staticmethod
+    def _yuv_outs(out_dtype):
+        """out_dtype of the 4:2:0 boundary -> (the requested kinds in order, 'f32' | 'u8' | 'yuv'; the mask; the layout of 'yuv' or
+        None; whether a tuple was asked for)"""
+        many = isinstance(out_dtype, (tuple, list))
+        kinds, layout = [], None
+        for d in (out_dtype if many else [out_dtype]):
+            if d is None or d == torch.float32:
+                kinds.append('f32')
+            elif d == torch.uint8:
+                kinds.append('u8')
+            elif isinstance(d, str) and d in ('nv12', 'i420'):
+                if layout is not None:
+                    raise ValueError('one 4:2:0 output layout per call')
+                layout = d
+                kinds.append('yuv')
+            else:
+                raise ValueError(f"out_dtype must be None, torch.float32, torch.uint8, 'nv12', 'i420' or a tuple of them, got {d!r}")
+        if not kinds or len(set(kinds)) != len(kinds):
+            raise ValueError(f'out_dtype names no output or one twice: {out_dtype!r}')
+        bits = {'f32': _native.OUT_F32, 'u8': _native.OUT_U8, 'yuv': _native.OUT_YUV420}
+        return kinds, sum(bits[k] for k in kinds), layout, many
+
+    def _yuv_side(self, t, QPs, slices, base_QPs):
+        """one clip's (3, t) side info, with forward()'s refusals"""
+        if slices is None:
+            raise TypeError('slices (n,t,1,1,1) is required: it selects the key frames (iconvsr_ipb_par.py:60-62)')
+        if QPs is None and (self.with_bias or not self.use_base_qp):
+            raise TypeError('QPs is required by this configuration (iconvsr_ipb_par.py:45-48)')
+        if base_QPs is None and self.use_base_qp:
+            raise TypeError('base_QPs is required when use_base_qp=True (iconvsr_ipb_par.py:45)')
+        zero = torch.zeros(t, device=slices.device)
+        return torch.stack([slices.reshape(t).float(), QPs.reshape(t).float() if QPs is not None else zero,
+                            base_QPs.reshape(t).float() if base_QPs is not None else zero])
+
+    def _forward_yuv(self, frames, QPs, slices, mvs, base_QPs, par_map, out_dtype, yuv_standard):
+        std = ops._yuv_standard(yuv_standard)
+        kinds, mask, layout, many = self._yuv_outs(out_dtype)
+        clips, lead = ops._yuv_clips(frames, 'lrs')
+        if not lead:
+            raise ValueError('forward() takes a batch: Yuv420Frames of (n,t,rows,cols) views')
+        descs = [ops._yuv_clip_desc(c, 'lrs') for c in clips]      # (every refusal before any GPU work)
+        n, (_, t, h, w) = len(clips), descs[0]
+        assert h >= 64 and w >= 64, f'The height and width of inputs should be at least 64, but got {h} and {w}.'
+        self._check_resident(t)
+        dev = frames.y.device
+        with torch.cuda.device(dev):
+            self._ensure_packed(dev)
+            mvs_c = mvs.detach().float().contiguous()
+            par_c = par_map.detach().float().contiguous()
+            if mvs_c.shape != (n, t, 4, h, w) or par_c.shape != (n, t, 3, h, w):
+                raise ValueError(f'The spatial sizes of input ({(h, w)}) and flow/partition maps '
+                                 f'({tuple(mvs_c.shape)}, {tuple(par_c.shape)}) are not the same.')
+            if self.sparse_val:
+                sparse_now = 0 if self.training else 1
+                if self.get_option(_native.OPT_SPARSE_EVAL) != sparse_now:
+                    self.set_option(_native.OPT_SPARSE_EVAL, sparse_now)
+            if self.sparse_val and not self.training and n != 1:
+                raise NotImplementedError('sparse_val=True evaluates one clip at a time: the reference reads feature[0] '
+                                          'only (sr_backbone_utils.py:262-275)')
+            side = torch.stack([self._yuv_side(t, QPs[b] if QPs is not None else None, slices[b] if slices is not None else None,
+                                               base_QPs[b] if base_QPs is not None else None) for b in range(n)], dim=1).cpu().contiguous()
+            if self.use_graphs and not self._profiling:
+                outs = self._forward_yuv_graphed(clips, mvs_c, par_c, side, std, mask, layout, (n, t, h, w))
+            else:
+                outs = self._alloc_yuv_outs(n, t, h, w, mask, layout, dev)
+                ws = self._get_workspace(n, t, h, w, dev, 'yuv', mask)
+                self._launch_clips_yuv(clips, list(mvs_c), list(par_c), side, outs, ws, t, h, w, std)
+        res = tuple(outs[k][0] for k in kinds)
+        return res if many else res[0]
+
+    def _alloc_yuv_outs(self, n, t, h, w, mask, layout, dev):
+        """-> {'f32' | 'u8' | 'yuv': (the (n,...) tensor returned, what the launch writes per clip)} for the bits of mask"""
+        s = 4 if self.vsr else 1
+        outs = {}
+        if mask & _native.OUT_F32:
+            x = torch.empty((n, t, 3, h * s, w * s), device=dev, dtype=torch.float32)
+            outs['f32'] = (x, list(x))
+        if mask & _native.OUT_U8:
+            x = torch.empty((n, t, h * s, w * s, 3), device=dev, dtype=torch.uint8)
+            outs['u8'] = (x, list(x))
+        if mask & _native.OUT_YUV420:
+            buf, views = ops.empty_yuv420((n, t), h * s, w * s, layout, dev)
+            outs['yuv'] = (buf, ops._yuv_clips(views, 'out')[0])
+        return outs
+
+    def _launch_clips_yuv(self, clips, mvs, par, side, outs, ws, t, h, w, std):
+        """One pnp_generator_forward_clips_yuv call on torch's current stream: per-clip plane views, nothing copied or concatenated."""
+        n = len(clips)
+        arr = (_native.ClipYuv * n)()
+        mask = 0
+        for kind, bit in (('f32', _native.OUT_F32), ('u8', _native.OUT_U8), ('yuv', _native.OUT_YUV420)):
+            mask |= bit if kind in outs else 0
+        for b in range(n):
+            lq = ops._yuv_clip_desc(clips[b], 'lrs')[0]
+            oy = ops._yuv_clip_desc(outs['yuv'][1][b], 'out')[0] if 'yuv' in outs else _native.Yuv420Planes()
+            arr[b] = _native.ClipYuv(lq, mvs[b].data_ptr(), par[b].data_ptr(), outs['f32'][1][b].data_ptr() if 'f32' in outs else None,
+                                     outs['u8'][1][b].data_ptr() if 'u8' in outs else None, oy)
+        fp = ctypes.POINTER(ctypes.c_float)
+        base = side.data_ptr()
+        P = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
+        rc = _native.lib().pnp_generator_forward_clips_yuv(
+            self._handle, P(self._flat), P(self._packed), ctypes.cast(arr, ctypes.c_void_p), n, std, mask, ctypes.cast(base, fp),
+            ctypes.cast(base + 4 * n * t, fp), ctypes.cast(base + 8 * n * t, fp), P(ws), ws.numel(), t, h, w,
+            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _native.check(rc, 'pnp_generator_forward_clips_yuv')
+
+    def _forward_yuv_graphed(self, clips, mvs_c, par_c, side, std, mask, layout, shape):
+        """use_graphs at the 4:2:0 boundary: the planes are copied into static planes of their own (1.5 B per pixel), the outputs out"""
+        n, t, h, w = shape
+        dev = mvs_c.device
+        key = ('yuv', n, t, h, w, str(dev), side.numpy().tobytes(), self._packed.data_ptr(), self._packed_floats, self.max_resident_features,
+               std, mask, layout)
+        ent = self._graphs.get(key)
+        fill = lambda e: [dst.copy_(src) for b in range(n) for dst, src in zip(e['clips'][b], clips[b])]      # noqa: E731
+        if ent is None:
+            mk = lambda hh, ww: torch.empty((n, t, hh, ww), device=dev, dtype=torch.uint8)      # noqa: E731
+            static = ops.Yuv420Frames(mk(h, w), mk(h // 2, w // 2), mk(h // 2, w // 2))
+            ent = dict(clips=ops._yuv_clips(static, 'lrs')[0], mvs=torch.empty_like(mvs_c), par=torch.empty_like(par_c), side=side.clone(),
+                       ws=torch.empty(self._workspace_bytes(t, h, w, 'yuv', mask) * self._contexts(n, h, w), device=dev, dtype=torch.uint8),
+                       outs=self._alloc_yuv_outs(n, t, h, w, mask, layout, dev))
+            run = lambda: self._launch_clips_yuv(ent['clips'], list(ent['mvs']), list(ent['par']), ent['side'], ent['outs'], ent['ws'],      # noqa: E731
+                                                 t, h, w, std)
+            fill(ent)
+            ent['mvs'].copy_(mvs_c)
+            ent['par'].copy_(par_c)
+            cur = torch.cuda.current_stream()
+            warm = torch.cuda.Stream()
+            warm.wait_stream(cur)
+            with torch.cuda.stream(warm):       # eager once: first-use attribute calls must not land in a capture
+                run()
+            cur.wait_stream(warm)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                run()
+            ent['graph'] = graph
+            while len(self._graphs) >= self.MAX_GRAPHS:
+                self._graphs.pop(next(iter(self._graphs)))
+            self._graphs[key] = ent
+        else:
+            fill(ent)
+            ent['mvs'].copy_(mvs_c)
+            ent['par'].copy_(par_c)
+        ent['graph'].replay()
+        return {k: (v[0].clone(), None) for k, v in ent['outs'].items()}
+
+    def _forward_clips_yuv(self, clips, out_dtype, yuv_standard):
+        std = ops._yuv_standard(yuv_standard)
+        kinds, mask, layout, many = self._yuv_outs(out_dtype)
+        if self.sparse_val and not self.training and len(clips) != 1:
+            raise NotImplementedError('sparse_val=True evaluates one clip at a time: the reference reads feature[0] '
+                                      'only (sr_backbone_utils.py:262-275)')
+        ys, cbs, crs, mv_l, par_l, sides, first = [], [], [], [], [], [], None
+        for lrs, QPs, slices, mvs, base_QPs, par_map in clips:
+            one, lead = ops._yuv_clips(lrs, 'lrs')
+            if len(one) != 1:
+                raise ValueError('a clip of forward_clips is one sample: Yuv420Frames of (t,...) or (1,t,...) views')
+            _, t, h, w = ops._yuv_clip_desc(one[0], 'lrs')
+            sig = (t, h, w, lrs.y.device)
+            if first is None:
+                first = sig
+            elif sig != first:
+                raise ValueError(f'the clips of one forward_clips call must agree in shape and device: {sig} against {first}')
+            assert h >= 64 and w >= 64, f'The height and width of inputs should be at least 64, but got {h} and {w}.'
+            mvs_c = mvs.detach().float().reshape(mvs.shape[-4:]).contiguous()
+            par_c = par_map.detach().float().reshape(par_map.shape[-4:]).contiguous()
+            if mvs_c.shape != (t, 4, h, w) or par_c.shape != (t, 3, h, w):
+                raise ValueError(f'The spatial sizes of input ({(h, w)}) and flow/partition maps '
+                                 f'({tuple(mvs_c.shape)}, {tuple(par_c.shape)}) are not the same.')
+            ys.append(one[0].y), cbs.append(one[0].cb), crs.append(one[0].cr)
+            mv_l.append(mvs_c)
+            par_l.append(par_c)
+            sides.append(self._yuv_side(t, QPs, slices, base_QPs))
+        t, h, w, dev = first
+        self._check_resident(t)
+        with torch.cuda.device(dev):
+            self._ensure_packed(dev)
+            if self.sparse_val:
+                sparse_now = 0 if self.training else 1
+                if self.get_option(_native.OPT_SPARSE_EVAL) != sparse_now:
+                    self.set_option(_native.OPT_SPARSE_EVAL, sparse_now)
+            side = torch.stack(sides, dim=1).cpu().contiguous()
+            flat = torch.ops.pnpvcve.generator_forward_clips_yuv(self._op_handle, ys, cbs, crs, mv_l, par_l, side, std, mask,
+                                                                 ops.YUV_LAYOUTS.index(layout) if layout else -1)
+        n = len(ys)
+        order = [k for k in ('f32', 'u8', 'yuv') if k in kinds]
+        per = {k: flat[j * n:(j + 1) * n] for j, k in enumerate(order)}
+        res = [tuple(per[k][i][None] for k in kinds) for i in range(n)]
+        return res if many else [r[0] for r in res]
+
+    def _forward_clips_yuv_native(self, ys, cbs, crs, mvs, par, side, std, mask, layout):
+        """Body of torch.ops.pnpvcve.generator_forward_clips_yuv: per-clip plane views -> the fp32 outputs (mask & 1), then the uint8
+        ones (mask & 2), then the packed 4:2:0 buffers (mask & 4), one freshly allocated tensor per clip."""
+        n = len(ys)
+        clips = [ops.Yuv420Frames(ys[b], cbs[b], crs[b]) for b in range(n)]
+        t, h, w = ys[0].shape
+        dev = ys[0].device
+        with torch.cuda.device(dev):
+            per = [self._alloc_yuv_outs(1, t, h, w, mask, layout, dev) for _ in range(n)]
+            outs = {k: (None, [p[k][1][0] for p in per]) for k in per[0]}
+            ws = self._get_workspace(n, t, h, w, dev, 'yuv', mask)
+            self._launch_clips_yuv(clips, mvs, par, side, outs, ws, t, h, w, std)
+        return [p[k][0][0] for k in ('f32', 'u8', 'yuv') if k in per[0] for p in per]
 
     def _forward_native(self, lrs_c, mvs_c, par_c, side):
         """Body of torch.ops.pnpvcve.generator_forward: contiguous fp32 CUDA tensors + the (3, n, t) host side info."""

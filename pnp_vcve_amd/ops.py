@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory and the stream; every computatio
 runs in libpnpvcve_hip.so.  All functions require CUDA(HIP) fp32 contiguous tensors (the frame converters and the metrics also take
 uint8 frames) and raise otherwise -- there is deliberately no CPU path.
 """
+import collections
 import contextlib
 import ctypes
 
@@ -659,4 +660,174 @@ def pixel_shuffle_conv(x, packed, act=0):
     out = torch.empty((2 * h, 2 * w, 64), device=x.device, dtype=torch.float32)
     _native.check(_native.lib().pnp_pixel_shuffle_conv_f32(_ptr(x), _ptr(packed), int(act), _ptr(out), h, w, _stream()),
                   'pnp_pixel_shuffle_conv_f32')
+    return out
+
+
+# ---------------------------------------------------------------- Y'CbCr 4:2:0 frames (include/pnpvcve.h states the arithmetic)
+_Yuv420Base = collections.namedtuple('Yuv420Frames', ['y', 'cb', 'cr'])
+
+
+class Yuv420Frames(_Yuv420Base):
+    """8-bit 4:2:0 frames as three uint8 CUDA VIEWS of wherever the decoder wrote them: y (n,t,h,w), cb and cr (n,t,h/2,w/2) (or
+    without the batch dimension: one clip).  Pitches, the chroma step and the frame strides are read from the tensors' strides: the
+    last-dimension stride is 1 for y and 1 (I420) or 2 (NV12 / NV21: cb and cr one byte apart in one buffer) for chroma.  Nothing is
+    copied; yuv420_views builds the views of a packed buffer."""
+    __slots__ = ()
+
+
+YUV_LAYOUTS = ('nv12', 'nv21', 'i420')
+
+
+def _yuv_standard(standard):
+    if isinstance(standard, str):
+        if standard not in _native.YUV_STANDARDS:
+            raise ValueError(f'yuv_standard must be one of {sorted(_native.YUV_STANDARDS)}, got {standard!r}')
+        return _native.YUV_STANDARDS[standard]
+    if int(standard) not in _native.YUV_STANDARDS.values():
+        raise ValueError(f'yuv_standard must be one of {sorted(_native.YUV_STANDARDS)} or 0..3, got {standard!r}')
+    return int(standard)
+
+
+def yuv420_views(buf, h, w, layout='nv12'):
+    """A packed uint8 buffer (..., 3h/2, pitch) -- or flat (..., nbytes) for I420 whose chroma rows are pitch/2 = w/2 apart -- ->
+    Yuv420Frames of views into it (no copy).  NV12 / NV21: h rows of Y, then h/2 rows of interleaved chroma pairs, all `pitch`
+    bytes apart.  I420: the Y plane, then the Cb plane and the Cr plane with rows pitch/2 apart (pitch even)."""
+    if layout not in YUV_LAYOUTS:
+        raise ValueError(f'layout must be one of {YUV_LAYOUTS}, got {layout!r}')
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise ValueError(f'4:2:0 frames need an even height and width, got {h} x {w}')
+    if buf.dtype != torch.uint8:
+        raise TypeError(f'buf must be uint8, got {buf.dtype}')
+    if buf.dim() >= 2 and buf.shape[-2] == h * 3 // 2 and buf.shape[-1] >= w and buf.stride(-1) == 1:
+        pitch = buf.shape[-1]
+        y = buf[..., :h, :w]
+        if layout != 'i420':
+            c = buf[..., h:, :w]
+            a, b = c[..., 0::2], c[..., 1::2]
+            return Yuv420Frames(y, a, b) if layout == 'nv12' else Yuv420Frames(y, b, a)
+        if pitch % 2 or buf.stride(-2) != pitch:
+            raise ValueError('an I420 buffer needs an even pitch and whole rows: its chroma rows are half a luma row long')
+        flat = buf.flatten(-2)          # (a view: the two last dimensions are contiguous)
+        n = (h // 2) * (pitch // 2)
+        cb = flat[..., h * pitch:h * pitch + n].unflatten(-1, (h // 2, pitch // 2))[..., :w // 2]
+        cr = flat[..., h * pitch + n:h * pitch + 2 * n].unflatten(-1, (h // 2, pitch // 2))[..., :w // 2]
+        return Yuv420Frames(y, cb, cr)
+    if layout == 'i420' and buf.dim() >= 1 and buf.shape[-1] == h * w * 3 // 2 and buf.stride(-1) == 1:
+        return yuv420_views(buf.unflatten(-1, (h * 3 // 2, w)), h, w, layout)
+    raise ValueError(f'buf must be (..., {h * 3 // 2}, pitch >= {w}) uint8 with a unit last stride, got {tuple(buf.shape)}')
+
+
+def _yuv_clip_desc(frames, what='frames'):
+    """Yuv420Frames of (t,h,w) / (t,h/2,w/2) views -> (_native.Yuv420Planes, t, h, w); every refusal a ValueError / TypeError raised
+    before any GPU work"""
+    if not isinstance(frames, Yuv420Frames):
+        raise TypeError(f'{what} must be ops.Yuv420Frames(y, cb, cr)')
+    y, cb, cr = frames
+    for name, x in (('y', y), ('cb', cb), ('cr', cr)):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise RuntimeError(f'{what}.{name} must be a CUDA/HIP tensor: the PnP-VCVE hot path has no CPU fallback')
+        if x.dtype != torch.uint8:
+            raise TypeError(f'{what}.{name} must be uint8, got {x.dtype}')
+        if x.dim() != 3:
+            raise ValueError(f'{what}.{name} must be (t,rows,cols) per clip, got {tuple(x.shape)}')
+    t, h, w = y.shape
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise ValueError(f'4:2:0 frames need an even height and width, got {h} x {w}')
+    if tuple(cb.shape) != (t, h // 2, w // 2) or tuple(cr.shape) != (t, h // 2, w // 2):
+        raise ValueError(f'cb and cr must be (t,h/2,w/2) = {(t, h // 2, w // 2)}, got {tuple(cb.shape)} and {tuple(cr.shape)}')
+    if y.stride(2) != 1:
+        raise ValueError(f'{what}.y must have a unit last stride, got {y.stride(2)}')
+    if cb.stride() != cr.stride() or cb.stride(2) not in (1, 2):
+        raise ValueError(f'{what}.cb and .cr must share their strides, with a last stride of 1 or 2: got {cb.stride()} and {cr.stride()}')
+    step = cb.stride(2)
+    if step == 2 and abs(cb.data_ptr() - cr.data_ptr()) != 1:
+        raise ValueError('chroma with a step of 2 must be interleaved: cb and cr one byte apart (NV12 / NV21)')
+    if y.stride(1) < w or cb.stride(1) < step * (w // 2) or (t > 1 and (y.stride(0) < 0 or cb.stride(0) < 0)):
+        raise ValueError(f'{what}: a pitch below the row\'s bytes (strides {y.stride()}, {cb.stride()})')
+    d = _native.Yuv420Planes(y.data_ptr(), cb.data_ptr(), cr.data_ptr(), y.stride(1), cb.stride(1), y.stride(0) if t > 1 else 0,
+                             cb.stride(0) if t > 1 else 0, step)
+    return d, t, h, w
+
+
+def _yuv_clips(frames, what='frames'):
+    """Yuv420Frames with or without the batch dimension -> (list of per-clip Yuv420Frames, lead shape)"""
+    if not isinstance(frames, Yuv420Frames):
+        raise TypeError(f'{what} must be ops.Yuv420Frames(y, cb, cr)')
+    if any(not isinstance(x, torch.Tensor) for x in frames):
+        raise TypeError(f'{what}: y, cb and cr must be tensors')
+    d = frames.y.dim()
+    if d not in (3, 4) or frames.cb.dim() != d or frames.cr.dim() != d:
+        raise ValueError(f'{what}: y, cb, cr must all be (n,t,rows,cols) or all (t,rows,cols), got {tuple(frames.y.shape)}, '
+                         f'{tuple(frames.cb.shape)}, {tuple(frames.cr.shape)}')
+    if d == 3:
+        return [frames], ()
+    n = frames.y.shape[0]
+    if frames.cb.shape[0] != n or frames.cr.shape[0] != n:
+        raise ValueError(f'{what}: y, cb and cr disagree in the batch size')
+    return [Yuv420Frames(frames.y[b], frames.cb[b], frames.cr[b]) for b in range(n)], (n,)
+
+
+def frames_from_yuv420(frames, standard='bt601-limited'):
+    """Yuv420Frames (n,t,...) or (t,...) -> (n,t,3,h,w) / (t,3,h,w) fp32 RGB planes, clamped to [0,1], chroma replicated: the
+    arithmetic of include/pnpvcve.h, bit-equal to tests/yuv_ref.py.  What generator.forward(Yuv420Frames) computes on, without this
+    fp32 clip."""
+    std = _yuv_standard(standard)
+    clips, lead = _yuv_clips(frames)
+    descs = [_yuv_clip_desc(c) for c in clips]
+    _, t, h, w = descs[0]
+    if any(d[1:] != (t, h, w) for d in descs):
+        raise ValueError('the clips of a batch must agree in shape')
+    dev = frames.y.device
+    with torch.cuda.device(dev):
+        out = torch.empty((len(clips), t, 3, h, w), device=dev, dtype=torch.float32)
+        for b, (d, _, _, _) in enumerate(descs):
+            if t:
+                _native.check(_native.lib().pnp_frames_from_yuv420(ctypes.byref(d), std, _ptr(out[b]), t, h, w, _stream()),
+                              'pnp_frames_from_yuv420')
+    return out if lead else out[0]
+
+
+def empty_yuv420(lead, h, w, layout, device):
+    """-> (packed uint8 buffer lead + (3h/2, w), its Yuv420Frames views)"""
+    buf = torch.empty(tuple(lead) + (h * 3 // 2, w), device=device, dtype=torch.uint8)
+    return buf, yuv420_views(buf, h, w, layout)
+
+
+def frames_to_yuv420(planes, standard='bt601-limited', layout='nv12', out=None):
+    """(n,t,3,h,w) or (t,3,h,w) fp32 CUDA planes -> (packed uint8 buffer (...,3h/2,w) in `layout`, its Yuv420Frames views): clamp,
+    luma, box-mean chroma, round half to even (include/pnpvcve.h).  out: Yuv420Frames views to write instead of a fresh buffer
+    (any pitch and address; returns (None, out))."""
+    std = _yuv_standard(standard)
+    planes = _chk(planes, 'planes')
+    if planes.dim() not in (4, 5) or planes.shape[-3] != 3:
+        raise ValueError(f'planes must be (n,t,3,h,w) or (t,3,h,w), got {tuple(planes.shape)}')
+    h, w = planes.shape[-2:]
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise ValueError(f'4:2:0 frames need an even height and width, got {h} x {w}')
+    lead = tuple(planes.shape[:-3])
+    with torch.cuda.device(planes.device):
+        buf = None
+        if out is None:
+            buf, out = empty_yuv420(lead, h, w, layout, planes.device)
+        clips, olead = _yuv_clips(out, 'out')
+        src = planes if planes.dim() == 5 else planes[None]
+        if len(clips) != src.shape[0]:
+            raise ValueError('out and planes disagree in the batch size')
+        for b, c in enumerate(clips):
+            d, t, oh, ow = _yuv_clip_desc(c, 'out')
+            if (t, oh, ow) != (src.shape[1], h, w):
+                raise ValueError(f'out is {(t, oh, ow)}, planes are {(src.shape[1], h, w)}')
+            if t:
+                _native.check(_native.lib().pnp_frames_to_yuv420(_ptr(src[b]), ctypes.byref(d), std, t, h, w, _stream()), 'pnp_frames_to_yuv420')
+    return buf, out
+
+
+def pack_lr_yuv420(frames, standard='bt601-limited', general=False):
+    """(include/pnpvcve_debug.h) one clip's Yuv420Frames (t,...) -> the (t,h,w,4) fp32 RGB0 conv source the forward unpacks them into;
+    general: the byte-load form whatever the alignment"""
+    d, t, h, w = _yuv_clip_desc(frames)
+    with torch.cuda.device(frames.y.device):
+        out = torch.empty((t, h, w, 4), device=frames.y.device, dtype=torch.float32)
+        _native.check(_native.lib().pnp_debug_pack_lr_yuv420(ctypes.byref(d), _yuv_standard(standard), _ptr(out), t, h, w, int(bool(general)),
+                                                             _stream()), 'pnp_debug_pack_lr_yuv420')
     return out

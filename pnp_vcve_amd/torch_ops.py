@@ -14,6 +14,10 @@ package).
                                                                 the same forward over clips given one by one (fp32 planes or uint8 HWC
                                                                 frames in; fp32 planes and / or uint8 HWC frames out, out_mask 1 | 2 | 3)
     torch.ops.pnpvcve.frames_from_rgb8(u8)                      RescaleToZeroOne + HWC->CHW of decoded frames
+    torch.ops.pnpvcve.generator_forward_clips_yuv(handle, y[], cb[], cr[], mvs[], par[], side, standard, out_mask, layout)
+                                                                the same forward on 8-bit 4:2:0 plane views (NV12 / NV21 / I420); fp32
+                                                                planes, uint8 HWC frames and / or packed 4:2:0 buffers out (out_mask 1..7)
+    torch.ops.pnpvcve.frames_from_yuv420(y, cb, cr, standard)   4:2:0 planes -> fp32 RGB planes (include/pnpvcve.h states the arithmetic)
 
     torch.ops.pnpvcve.conv3x3(srcs, packed_w, bias, gamma, packed_w1x1, par, residual, act)
                                                                 basicvsr_net.py:484, sr_backbone_utils.py:304-333 halves, iconvsr.py:365
@@ -121,6 +125,44 @@ def _(handle, lrs, mvs, par, side, out_mask):
                 continue
             t, (h, w) = x.shape[0], (x.shape[1:3] if x.dtype == torch.uint8 else x.shape[2:4])
             outs.append(x.new_empty((t, 3, h * s, w * s) if bit == 1 else (t, h * s, w * s, 3), dtype=dt))
+    return outs
+
+
+@torch.library.custom_op('pnpvcve::frames_from_yuv420', mutates_args=())
+def frames_from_yuv420(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, standard: int) -> torch.Tensor:
+    """uint8 views y (...,h,w), cb / cr (...,h/2,w/2) with 3 or 4 dimensions -> (...,3,h,w) fp32 RGB; standard = PNP_YUV_*"""
+    return ops.frames_from_yuv420(ops.Yuv420Frames(y, cb, cr), int(standard))
+
+
+@frames_from_yuv420.register_fake
+def _(y, cb, cr, standard):
+    return y.new_empty(tuple(y.shape[:-2]) + (3,) + tuple(y.shape[-2:]), dtype=torch.float32)
+
+
+@torch.library.custom_op('pnpvcve::generator_forward_clips_yuv', mutates_args=())
+def generator_forward_clips_yuv(handle: int, y: list[torch.Tensor], cb: list[torch.Tensor], cr: list[torch.Tensor], mvs: list[torch.Tensor],
+                                par: list[torch.Tensor], side: torch.Tensor, standard: int, out_mask: int, layout: int) -> list[torch.Tensor]:
+    """one clip per list entry: y[i] (t,h,w), cb[i] / cr[i] (t,h/2,w/2) uint8 views; -> per clip the fp32 planes (out_mask & 1), then
+    the uint8 frames (& 2), then the packed (t,3H/2,W) 4:2:0 buffers (& 4) in layout 0 'nv12' | 2 'i420' (ops.YUV_LAYOUTS; -1 = none)"""
+    m = _GENERATORS.get(handle)
+    if m is None:
+        raise RuntimeError(f'pnpvcve::generator_forward_clips_yuv: unknown generator handle {handle}')
+    return m._forward_clips_yuv_native(list(y), list(cb), list(cr), list(mvs), list(par), side, int(standard), int(out_mask),
+                                       ops.YUV_LAYOUTS[layout] if layout >= 0 else None)
+
+
+@generator_forward_clips_yuv.register_fake
+def _(handle, y, cb, cr, mvs, par, side, standard, out_mask, layout):
+    m = _GENERATORS.get(handle)
+    s = 4 if (m is not None and m.vsr) else 1
+    outs = []
+    for bit in (1, 2, 4):
+        for x in y:
+            if not out_mask & bit:
+                continue
+            t, h, w = x.shape
+            shape = {1: (t, 3, h * s, w * s), 2: (t, h * s, w * s, 3), 4: (t, h * s * 3 // 2, w * s)}[bit]
+            outs.append(x.new_empty(shape, dtype=torch.float32 if bit == 1 else torch.uint8))
     return outs
 
 
