@@ -41,6 +41,10 @@ int pnp_debug_wino_gate_word(const int* gate_word_dev);
  * PNP_ERR_BAD_ARG.  Process-wide, not thread-safe: a test hook. */
 int pnp_debug_wino_tile_rows(int row0, int nrows);
 
+/* A timeline buffer (the 16 u64 per block of pnp_conv3x3_wino_f32_ex; [1] sums the frame's chunks and every source segment of a tile)
+ * for the NEXT pnp_conv3x3_wino_ms_f32 calls (tile kernel only).  NULL = none.  Process-wide, not thread-safe: a tracing hook. */
+int pnp_debug_wino_ms_trace(void* trace_dev);
+
 /* The byte-frame unpacking in front of pnp_generator_forward_clips' convs, alone: lq_dev (t,h,w,3) uint8 -> lr4_dev (t,h,w,4) fp32
  * RGB0, every byte through the table of pnp_frames_from_rgb8.  any_size = 0: the form for whole 12-byte groups on a 4-aligned address
  * (PNP_ERR_BAD_ARG otherwise, before any launch); 1: the form pnp_generator_set_any_size adds, any address and any t*h*w. */

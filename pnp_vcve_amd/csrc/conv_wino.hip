@@ -136,10 +136,6 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
     const int H = a.H, W = a.W;
     const int tiles_x = (W + 15) >> 4;
     // MS with the ring as LDS-DMA loads: no run-time `last source?` branch inside a chunk (every chunk's wait counts its own requests).
-    // (MSF, the tile loop's last_seg and tqk, hreg[3] and the never-taken register branch of the MS weight requests only keep the
-    //  capture list of `chunk` as it was: without them no kernel computes anything else, but the register allocation of the MS and
-    //  gated kernels moves -- a change for a follow-up with a GPU A/B)
-    constexpr bool MSF = MS;
     // the rolling input transform cut at the tile seam: the branch kernels only (see the end of the tile loop)
     constexpr bool SEAM = PAR;
     if (a.gate) {      // (block-uniform: a scalar load)
@@ -212,7 +208,7 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
     //  tile (ty', tx') = (2 wave + (kq >> 1), 4 (kq & 1) + r), pixel (a, b) of it: see the epilogue)
 
     f32x4 acc[16][4];
-    f32x4 V[16], d0[4], d1[4], d2[4], d3[4], bf[2][4], breg[4], hreg[3], tt[4];
+    f32x4 V[16], d0[4], d1[4], d2[4], d3[4], bf[2][4], breg[4], hreg, tt[4];
     unsigned hoff[6];
 
     auto row_tf = [&](int i) {
@@ -225,17 +221,45 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
         V[4 * i + 3] = tt[1] - tt[3];
     };
     // per-lane offsets of the six halo float4 this thread moves per slab (element e = t + 256 i of the slab's LDS image), for the tile at
-    // (y0, x0); recomputed per tile from the laundered thread id so that they do not stay live as 12 more registers
+    // (y0, x0).  What does not depend on the tile -- halo row ry and halo column rx of each element -- is worked out once per block and
+    // kept packed in TWO registers, three fields each: ry << 5 | rx (10 bits) for elements 0-4, whose channel quad is the thread's own
+    // (e & 3 = t & 3), and ry << 7 | rx << 2 | quad (12 bits) for the sixth, which most threads clamp to the slab's last element.  Per
+    // tile a field unpacks to ((ry W + rx) 16 + quad) 16 bytes; the in-bounds test runs only where the tile's halo reaches over the
+    // frame's edge, which is block-uniform (a scalar branch): 93 % of a 720p frame's tiles take the unmasked form.  Recomputing all of
+    // it per tile from the thread id cost ~150 vector-ALU instructions with no MFMA beside them; three packed registers (14-bit fields
+    // with the quad) measured +0.4 %, two +0.7 %, the edge split alone nothing (profiles/wino_handover_ab.txt).  (The packed registers
+    // are laundered per use: left visible, the unpacking is loop-invariant and gets hoisted out of the tile loop -- twelve live registers
+    // again, at the register limit.)
+    unsigned hpk[2];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        int e = t + 256 * i;
+        e = e < NPX * 4 ? e : NPX * 4 - 1;
+        const int pl = e >> 2, quad = e & 3, ry = (pl * 3641) >> 16, col = pl - ry * HP;      // pl / 18 for pl < 324
+        const int rx = col < 9 ? 2 * col : 2 * col - 17;
+        const unsigned f = i < 5 ? (unsigned)(ry << 5 | rx) : (unsigned)(ry << 7 | rx << 2 | quad);
+        hpk[i / 3] = (i % 3) ? (hpk[i / 3] | f << (10 * (i % 3))) : f;
+    }
     auto halo_offsets = [&](int tq, int y0, int x0) {
 #pragma unroll
+        for (int j = 0; j < 2; ++j) asm volatile("" : "+v"(hpk[j]));
+        const bool edge = y0 < 1 || x0 < 1 || y0 + 17 > H || x0 + 17 > W;
+        const unsigned q0 = (unsigned)tq & 3u;
+        unsigned ryv[6], rxv[6];
+#pragma unroll
         for (int i = 0; i < 6; ++i) {
-            int e = tq + 256 * i;
-            e = e < NPX * 4 ? e : NPX * 4 - 1;
-            const int pl = e >> 2, quad = e & 3, ry = (pl * 3641) >> 16, col = pl - ry * HP;      // pl / 18 for pl < 324
-            const int rx = col < 9 ? 2 * col : 2 * col - 17;
-            const int gy = y0 - 1 + ry, gx = x0 - 1 + rx;
-            const bool inb = (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-            hoff[i] = inb ? (unsigned)(ry * W + rx) * 256u + (unsigned)quad * 16u : OOBW;
+            const unsigned f = hpk[i / 3] >> (10 * (i % 3));
+            ryv[i] = i < 5 ? (f >> 5) & 31u : f >> 7;
+            rxv[i] = i < 5 ? f & 31u : (f >> 2) & 31u;
+            hoff[i] = (((ryv[i] * (unsigned)W + rxv[i]) << 4) + (i < 5 ? q0 : f & 3u)) << 4;
+        }
+        if (edge) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                const int gy = y0 - 1 + (int)ryv[i], gx = x0 - 1 + (int)rxv[i];
+                const bool inb = (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
+                hoff[i] = inb ? hoff[i] : OOBW;
+            }
         }
     };
     // partition values of the wave's pixels for the tile at (y0, x0): global -> registers (pv_request), then -> LDS, signed, with the
@@ -442,11 +466,10 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
         if constexpr (!MS) halo_offsets(tq, nty0, ntx0);
         const unsigned tq16 = (unsigned)tq * 16u;
         const int wave_s = __builtin_amdgcn_readfirstlane(tq >> 6);      // the wave's index as a scalar (LDS-DMA destinations go through M0)
-        int tqk = tq;            // the thread id the chunks derive their per-lane constants from
+        const int tqk = tq;      // the thread id the chunks derive their per-lane constants from
         // MS: per segment (= one 64-channel source): where its weight image starts, descriptor, base, chunk and piece stride of the next
         // segment's (after the tile's last source: the next tile's RGB chunks), and the tile origin of the slabs it refills
         unsigned u_so = 0, ref_so = nso, nx_base = 0, nx_cs = 16384, nx_ps = 4096;
-        bool last_seg = true;
         __amdgpu_buffer_rsrc_t r_nx = r_u;
         int need = 7, fold = -1;
         float foldc = 0.f;
@@ -576,10 +599,8 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                     if ((g & 15) < 4 && !(pj == 3 && NEXT_IS_BR)) {
                         // (MS, the tile's last chunk: the next one is an RGB chunk of the next tile, which reads its own fragments -- the read
                         //  here is then of no use, and harmless; a run-time `last source?` test per gap would cut the straight-line schedule)
-                        if (MSF || !(MS && C == 15 && pj == 3 && last_seg)) {
-                            const unsigned nb = pj < 3 ? (C & 3) * 16384 + (pj + 1) * 4096 : ((C + 1) & 3) * 16384;
-                            bf[(pj + 1) & 1][g & 3] = lds4(nb + bl + (g & 3) * 1024);
-                        }
+                        const unsigned nb = pj < 3 ? (C & 3) * 16384 + (pj + 1) * 4096 : ((C + 1) & 3) * 16384;
+                        bf[(pj + 1) & 1][g & 3] = lds4(nb + bl + (g & 3) * 1024);
                     }
                     if constexpr (MS) {
                         // the chunk three ahead: this source's, the next source's first chunks, or (last source) the next tile's RGB chunks,
@@ -590,11 +611,6 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                             auto* dst = (__attribute__((address_space(3))) void*)(smem + (NC & 3) * 16384 + (g - 4) * 4096 + wave_s * 1024);
                             if (C < 13) __builtin_amdgcn_raw_ptr_buffer_load_lds(r_u, dst, 16, (int)tq16, (int)(u_so + (C + 3) * 16384 + (g - 4) * 4096), 0, 0);
                             else __builtin_amdgcn_raw_ptr_buffer_load_lds(r_nx, dst, 16, (int)tq16, (int)(nx_base + (C - 13) * nx_cs + (g - 4) * nx_ps), 0, 0);
-                        } else if (g >= 4 && g < 8) {      // (never taken: see MSF)
-                            if (C < 13) breg[g - 4] = bload4(r_u, tq16, u_so + (C + 3) * 16384 + (g - 4) * 4096);
-                            else if (MSF) breg[g - 4] = bload4(r_nx, tq16, nx_base + (C - 13) * nx_cs + (g - 4) * nx_ps);
-                            else if (!last_seg) breg[g - 4] = bload4(r_u, tq16, nx_base + (C - 13) * 16384 + (g - 4) * 4096);
-                            else if (g == 4) breg[0] = bload4(r_urgb, tq16, (C - 13) * 4096);
                         }
                     } else if (!PAR && g >= 4 && g < 8) {
                         // chunk C + 3 straight into its ring slot (the slot of chunk C - 1: every wave left it before the barrier at the top of
@@ -615,11 +631,11 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                         auto* dst = (__attribute__((address_space(3))) void*)(smem + RING_B + S * SLAB_B + i * 4096 + wave_s * 1024);
                         __builtin_amdgcn_raw_ptr_buffer_load_lds(r_src, dst, 16, (int)hoff[i], (int)(ref_so + S * 64), 0, 0);
                     }
-                    if (PG == 2 && g == 13) hreg[0] = bload4(r_src, hoff[5], ref_so + S * 64);
+                    if (PG == 2 && g == 13) hreg = bload4(r_src, hoff[5], ref_so + S * 64);
                     if (PG == 3 && g == 8) {
                         int e = tqk + 256 * 5;
                         e = e < NPX * 4 ? e : NPX * 4 - 1;
-                        *reinterpret_cast<f32x4*>(smem + RING_B + S * SLAB_B + e * 16) = hreg[0];
+                        *reinterpret_cast<f32x4*>(smem + RING_B + S * SLAB_B + e * 16) = hreg;
                     }
                     // MS: the next tile's RGB halo, requested in step 1 (this tile's RGB patch was read before its first chunk) -- by every
                     // segment: the same pixels again, but no run-time branch in the chunk and no value that lives across one
@@ -816,7 +832,7 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
             // ---- then one segment of 16 chunks per 64-channel source
             const int nw = a.nsrc;
             for (int ks = 0; ks < nw; ++ks) {
-                last_seg = ks + 1 >= nw;
+                const bool last_seg = ks + 1 >= nw;
                 u_so = a.u_off[ks];
                 r_nx = rsrc_of(last_seg ? a.Urgb : a.ubase, last_seg ? 4u * 4096u : OOBW);
                 nx_base = last_seg ? 0u : a.u_off[ks + 1];

@@ -184,6 +184,11 @@ static int wino_ms_op(int nsrc, const float* const* srcs, const float* const* wi
                       int h, int w, int units, void* st);
 
 static int g_debug_wino_row0 = 0, g_debug_wino_rows = 0;
+static void* g_debug_wino_ms_trace = nullptr;
+int pnp_debug_wino_ms_trace(void* trace_dev) {
+    g_debug_wino_ms_trace = trace_dev;
+    return 0;
+}
 int pnp_debug_wino_tile_rows(int row0, int nrows) {
     if (row0 < 0 || nrows < 0) return PNP_ERR_BAD_ARG;
     g_debug_wino_row0 = row0;
@@ -206,7 +211,7 @@ static int wino_ms_op(int nsrc, const float* const* srcs, const float* const* wi
     if (nsrc < 2 || nsrc > 4 || !srcs || !wino_w || !out || act < 0 || act > 2) return PNP_ERR_BAD_ARG;
     if (!op_map_fits(h, w)) return PNP_ERR_UNSUPPORTED;
     static const int channels[4] = {4, 64, 64, 64};
-    ConvArgs a = op_conv_args(nsrc, srcs, channels, bias, nullptr, nullptr, nullptr, nullptr, act, out, h, w, nullptr);
+    ConvArgs a = op_conv_args(nsrc, srcs, channels, bias, nullptr, nullptr, nullptr, nullptr, act, out, h, w, units ? nullptr : g_debug_wino_ms_trace);
     for (int s = 0; s < nsrc; ++s) {
         if (!srcs[s] || !wino_w[s]) return PNP_ERR_BAD_ARG;
         a.wwino_src[s] = wino_w[s];

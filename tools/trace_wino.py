@@ -1,5 +1,6 @@
 """Per-tile cycle split of the Winograd conv (csrc/conv_wino.hip) from its timeline buffer: K loop vs epilogue, in-kernel clock,
-block lifetimes.    python tools/trace_wino.py [--h 720 --w 1280] [--kind back|hr|front|front_dense]"""
+block lifetimes.    python tools/trace_wino.py [--h 720 --w 1280] [--kind back|hr|front|front_dense|ms]
+--kind ms: the multi-source input conv (frame + 1, 2, 3 sources); a source segment's cycles = the K-loop difference between two counts."""
 import argparse
 import ctypes
 import os
@@ -53,11 +54,28 @@ def main():
         # no partition record anywhere (an I frame): the branch chunks hold no MFMA -- what the PAR structure costs by itself
         'front_zero': lambda tr: ops.conv3x3_wino(x, ug, bias=b, gamma=gamma, wino_w1x1=up, par=par * 0, par_flags=flags, act=1, trace=tr),
     }
+    # the input conv over [frame, n wide sources]: its K loop is the frame's four chunks + one 16-chunk segment per source
+    lr4 = torch.rand(h, w, 4, device=dev, generator=g)
+    lr4[..., 3] = 0
+    urgb = ops.wino_rgb_image(ops.pack_conv3x3(torch.randn(64, 3, 3, 3, device=dev, generator=g) * 0.05, cbase=0, csrc=3))
+    imgs = torch.stack([u, ug, u])
+
+    def ms(nwide):
+        def run(tr):
+            _native.lib().pnp_debug_wino_ms_trace(ctypes.c_void_p(tr.data_ptr()))
+            try:
+                return ops.conv3x3_wino_ms([lr4] + [x, res, x][:nwide], [urgb] + [imgs[k] for k in range(nwide)], bias=b, act=2)
+            finally:
+                _native.lib().pnp_debug_wino_ms_trace(None)
+        return run
+    for nwide in (1, 2, 3):
+        kinds[f'ms{nwide}'] = ms(nwide)
+    ms_k = {}
     if args.kind == 'all':
         tr0 = torch.zeros(256 * 16, dtype=torch.int64, device=dev)
         print('front_fold == front (branch kernel), bit for bit:', bool(torch.equal(kinds['front_fold'](tr0), kinds['front'](tr0))), flush=True)
     for name, fn in kinds.items():
-        if args.kind not in ('all', name):
+        if args.kind not in ('all', name) and not (args.kind == 'ms' and name.startswith('ms')):
             continue
         tr = torch.zeros(256 * 16, dtype=torch.int64, device=dev)
         for _ in range(20):        # the clock settles under load
@@ -72,10 +90,16 @@ def main():
               f'epilogue {np.median(d[:, 2] / n):7.0f}  (branch chunks {np.median(d[:, 8] / n):6.0f})  other {np.median((life - d[:, 1] - d[:, 2]) / n):6.0f}  '
               f'lifetime median {np.median(life):9.0f} max {life.max():9.0f} cycles  clock {np.median(clk):.2f} GHz  '
               f'launch {(d[:, 14].max() - d[:, 13].min()) * 10e-3:.1f} us', flush=True)
+        if name.startswith('ms'):
+            ms_k[int(name[2:])] = (np.median(d[:, 1] / n), np.median(life / n))
         q = d[d[:, 4] > 0]
         if len(q):      # blocks with a quadrant unit behind their last whole tile: wait for loads + barrier | four steps | output
             print(f'{"":12s} quadrant units {len(q)}: start -> first step {np.median(q[:, 5] - q[:, 4]):6.0f} cycles, steps {np.median(q[:, 6] - q[:, 5]):6.0f}, '
                   f'output {np.median(q[:, 3] - q[:, 6]):6.0f}; lifetime of these blocks {np.median(q[:, 3] - q[:, 0]):9.0f} vs the others {np.median((d[d[:, 4] == 0])[:, 3] - (d[d[:, 4] == 0])[:, 0]):9.0f}', flush=True)
+    if len(ms_k) == 3:
+        (k1, l1), (k2, l2), (k3, l3) = ms_k[1], ms_k[2], ms_k[3]
+        print(f'{"ms":12s} cycles per source segment (K loop): second {k2 - k1:.0f}, third {k3 - k2:.0f}; frame chunks + first segment {k1:.0f}; '
+              f'per tile with everything: {l1:.0f} / {l2:.0f} / {l3:.0f} (a segment: {l2 - l1:.0f}, {l3 - l2:.0f})', flush=True)
 
 
 if __name__ == '__main__':
