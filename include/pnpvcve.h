@@ -272,6 +272,36 @@ int pnp_frames_from_yuv420(const pnp_yuv420_planes* in_host_desc, int yuv_standa
 int pnp_frames_to_yuv420(const float* planes_dev, const pnp_yuv420_planes* out_host_desc, int yuv_standard, int n, int h, int w,
                          void* stream);
 
+/* Plane metrics of two 4:2:0 clips (plane_metrics.hip): what a codec-enhancement result is scored by -- PSNR / SSIM of the Y, the Cb
+ * and the Cr plane, each on its own, read from the 8-bit planes where they lie (1.5 B per pixel and clip; no RGB, no second rounding).
+ * The reference has no such path; the statistics are the ones of pnp_psnr_sse_f32 / pnp_ssim_partials_f32 below, per plane.  This is
+ * the ONE statement of the arithmetic.
+ *   a_host_desc, b_host_desc: HOST structs of device addresses, `frames` frames of h x w each (h, w even), described each on its own
+ *   (the generator's NV12 output against an I420 ground truth): any byte address, any pitch that holds a row, any frame stride,
+ *   c_step 1 | 2.  The reading rule is the one above: no byte outside [plane, plane + rows * pitch) of a plane is read; aligned
+ *   dword loads where the dwords lie inside the plane's rows, byte loads at heads, tails and misaligned rows (the same values).
+ *   crop_border (even): the Y plane is cropped by crop_border on every side, the chroma planes by crop_border / 2.
+ * PSNR: sse_dev (frames, 3) uint64 = the exact sum of squared byte differences of the cropped Y, Cb and Cr plane of each frame
+ *   (integer: order-independent, deterministic).  The host forms PSNR_p = 10 log10(255^2 N_p / SSE_p) with N_Y = (h - 2c)(w - 2c),
+ *   N_C = (h/2 - c/2)(w/2 - c/2), c = crop_border; infinite where SSE_p = 0; PSNR_YUV = (6 PSNR_Y + PSNR_Cb + PSNR_Cr) / 8.
+ * SSIM: pnp_ssim_partials_f32's window, tiling and summation order on the bytes as they are: the partials of a plane are, bit for
+ *   bit, those of pnp_ssim_partials_f32 on the (frames,1,rows,cols) fp32 plane (float)byte / 255.0f with the plane's crop.
+ *   pnp_ssim_blocks_yuv420: the blocks of one plane (plane = PNP_PLANE_Y | PNP_PLANE_CB | PNP_PLANE_CR): pnp_ssim_blocks(h, w, crop)
+ *   for Y, pnp_ssim_blocks(h/2, w/2, crop/2) for Cb / Cr; 0 when it cannot run.  partials_dev: for each plane of plane_mask in the
+ *   order Y, Cb, Cr, [frames][blocks of that plane] doubles, one plane after the other; SSIM_p(frame) = sum of its partials in index
+ *   order / ((rows - 2 crop_p - 10)(cols - 2 crop_p - 10)).
+ * PNP_ERR_BAD_ARG, decided on the host before any HIP call: a NULL descriptor, plane or output; frames < 1; odd or < 2 h / w; a
+ * negative or odd crop_border; 2 crop >= h or w; c_step not 1 or 2; a pitch below the row's bytes; plane_mask 0 or beyond 7; for
+ * SSIM a cropped plane of the mask smaller than 11x11. */
+#define PNP_PLANE_Y 1
+#define PNP_PLANE_CB 2
+#define PNP_PLANE_CR 4
+int pnp_psnr_sse_yuv420(const pnp_yuv420_planes* a_host_desc, const pnp_yuv420_planes* b_host_desc,
+                        unsigned long long* sse_dev, int frames, int h, int w, int crop_border, void* stream);
+int pnp_ssim_blocks_yuv420(int h, int w, int crop_border, int plane);
+int pnp_ssim_partials_yuv420(const pnp_yuv420_planes* a_host_desc, const pnp_yuv420_planes* b_host_desc, int plane_mask,
+                             double* partials_dev, int frames, int h, int w, int crop_border, void* stream);
+
 /* Optional per-launch timing with HIP events recorded on the caller's stream around every
  * kernel of pnp_generator_forward (measurement aid for bench.py; replaces the reference's
  * wall-clock print, mmedit/models/restorers/basicvsr.py:176-182).  Enable, run forwards,

@@ -41,6 +41,7 @@ FRAMES_F32_NCHW, FRAMES_U8_HWC = 0, 1        # PNP_FRAMES_*
 OUT_F32, OUT_U8, OUT_YUV420 = 1, 2, 4        # PNP_OUT_* (a mask; OUT_YUV420 on pnp_generator_forward_clips_yuv only)
 YUV_STANDARDS = {'bt601-limited': 0, 'bt601-full': 1, 'bt709-limited': 2, 'bt709-full': 3}      # PNP_YUV_*
 COLOR_NONE, COLOR_Y = 0, 1                   # PNP_COLOR_* (the metrics' convert_to)
+PLANE_Y, PLANE_CB, PLANE_CR = 1, 2, 4        # PNP_PLANE_* (a mask: the planes pnp_ssim_partials_yuv420 scores)
 
 # name -> (restype, argtypes); every symbol include/pnpvcve.h declares
 SIGNATURES = {
@@ -76,6 +77,9 @@ SIGNATURES = {
     'pnp_generator_workspace_bytes_yuv': (c_int64, [c_void_p, c_int, c_int, c_int, c_int]),
     'pnp_frames_from_yuv420': (c_int, [POINTER(Yuv420Planes), c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     'pnp_frames_to_yuv420': (c_int, [c_void_p, POINTER(Yuv420Planes), c_int, c_int, c_int, c_int, c_void_p]),
+    'pnp_psnr_sse_yuv420': (c_int, [POINTER(Yuv420Planes), POINTER(Yuv420Planes), c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'pnp_ssim_blocks_yuv420': (c_int, [c_int, c_int, c_int, c_int]),
+    'pnp_ssim_partials_yuv420': (c_int, [POINTER(Yuv420Planes), POINTER(Yuv420Planes), c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'pnp_generator_set_precision': (c_int, [c_void_p, c_int]),
     'pnp_generator_get_precision': (c_int, [c_void_p]),
     'pnp_generator_set_option': (c_int, [c_void_p, c_int, c_int]),

@@ -12,8 +12,15 @@ def _to_device(data, device, byte_frames=False, byte_metrics=False):
     byte_frames: frames uploaded as uint8 stay what the decoder made -- `lq` is the (n,T,H,W,3) uint8 tensor itself, which the
     generator reads directly (generator.forward's byte frames), and `gt` becomes fp32 planes in one kernel (ops.frames_from_rgb8:
     the same 256 values as the loop below, bit for bit).
-    byte_metrics (with byte_frames): `gt` stays the (n,T,H,W,3) uint8 tensor too -- the device metrics read the bytes."""
+    byte_metrics (with byte_frames): `gt` stays the (n,T,H,W,3) uint8 tensor too -- the device metrics read the bytes.
+    Raw 4:2:0 clips (Yuv420ClipFolderDataset: `lq_yuv` / `gt_yuv`, packed (n,T,3h/2,w) uint8) are uploaded as they are, 1.5 B per
+    pixel, and become ops.Yuv420Frames views of those buffers (`lq`, `gt`) in the layout the sample's meta names: nothing is converted."""
     out = {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in data.items()}
+    for k in ('lq', 'gt'):
+        if k + '_yuv' in out:
+            from .ops import yuv420_views
+            buf = out.pop(k + '_yuv')                                      # (n, T, 3h/2, w)
+            out[k] = yuv420_views(buf, buf.shape[-2] * 2 // 3, buf.shape[-1], data['meta'][0]['layout'])
     if byte_frames:
         from .ops import frames_from_rgb8
         if 'lq_u8' in out:
@@ -35,8 +42,11 @@ def _to_device(data, device, byte_frames=False, byte_metrics=False):
     if 'mv_records' in out:
         from .ops import rasterise_side_info
         rec, rf = out.pop('mv_records'), out.pop('rec_frame')
-        t = out['lq'].shape[1]
-        h, w = out['lq'].shape[2:4] if out['lq'].dtype == torch.uint8 else out['lq'].shape[-2:]
+        if isinstance(out['lq'], tuple):           # ops.Yuv420Frames
+            t, (h, w) = out['lq'].y.shape[1], out['lq'].y.shape[-2:]
+        else:
+            t = out['lq'].shape[1]
+            h, w = out['lq'].shape[2:4] if out['lq'].dtype == torch.uint8 else out['lq'].shape[-2:]
         sl = [float(v) for v in data['slices'].reshape(-1)[:t]]
         mvs, par = rasterise_side_info(rec.float(), rf.int(), sl, h, w)
         out['mvs'], out['partitions'] = mvs.unsqueeze(0), par.unsqueeze(0)
@@ -91,8 +101,9 @@ class ClipPrefetcher:
             if ev is not None:
                 torch.cuda.current_stream(self.device).wait_event(ev)
                 for v in dev.values():
-                    if torch.is_tensor(v):
-                        v.record_stream(torch.cuda.current_stream(self.device))
+                    for x in (v if isinstance(v, tuple) else (v,)):        # (ops.Yuv420Frames: views of one uploaded buffer)
+                        if torch.is_tensor(x):
+                            x.record_stream(torch.cuda.current_stream(self.device))
             yield dev
 
 
@@ -109,14 +120,23 @@ def single_gpu_test(model, dataset, save_image=False, save_path=None, device='cu
 GENERATOR_INPUTS = ('lq', 'QPs', 'slices', 'mvs', 'base_QPs', 'partitions')
 
 
+def _frames(x):
+    """the frame count of a clip's `lq`: a (n,t,...) tensor or ops.Yuv420Frames of such views"""
+    return x.y.shape[1] if isinstance(x, tuple) else x.shape[1]
+
+
 def _pairable(a, b):
     """two clips can go through the generator as one batch: same shapes of everything it reads"""
+    if isinstance(a.get('lq'), tuple) or isinstance(b.get('lq'), tuple):       # ops.Yuv420Frames: the Y planes stand for the frames
+        if not (isinstance(a.get('lq'), tuple) and isinstance(b.get('lq'), tuple)):
+            return False
+        a, b = dict(a, lq=a['lq'].y), dict(b, lq=b['lq'].y)
     return all(torch.is_tensor(a.get(k)) and torch.is_tensor(b.get(k)) and a[k].shape == b[k].shape and a[k].device == b[k].device
                for k in GENERATOR_INPUTS)
 
 
 def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cuda', metrics=('PSNR', 'SSIM'), clips_in_flight=1,
-                   byte_frames=False, byte_metrics=False):
+                   byte_frames=False, byte_metrics=False, yuv_frames=False, yuv_out_layout='i420'):
     """Returns, on every rank, the ordered per-clip results [{'eval_result': {...}}, ...].
 
     clips_in_flight = 2: two clips of equal shape are enhanced by ONE generator call (a batch of two), which the generator runs
@@ -134,7 +154,13 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
     byte_metrics (default off; implies byte_frames): the metrics read bytes as well -- `gt` stays the decoder's uint8 frames, the
     generator is asked for uint8 frames only, with or without save_image, and PSNR / SSIM are computed from the two byte clips
     (ops.psnr_frames / ssim_frames: 6 B per pixel and frame instead of 24, and no fp32 copy of either clip).  The same values: the
-    metrics round the fp32 planes to exactly these bytes."""
+    metrics round the fp32 planes to exactly these bytes.
+
+    yuv_frames (default off; a dataset of raw 4:2:0 clips, Yuv420ClipFolderDataset): the generator reads the decoder's planes and is
+    asked for packed 4:2:0 in `yuv_out_layout` ('i420' | 'nv12') ONLY, the ground truth stays 8-bit planes on the device, the metrics
+    are the plane metrics of BasicVSR.evaluate (ops.psnr_yuv420 / ssim_yuv420: 'PSNR' / 'SSIM' score the Y plane; 'PSNR_U', 'PSNR_V',
+    'SSIM_U', 'SSIM_V', 'PSNR_YUV' are accepted too), and save_image writes <save_path>/<clip>.yuv -- exactly the bytes of
+    ops.frames_to_yuv420(fp32 output, standard, layout).  A pair goes through generator.forward_clips by pointer, as under byte_frames."""
     import time
     model.eval()
     rank, world = get_dist_info()
@@ -148,8 +174,19 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
 
     byte_frames = (bool(byte_frames) or bool(byte_metrics)) and dev.type == 'cuda' and hasattr(model, 'generator') and not getattr(model, 'psnr_only', False)
     byte_metrics = bool(byte_metrics) and byte_frames
+    yuv_frames = bool(yuv_frames)
+    if yuv_frames:
+        if dev.type != 'cuda' or not hasattr(model, 'generator') or getattr(model, 'psnr_only', False):
+            raise ValueError('yuv_frames runs the generator on the GPU: a CUDA/HIP device and a model with a generator (not psnr_only)')
+        if byte_frames:
+            raise ValueError('yuv_frames and byte_frames / byte_metrics are two boundaries: pick one')
+        if yuv_out_layout not in ('i420', 'nv12'):
+            raise ValueError(f"yuv_out_layout must be 'i420' or 'nv12', got {yuv_out_layout!r}")
+    yuv_standard = getattr(dataset, 'yuv_standard', 'bt601-limited')
     out_dtype = None
-    if byte_metrics:
+    if yuv_frames:
+        out_dtype = yuv_out_layout
+    elif byte_metrics:
         out_dtype = torch.uint8
     elif byte_frames:
         test_cfg = getattr(model, 'test_cfg', None)
@@ -159,11 +196,13 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
     def finish(data, out=None, fps=None):
         with torch.no_grad():
             kw = {} if out is None else {'precomputed_output': out}
-            if byte_frames:
+            if byte_frames or yuv_frames:
                 kw['out_dtype'] = out_dtype
+            if yuv_frames:
+                kw['yuv_standard'] = yuv_standard
             res = model(test_mode=True, save_image=save_image, save_path=save_path, **kw, **data)
         if fps is None:
-            fps = data['lq'].shape[1] / model.last_forward_seconds if getattr(model, 'last_forward_seconds', None) else 0.0
+            fps = _frames(data['lq']) / model.last_forward_seconds if getattr(model, 'last_forward_seconds', None) else 0.0
         local.append([float(res['eval_result'].get(m, float('nan'))) for m in metrics] + [fps])
 
     held = None
@@ -178,11 +217,12 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
             finish(held)
             held = data
             continue
-        if byte_frames:         # the two clips where they are: no concatenation
+        if byte_frames or yuv_frames:         # the two clips where they are: no concatenation
             with torch.no_grad():
                 torch.cuda.synchronize()
                 t0 = time.time()
-                outs = model.generator.forward_clips([tuple(c[k] for k in GENERATOR_INPUTS) for c in (held, data)], out_dtype=out_dtype)
+                kw = {'yuv_standard': yuv_standard} if yuv_frames else {}
+                outs = model.generator.forward_clips([tuple(c[k] for k in GENERATOR_INPUTS) for c in (held, data)], out_dtype=out_dtype, **kw)
                 torch.cuda.synchronize()
                 dt = time.time() - t0
         else:
@@ -195,7 +235,7 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
                 dt = time.time() - t0
             outs = (out[0:1], out[1:2])
         model.last_forward_seconds = dt
-        fps = (held['lq'].shape[1] + data['lq'].shape[1]) / dt
+        fps = (_frames(held['lq']) + _frames(data['lq'])) / dt
         finish(held, outs[0], fps)
         finish(data, outs[1], fps)
         held = None

@@ -1,0 +1,283 @@
+// Plane PSNR / SSIM of 8-bit 4:2:0 clips (include/pnpvcve.h, pnp_psnr_sse_yuv420 / pnp_ssim_partials_yuv420): the statistics of
+// metrics.hip read from the decoder's planes where they lie -- NV12 / NV21 / I420, any address and pitch, each of the two clips
+// described on its own -- 1.5 B per pixel and clip, no RGB and no fp32 copy in between.  What a codec-enhancement result is scored by:
+// Y, Cb and Cr on their own (and the 6:1:1 mean the host forms).  plane_load.h fetches; the statistics are metrics.hip's.
+#include "plane_load.h"
+#include "prep.h"
+#include "yuv.h"
+#include <cmath>
+
+namespace {
+
+// The chroma of one clip: paired (NV12 / NV21: one load gives both planes; c[0] is the pair at the lower address and cr_first says
+// which plane that is) or two planes of their own (I420; c[0] = Cb, c[1] = Cr).
+struct ChromaSrc {
+    PnpPlaneSrc c[2];
+    int paired, cr_first;
+};
+
+PnpPlaneSrc luma_src(const pnp_yuv420_planes& p, int h, int w) { return PnpPlaneSrc{p.y, p.y_pitch, p.y_frame, 1, h, w}; }
+
+ChromaSrc chroma_src(const pnp_yuv420_planes& p, int h, int w) {
+    ChromaSrc s;
+    const int rows = h / 2, cols = w / 2;
+    const uintptr_t cb = reinterpret_cast<uintptr_t>(p.cb), cr = reinterpret_cast<uintptr_t>(p.cr);
+    s.paired = p.c_step == 2 && (cb > cr ? cb - cr : cr - cb) == 1;
+    s.cr_first = cr < cb;
+    if (s.paired) {
+        s.c[0] = s.c[1] = PnpPlaneSrc{s.cr_first ? p.cr : p.cb, p.c_pitch, p.c_frame, 2, rows, 2 * cols};
+    } else {
+        const int rowbytes = p.c_step * (cols - 1) + 1;
+        s.c[0] = PnpPlaneSrc{p.cb, p.c_pitch, p.c_frame, p.c_step, rows, rowbytes};
+        s.c[1] = PnpPlaneSrc{p.cr, p.c_pitch, p.c_frame, p.c_step, rows, rowbytes};
+    }
+    return s;
+}
+
+// sum over the four bytes of (x_j - y_j)^2; absent samples are 0 in both words
+__device__ __forceinline__ unsigned sq4(unsigned x, unsigned y) {
+    unsigned e = 0;
+#pragma unroll
+    for (int k = 0; k < 32; k += 8) {
+        const int d = (int)((x >> k) & 255u) - (int)((y >> k) & 255u);
+        e += (unsigned)(d * d);
+    }
+    return e;
+}
+
+__device__ __forceinline__ void load_chroma4(const ChromaSrc& s, long f, int row, int col, int npix, unsigned& cb, unsigned& cr) {
+    unsigned o[2];
+    if (s.paired) {
+        pnp_plane_load4(s.c[0], f, row, col, npix, o);
+        cb = s.cr_first ? o[1] : o[0];
+        cr = s.cr_first ? o[0] : o[1];
+    } else {
+        pnp_plane_load4(s.c[0], f, row, col, npix, o);
+        cb = o[0];
+        pnp_plane_load4(s.c[1], f, row, col, npix, o);
+        cr = o[0];
+    }
+}
+
+struct PsnrYuvArgs {
+    PnpPlaneSrc ay, by;
+    ChromaSrc ac, bc;
+    PnpPlaneRuns ry, rc;            // the cropped Y plane; the cropped chroma planes (one group = four Cb and four Cr samples)
+    unsigned long long* sse;        // (frames, 3), zeroed by the launcher
+};
+
+// The exact integer SSE of the three planes in ONE launch.  A block is 64 x 4 threads: a wave walks the groups of one row (64 groups =
+// 256 contiguous bytes a step), the block's four waves and the grid's x walk the rows -- first the Y plane's, then the chroma planes'
+// -- so a wave never diverges and nothing is divided.  Integer sums and one integer atomic per block and plane: psnr_sse_kernel's
+// scheme, order-independent and deterministic.
+__global__ __launch_bounds__(256) void psnr_yuv420_kernel(const PsnrYuvArgs s) {
+    const long frame = blockIdx.y;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    unsigned long long acc[3] = {0, 0, 0};
+    const int total = s.ry.rows + s.rc.rows;
+    for (int r = blockIdx.x * 4 + ty; r < total; r += gridDim.x * 4) {
+        int row, col, npix;
+        if (r < s.ry.rows) {
+#pragma unroll 4
+            for (int gx = tx; gx < s.ry.gpr; gx += 64) {
+                pnp_plane_group(s.ry, r, gx, row, col, npix);
+                unsigned a[2], b[2];
+                pnp_plane_load4(s.ay, frame, row, col, npix, a);
+                pnp_plane_load4(s.by, frame, row, col, npix, b);
+                acc[0] += sq4(a[0], b[0]);
+            }
+        } else {
+#pragma unroll 2
+            for (int gx = tx; gx < s.rc.gpr; gx += 64) {
+                pnp_plane_group(s.rc, r - s.ry.rows, gx, row, col, npix);
+                unsigned acb, acr, bcb, bcr;
+                load_chroma4(s.ac, frame, row, col, npix, acb, acr);
+                load_chroma4(s.bc, frame, row, col, npix, bcb, bcr);
+                acc[1] += sq4(acb, bcb);
+                acc[2] += sq4(acr, bcr);
+            }
+        }
+    }
+    // wave reduction, the block's four waves through LDS, then one atomic per block and plane
+    __shared__ unsigned long long red[4][3];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        unsigned long long v = acc[p];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (tx == 0) red[ty][p] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const unsigned long long v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+        if (v) atomicAdd(&s.sse[frame * 3 + threadIdx.x], v);
+    }
+}
+
+// ssim_kernel (metrics.hip) with the plane loader in front: tiling, LDS layout and both passes are ssim_kernel's, statement for
+// statement, so a plane gives the partials of its (frames,1,rows,cols) fp32 plane byte / 255.0f bit for bit (to_u8 of that value is
+// the byte).  One launch serves every plane of the mask: blocks [blk0, blk0 + blocks) of the grid's x are plane k's.
+struct SsimPlane {
+    PnpPlaneSrc a, b;
+    int a_sel, b_sel;       // which word of the loader's pair the plane is (1: the second of an interleaved pair)
+    int H, W, crop, oh, ow, tiles_x, blocks, blk0;
+    long out0;              // first partial of this plane
+};
+struct SsimYuvArgs {
+    double g[11];
+    SsimPlane pl[3];
+    int nplanes;
+    double* partial;
+};
+
+__global__ __launch_bounds__(256) void ssim_yuv420_kernel(const SsimYuvArgs s) {
+    __shared__ float ta[26 * 42], tb[26 * 42];
+    __shared__ double hm[5][26 * 32];
+    __shared__ double red[4];
+    SsimPlane p = s.pl[0];
+    if (s.nplanes > 1 && (int)blockIdx.x >= s.pl[1].blk0) p = s.pl[1];
+    if (s.nplanes > 2 && (int)blockIdx.x >= s.pl[2].blk0) p = s.pl[2];
+    const int blk = blockIdx.x - p.blk0, t = threadIdx.x;
+    const long frame = blockIdx.y;
+    const int ty0 = (blk / p.tiles_x) * 16, tx0 = (blk % p.tiles_x) * 32;        // in valid-map coordinates
+    for (int i = t; i < 26 * 11; i += 256) {                                      // a row of the tile = 10 groups of four and one of two
+        const int r = i / 11, gc = i - r * 11;
+        const int y = p.crop + ty0 + r, x = p.crop + tx0 + 4 * gc;
+        int npix = 42 - 4 * gc < 4 ? 42 - 4 * gc : 4;
+        if (p.W - p.crop - x < npix) npix = p.W - p.crop - x;
+        unsigned wa[2] = {0, 0}, wb[2] = {0, 0};
+        if (y < p.H - p.crop && npix > 0) {
+            pnp_plane_load4(p.a, frame, y, x, npix, wa);
+            pnp_plane_load4(p.b, frame, y, x, npix, wb);
+        }
+        const unsigned va = p.a_sel ? wa[1] : wa[0], vb = p.b_sel ? wb[1] : wb[0];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (4 * gc + j < 42) {
+                ta[r * 42 + 4 * gc + j] = (float)((va >> (8 * j)) & 255u);
+                tb[r * 42 + 4 * gc + j] = (float)((vb >> (8 * j)) & 255u);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = t; i < 26 * 32; i += 256) {
+        const int r = i >> 5, c = i & 31;
+        double m1 = 0, m2 = 0, s11 = 0, s22 = 0, s12 = 0;
+#pragma unroll
+        for (int k = 0; k < 11; ++k) {
+            const double x = ta[r * 42 + c + k], y = tb[r * 42 + c + k], gk = s.g[k];
+            m1 += gk * x;
+            m2 += gk * y;
+            s11 += gk * x * x;
+            s22 += gk * y * y;
+            s12 += gk * x * y;
+        }
+        hm[0][i] = m1;
+        hm[1][i] = m2;
+        hm[2][i] = s11;
+        hm[3][i] = s22;
+        hm[4][i] = s12;
+    }
+    __syncthreads();
+    const double C1 = (0.01 * 255) * (0.01 * 255), C2 = (0.03 * 255) * (0.03 * 255);
+    double acc = 0;
+    for (int i = t; i < 16 * 32; i += 256) {
+        const int r = i >> 5, c = i & 31;
+        if (ty0 + r >= p.oh || tx0 + c >= p.ow) continue;
+        double v[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < 11; ++k)
+#pragma unroll
+            for (int q = 0; q < 5; ++q) v[q] += s.g[k] * hm[q][(r + k) * 32 + c];
+        const double mu1 = v[0], mu2 = v[1];
+        const double sg1 = v[2] - mu1 * mu1, sg2 = v[3] - mu2 * mu2, sg12 = v[4] - mu1 * mu2;
+        acc += ((2 * mu1 * mu2 + C1) * (2 * sg12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (sg1 + sg2 + C2));
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((t & 63) == 0) red[t >> 6] = acc;
+    __syncthreads();
+    if (t == 0) s.partial[p.out0 + frame * p.blocks + blk] = red[0] + red[1] + red[2] + red[3];
+}
+
+// what both entries refuse before they look at their statistic
+bool planes_args_ok(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, const void* out, int frames, int h, int w, int crop) {
+    if (!a || !b || !out || frames < 1 || h < 2 || w < 2 || (h & 1) || (w & 1)) return false;
+    if (crop < 0 || (crop & 1) || 2 * crop >= h || 2 * crop >= w) return false;
+    return yuv_planes_ok(*a, w) && yuv_planes_ok(*b, w);
+}
+
+}  // namespace
+
+extern "C" int pnp_psnr_sse_yuv420(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, unsigned long long* sse, int frames, int h,
+                                   int w, int crop_border, void* stream) {
+    if (!planes_args_ok(a, b, sse, frames, h, w, crop_border)) return PNP_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int ze = launch_zero_words(sse, 2L * 3 * frames, st);      // a kernel, not a memset node (prep.h)
+    if (ze != PNP_OK) return ze;
+    PsnrYuvArgs s;
+    s.ay = luma_src(*a, h, w);
+    s.by = luma_src(*b, h, w);
+    s.ac = chroma_src(*a, h, w);
+    s.bc = chroma_src(*b, h, w);
+    s.ry = pnp_plane_runs(h, w, crop_border);
+    s.rc = pnp_plane_runs(h / 2, w / 2, crop_border / 2);
+    s.sse = sse;
+    int bx = (s.ry.rows + s.rc.rows + 3) / 4;                        // a row a wave, up to 4096 rows in flight per frame
+    bx = bx > 1024 ? 1024 : bx;
+    hipLaunchKernelGGL(psnr_yuv420_kernel, dim3(bx, frames), dim3(256), 0, st, s);
+    return (int)hipGetLastError();
+}
+
+extern "C" int pnp_ssim_blocks_yuv420(int h, int w, int crop_border, int plane) {
+    if (h < 2 || w < 2 || (h & 1) || (w & 1) || crop_border < 0 || (crop_border & 1)) return 0;
+    if (plane == PNP_PLANE_Y) return pnp_ssim_blocks(h, w, crop_border);
+    if (plane == PNP_PLANE_CB || plane == PNP_PLANE_CR) return pnp_ssim_blocks(h / 2, w / 2, crop_border / 2);
+    return 0;
+}
+
+extern "C" int pnp_ssim_partials_yuv420(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, int plane_mask, double* partials,
+                                        int frames, int h, int w, int crop_border, void* stream) {
+    if (!planes_args_ok(a, b, partials, frames, h, w, crop_border) || plane_mask < 1 || plane_mask > 7) return PNP_ERR_BAD_ARG;
+    SsimYuvArgs s;
+    s.nplanes = 0;
+    s.partial = partials;
+    const ChromaSrc ac = chroma_src(*a, h, w), bc = chroma_src(*b, h, w);
+    int blk0 = 0;
+    long out0 = 0;
+    for (int k = 0; k < 3; ++k) {
+        const int bit = 1 << k;
+        if (!(plane_mask & bit)) continue;
+        const int nb = pnp_ssim_blocks_yuv420(h, w, crop_border, bit);
+        if (nb < 1) return PNP_ERR_BAD_ARG;                          // a cropped plane of the mask below 11x11
+        SsimPlane& p = s.pl[s.nplanes++];
+        if (bit == PNP_PLANE_Y) {
+            p.a = luma_src(*a, h, w);
+            p.b = luma_src(*b, h, w);
+            p.a_sel = p.b_sel = 0;
+            p.H = h, p.W = w, p.crop = crop_border;
+        } else {
+            const int cr = bit == PNP_PLANE_CR;
+            p.a = ac.c[cr];
+            p.b = bc.c[cr];
+            p.a_sel = ac.paired && cr != ac.cr_first;                // the plane one byte behind the pair's first
+            p.b_sel = bc.paired && cr != bc.cr_first;
+            p.H = h / 2, p.W = w / 2, p.crop = crop_border / 2;
+        }
+        p.oh = p.H - 2 * p.crop - 10;
+        p.ow = p.W - 2 * p.crop - 10;
+        p.tiles_x = (p.ow + 31) / 32;
+        p.blocks = nb;
+        p.blk0 = blk0;
+        p.out0 = out0;
+        blk0 += nb;
+        out0 += (long)frames * nb;
+    }
+    for (int k = s.nplanes; k < 3; ++k) s.pl[k] = s.pl[0];
+    double sum = 0;
+    for (int i = 0; i < 11; ++i) {                       // cv2.getGaussianKernel(11, 1.5)
+        s.g[i] = exp(-((i - 5.0) * (i - 5.0)) / (2 * 1.5 * 1.5));
+        sum += s.g[i];
+    }
+    for (int i = 0; i < 11; ++i) s.g[i] /= sum;
+    hipLaunchKernelGGL(ssim_yuv420_kernel, dim3(blk0, frames), dim3(256), 0, (hipStream_t)stream, s);
+    return (int)hipGetLastError();
+}

@@ -172,6 +172,103 @@ class CompressedClipFolderDataset(_EvalMixin, torch.utils.data.Dataset):
         return dict(lq_u8=torch.from_numpy(lq), gt_u8=torch.from_numpy(gt), **side)
 
 
+@DATASETS.register_module()
+class Yuv420ClipFolderDataset(_EvalMixin, torch.utils.data.Dataset):
+    """Raw 8-bit 4:2:0 clips, what a decoder writes with `-pix_fmt yuv420p` (or nv12 / nv21) -- the frames never become RGB on the way
+    to the generator or to the metrics (apis.multi_gpu_test(yuv_frames=True)):
+
+        <lq_folder>/<clip>.yuv           raw frames back to back, layout 'i420' (yuv420p, default) | 'nv12' | 'nv21', tightly packed
+        <gt_folder>/<clip>.yuv           the same, scale*height x scale*width
+        <mv_folder>/<clip>/<%08d>.npy    the decoder MV records of CompressedClipFolderDataset, one file per frame
+        qp_slice_file                    the same JSON {crfXX: {clip: {frame: {'slice': 'I|P|B', 'QP': q}}}}
+
+    height, width: the frame size of the lq clips (a raw file does not carry it).  mv_folder defaults to lq_folder with its last
+    'yuv' path component replaced by 'mv'; the base QP comes from the crfNN path component, as in CompressedClipFolderDataset.
+    A sample carries lq_yuv / gt_yuv, packed uint8 (T, 3h/2, w) buffers as on disk, the side info and MV records of the PNG dataset,
+    and meta with `layout` and `yuv_standard`."""
+
+    def __init__(self, lq_folder, gt_folder, height, width, layout='i420', yuv_standard='bt601-limited', mv_folder=None,
+                 num_input_frames=100, scale=1, repeat=1, qp_slice_file=None, replace_qp_withIPB=False, pipeline=None, test_mode=True,
+                 **unused):
+        import json
+        import os
+        if not isinstance(repeat, int):
+            raise TypeError(f'"repeat" must be an integer, but got {type(repeat)}.')
+        if layout not in ('i420', 'nv12', 'nv21'):
+            raise ValueError(f"layout must be 'i420', 'nv12' or 'nv21', got {layout!r}")
+        if yuv_standard not in ('bt601-limited', 'bt601-full', 'bt709-limited', 'bt709-full'):
+            raise ValueError(f'unknown yuv_standard {yuv_standard!r}')
+        self.h, self.w, self.scale = int(height), int(width), int(scale)
+        if self.h < 2 or self.w < 2 or self.h % 2 or self.w % 2 or self.scale < 1:
+            raise ValueError(f'4:2:0 frames need an even height and width (and scale >= 1), got {height} x {width}, scale {scale}')
+        self.lq_folder, self.gt_folder = str(lq_folder), str(gt_folder)
+        self.layout, self.yuv_standard, self.num_input_frames = layout, yuv_standard, int(num_input_frames)
+        if mv_folder is None:
+            parts = self.lq_folder.rstrip('/').split('/')
+            where = [i for i, p in enumerate(parts) if p == 'yuv']
+            if not where:
+                raise ValueError(f"mv_folder is not given and lq_folder {self.lq_folder!r} has no 'yuv' path component to replace by 'mv'")
+            parts[where[-1]] = 'mv'
+            mv_folder = '/'.join(parts)
+        self.mv_folder = str(mv_folder)
+        self.replace_qp = bool(replace_qp_withIPB)
+        self.table = None
+        if qp_slice_file is not None:
+            with open(qp_slice_file) as f:
+                self.table = json.load(f)
+        clips = sorted(f[:-4] for f in os.listdir(self.lq_folder) if f.endswith('.yuv'))
+        self.keys = clips * repeat
+
+    def __len__(self):
+        return len(self.keys)
+
+    @staticmethod
+    def _read_yuv(path, h, w, max_frames):
+        """-> the first min(frames in the file, max_frames) frames as (T, 3h/2, w) uint8"""
+        import os
+        import numpy as np
+        per = h * w * 3 // 2
+        size = os.path.getsize(path)
+        if size < per or size % per:
+            raise ValueError(f'{path}: {size} bytes is not a whole number (>= 1) of {h} x {w} 4:2:0 frames of {per} bytes')
+        t = min(size // per, max_frames)
+        return np.fromfile(path, dtype=np.uint8, count=t * per).reshape(t, h * 3 // 2, w)
+
+    def __getitem__(self, idx):
+        import os
+        import numpy as np
+        key = self.keys[idx]
+        lq_path, gt_path = os.path.join(self.lq_folder, key + '.yuv'), os.path.join(self.gt_folder, key + '.yuv')
+        lq = self._read_yuv(lq_path, self.h, self.w, self.num_input_frames)
+        T = lq.shape[0]
+        gt = self._read_yuv(gt_path, self.h * self.scale, self.w * self.scale, T)
+        if gt.shape[0] != T:
+            raise ValueError(f'{gt_path}: {gt.shape[0]} frames for the {T} of {lq_path}')
+        parts = self.lq_folder.rstrip('/').split('/')
+        crf_dir = parts[-2] if len(parts) > 1 else ''
+        base_qp = int(crf_dir.split('crf')[1]) if 'crf' in crf_dir else 0          # loading_ipb.py:239
+        slices, qps, recs = [], [], []
+        for i in range(T):
+            frame = str(i)
+            if crf_dir.startswith('crf') and self.table is not None:                # loading_ipb.py:298-312
+                e = self.table[crf_dir][key][frame]
+                sl = e['slice']
+                qp = ord(sl) if self.replace_qp else e['QP']
+            else:
+                sl = 'I' if i == 0 else 'P'
+                qp = ord(sl) if self.replace_qp else 0.0
+            slices.append(float(ord(sl)))
+            qps.append(float(qp) / 255.0)
+            recs.append(np.load(os.path.join(self.mv_folder, key, f'{i:08d}.npy')).astype(np.float32).reshape(-1, 10))
+        rec_frame = [np.full((r.shape[0],), t, np.int32) for t, r in enumerate(recs)]
+        return dict(lq_yuv=torch.from_numpy(lq), gt_yuv=torch.from_numpy(gt),
+                    slices=torch.tensor(slices, dtype=torch.float32).view(T, 1, 1, 1),
+                    QPs=torch.tensor(qps, dtype=torch.float32).view(T, 1, 1, 1),
+                    base_QPs=torch.full((T, 1, 1, 1), base_qp / 255.0, dtype=torch.float32),
+                    mv_records=torch.from_numpy(np.concatenate(recs)), rec_frame=torch.from_numpy(np.concatenate(rec_frame)),
+                    meta=dict(key=f'{key}/{0:08d}', lq_path=lq_path, gt_path=gt_path, layout=self.layout, yuv_standard=self.yuv_standard))
+
+
 def collate(batch):
     """samples_per_gpu=1 (forced by the reference, tools/test.py:110): add the batch dim."""
     out = {}

@@ -45,12 +45,18 @@ class FrameWriter:
         # defaults to Z_BEST_SPEED + RLE), PIL's default 6 takes 1.8x as long per 720p frame for 12 % smaller files
         Image.fromarray(rgb).save(path, compress_level=1)
 
-    def submit(self, path, rgb_uint8_hwc):
+    @staticmethod
+    def _write_bytes(path, array):
+        os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+        with open(path, 'wb') as f:
+            array.tofile(f)
+
+    def _submit(self, write, path, data):
         self._slots.acquire()
 
         def job():
             try:
-                self._write(path, rgb_uint8_hwc)
+                write(path, data)
             finally:
                 self._slots.release()
 
@@ -58,6 +64,14 @@ class FrameWriter:
         with self._lock:
             self._futures.append(fut)
         return fut
+
+    def submit(self, path, rgb_uint8_hwc):
+        return self._submit(self._write, path, rgb_uint8_hwc)
+
+    def submit_bytes(self, path, array):
+        """Raw write-back: the bytes of a C-contiguous numpy array as they are (a clip's packed 4:2:0 frames -> one .yuv file), one
+        job per file."""
+        return self._submit(self._write_bytes, path, array)
 
     def drain(self):
         """Wait for every frame queued so far (the pool stays usable); raise the first failure."""

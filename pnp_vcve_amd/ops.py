@@ -831,3 +831,91 @@ def pack_lr_yuv420(frames, standard='bt601-limited', general=False):
         _native.check(_native.lib().pnp_debug_pack_lr_yuv420(ctypes.byref(d), _yuv_standard(standard), _ptr(out), t, h, w, int(bool(general)),
                                                              _stream()), 'pnp_debug_pack_lr_yuv420')
     return out
+
+
+# ---------------------------------------------------------------- plane metrics of 4:2:0 clips (include/pnpvcve.h states the arithmetic)
+_PLANE_BITS = {'y': _native.PLANE_Y, 'u': _native.PLANE_CB, 'v': _native.PLANE_CR}
+
+
+def _yuv_metric_pair(a, b, crop_border):
+    """two Yuv420Frames that show the same frames, (n,t,...) or (t,...), each in a layout of its own -> (per-clip descriptor pairs,
+    lead shape, t, h, w, crop); every refusal a ValueError / TypeError raised before any GPU work"""
+    clips_a, lead_a = _yuv_clips(a, 'a')
+    clips_b, lead_b = _yuv_clips(b, 'b')
+    da = [_yuv_clip_desc(c, 'a') for c in clips_a]
+    db = [_yuv_clip_desc(c, 'b') for c in clips_b]
+    t, h, w = da[0][1:]
+    if lead_a != lead_b or any(d[1:] != (t, h, w) for d in da + db):
+        raise ValueError(f'the two clips differ in shape: {tuple(a.y.shape)} and {tuple(b.y.shape)}')
+    if a.y.device != b.y.device:
+        raise RuntimeError('a and b must be on the same device')
+    if isinstance(crop_border, bool) or int(crop_border) != crop_border:
+        raise TypeError(f'crop_border must be an integer, got {crop_border!r}')
+    crop = int(crop_border)
+    if crop < 0 or crop % 2:
+        raise ValueError(f'crop_border must be even and >= 0 (the chroma planes are cropped by half of it), got {crop}')
+    if 2 * crop >= h or 2 * crop >= w:
+        raise ValueError(f'a crop of {crop} leaves nothing of {h} x {w} frames')
+    return [(x[0], y[0]) for x, y in zip(da, db)], lead_a + (t,), t, h, w, crop
+
+
+def psnr_sse_yuv420(a, b, crop_border=0):
+    """The statistic behind psnr_yuv420: the exact sum of squared byte differences of the cropped Y, Cb and Cr planes of every frame, an
+    int64 CPU tensor lead + (3,) (pnp_psnr_sse_yuv420: integer, the same bits every run)."""
+    pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border)
+    dev = a.y.device
+    with torch.cuda.device(dev):
+        sse = torch.empty((len(pairs), t, 3), dtype=torch.int64, device=dev)
+        for i, (da, db) in enumerate(pairs):
+            if t:
+                _native.check(_native.lib().pnp_psnr_sse_yuv420(ctypes.byref(da), ctypes.byref(db), _ptr(sse[i]), t, h, w, crop, _stream()),
+                              'pnp_psnr_sse_yuv420')
+    return sse.cpu().reshape(lead + (3,))
+
+
+def psnr_yuv420(a, b, crop_border=0):
+    """Per-frame plane PSNR of two 8-bit 4:2:0 clips, read from the planes where they lie (1.5 B per pixel and clip).
+    a, b: Yuv420Frames (n,t,...) or (t,...) of one shape, each in its own layout (NV12 output against an I420 ground truth); the Y
+    plane is cropped by crop_border (even), the chroma planes by crop_border / 2.  Returns a float64 CPU tensor lead + (3,) = Y, U, V:
+    PSNR_p = 10 log10(255^2 N_p / SSE_p) with N_p the samples of the cropped plane, inf where the planes are equal."""
+    import numpy as np
+    sse = psnr_sse_yuv420(a, b, crop_border).numpy().astype(np.float64)
+    h, w = a.y.shape[-2:]
+    crop = int(crop_border)
+    n_y, n_c = (h - 2 * crop) * (w - 2 * crop), (h // 2 - crop) * (w // 2 - crop)
+    with np.errstate(divide='ignore'):
+        out = 10.0 * np.log10(255.0 ** 2 * np.array([n_y, n_c, n_c], np.float64) / sse)
+    out[sse == 0] = np.inf
+    return torch.from_numpy(out)
+
+
+def ssim_yuv420(a, b, crop_border=0, planes='y'):
+    """Per-frame plane SSIM of two 8-bit 4:2:0 clips (pnp_ssim_partials_yuv420: ssim_frames' window and fp64 arithmetic on the bytes of a
+    plane).  planes: any of 'y', 'u', 'v' in any order ('yuv', 'u', 'vy', ...); returns a float64 CPU tensor lead + (len(planes),) in
+    that order.  Crop as psnr_yuv420."""
+    if not isinstance(planes, str) or not planes or len(set(planes.lower())) != len(planes) or any(p not in _PLANE_BITS for p in planes.lower()):
+        raise ValueError(f"planes must name each of 'y', 'u', 'v' at most once, got {planes!r}")
+    planes = planes.lower()
+    pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border)
+    L = _native.lib()
+    mask = sum(_PLANE_BITS[p] for p in planes)
+    order = [p for p in 'yuv' if p in planes]                      # the order the library writes
+    nb = {p: int(L.pnp_ssim_blocks_yuv420(h, w, crop, _PLANE_BITS[p])) for p in order}
+    if any(v < 1 for v in nb.values()):
+        raise ValueError('a cropped plane is smaller than the 11x11 SSIM window')
+    dev = a.y.device
+    res = torch.empty((len(pairs), t, len(planes)), dtype=torch.float64)
+    with torch.cuda.device(dev):
+        for i, (da, db) in enumerate(pairs):
+            if not t:
+                continue
+            part = torch.empty(t * sum(nb.values()), dtype=torch.float64, device=dev)
+            _native.check(L.pnp_ssim_partials_yuv420(ctypes.byref(da), ctypes.byref(db), mask, _ptr(part), t, h, w, crop, _stream()),
+                          'pnp_ssim_partials_yuv420')
+            off = 0
+            for p in order:
+                rows, cols, c = (h, w, crop) if p == 'y' else (h // 2, w // 2, crop // 2)
+                n = (rows - 2 * c - 10) * (cols - 2 * c - 10)
+                res[i, :, planes.index(p)] = (part[off:off + t * nb[p]].reshape(t, nb[p]).sum(dim=1) / n).cpu()
+                off += t * nb[p]
+    return res.reshape(lead + (len(planes),))

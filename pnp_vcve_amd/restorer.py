@@ -93,7 +93,19 @@ class BasicVSR(nn.Module):
         raise NotImplementedError('training is out of scope of the MI355X hot-path build')
 
     def evaluate(self, output, gt):
-        """basicvsr.py:119-153."""
+        """basicvsr.py:119-153.
+        4:2:0 clips (not in the reference): when `output` and `gt` are both ops.Yuv420Frames -- one clip, (t,...) or (1,t,...) views,
+        each in a layout of its own -- the metrics are PLANE metrics read from the 8-bit planes on the device (ops.psnr_yuv420 /
+        ssim_yuv420): 'PSNR' / 'SSIM' score the Y plane, and in this mode only 'PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V' and 'PSNR_YUV'
+        = (6 PSNR_Y + PSNR_U + PSNR_V) / 8 per frame are accepted too; every value is the mean over frames.  crop_border (even) crops
+        the Y plane, half of it the chroma planes.  test_cfg.convert_to may be None or 'y' and both mean the same here: the decoder's
+        Y' plane IS the luma -- it is NOT the BT.601 Y that convert_to='y' derives from RGB bytes, so the two modes' numbers differ."""
+        from .ops import Yuv420Frames
+        if isinstance(output, Yuv420Frames) or isinstance(gt, Yuv420Frames):
+            if not (isinstance(output, Yuv420Frames) and isinstance(gt, Yuv420Frames)):
+                raise ValueError('plane metrics compare two 4:2:0 clips: output and gt must both be ops.Yuv420Frames '
+                                 "(ask the generator for out_dtype='i420' / 'nv12', or convert with ops.frames_to_yuv420)")
+            return self._evaluate_yuv(output, gt)
         crop_border = self.test_cfg['crop_border']
         convert_to = self.test_cfg.get('convert_to', None)
         eval_result = dict()
@@ -134,15 +146,67 @@ class BasicVSR(nn.Module):
                                                                    convert_to=convert_to)
         return eval_result
 
+    YUV_OUT_LAYOUTS = ('nv12', 'i420')      # the packed 4:2:0 layouts generator.forward writes
+    YUV_METRICS = ('PSNR', 'SSIM', 'PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V', 'PSNR_YUV')
+
+    def _evaluate_yuv(self, output, gt):
+        """evaluate() of two ops.Yuv420Frames clips: plane PSNR / SSIM on the device, means over the clip's frames"""
+        from .ops import Yuv420Frames, psnr_yuv420, ssim_yuv420
+        crop_border = self.test_cfg['crop_border']
+        convert_to = self.test_cfg.get('convert_to', None)
+        if not (convert_to is None or (isinstance(convert_to, str) and convert_to.lower() == 'y')):
+            raise ValueError('Wrong color model. Supported values are "Y" and None.')
+        metrics = list(self.test_cfg['metrics'])
+        for metric in metrics:
+            if metric not in self.YUV_METRICS:
+                raise ValueError(f'4:2:0 clips are scored by {self.YUV_METRICS}, got {metric!r}')
+
+        def one_clip(x, name):
+            if x.y.dim() == 4:
+                if x.y.size(0) != 1:
+                    raise ValueError(f'evaluate() expects one clip per call (samples_per_gpu=1), got a batch of {x.y.size(0)}')
+                return Yuv420Frames(x.y[0], x.cb[0], x.cr[0])
+            return x
+
+        output, gt = one_clip(output, 'output'), one_clip(gt, 'gt')
+        gt = Yuv420Frames(*[p.to(output.y.device) for p in gt])
+        eval_result = dict()
+        psnr = psnr_yuv420(output, gt, crop_border) if any(m.startswith('PSNR') for m in metrics) else None      # (t, 3)
+        col = {'SSIM': 'y', 'SSIM_U': 'u', 'SSIM_V': 'v'}
+        planes = ''.join(dict.fromkeys(col[m] for m in metrics if m in col))
+        ssim = ssim_yuv420(output, gt, crop_border, planes) if planes else None                                    # (t, len(planes))
+        for metric in metrics:
+            if metric in col:
+                eval_result[metric] = float(ssim[:, planes.index(col[metric])].mean())
+            elif metric == 'PSNR_YUV':
+                eval_result[metric] = float(((6.0 * psnr[:, 0] + psnr[:, 1] + psnr[:, 2]) / 8.0).mean())
+            else:
+                eval_result[metric] = float(psnr[:, ('PSNR', 'PSNR_U', 'PSNR_V').index(metric)].mean())
+        return eval_result
+
     def forward_test(self, lq, gt=None, QPs=None, slices=None, mvs=None, base_QPs=None, par_map=None, meta=None,
-                     save_image=False, save_path=None, iteration=None, precomputed_output=None, out_dtype=None):
+                     save_image=False, save_path=None, iteration=None, precomputed_output=None, out_dtype=None,
+                     yuv_standard='bt601-limited'):
         """basicvsr.py:155-233.  `precomputed_output` (not in the reference): this clip's enhanced frames when the caller has
         already run the generator -- apis.multi_gpu_test does so for two clips at a time, which the generator interleaves on two
         streams; evaluation and saving then proceed clip by clip exactly as below.
         Byte frames (not in the reference): `lq` may be the decoder's uint8 (n,t,h,w,3) frames, and `out_dtype` (generator.forward's)
         asks the generator for the display bytes as well as / instead of the fp32 planes: the PNG writer takes the bytes as they
         are, and so do the metrics when the bytes are all there is (`gt` may then be a uint8 (n,t,h,w,3) clip too); only the
-        centre-frame case (a 4-D `gt`) still needs the fp32 planes."""
+        centre-frame case (a 4-D `gt`) still needs the fp32 planes.
+        4:2:0 frames (not in the reference): `lq` may be ops.Yuv420Frames in the colour standard `yuv_standard`, and with
+        out_dtype = 'i420' | 'nv12' the generator writes packed 4:2:0 only (`precomputed_output`: that packed buffer): the
+        metrics are then evaluate()'s plane metrics against a Yuv420Frames `gt`, and save_image writes <save_path>/<clip>.yuv -- the
+        buffer's bytes, frames in order, one FrameWriter job per clip."""
+        from . import ops
+        yuv_in = isinstance(lq, ops.Yuv420Frames)
+        yuv_layout = out_dtype if (yuv_in and isinstance(out_dtype, str) and out_dtype in self.YUV_OUT_LAYOUTS) else None
+        if isinstance(gt, ops.Yuv420Frames) and yuv_layout is None:
+            raise ValueError("a 4:2:0 ground truth is compared with 4:2:0 output: lq must be ops.Yuv420Frames and out_dtype one of "
+                             f'{self.YUV_OUT_LAYOUTS}')
+        if yuv_layout is not None:
+            return self._forward_test_yuv(lq, gt, QPs, slices, mvs, base_QPs, par_map, meta, save_image, save_path, iteration,
+                                          precomputed_output, yuv_layout, yuv_standard)
         if precomputed_output is not None:
             output = precomputed_output
         elif not self.psnr_only:
@@ -150,6 +214,8 @@ class BasicVSR(nn.Module):
                 torch.cuda.synchronize()
                 begin = time.time()
                 kw = {} if out_dtype is None else {'out_dtype': out_dtype}
+                if yuv_in:
+                    kw['yuv_standard'] = yuv_standard
                 output = self.generator(lq, QPs, slices, mvs, base_QPs, par_map, **kw)
                 torch.cuda.synchronize()
                 self.last_forward_seconds = time.time() - begin
@@ -173,7 +239,9 @@ class BasicVSR(nn.Module):
             results = dict(eval_result=self.evaluate(output, gt))
         else:
             lq_planes = lq
-            if lq.dtype == torch.uint8 and lq.ndim == 5 and lq.is_cuda:       # byte frames: hand back the planes the caller knows
+            if yuv_in:
+                lq_planes = ops.frames_from_yuv420(lq, yuv_standard)
+            elif lq.dtype == torch.uint8 and lq.ndim == 5 and lq.is_cuda:       # byte frames: hand back the planes the caller knows
                 from .ops import frames_from_rgb8
                 lq_planes = frames_from_rgb8(lq)
             results = dict(lq=lq_planes.cpu(), output=output.cpu())
@@ -198,6 +266,50 @@ class BasicVSR(nn.Module):
                     img_name = meta[0]['key'].replace('/', '_')
                     name = f'{img_name}.png' if iteration is None else f'{img_name}-{iteration + 1:06d}.png'
                     writer.submit(osp.join(save_path, name), frames_to_uint8_hwc(output[0])[0])
+            finally:
+                if own:
+                    writer.close()
+        return results
+
+    def _forward_test_yuv(self, lq, gt, QPs, slices, mvs, base_QPs, par_map, meta, save_image, save_path, iteration, precomputed_output,
+                          layout, yuv_standard):
+        """forward_test with 4:2:0 planes in and packed 4:2:0 out: the generator's (n,t,3H/2,W) uint8 buffer is all that exists of the output"""
+        from . import ops
+        if gt is not None and not isinstance(gt, ops.Yuv420Frames):
+            raise ValueError('4:2:0 output is scored against a 4:2:0 ground truth (ops.Yuv420Frames); the centre-frame case and RGB ground '
+                             'truths read the fp32 planes')
+        if precomputed_output is not None:
+            buf = precomputed_output
+        elif self.psnr_only:
+            raise ValueError('psnr_only scores the input frames: evaluate(lq, gt) does that for 4:2:0 clips')
+        else:
+            with torch.no_grad():
+                torch.cuda.synchronize()
+                begin = time.time()
+                buf = self.generator(lq, QPs, slices, mvs, base_QPs, par_map, out_dtype=layout, yuv_standard=yuv_standard)
+                torch.cuda.synchronize()
+                self.last_forward_seconds = time.time() - begin
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.dim() != 4 or buf.shape[-2] % 3:
+            raise ValueError('the 4:2:0 output is the packed (n,t,3H/2,W) uint8 buffer the generator returns')
+        H, W = buf.shape[-2] * 2 // 3, buf.shape[-1]
+        output = ops.yuv420_views(buf, H, W, layout)
+        if self.test_cfg is not None and self.test_cfg.get('metrics', None):
+            assert gt is not None, 'evaluation with metrics must have gt images.'
+            results = dict(eval_result=self.evaluate(output, gt))
+        else:
+            results = dict(lq=ops.frames_from_yuv420(lq, yuv_standard).cpu(), output=buf.cpu())
+            if gt is not None:
+                results['gt'] = ops.Yuv420Frames(*[p.cpu() for p in gt])
+        if save_image:
+            from .io_async import FrameWriter
+            writer = getattr(self, 'frame_writer', None)
+            own = writer is None
+            if own:
+                writer = FrameWriter(max_workers=1)
+            try:
+                clip = meta[0]['key'].split('/')[0]
+                name = f'{clip}.yuv' if iteration is None else f'{clip}-{iteration + 1:06d}.yuv'
+                writer.submit_bytes(osp.join(save_path, name), buf[0].contiguous().cpu().numpy())
             finally:
                 if own:
                     writer.close()

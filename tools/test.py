@@ -52,6 +52,13 @@ def parse_args():
                    help='implies --byte-frames; PSNR / SSIM read bytes too: the ground truth stays uint8 on the device and the generator '
                         'writes display bytes only, with or without --save-path (6 B per pixel into the metrics instead of 24).  Same '
                         'metrics; default off')
+    p.add_argument('--yuv-frames', action='store_true',
+                   help='raw 4:2:0 evaluation (a Yuv420ClipFolderDataset of .yuv clips): the generator reads the planes and writes packed '
+                        '4:2:0 only, the ground truth stays 8-bit planes on the device, PSNR / SSIM are the Y plane\'s (PSNR_U, PSNR_V, '
+                        'SSIM_U, SSIM_V and the 6:1:1 PSNR_YUV may be listed in test_cfg.metrics too) and --save-path gets one <clip>.yuv '
+                        'per clip; default off')
+    p.add_argument('--yuv-out-layout', choices=['i420', 'nv12'], default='i420',
+                   help='with --yuv-frames: the layout of the packed 4:2:0 output (and of the written .yuv files); default i420 (yuv420p)')
     p.add_argument('--any-size', action='store_true',
                    help='run frames whose height or width is no multiple of 4 (generator.any_size; the same as --cfg-options '
                         'model.generator.any_size=True): the same formulas on the frame as given, no padding.  Default off: such '
@@ -110,7 +117,8 @@ def main():
     try:
         outputs = multi_gpu_test(model, dataset, save_image=args.save_path is not None, save_path=args.save_path,
                                  device=dev, metrics=tuple(cfg.test_cfg['metrics']), clips_in_flight=args.clips_in_flight,
-                                 byte_frames=args.byte_frames or args.byte_metrics, byte_metrics=args.byte_metrics)
+                                 byte_frames=args.byte_frames or args.byte_metrics, byte_metrics=args.byte_metrics,
+                                 yuv_frames=args.yuv_frames, yuv_out_layout=args.yuv_out_layout)
     finally:
         if getattr(model, 'frame_writer', None) is not None:
             model.frame_writer.close()
