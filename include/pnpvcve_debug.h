@@ -34,6 +34,12 @@ int pnp_conv3x3_wino_f32_ex(const float* src_dev, const float* wino_w_dev, const
  * plane) for the NEXT pnp_conv3x3_wino_f32_ex calls with branches: they then take the one gated launch the generator uses (fold-only
  * body when bit 3 is set).  A device int; NULL = back to the ungated branch kernel.  Process-wide, not thread-safe: a tracing hook. */
 int pnp_debug_wino_gate_word(const int* gate_word_dev);
+/* The frame's fold table, which the fold-only body reads instead of the partition planes (pnp_generator_forward makes it in front of
+ * every branch run; a gated pnp_conv3x3_wino_f32_ex call makes its own): for a (3, h, w) partition map, 4 * ceil(h / 16) * ceil(w / 16)
+ * records of two 32-bit words -- the plane to fold (0..2, or -1) and the bits of the fp32 factor 0.25f * value -- one per 8x8
+ * quadrant, in the order record((tile_y * tiles_x + tile_x) * 4 + 2 * (qy & 1) + (qx & 1)) with tile = quadrant >> 1; from the
+ * quadrant's first pixel: the lowest plane that is nonzero there, -1 and 0 if none is or the quadrant lies outside the frame. */
+int pnp_debug_par_fold_table(const float* par_dev, void* table_dev, int h, int w, void* stream);
 
 /* The NEXT pnp_conv3x3_wino_f32 / _ex / pnp_conv3x3_wino_ms_f32 calls (tile kernels, not the quadrant-unit forms) compute the 16-pixel
  * tile rows [row0, row0 + nrows) of the frame only and leave the rest of out_dev untouched -- one part of a row-band chain

@@ -158,6 +158,7 @@ DEBUG_SIGNATURES['pnp_dcn_nhwc_f32_ex'] = (c_int, [c_void_p, c_void_p, c_void_p,
 
 DEBUG_SIGNATURES['pnp_dcn_trace_u64s'] = (c_int, [])
 DEBUG_SIGNATURES['pnp_debug_wino_gate_word'] = (c_int, [c_void_p])
+DEBUG_SIGNATURES['pnp_debug_par_fold_table'] = (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p])
 DEBUG_SIGNATURES['pnp_debug_wino_tile_rows'] = (c_int, [c_int, c_int])
 DEBUG_SIGNATURES['pnp_debug_wino_ms_trace'] = (c_int, [c_void_p])
 DEBUG_SIGNATURES['pnp_debug_pack_lr_u8'] = (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p])

@@ -2,6 +2,7 @@
 // MFMA pipe of gfx950.  See conv_mfma.hip for the design notes.
 #pragma once
 #include "common.h"
+#include "fold_table.h"
 
 // One conv of a row-band chain (generator.hip run_branch) on the Winograd tile kernels: tile rows [0, row) run
 // on the caller's stream (chain A), tile rows [row, rows) on `side` (chain B).  `ready` is recorded on the caller's stream IN FRONT of
@@ -73,6 +74,10 @@ struct ConvArgs {
     // 4:2:0 frames (launch_conv_last_io only; behind the byte fields for the same reason):
     const float* lr_rgb0;         // out_mode 2/3: the frame to add as (h,w,4) fp32 RGB0, the conv source the pack launch wrote into the workspace
                                   // (pixel stride 4), read INSTEAD of lr / lr_u8; or nullptr
+    // the Winograd tile kernels' gated front halves only (last, for the same reason):
+    const PnpFoldRec* fold_tab;   // with par_any: the frame's fold table (fold_table.h, launch_par_fold_table), which the fold-only body
+                                  // reads INSTEAD of the partition planes; nullptr: the branch kernel runs whatever the word says (the same
+                                  // values bit for bit).  The quadrant-unit kernels of small frames do not use it
 };
 
 enum { CONV_CFG_BIG = 0,    // 8x16 pixel tile, 64 output channels per block
@@ -146,6 +151,8 @@ int launch_conv3x3_f16x3(const ConvArgs& a, int cfg, hipStream_t stream);
 // bits 0..2: plane j has a nonzero value in the tile; bits 3..5: every value of plane j in the tile is 0 or PNP_PAR_UNIT
 // frames consecutive (3, H, W) maps -> frames consecutive flag arrays
 int launch_par_tile_flags(const float* par, long par_plane, int* flags, int frames, int H, int W, hipStream_t stream);
+// the frames' fold tables (fold_table.h; pnp_fold_records(H, W) records per frame, frames consecutive) for ConvArgs::fold_tab
+int launch_par_fold_table(const float* par, long par_plane, PnpFoldRec* tab, int frames, int H, int W, hipStream_t stream);
 int launch_par_frame_any(const int* flags, int* any, int frames, int H, int W, hipStream_t stream);
 
 // conv_last on the vector ALUs (conv_last.hip): OIHW (3,64,3,3) -> [9][64][4]; 2304 floats

@@ -469,6 +469,31 @@ __global__ __launch_bounds__(256) void par_frame_any_kernel(const int* __restric
 }
 }  // namespace
 
+namespace {
+// The fold table of each frame (fold_table.h): one thread per 8x8 quadrant of the frame rounded up to whole 16x16 tiles reads the three
+// plane values of the quadrant's first pixel -- the values bit 6 above compares the quadrant's other pixels with -- and writes the
+// record.  blockIdx.y = frame: par advances by 3 planes, tab by the frame's record count
+__global__ __launch_bounds__(256) void par_fold_table_kernel(const float* __restrict__ par, long plane, PnpFoldRec* __restrict__ tab,
+                                                             int H, int W, int tiles_x, int nrec) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= nrec) return;
+    par += (long)blockIdx.y * 3 * plane;
+    const int tile = r >> 2, ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int gy = 16 * ty + 8 * ((r >> 1) & 1), gx = 16 * tx + 8 * (r & 1);
+    const bool in = gy < H && gx < W;
+    const long px = (long)gy * W + gx;
+    const float v0 = in ? par[px] : 0.f, v1 = in ? par[plane + px] : 0.f, v2 = in ? par[2 * plane + px] : 0.f;
+    tab[(long)blockIdx.y * nrec + pnp_fold_index(gy >> 3, gx >> 3, tiles_x)] = pnp_fold_record(v0, v1, v2);
+}
+}  // namespace
+
+int launch_par_fold_table(const float* par, long par_plane, PnpFoldRec* tab, int frames, int H, int W, hipStream_t stream) {
+    if (!par || !tab || frames < 1 || H < 1 || W < 1) return PNP_ERR_BAD_ARG;
+    const int nrec = (int)pnp_fold_records(H, W);
+    hipLaunchKernelGGL(par_fold_table_kernel, dim3((nrec + 255) / 256, frames), dim3(256), 0, stream, par, par_plane, tab, H, W, (W + 15) / 16, nrec);
+    return (int)hipGetLastError();
+}
+
 int launch_par_frame_any(const int* flags, int* any, int frames, int H, int W, hipStream_t stream) {
     const int tiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
     hipLaunchKernelGGL(par_frame_any_kernel, dim3(frames), dim3(256), 0, stream, flags, any, tiles);

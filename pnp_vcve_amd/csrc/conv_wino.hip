@@ -117,13 +117,15 @@ struct WinoArgs {
     int quad;               // the tiles beyond an XCD band's whole rounds are worked on as four 8x8 quadrants by four blocks (see the kernel's tail)
     int tile0, tcount;      // the launch works on tiles [tile0, tile0 + tcount) of the frame (row-major; whole tile rows: ConvArgs::tile_row0).
                             // Only the strip walk knows: halo, edges, flags and the gate are the full frame's
+    const PnpFoldRec* fold_tab;   // the fold-only body of the tile kernels: the frame's fold table (ConvArgs::fold_tab, fold_table.h); read-only here
 };
 
 // FO ("fold only"): the front half of a frame whose EVERY 8x8 quadrant is all zero or carries one constant partition plane (the gate
 // of launch_conv3x3_wino: par_frame_any's bit 3): the plain kernel's chunk structure -- no branch chunks, no branch MFMAs, accumulators
 // from an inline zero -- plus, per step, the quadrant's plane folded into the B fragments of positions (1,1) (1,2) (2,1) (2,2) exactly
-// as the branch kernel does it for such a wave (same FMAs, same MFMA order: bit-identical values).  The plane and its value come from
-// one pixel of the quadrant; its 1x1 fragments straight from L2.
+// as the branch kernel does it for such a wave (same FMAs, same MFMA order: bit-identical values).  The plane and its factor come from
+// the frame's fold table (WinoArgs::fold_tab: one record per quadrant, made in front of the branch run from one pixel of the
+// quadrant); its 1x1 fragments straight from L2.
 template <bool PAR, bool RES, bool MS, bool FO = false>
 __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
     static_assert(!MS || (!PAR && !RES), "the multi-source form is the input conv: no branches, no residual");
@@ -317,29 +319,24 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
                 }
         }
     };
-    // FO: plane and factor of the wave's quadrant of the tile at (y0, x0), from its first pixel (the frame passed the gate: the quadrant
-    // is all zero or one constant plane); requested at the top of an epilogue, finished behind it
-    float fov[3] = {0.f, 0.f, 0.f};
+    // FO: plane and factor of the wave's quadrant of tile `tl` (the frame passed the gate: the quadrant is all zero or one constant
+    // plane) = its record of the frame's fold table, which launch_par_fold_table made from the quadrant's first pixel in front of the
+    // run (fold_table.h; the factor is the 0.25f * value this body used to compute per tile, the same bits).  ONE scalar load of 8 bytes
+    // through the constant cache -- the table is read-only here and the address wave-uniform -- issued at the top of an epilogue and
+    // wanted behind it: no vector-memory request is added to any chunk's count, no vector register lives from the request to its use,
+    // and the K loop is the plain kernel's.  (As three loads of the planes themselves the values came through the vector memory path,
+    // and the spill reload behind them -- an s_waitcnt vmcnt(0) -- waited out their round trip where no MFMA runs.  Issued inside the
+    // tile's last step instead, the two scalar registers cost the K loop four spill instructions: profiles/wino_front_fold_ab.txt.)
     int fo_next = -1;
     float foc_next = 0.f;
-    auto fo_request = [&](int y0, int x0, int quadrant) {       // quadrant < 0: the wave's own
+    const int wave_base = FO ? __builtin_amdgcn_readfirstlane(t & ~63) : 0;      // 64 x the wave's index, a scalar
+    auto fo_load = [&](int tl, int quadrant) {       // quadrant < 0: the wave's own
         if constexpr (FO) {
-            const int wv = quadrant >= 0 ? quadrant : __builtin_amdgcn_readfirstlane(t >> 6);
-            const int gy = y0 + 8 * (wv >> 1), gx = x0 + 8 * (wv & 1);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) fov[j] = (gy < H && gx < W) ? a.par[(long)j * a.par_plane + (long)gy * W + gx] : 0.f;
-        }
-    };
-    auto fo_finish = [&]() {
-        if constexpr (FO) {
-            fo_next = -1;
-            foc_next = 0.f;
-#pragma unroll
-            for (int j = 2; j >= 0; --j)
-                if (fov[j] != 0.f) {
-                    fo_next = j;
-                    foc_next = 0.25f * fov[j];
-                }
+            const int wv = quadrant >= 0 ? quadrant : wave_base >> 6;
+            typedef const __attribute__((address_space(4))) PnpFoldRec* CRec;
+            const CRec rec = (CRec)(uintptr_t)a.fold_tab + ((long)tl * 4 + wv);
+            fo_next = rec->plane;
+            foc_next = __builtin_bit_cast(float, rec->factor_bits);
         }
     };
     // MS: the frame's halo (18 x 18 pixels x RGB0 = 5 KiB) lives where the branch kernels keep their partition values; pixel order as in
@@ -426,8 +423,7 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
         rgb_store(t);
         pv_request(t, ty0, tx0);
         pv_finish(t);
-        fo_request(ty0, tx0, -1);
-        fo_finish();
+        fo_load(tile, -1);
         __syncthreads();
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -441,7 +437,7 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
         row_tf(2);
     }
     // (the B fragment of lane l, N tile n, position column pj of a chunk in slot z sits at z * 16384 + (pj * 4 + n) * 1024 + l * 16)
-    const unsigned bl = (unsigned)lane * 16u;
+    unsigned bl = (unsigned)lane * 16u;
     if constexpr (!PAR && !MS) {
 #pragma unroll
         for (int n = 0; n < 4; ++n) bf[0][n] = lds4(bl + n * 1024);
@@ -455,8 +451,19 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
     int dbg_n = 0;
     unsigned long long dbg_q0 = 0, dbg_q1 = 0, dbg_q2 = 0;
     int tq = t;
+    // FO: the thread id is made again at the top of every tile and of every epilogue -- the lane's index from v_mbcnt, the wave's from a
+    // scalar -- instead of living across them.  In this body the allocator kept it in scratch, and each of its two reloads per tile is
+    // an s_waitcnt vmcnt(0): in the epilogue for the last chunk's requests, at the tile's top for the epilogue's sixteen stores
+    // (profiles/wino_front_fold_ab.txt).  (volatile: left to the optimiser the three instructions are loop-invariant and hoisted.)
+    auto thread_id = [&]() -> int {
+        int l;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+        return wave_base | l;
+    };
     for (;;) {
+        if constexpr (FO) tq = thread_id();
         asm volatile("" : "+v"(tq));
+        if constexpr (FO) bl = ((unsigned)tq & 63u) * 16u;      // (likewise: it lived in scratch too, reloaded at the tile's top)
         const int ntile = tile + tstep;
         const bool has_next = ntile < tend;
         // (behind the block's last whole tile the "next tile" of the halo pipeline is the tile its quadrant unit belongs to)
@@ -872,12 +879,13 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
         // (next = the block's quadrant unit: every wave fetches quadrant qquad's values)
         const int tqp = (!has_next && qtile >= 0) ? ((qquad << 6) | (tq & 63)) : tq;
         pv_request(tqp, nty0, ntx0);
-        fo_request(nty0, ntx0, (!has_next && qtile >= 0) ? qquad : -1);
+        fo_load(ptile, (!has_next && qtile >= 0) ? qquad : -1);
         auto epilogue = [&](auto partial_c) {
             constexpr bool PARTIAL = decltype(partial_c)::value;
             // (the thread id laundered once more: everything the epilogue derives from it is computed HERE -- hoisted to the top of the
             //  tile it lives through the K loop at the register limit, i.e. in scratch, and each reload is an s_waitcnt vmcnt(0))
             int te = tq;
+            if constexpr (FO) te = thread_id();
             asm volatile("" : "+v"(te));
             const int lq = te & 63, wq = te >> 6, kqq = lq >> 4, mq = lq & 15;
             // accumulator register r of this lane is tile (row kq, column r) of the wave's 4x4 tiles; value (q = 2 a + b, r) is pixel
@@ -942,7 +950,6 @@ __device__ __forceinline__ void wino_tile_body(const WinoArgs& a) {
         if (partial) epilogue(std::true_type{});
         else epilogue(std::false_type{});
         pv_finish(tqp);
-        fo_finish();
         ++dbg_n;
         if (a.dbg) dbg_e += __builtin_amdgcn_s_memtime() - dbg_b;
         if (!has_next) break;
@@ -1817,11 +1824,13 @@ static int launch_wino_rows(const ConvArgs& a, int row0, int nrows, hipStream_t 
         w.rgb = a.src[0];
         w.Urgb = a.wwino_rgb;
         return launch_conv3x3_wino_ms_raw(&w, grid, a.wino_units ? 1 : 0, ntiles, stream);
-    } else if (a.wpar && a.par_any) {
+    } else if (a.wpar && a.par_any && a.fold_tab) {
         // ONE launch behind a device-side gate on the frame's partition word (launch_par_frame_any): the fold-only body when EVERY 8x8
         // quadrant of the frame is all zero or carries one constant plane (one-hot maps on >= 8x8 codec blocks, frames without records),
-        // the branch body otherwise.  Bit-identical results either way.
+        // the branch body otherwise.  Bit-identical results either way.  (The fold-only body reads the frame's fold table: a caller
+        // that has the word but no table gets the branch kernel below on every frame.)
         w.gate = a.par_any;
+        w.fold_tab = a.fold_tab;
         if (a.residual) hipLaunchKernelGGL((conv3x3_wino_gated_kernel<true>), dim3(grid), dim3(256), WINO_LDS, stream, w);       // channel-last blocks
         else hipLaunchKernelGGL((conv3x3_wino_gated_kernel<false>), dim3(grid), dim3(256), WINO_LDS, stream, w);
     } else if (a.wpar && a.residual) hipLaunchKernelGGL((conv3x3_wino_kernel<true, true, false>), dim3(grid), dim3(256), WINO_LDS, stream, w);

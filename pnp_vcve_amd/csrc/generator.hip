@@ -31,6 +31,7 @@
 #ifdef PNP_HOST_STUB
 #include "host_stub/io_stub.h"   // recording stand-ins for the byte-frame launchers (prep.h, conv_mfma.h) of the host-only scheduler tests
 #include "host_stub/yuv_stub.h"  // ... and for the 4:2:0 launchers (yuv.h)
+#include "host_stub/fold_stub.h" // ... and for the fold table's launcher (conv_mfma.h)
 #endif
 
 namespace {
@@ -387,7 +388,9 @@ struct ConvCall {
     ConvCall& gamma(const float* g) { gamma_ = g; return *this; }
     const int* par_flags_ = nullptr;
     const int* par_any_ = nullptr;
-    ConvCall& gate(const int* frame_any) { par_any_ = frame_any; return *this; }       // see ConvArgs::par_any
+    const PnpFoldRec* fold_tab_ = nullptr;
+    // see ConvArgs::par_any, ConvArgs::fold_tab
+    ConvCall& gate(const int* frame_any, const PnpFoldRec* fold_tab = nullptr) { par_any_ = frame_any; fold_tab_ = fold_tab; return *this; }
     ConvCall& partition(const float* w1x1, const float* par, const int* tile_flags = nullptr) {
         wpar_ = w1x1;
         par_ = par;
@@ -438,6 +441,7 @@ struct Workspace {
     uint16_t *x16, *slots16;
     int* parany;      // per frame: OR of its tile flags (ConvArgs::par_any)
     int* parflags;    // per frame, per 8x16 tile: which partition planes are nonzero there (ConvArgs::par_flags)
+    PnpFoldRec* foldtab;   // PNP_PREC_F32: two fold tables (ConvArgs::fold_tab), one per branch run in flight like the image buffers of `wino`
     float* wino;      // PNP_PREC_F32: Winograd images of one branch's dynamic convs for the frame in flight (2 per block; gain folded in)
     int* queue;       // PNP_PREC_F16X3: the split kernel's tile queue (ConvArgs::tile_queue), 16 ints, zero between launches
     // byte frames on a last conv that keeps its fp32 interface (io_staged): ONE frame of fp32 planes each way, converted per frame
@@ -663,6 +667,8 @@ Workspace carve(const pnp_generator* g, char* base, int t, int h, int w, int lq_
     const bool mir = g->prec == PNP_PREC_F16 && g->cfg.deform == 0;      // sized whether or not PNP_OPT_F16_MIRRORS is on
     W.x16 = mir ? reinterpret_cast<uint16_t*>(take(hw * 32)) : nullptr;
     W.slots16 = mir ? reinterpret_cast<uint16_t*>(take(hw * 32 * nslots)) : nullptr;
+    // (a record is 8 bytes = two floats; sized by the frame, not by the clip: what the workspace grows by per frame stays what it was)
+    W.foldtab = g->prec == PNP_PREC_F32 ? reinterpret_cast<PnpFoldRec*>(take(2 * 2 * pnp_fold_records(h, w))) : nullptr;
     W.parany = reinterpret_cast<int*>(take(t));        // (not last: the harness shrinks the workspace and expects the last region to be touched)
     W.parflags = reinterpret_cast<int*>(take(t * par_flag_tiles(h, w)));
     W.queue = g->prec == PNP_PREC_F16X3 ? reinterpret_cast<int*>(take(16)) : nullptr;
@@ -1018,6 +1024,7 @@ struct ClipRun {
         }
         a.wino_units = (q.wino_ || a.wwino_rgb) ? q.units_ : 0;
         a.par_any = (q.wino_ && q.wpar_) ? q.par_any_ : nullptr;       // (tile kernels and quadrant-unit kernels alike: one gated launch)
+        a.fold_tab = a.par_any ? q.fold_tab_ : nullptr;
         a.wpar_h = twin(q.wpar_);
         a.wpar_h_scaled = (g->prec == PNP_PREC_F16X3 && a.wpar_h) ? 1 : 0;     // the packed buffer holds 3 + 3 branch images (build_layout)
         a.par = q.par_, a.par_flags = q.par_flags_;
@@ -1224,12 +1231,28 @@ struct ClipRun {
         return 0;
     }
 
+    // Frame i's fold table (fold_table.h) into table buffer `buf`, in front of the branch run that reads it: plane and factor of every
+    // 8x8 quadrant, which each of the run's gated front halves would otherwise derive again per tile from the partition planes.  One
+    // small launch on the caller's stream, in plain stream order behind the frame's partition map (bounded schedule: its one-frame
+    // buffer) and in front of both chains of the run; two buffers, used like the image buffers of W.wino (run s writes s & 1, which
+    // run s - 2 read last).  Per run and not per clip: a table per frame of the clip would be workspace that grows with the clip.
+    bool fold_on() const { return W.foldtab && wino_on && par_skip && !wino_units(h, w); }
+    PnpFoldRec* fold_buf(int buf) const { return W.foldtab + (int64_t)buf * pnp_fold_records(h, w); }
+    const float* par_of(int i) const { return sparse_per_frame ? W.parbin : par_b + (int64_t)i * 3 * hw; }
+    int fold_table(int i, int buf) {
+        if (!fold_on()) return 0;
+        const int rc = launch_par_fold_table(par_of(i), hw, fold_buf(buf), 1, h, w, st);
+        untimed(g);
+        return rc;
+    }
+
     // input conv over the virtual concat `in` (sources already added), then the BAE blocks
     // (out: the frame map its last block writes, Step::out)
     int run_branch(int brid, int i, int out, int buf, ConvCall in) {
         const BranchPk& B = g->br[brid];
         const float* wbuf = W.wino ? wino_buf(buf) : nullptr;
-        const float* parp = sparse_per_frame ? W.parbin : par_b + (int64_t)i * 3 * hw;
+        const float* parp = par_of(i);
+        const PnpFoldRec* ftab = fold_on() ? fold_buf(buf) : nullptr;
         const int* pflags = par_skip ? W.parflags + (int64_t)i * par_flag_tiles(h, w) : nullptr;
         // the frame's partition word (launch_par_frame_any) gates the front halves on the device: fold-only kernel / branch kernel
         // (launch_conv3x3_wino); an I frame usually carries no record at all (its word is then 8: all quadrants zero)
@@ -1261,7 +1284,7 @@ struct ClipRun {
             const float* u1 = !wino_on ? nullptr : (c.one_layer ? packed + K.conv1_wino : wbuf + (int64_t)(2 * k + 1) * PNP_WINO_IMG_FLOATS);
             if (c.channel_first) {   // sr_backbone_utils.py:305-313
                 r = conv(ConvCall(h, w, cfg_lr).source(x, 64, w2).mirror16(x16).bias(b2).gamma(g2)
-                             .partition(packed + K.w1x1, parp, pflags).gate(pany).wino(u2, wi(K.w1x1_wino)).units(un).act(1).to(W.tmp1).f16_map(o16));
+                             .partition(packed + K.w1x1, parp, pflags).gate(pany, ftab).wino(u2, wi(K.w1x1_wino)).units(un).act(1).to(W.tmp1).f16_map(o16));
                 if (!r)
                     r = conv(ConvCall(h, w, cfg_lr).source(W.tmp1, 64, w1).bias(b1).gamma(g1).wino(u1).units(un).residual(x).to(dst)
                                  .f16_map(s16).also16(dst16));
@@ -1270,7 +1293,7 @@ struct ClipRun {
                              .f16_map(o16));
                 if (!r)
                     r = conv(ConvCall(h, w, cfg_lr).source(W.tmp1, 64, w2).bias(b2).gamma(g2)
-                                 .partition(packed + K.w1x1, parp, pflags).gate(pany).wino(u2, wi(K.w1x1_wino)).units(un).residual(x).to(dst).f16_map(s16).also16(dst16));
+                                 .partition(packed + K.w1x1, parp, pflags).gate(pany, ftab).wino(u2, wi(K.w1x1_wino)).units(un).residual(x).to(dst).f16_map(s16).also16(dst16));
             }
             if (r) return r;
             x = dst;
@@ -1375,6 +1398,8 @@ struct ClipRun {
             rc = branch_images(steps[si + 1].sweep, steps[si + 1].frame, (int)((si + 1) & 1));
             if (rc) return rc;
         }
+        rc = fold_table(i, (int)(si & 1));
+        if (rc) return rc;
         rc = chain.open(1 + 2 * c.num_blocks + (hr_in_chain ? 1 : 0));
         if (rc) return rc;
         rc = run_branch(sp.sweep, i, sp.out, (int)(si & 1), in);

@@ -254,6 +254,34 @@ int pnp_debug_wino_gate_word(const int* gate_word_dev) {
     return 0;
 }
 
+int pnp_debug_par_fold_table(const float* par, void* table, int h, int w, void* st) {
+    if (!par || !table || h < 1 || w < 1) return PNP_ERR_BAD_ARG;
+    return launch_par_fold_table(par, (long)h * w, static_cast<PnpFoldRec*>(table), 1, h, w, (hipStream_t)st);
+}
+
+// The fold-only body of the gated launch reads the frame's fold table (ConvArgs::fold_tab), which the clip scheduler makes in its
+// workspace in front of every branch run.  This stand-alone entry reaches the gated launch under the test hook above only and has no
+// workspace: it keeps one table per device, grown on demand, and makes it again on every such call, on the call's stream in front of
+// the conv.  Like the hook itself this is process-wide and for one stream at a time.
+static int debug_fold_table(const float* par, int h, int w, hipStream_t st, const PnpFoldRec** out) {
+    static std::mutex mu;
+    static PnpFoldRec* tab[PnpPerDevice::MAXDEV] = {};
+    static long cap[PnpPerDevice::MAXDEV] = {};
+    int dev = 0;
+    PNP_CHECK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= PnpPerDevice::MAXDEV) return PNP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lock(mu);
+    const long need = pnp_fold_records(h, w);
+    if (cap[dev] < need) {
+        if (tab[dev]) PNP_CHECK(hipFree(tab[dev]));       // (waits for the device: no launch still reads the old table)
+        tab[dev] = nullptr, cap[dev] = 0;
+        PNP_CHECK(hipMalloc(reinterpret_cast<void**>(&tab[dev]), (size_t)need * sizeof(PnpFoldRec)));
+        cap[dev] = need;
+    }
+    *out = tab[dev];
+    return launch_par_fold_table(par, (long)h * w, tab[dev], 1, h, w, st);
+}
+
 int pnp_conv3x3_wino_f32_ex(const float* src, const float* wino_w, const float* bias, const float* gamma, const float* wino_w1x1,
                             const float* par, const int* par_flags, const float* residual, int act, float* out, int h, int w,
                             void* trace, void* st) {
@@ -273,6 +301,10 @@ int pnp_conv3x3_wino_f32_ex(const float* src, const float* wino_w, const float* 
         a.tile_rows = g_debug_wino_rows;
     }
     if (!conv_wino_eligible(a, CONV_CFG_BIG, 1)) return PNP_ERR_UNSUPPORTED;
+    if (a.par_any && !units) {
+        const int rc = debug_fold_table(par, h, w, (hipStream_t)st, &a.fold_tab);
+        if (rc) return rc;
+    }
     return launch_conv3x3_wino(a, (hipStream_t)st);
 }
 

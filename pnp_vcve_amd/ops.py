@@ -158,6 +158,20 @@ def par_tile_flags(par):
 
 
 @_on_device_of_first_tensor
+def par_fold_table(par):
+    """(3,h,w) partition planes -> int32 (4 * tiles16, 2): the frame's fold table (csrc/fold_table.h), per 8x8 quadrant in 16x16-tile-major
+    order the plane the fold-only Winograd body folds (-1: none) and the bits of its fp32 factor 0.25f * value."""
+    par = _chk(par, 'par')
+    if par.dim() != 3 or par.shape[0] != 3:
+        raise ValueError('par must be (3,h,w)')
+    h, w = par.shape[1:]
+    out = torch.empty((4 * ((h + 15) // 16) * ((w + 15) // 16), 2), device=par.device, dtype=torch.int32)
+    _native.check(_native.lib().pnp_debug_par_fold_table(_ptr(par), ctypes.c_void_p(out.data_ptr()), h, w, _stream()),
+                  'pnp_debug_par_fold_table')
+    return out
+
+
+@_on_device_of_first_tensor
 def f16_image(packed):
     """fp32 packed weight image (whole chunks) -> fp16 image for conv3x3(..., fp16=True)."""
     packed = _chk(packed, 'packed')
