@@ -229,7 +229,7 @@ int64_t pnp_generator_workspace_bytes_io(const pnp_generator* g, int t, int h, i
  *   rounding half to even; per pixel pb = (b - yl) * (0.5 / (1 - Kb)), pr = (r - yl) * (0.5 / (1 - Kr)); the chroma sample of a 2x2
  *   block is the BOX MEAN ((p00 + p01) + (p10 + p11)) * 0.25 (rows top then bottom, columns left then right) and
  *   Cb = clamp(rint(128 + sc * mean_pb), 0, 255), Cr likewise.  Box-down and replicate-up are consistent (centre siting); other
- *   sitings and filters, 10 bit, 4:2:2 and 4:4:4 are not offered.  Limited-range white (235,128,128) gives 0.99999994, not 1.
+ *   sitings and filters, 4:2:2 and 4:4:4 are not offered (10 and 12 bit: pnp_yuv420_planes16 below).  Limited-range white (235,128,128) gives 0.99999994, not 1.
  * A plane pointer may sit at ANY byte address and a pitch may be any value that holds a row, odd ones too.  No byte outside
  * [plane, plane + rows * pitch) of a plane is read or written, and inside it the bytes of a row beyond the frame's width are never
  * written.  Planes and pitches that are 4-byte aligned take a faster form of the unpacking (same values).
@@ -301,6 +301,68 @@ int pnp_psnr_sse_yuv420(const pnp_yuv420_planes* a_host_desc, const pnp_yuv420_p
 int pnp_ssim_blocks_yuv420(int h, int w, int crop_border, int plane);
 int pnp_ssim_partials_yuv420(const pnp_yuv420_planes* a_host_desc, const pnp_yuv420_planes* b_host_desc, int plane_mask,
                              double* partials_dev, int frames, int h, int w, int crop_border, void* stream);
+
+/* 10 / 12-bit 4:2:0 boundary (yuv16.hip): the same boundary on the planes HEVC Main10 / VVC decoders and reference software write.
+ * The reference has no such path; tests/yuv16_ref.py restates the arithmetic below in numpy.  This is the ONE statement of it.
+ *   Containers: bit depth d = 10 | 12, a sample in a 16-bit little-endian word; LOW-aligned (yuv420p10le / yuv420p12le: the value in
+ *   the low d bits, msb_aligned = 0) or HIGH-aligned (P010 / P012: the value in the high d bits, msb_aligned = 1).  Reading is total
+ *   and deterministic: a low-aligned word is taken & (2^d - 1), a high-aligned word >> (16 - d).  Writing sets the bits outside the
+ *   value to zero.
+ *   Range constants, with s = 2^(d-8): limited range yoff = 16 s, sy = 219 s, sc = 224 s; full range yoff = 0, sy = sc = 2^d - 1; the
+ *   chroma midpoint is 2^(d-1) in both (it takes the place of 128).
+ *   Kr, Kb, the formulas, the clamp to [0, 1], replicated chroma on the way in and the box mean on the way out are those of the 8-bit
+ *   statement above, word for word, with these constants; rounding is rint, half to even, clamped to [0, 2^d - 1].  Every constant
+ *   is evaluated in double and rounded to fp32 ONCE; every later product and sum is an fp32 operation of its own, no contraction.
+ *   The limited-range identity: in limited range every constant is the 8-bit one times an exact power of two (cy, crv, ... divided by
+ *   s; yoff, sy, sc and the midpoint times s), and float(s Y - 16 s) = s float(Y - 16) exactly.  So planes whose samples are s
+ *   times an 8-bit clip's samples convert to the SAME fp32 RGB as that clip, bit for bit (tests/test_yuv16_ref.py and the GPU
+ *   suite rest on this: it ties this path to the pinned 8-bit one).  Full range has no such identity: 2^d - 1 is no multiple of 255.
+ *   Limited-range white (235 s, 128 s, 128 s) therefore gives 0.99999994 here too.
+ * pnp_yuv420_planes16: pointers, pitches and frame strides must be EVEN (pitches and strides are in BYTES, c_step in SAMPLES);
+ * beyond that any address and any pitch that holds a row.  The 8-bit rule carries over: no byte outside [plane, plane + rows *
+ * pitch) of a plane is read or written, and inside it no byte of a row beyond the frame's width is written.  Planes, pitches and
+ * strides that are 8-byte aligned (w a multiple of 4; interleaved chroma: the pair's first plane) take a faster form of the
+ * unpacking (same values).
+ * pnp_generator_forward_clips_yuv16: pnp_generator_forward_clips_yuv on such planes.  out_mask as there; PNP_OUT_YUV420 selects
+ * out_yuv16, whose depth and container may differ from the input's.  The workspace is exactly that of
+ * pnp_generator_workspace_bytes_yuv (every staged frame is fp32).  The fp32 output is bit-identical to the fp32 forward on
+ * pnp_frames_from_yuv420p16 of the planes, and the planes written are pnp_frames_to_yuv420p16 of the fp32 output.
+ * Plane metrics: pnp_psnr_sse_yuv420p16 is pnp_psnr_sse_yuv420 on the sample values (exact uint64; a squared difference reaches
+ * 2^24, sums are 64-bit from the start); the host applies the peak (2^d - 1)^2.  pnp_ssim_partials_yuv420p16: the window, tiling,
+ * block counts (pnp_ssim_blocks_yuv420 as is) and summation order of pnp_ssim_partials_yuv420 on the sample values as floats, with
+ * C1 = (0.01 L)^2, C2 = (0.03 L)^2, L = 2^d - 1.  The two clips are described each on its own (layout, pitch, container), but their
+ * bit_depth must agree.
+ * Errors, decided on the host before any HIP call: PNP_ERR_BAD_ARG for what the 8-bit entries refuse (standard, mask, NULL plane or
+ * output the mask needs, c_step not 1 or 2, odd h or w, frames / crop / plane_mask of the metrics) and for a bit_depth that is not 10
+ * or 12, msb_aligned not 0 or 1, an odd pointer, pitch or frame stride, a pitch below 2 w (Y) or 2 c_step w/2 (chroma) bytes, and
+ * differing depths in a metric call; then the forward's own, in their order. */
+typedef struct pnp_yuv420_planes16 {    /* t frames of h x w, 10 or 12 bit in 16-bit words, 4:2:0 */
+    unsigned short *y, *cb, *cr;        /* first frame's planes; P010: cr == cb + 1, c_step 2; yuv420p10le: c_step 1 */
+    int64_t y_pitch, c_pitch;           /* BYTES between rows (>= 2 w, >= 2 c_step w/2), even */
+    int64_t y_frame, c_frame;           /* BYTES between frames of the Y plane / of the chroma planes, even */
+    int c_step;                         /* 1 | 2: SAMPLES between chroma samples of a row */
+    int bit_depth;                      /* 10 | 12 */
+    int msb_aligned;                    /* 0: value in the low bits; 1: in the high bits (P010 / P012) */
+} pnp_yuv420_planes16;
+typedef struct pnp_clip_yuv16 {
+    pnp_yuv420_planes16 lq;             /* read only */
+    const float *mvs_dev, *par_dev;     /* as in pnp_clip_io */
+    float* out_f32_dev;                 /* PNP_OUT_F32 */
+    unsigned char* out_u8_dev;          /* PNP_OUT_U8 */
+    pnp_yuv420_planes16 out_yuv16;      /* PNP_OUT_YUV420: H x W = h x w, or 4h x 4w with cfg.vsr */
+} pnp_clip_yuv16;
+int pnp_generator_forward_clips_yuv16(const pnp_generator* g, const float* flat_dev, const float* packed_dev,
+                                      const pnp_clip_yuv16* clips_host, int n, int yuv_standard, int out_mask,
+                                      const float* slices_host, const float* qps_host, const float* base_qps_host,
+                                      void* workspace_dev, int64_t workspace_bytes, int t, int h, int w, void* stream);
+int pnp_frames_from_yuv420p16(const pnp_yuv420_planes16* in_host_desc, int yuv_standard, float* out_planes_dev, int n, int h, int w,
+                              void* stream);
+int pnp_frames_to_yuv420p16(const float* planes_dev, const pnp_yuv420_planes16* out_host_desc, int yuv_standard, int n, int h, int w,
+                            void* stream);
+int pnp_psnr_sse_yuv420p16(const pnp_yuv420_planes16* a_host_desc, const pnp_yuv420_planes16* b_host_desc,
+                           unsigned long long* sse_dev, int frames, int h, int w, int crop_border, void* stream);
+int pnp_ssim_partials_yuv420p16(const pnp_yuv420_planes16* a_host_desc, const pnp_yuv420_planes16* b_host_desc, int plane_mask,
+                                double* partials_dev, int frames, int h, int w, int crop_border, void* stream);
 
 /* Optional per-launch timing with HIP events recorded on the caller's stream around every
  * kernel of pnp_generator_forward (measurement aid for bench.py; replaces the reference's

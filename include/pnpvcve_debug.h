@@ -61,6 +61,10 @@ int pnp_debug_pack_lr_u8(const unsigned char* lq_dev, float* lr4_dev, int t, int
  * aligned and w is a multiple of 4); 1: the byte-load form whatever the alignment.  Same values either way. */
 int pnp_debug_pack_lr_yuv420(const pnp_yuv420_planes* in_host_desc, int yuv_standard, float* lr4_dev, int t, int h, int w,
                              int general, void* stream);
+/* The same for 10 / 12-bit planes (pnp_generator_forward_clips_yuv16): the values of pnp_frames_from_yuv420p16.  general = 0: the
+ * aligned form where planes, pitches and strides are 8-byte aligned and w is a multiple of 4; 1: the 2-byte-load form. */
+int pnp_debug_pack_lr_yuv420p16(const pnp_yuv420_planes16* in_host_desc, int yuv_standard, float* lr4_dev, int t, int h, int w,
+                                int general, void* stream);
 
 /* The row-band plan of pnp_generator_set_band_split as a pure function: for a chain of nconv convs on a frame of `rows` tile rows,
  * writes the boundary row a_n of each conv (chain A: tile rows [0, a_n), chain B: [a_n, rows); a_n = a_0 - n) to bounds[0 .. nconv)

@@ -37,6 +37,18 @@ class ClipYuv(ctypes.Structure):
                 ('out_yuv', Yuv420Planes)]
 
 
+class Yuv420Planes16(ctypes.Structure):
+    """pnp_yuv420_planes16: t frames of 10 / 12-bit 4:2:0 planes in 16-bit words (device addresses, byte strides, c_step in samples)"""
+    _fields_ = [('y', c_void_p), ('cb', c_void_p), ('cr', c_void_p), ('y_pitch', c_int64), ('c_pitch', c_int64), ('y_frame', c_int64),
+                ('c_frame', c_int64), ('c_step', c_int), ('bit_depth', c_int), ('msb_aligned', c_int)]
+
+
+class ClipYuv16(ctypes.Structure):
+    """pnp_clip_yuv16: one clip of a pnp_generator_forward_clips_yuv16 batch"""
+    _fields_ = [('lq', Yuv420Planes16), ('mvs_dev', c_void_p), ('par_dev', c_void_p), ('out_f32_dev', c_void_p), ('out_u8_dev', c_void_p),
+                ('out_yuv16', Yuv420Planes16)]
+
+
 FRAMES_F32_NCHW, FRAMES_U8_HWC = 0, 1        # PNP_FRAMES_*
 OUT_F32, OUT_U8, OUT_YUV420 = 1, 2, 4        # PNP_OUT_* (a mask; OUT_YUV420 on pnp_generator_forward_clips_yuv only)
 YUV_STANDARDS = {'bt601-limited': 0, 'bt601-full': 1, 'bt709-limited': 2, 'bt709-full': 3}      # PNP_YUV_*
@@ -80,6 +92,14 @@ SIGNATURES = {
     'pnp_psnr_sse_yuv420': (c_int, [POINTER(Yuv420Planes), POINTER(Yuv420Planes), c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'pnp_ssim_blocks_yuv420': (c_int, [c_int, c_int, c_int, c_int]),
     'pnp_ssim_partials_yuv420': (c_int, [POINTER(Yuv420Planes), POINTER(Yuv420Planes), c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'pnp_generator_forward_clips_yuv16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                                  POINTER(c_float), POINTER(c_float), POINTER(c_float),
+                                                  c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    'pnp_frames_from_yuv420p16': (c_int, [POINTER(Yuv420Planes16), c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'pnp_frames_to_yuv420p16': (c_int, [c_void_p, POINTER(Yuv420Planes16), c_int, c_int, c_int, c_int, c_void_p]),
+    'pnp_psnr_sse_yuv420p16': (c_int, [POINTER(Yuv420Planes16), POINTER(Yuv420Planes16), c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'pnp_ssim_partials_yuv420p16': (c_int, [POINTER(Yuv420Planes16), POINTER(Yuv420Planes16), c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                            c_void_p]),
     'pnp_generator_set_precision': (c_int, [c_void_p, c_int]),
     'pnp_generator_get_precision': (c_int, [c_void_p]),
     'pnp_generator_set_option': (c_int, [c_void_p, c_int, c_int]),
@@ -163,6 +183,7 @@ DEBUG_SIGNATURES['pnp_debug_wino_tile_rows'] = (c_int, [c_int, c_int])
 DEBUG_SIGNATURES['pnp_debug_wino_ms_trace'] = (c_int, [c_void_p])
 DEBUG_SIGNATURES['pnp_debug_pack_lr_u8'] = (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
 DEBUG_SIGNATURES['pnp_debug_pack_lr_yuv420'] = (c_int, [POINTER(Yuv420Planes), c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
+DEBUG_SIGNATURES['pnp_debug_pack_lr_yuv420p16'] = (c_int, [POINTER(Yuv420Planes16), c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
 DEBUG_SIGNATURES['pnp_band_plan'] = (c_int, [c_int, c_int, c_int, POINTER(c_int)])
 DEBUG_SIGNATURES['pnp_conv3x3_wino_f32_ex'] = (c_int, [c_void_p] * 8 + [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p])
 DEBUG_SIGNATURES['pnp_conv3x3_f16_maps'] = (c_int, [c_int, POINTER(c_void_p), POINTER(c_int), c_int, POINTER(c_void_p), c_void_p,

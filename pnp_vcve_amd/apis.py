@@ -14,13 +14,18 @@ def _to_device(data, device, byte_frames=False, byte_metrics=False):
     the same 256 values as the loop below, bit for bit).
     byte_metrics (with byte_frames): `gt` stays the (n,T,H,W,3) uint8 tensor too -- the device metrics read the bytes.
     Raw 4:2:0 clips (Yuv420ClipFolderDataset: `lq_yuv` / `gt_yuv`, packed (n,T,3h/2,w) uint8) are uploaded as they are, 1.5 B per
-    pixel, and become ops.Yuv420Frames views of those buffers (`lq`, `gt`) in the layout the sample's meta names: nothing is converted."""
+    pixel, and become ops.Yuv420Frames views of those buffers (`lq`, `gt`) in the layout the sample's meta names: nothing is converted.
+    Where the meta names a bit_depth of 10 or 12 the buffers are 16-bit words (3 B per pixel) and the views ops.Yuv420Frames16."""
     out = {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in data.items()}
     for k in ('lq', 'gt'):
         if k + '_yuv' in out:
-            from .ops import yuv420_views
+            from .ops import yuv420_views, yuv420p16_views
             buf = out.pop(k + '_yuv')                                      # (n, T, 3h/2, w)
-            out[k] = yuv420_views(buf, buf.shape[-2] * 2 // 3, buf.shape[-1], data['meta'][0]['layout'])
+            meta = data['meta'][0]
+            if meta.get('bit_depth', 8) != 8:
+                out[k] = yuv420p16_views(buf, buf.shape[-2] * 2 // 3, buf.shape[-1], (meta['layout'], meta['bit_depth'], meta.get('msb_aligned', False)))
+            else:
+                out[k] = yuv420_views(buf, buf.shape[-2] * 2 // 3, buf.shape[-1], meta['layout'])
     if byte_frames:
         from .ops import frames_from_rgb8
         if 'lq_u8' in out:
@@ -160,7 +165,10 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
     asked for packed 4:2:0 in `yuv_out_layout` ('i420' | 'nv12') ONLY, the ground truth stays 8-bit planes on the device, the metrics
     are the plane metrics of BasicVSR.evaluate (ops.psnr_yuv420 / ssim_yuv420: 'PSNR' / 'SSIM' score the Y plane; 'PSNR_U', 'PSNR_V',
     'SSIM_U', 'SSIM_V', 'PSNR_YUV' are accepted too), and save_image writes <save_path>/<clip>.yuv -- exactly the bytes of
-    ops.frames_to_yuv420(fp32 output, standard, layout).  A pair goes through generator.forward_clips by pointer, as under byte_frames."""
+    ops.frames_to_yuv420(fp32 output, standard, layout).  A pair goes through generator.forward_clips by pointer, as under byte_frames.
+    A dataset of 10 / 12-bit clips (its samples' meta carry the depth) goes the same way as ops.Yuv420Frames16; yuv_out_layout then
+    also takes 'p010' | 'p012' | 'yuv420p10le' | 'yuv420p12le', the ground truth and the output must agree in depth, and the file is
+    ops.frames_to_yuv420p16's words, little-endian."""
     import time
     model.eval()
     rank, world = get_dist_info()
@@ -180,8 +188,14 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
             raise ValueError('yuv_frames runs the generator on the GPU: a CUDA/HIP device and a model with a generator (not psnr_only)')
         if byte_frames:
             raise ValueError('yuv_frames and byte_frames / byte_metrics are two boundaries: pick one')
-        if yuv_out_layout not in ('i420', 'nv12'):
-            raise ValueError(f"yuv_out_layout must be 'i420' or 'nv12', got {yuv_out_layout!r}")
+        from .ops import YUV16_LAYOUTS
+        depth = getattr(dataset, 'bit_depth', 8)
+        if yuv_out_layout not in ('i420', 'nv12') and yuv_out_layout not in YUV16_LAYOUTS:
+            raise ValueError(f"yuv_out_layout must be 'i420' or 'nv12', or one of {sorted(YUV16_LAYOUTS)} for a 10 / 12-bit dataset, "
+                             f'got {yuv_out_layout!r}')
+        if YUV16_LAYOUTS.get(yuv_out_layout, (None, 8))[1] != depth:
+            raise ValueError(f'yuv_out_layout {yuv_out_layout!r} does not have the dataset\'s bit depth ({depth}): the output is scored '
+                             f'against the ground truth at one depth')
     yuv_standard = getattr(dataset, 'yuv_standard', 'bt601-limited')
     out_dtype = None
     if yuv_frames:

@@ -5,6 +5,7 @@
 #include "plane_load.h"
 #include "prep.h"
 #include "yuv.h"
+#include "yuv16.h"
 #include <cmath>
 
 namespace {
@@ -116,8 +117,27 @@ __global__ __launch_bounds__(256) void psnr_yuv420_kernel(const PsnrYuvArgs s) {
 // ssim_kernel (metrics.hip) with the plane loader in front: tiling, LDS layout and both passes are ssim_kernel's, statement for
 // statement, so a plane gives the partials of its (frames,1,rows,cols) fp32 plane byte / 255.0f bit for bit (to_u8 of that value is
 // the byte).  One launch serves every plane of the mask: blocks [blk0, blk0 + blocks) of the grid's x are plane k's.
+// One plane of a 10 / 12-bit clip (pnp_yuv420_planes16): 2-byte loads, sample (row, col) of frame f is the word at
+// p + f * frame + row * pitch (bytes) + col * step (samples), read as (word >> shift) & mask.
+struct Plane16 {
+    const unsigned short* p;
+    long pitch, frame;
+    int step;
+    unsigned shift, mask;
+};
+__device__ __forceinline__ unsigned load16(const Plane16& s, long f, int row, int col) {
+    const unsigned short* q = reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(s.p) + f * s.frame + (long)row * s.pitch);
+    return ((unsigned)q[(long)col * s.step] >> s.shift) & s.mask;
+}
+Plane16 plane16(const pnp_yuv420_planes16& p, int plane) {      // plane: 0 Y | 1 Cb | 2 Cr
+    const unsigned shift = p.msb_aligned ? 16u - (unsigned)p.bit_depth : 0u, mask = (1u << p.bit_depth) - 1u;
+    if (plane == 0) return Plane16{p.y, p.y_pitch, p.y_frame, 1, shift, mask};
+    return Plane16{plane == 1 ? p.cb : p.cr, p.c_pitch, p.c_frame, p.c_step, shift, mask};
+}
+
 struct SsimPlane {
     PnpPlaneSrc a, b;
+    Plane16 a16, b16;       // the 16-bit sample path's planes (ssim_yuv420_kernel<true>)
     int a_sel, b_sel;       // which word of the loader's pair the plane is (1: the second of an interleaved pair)
     int H, W, crop, oh, ow, tiles_x, blocks, blk0;
     long out0;              // first partial of this plane
@@ -127,8 +147,12 @@ struct SsimYuvArgs {
     SsimPlane pl[3];
     int nplanes;
     double* partial;
+    double L;               // the 16-bit sample path's peak 2^d - 1 (the 8-bit path's is the constant 255)
 };
 
+// S16: the samples are the values of 16-bit words (Plane16), fetched one by one; otherwise bytes through the plane loader.  Only the
+// tile fill and the peak differ: both passes are one body.
+template <bool S16>
 __global__ __launch_bounds__(256) void ssim_yuv420_kernel(const SsimYuvArgs s) {
     __shared__ float ta[26 * 42], tb[26 * 42];
     __shared__ double hm[5][26 * 32];
@@ -139,7 +163,16 @@ __global__ __launch_bounds__(256) void ssim_yuv420_kernel(const SsimYuvArgs s) {
     const int blk = blockIdx.x - p.blk0, t = threadIdx.x;
     const long frame = blockIdx.y;
     const int ty0 = (blk / p.tiles_x) * 16, tx0 = (blk % p.tiles_x) * 32;        // in valid-map coordinates
-    for (int i = t; i < 26 * 11; i += 256) {                                      // a row of the tile = 10 groups of four and one of two
+    if (S16) {
+        for (int i = t; i < 26 * 42; i += 256) {
+            const int r = i / 42, cx = i - r * 42;
+            const int y = p.crop + ty0 + r, x = p.crop + tx0 + cx;
+            const bool in = y < p.H - p.crop && x < p.W - p.crop;       // absent samples are 0 in both tiles
+            ta[i] = in ? (float)load16(p.a16, frame, y, x) : 0.f;
+            tb[i] = in ? (float)load16(p.b16, frame, y, x) : 0.f;
+        }
+    }
+    for (int i = t; !S16 && i < 26 * 11; i += 256) {                              // a row of the tile = 10 groups of four and one of two
         const int r = i / 11, gc = i - r * 11;
         const int y = p.crop + ty0 + r, x = p.crop + tx0 + 4 * gc;
         int npix = 42 - 4 * gc < 4 ? 42 - 4 * gc : 4;
@@ -178,7 +211,8 @@ __global__ __launch_bounds__(256) void ssim_yuv420_kernel(const SsimYuvArgs s) {
         hm[4][i] = s12;
     }
     __syncthreads();
-    const double C1 = (0.01 * 255) * (0.01 * 255), C2 = (0.03 * 255) * (0.03 * 255);
+    const double L = S16 ? s.L : 255.0;
+    const double C1 = (0.01 * L) * (0.01 * L), C2 = (0.03 * L) * (0.03 * L);
     double acc = 0;
     for (int i = t; i < 16 * 32; i += 256) {
         const int r = i >> 5, c = i & 31;
@@ -203,6 +237,63 @@ bool planes_args_ok(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, cons
     if (!a || !b || !out || frames < 1 || h < 2 || w < 2 || (h & 1) || (w & 1)) return false;
     if (crop < 0 || (crop & 1) || 2 * crop >= h || 2 * crop >= w) return false;
     return yuv_planes_ok(*a, w) && yuv_planes_ok(*b, w);
+}
+
+bool planes16_args_ok(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, const void* out, int frames, int h, int w, int crop) {
+    if (!a || !b || !out || frames < 1 || h < 2 || w < 2 || (h & 1) || (w & 1)) return false;
+    if (crop < 0 || (crop & 1) || 2 * crop >= h || 2 * crop >= w) return false;
+    return yuv16_planes_ok(*a, w) && yuv16_planes_ok(*b, w) && a->bit_depth == b->bit_depth;
+}
+
+void ssim_window(double* g) {                            // cv2.getGaussianKernel(11, 1.5)
+    double sum = 0;
+    for (int i = 0; i < 11; ++i) {
+        g[i] = exp(-((i - 5.0) * (i - 5.0)) / (2 * 1.5 * 1.5));
+        sum += g[i];
+    }
+    for (int i = 0; i < 11; ++i) g[i] /= sum;
+}
+
+// The exact integer SSE of the three planes of two 16-bit clips in one launch: psnr_yuv420_kernel's walk (a wave a row, first the Y
+// plane's rows, then the chroma planes') with one 2-byte load per sample.  A squared difference reaches 2^24: 64-bit sums throughout.
+struct Psnr16Args {
+    Plane16 a[3], b[3];
+    int crop, ry, wy, rc, wc;       // crop of the Y plane (the chroma planes': crop / 2); rows and columns of the cropped planes
+    unsigned long long* sse;        // (frames, 3), zeroed by the launcher
+};
+__global__ __launch_bounds__(256) void psnr_yuv420p16_kernel(const Psnr16Args s) {
+    const long frame = blockIdx.y;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    unsigned long long acc[3] = {0, 0, 0};
+    const int total = s.ry + s.rc, cc = s.crop >> 1;
+    for (int r = blockIdx.x * 4 + ty; r < total; r += gridDim.x * 4) {
+        if (r < s.ry) {
+            for (int x = tx; x < s.wy; x += 64) {
+                const long d = (long)load16(s.a[0], frame, s.crop + r, s.crop + x) - (long)load16(s.b[0], frame, s.crop + r, s.crop + x);
+                acc[0] += (unsigned long long)(d * d);
+            }
+        } else {
+            const int row = cc + r - s.ry;
+            for (int x = tx; x < s.wc; x += 64) {
+                const long db = (long)load16(s.a[1], frame, row, cc + x) - (long)load16(s.b[1], frame, row, cc + x);
+                const long dr = (long)load16(s.a[2], frame, row, cc + x) - (long)load16(s.b[2], frame, row, cc + x);
+                acc[1] += (unsigned long long)(db * db);
+                acc[2] += (unsigned long long)(dr * dr);
+            }
+        }
+    }
+    __shared__ unsigned long long red[4][3];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        unsigned long long v = acc[p];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (tx == 0) red[ty][p] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const unsigned long long v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+        if (v) atomicAdd(&s.sse[frame * 3 + threadIdx.x], v);
+    }
 }
 
 }  // namespace
@@ -249,6 +340,7 @@ extern "C" int pnp_ssim_partials_yuv420(const pnp_yuv420_planes* a, const pnp_yu
         const int nb = pnp_ssim_blocks_yuv420(h, w, crop_border, bit);
         if (nb < 1) return PNP_ERR_BAD_ARG;                          // a cropped plane of the mask below 11x11
         SsimPlane& p = s.pl[s.nplanes++];
+        p.a16 = p.b16 = Plane16{};
         if (bit == PNP_PLANE_Y) {
             p.a = luma_src(*a, h, w);
             p.b = luma_src(*b, h, w);
@@ -272,12 +364,62 @@ extern "C" int pnp_ssim_partials_yuv420(const pnp_yuv420_planes* a, const pnp_yu
         out0 += (long)frames * nb;
     }
     for (int k = s.nplanes; k < 3; ++k) s.pl[k] = s.pl[0];
-    double sum = 0;
-    for (int i = 0; i < 11; ++i) {                       // cv2.getGaussianKernel(11, 1.5)
-        s.g[i] = exp(-((i - 5.0) * (i - 5.0)) / (2 * 1.5 * 1.5));
-        sum += s.g[i];
+    ssim_window(s.g);
+    s.L = 255.0;
+    hipLaunchKernelGGL(ssim_yuv420_kernel<false>, dim3(blk0, frames), dim3(256), 0, (hipStream_t)stream, s);
+    return (int)hipGetLastError();
+}
+
+extern "C" int pnp_psnr_sse_yuv420p16(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, unsigned long long* sse, int frames, int h,
+                                      int w, int crop_border, void* stream) {
+    if (!planes16_args_ok(a, b, sse, frames, h, w, crop_border)) return PNP_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int ze = launch_zero_words(sse, 2L * 3 * frames, st);      // a kernel, not a memset node (prep.h)
+    if (ze != PNP_OK) return ze;
+    Psnr16Args s;
+    for (int k = 0; k < 3; ++k) s.a[k] = plane16(*a, k), s.b[k] = plane16(*b, k);
+    s.crop = crop_border;
+    s.ry = h - 2 * crop_border, s.wy = w - 2 * crop_border;
+    s.rc = h / 2 - crop_border, s.wc = w / 2 - crop_border;
+    s.sse = sse;
+    int bx = (s.ry + s.rc + 3) / 4;
+    bx = bx > 1024 ? 1024 : bx;
+    hipLaunchKernelGGL(psnr_yuv420p16_kernel, dim3(bx, frames), dim3(256), 0, st, s);
+    return (int)hipGetLastError();
+}
+
+extern "C" int pnp_ssim_partials_yuv420p16(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, int plane_mask, double* partials,
+                                           int frames, int h, int w, int crop_border, void* stream) {
+    if (!planes16_args_ok(a, b, partials, frames, h, w, crop_border) || plane_mask < 1 || plane_mask > 7) return PNP_ERR_BAD_ARG;
+    SsimYuvArgs s;
+    s.nplanes = 0;
+    s.partial = partials;
+    s.L = (double)((1 << a->bit_depth) - 1);
+    int blk0 = 0;
+    long out0 = 0;
+    for (int k = 0; k < 3; ++k) {
+        const int bit = 1 << k;
+        if (!(plane_mask & bit)) continue;
+        const int nb = pnp_ssim_blocks_yuv420(h, w, crop_border, bit);
+        if (nb < 1) return PNP_ERR_BAD_ARG;                          // a cropped plane of the mask below 11x11
+        SsimPlane& p = s.pl[s.nplanes++];
+        p.a = p.b = PnpPlaneSrc{};
+        p.a_sel = p.b_sel = 0;
+        p.a16 = plane16(*a, k);
+        p.b16 = plane16(*b, k);
+        if (bit == PNP_PLANE_Y) p.H = h, p.W = w, p.crop = crop_border;
+        else p.H = h / 2, p.W = w / 2, p.crop = crop_border / 2;
+        p.oh = p.H - 2 * p.crop - 10;
+        p.ow = p.W - 2 * p.crop - 10;
+        p.tiles_x = (p.ow + 31) / 32;
+        p.blocks = nb;
+        p.blk0 = blk0;
+        p.out0 = out0;
+        blk0 += nb;
+        out0 += (long)frames * nb;
     }
-    for (int i = 0; i < 11; ++i) s.g[i] /= sum;
-    hipLaunchKernelGGL(ssim_yuv420_kernel, dim3(blk0, frames), dim3(256), 0, (hipStream_t)stream, s);
+    for (int k = s.nplanes; k < 3; ++k) s.pl[k] = s.pl[0];
+    ssim_window(s.g);
+    hipLaunchKernelGGL(ssim_yuv420_kernel<true>, dim3(blk0, frames), dim3(256), 0, (hipStream_t)stream, s);
     return (int)hipGetLastError();
 }

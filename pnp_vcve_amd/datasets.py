@@ -185,11 +185,14 @@ class Yuv420ClipFolderDataset(_EvalMixin, torch.utils.data.Dataset):
     height, width: the frame size of the lq clips (a raw file does not carry it).  mv_folder defaults to lq_folder with its last
     'yuv' path component replaced by 'mv'; the base QP comes from the crfNN path component, as in CompressedClipFolderDataset.
     A sample carries lq_yuv / gt_yuv, packed uint8 (T, 3h/2, w) buffers as on disk, the side info and MV records of the PNG dataset,
-    and meta with `layout` and `yuv_standard`."""
+    and meta with `layout` and `yuv_standard`.
+    bit_depth 10 | 12: the files hold 16-bit little-endian samples (`-pix_fmt yuv420p10le` / `yuv420p12le`, VTM / HM output; with
+    msb_aligned the value sits in the word's high bits, as in P010 / P012 with layout 'nv12'), a frame is 3 h w bytes, the buffers are
+    int16 (T, 3h/2, w) -- the words as they are, uploaded as they are -- and meta carries `bit_depth` and `msb_aligned`."""
 
     def __init__(self, lq_folder, gt_folder, height, width, layout='i420', yuv_standard='bt601-limited', mv_folder=None,
                  num_input_frames=100, scale=1, repeat=1, qp_slice_file=None, replace_qp_withIPB=False, pipeline=None, test_mode=True,
-                 **unused):
+                 bit_depth=8, msb_aligned=False, **unused):
         import json
         import os
         if not isinstance(repeat, int):
@@ -198,6 +201,11 @@ class Yuv420ClipFolderDataset(_EvalMixin, torch.utils.data.Dataset):
             raise ValueError(f"layout must be 'i420', 'nv12' or 'nv21', got {layout!r}")
         if yuv_standard not in ('bt601-limited', 'bt601-full', 'bt709-limited', 'bt709-full'):
             raise ValueError(f'unknown yuv_standard {yuv_standard!r}')
+        if isinstance(bit_depth, bool) or bit_depth not in (8, 10, 12):
+            raise ValueError(f'bit_depth must be 8, 10 or 12, got {bit_depth!r}')
+        if msb_aligned and bit_depth == 8:
+            raise ValueError('msb_aligned describes 16-bit containers: bit_depth 10 or 12')
+        self.bit_depth, self.msb_aligned = int(bit_depth), bool(msb_aligned)
         self.h, self.w, self.scale = int(height), int(width), int(scale)
         if self.h < 2 or self.w < 2 or self.h % 2 or self.w % 2 or self.scale < 1:
             raise ValueError(f'4:2:0 frames need an even height and width (and scale >= 1), got {height} x {width}, scale {scale}')
@@ -223,15 +231,19 @@ class Yuv420ClipFolderDataset(_EvalMixin, torch.utils.data.Dataset):
         return len(self.keys)
 
     @staticmethod
-    def _read_yuv(path, h, w, max_frames):
-        """-> the first min(frames in the file, max_frames) frames as (T, 3h/2, w) uint8"""
+    def _read_yuv(path, h, w, max_frames, bit_depth=8):
+        """-> the first min(frames in the file, max_frames) frames as (T, 3h/2, w) uint8, or int16 words (little-endian in the file) for
+        bit_depth 10 | 12"""
         import os
         import numpy as np
-        per = h * w * 3 // 2
+        wide = bit_depth != 8
+        per = h * w * 3 // 2 * (2 if wide else 1)
         size = os.path.getsize(path)
         if size < per or size % per:
-            raise ValueError(f'{path}: {size} bytes is not a whole number (>= 1) of {h} x {w} 4:2:0 frames of {per} bytes')
+            raise ValueError(f'{path}: {size} bytes is not a whole number (>= 1) of {h} x {w} {bit_depth}-bit 4:2:0 frames of {per} bytes')
         t = min(size // per, max_frames)
+        if wide:
+            return np.fromfile(path, dtype='<i2', count=t * per // 2).astype(np.int16, copy=False).reshape(t, h * 3 // 2, w)
         return np.fromfile(path, dtype=np.uint8, count=t * per).reshape(t, h * 3 // 2, w)
 
     def __getitem__(self, idx):
@@ -239,9 +251,9 @@ class Yuv420ClipFolderDataset(_EvalMixin, torch.utils.data.Dataset):
         import numpy as np
         key = self.keys[idx]
         lq_path, gt_path = os.path.join(self.lq_folder, key + '.yuv'), os.path.join(self.gt_folder, key + '.yuv')
-        lq = self._read_yuv(lq_path, self.h, self.w, self.num_input_frames)
+        lq = self._read_yuv(lq_path, self.h, self.w, self.num_input_frames, self.bit_depth)
         T = lq.shape[0]
-        gt = self._read_yuv(gt_path, self.h * self.scale, self.w * self.scale, T)
+        gt = self._read_yuv(gt_path, self.h * self.scale, self.w * self.scale, T, self.bit_depth)
         if gt.shape[0] != T:
             raise ValueError(f'{gt_path}: {gt.shape[0]} frames for the {T} of {lq_path}')
         parts = self.lq_folder.rstrip('/').split('/')
@@ -266,7 +278,8 @@ class Yuv420ClipFolderDataset(_EvalMixin, torch.utils.data.Dataset):
                     QPs=torch.tensor(qps, dtype=torch.float32).view(T, 1, 1, 1),
                     base_QPs=torch.full((T, 1, 1, 1), base_qp / 255.0, dtype=torch.float32),
                     mv_records=torch.from_numpy(np.concatenate(recs)), rec_frame=torch.from_numpy(np.concatenate(rec_frame)),
-                    meta=dict(key=f'{key}/{0:08d}', lq_path=lq_path, gt_path=gt_path, layout=self.layout, yuv_standard=self.yuv_standard))
+                    meta=dict(key=f'{key}/{0:08d}', lq_path=lq_path, gt_path=gt_path, layout=self.layout, yuv_standard=self.yuv_standard,
+                              bit_depth=self.bit_depth, msb_aligned=self.msb_aligned))
 
 
 def collate(batch):

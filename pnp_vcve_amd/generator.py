@@ -342,8 +342,13 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         colour standard `yuv_standard` ('bt601-limited' | 'bt601-full' | 'bt709-limited' | 'bt709-full') -- bit-identical to
         forward(ops.frames_from_yuv420(lrs, yuv_standard), ...), without the fp32 clip.  out_dtype then also takes 'nv12' / 'i420'
         (a packed uint8 (n,t,3H/2,W) buffer, ops.frames_to_yuv420's arithmetic on the same fp32 values) and a tuple or list of
-        dtypes (several outputs, returned as a tuple in that order)."""
-        if isinstance(lrs, ops.Yuv420Frames):
+        dtypes (several outputs, returned as a tuple in that order).
+
+        10 / 12-bit 4:2:0 frames: an ops.Yuv420Frames16 `lrs` (P010 / P012 / yuv420p10le / yuv420p12le views) -- bit-identical to
+        forward(ops.frames_from_yuv420p16(lrs, yuv_standard), ...).  out_dtype then also takes 'p010' | 'p012' | 'yuv420p10le' |
+        'yuv420p12le' (a packed (n,t,3H/2,W) buffer of 16-bit words of lrs' dtype, ops.frames_to_yuv420p16's arithmetic; its depth and
+        container need not be the input's) beside 'nv12' / 'i420'.  16-bit planes out of 8-bit planes in are refused."""
+        if ops.is_yuv(lrs):
             return self._forward_yuv(lrs, QPs, slices, mvs, base_QPs, par_map, out_dtype, yuv_standard)
         if not lrs.is_cuda:
             raise RuntimeError('PnP-VCVE generator: inputs must be CUDA/HIP tensors; this build has no CPU path '
@@ -455,7 +460,7 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         Clips whose lrs are ops.Yuv420Frames (each clip's planes in allocations of their own) take yuv_standard and the out_dtype
         values of forward()'s 4:2:0 boundary."""
         clips = list(clips)
-        if clips and isinstance(clips[0][0], ops.Yuv420Frames):
+        if clips and ops.is_yuv(clips[0][0]):
             return self._forward_clips_yuv(clips, out_dtype, yuv_standard)
         mask = self._out_mask(out_dtype)
         if not clips:
@@ -546,17 +551,40 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
                 kinds.append('f32')
             elif d == torch.uint8:
                 kinds.append('u8')
-            elif isinstance(d, str) and d in ('nv12', 'i420'):
+            elif isinstance(d, str) and (d in ('nv12', 'i420') or d in ops.YUV16_LAYOUTS):
                 if layout is not None:
                     raise ValueError('one 4:2:0 output layout per call')
                 layout = d
                 kinds.append('yuv')
             else:
-                raise ValueError(f"out_dtype must be None, torch.float32, torch.uint8, 'nv12', 'i420' or a tuple of them, got {d!r}")
+                raise ValueError(f"out_dtype must be None, torch.float32, torch.uint8, 'nv12', 'i420', one of {sorted(ops.YUV16_LAYOUTS)} "
+                                 f"or a tuple of them, got {d!r}")
         if not kinds or len(set(kinds)) != len(kinds):
             raise ValueError(f'out_dtype names no output or one twice: {out_dtype!r}')
         bits = {'f32': _native.OUT_F32, 'u8': _native.OUT_U8, 'yuv': _native.OUT_YUV420}
         return kinds, sum(bits[k] for k in kinds), layout, many
+
+    @staticmethod
+    def _yuv_out_route(lrs, kinds, layout):
+        """What the planes output of a call needs beside the library's own: (None, out_dtype) where the library writes it, or -- 8-bit
+        planes of a 10 / 12-bit clip, which the library's entry for such clips does not write -- (layout, the out_dtype tuple to run
+        instead: the other outputs and the fp32 one the planes are then made of).  16-bit planes of an 8-bit clip are refused."""
+        sixteen = isinstance(lrs, ops.Yuv420Frames16)
+        if layout in ops.YUV16_LAYOUTS and not sixteen:
+            raise ValueError(f'out_dtype {layout!r}: 10 / 12-bit planes out of 8-bit planes in are not offered (the input holds no such '
+                             f'precision); pass ops.Yuv420Frames16 frames or ask for \'nv12\' / \'i420\'')
+        if not sixteen or layout not in ('nv12', 'i420'):
+            return None, None
+        run = [torch.float32 if k == 'f32' else torch.uint8 for k in kinds if k != 'yuv']
+        return layout, tuple(run if 'f32' in kinds else run + [torch.float32])
+
+    @staticmethod
+    def _yuv8_of_16(res, kinds, layout, std):
+        """the outputs `kinds` asks for, from a run of _yuv_out_route's out_dtype: the 8-bit planes are ops.frames_to_yuv420 of the fp32 output"""
+        ran = [k for k in kinds if k != 'yuv'] + ([] if 'f32' in kinds else ['f32'])
+        got = dict(zip(ran, res))
+        got['yuv'] = ops.frames_to_yuv420(got['f32'], std, layout)[0]
+        return tuple(got[k] for k in kinds)
 
     def _yuv_side(self, t, QPs, slices, base_QPs):
         """one clip's (3, t) side info, with forward()'s refusals"""
@@ -573,10 +601,14 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
     def _forward_yuv(self, frames, QPs, slices, mvs, base_QPs, par_map, out_dtype, yuv_standard):
         std = ops._yuv_standard(yuv_standard)
         kinds, mask, layout, many = self._yuv_outs(out_dtype)
-        clips, lead = ops._yuv_clips(frames, 'lrs')
+        clips, lead = ops._any_yuv_clips(frames, 'lrs')
         if not lead:
             raise ValueError('forward() takes a batch: Yuv420Frames of (n,t,rows,cols) views')
-        descs = [ops._yuv_clip_desc(c, 'lrs') for c in clips]      # (every refusal before any GPU work)
+        descs = [ops._any_yuv_clip_desc(c, 'lrs') for c in clips]      # (every refusal before any GPU work)
+        via8, run_dtype = self._yuv_out_route(frames, kinds, layout)
+        if via8:
+            res = self._yuv8_of_16(self._forward_yuv(frames, QPs, slices, mvs, base_QPs, par_map, run_dtype, yuv_standard), kinds, via8, std)
+            return res if many else res[0]
         n, (_, t, h, w) = len(clips), descs[0]
         assert h >= 64 and w >= 64, f'The height and width of inputs should be at least 64, but got {h} and {w}.'
         self._check_resident(t)
@@ -600,14 +632,15 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
             if self.use_graphs and not self._profiling:
                 outs = self._forward_yuv_graphed(clips, mvs_c, par_c, side, std, mask, layout, (n, t, h, w))
             else:
-                outs = self._alloc_yuv_outs(n, t, h, w, mask, layout, dev)
+                outs = self._alloc_yuv_outs(n, t, h, w, mask, layout, dev, frames.y.dtype)
                 ws = self._get_workspace(n, t, h, w, dev, 'yuv', mask)
                 self._launch_clips_yuv(clips, list(mvs_c), list(par_c), side, outs, ws, t, h, w, std)
         res = tuple(outs[k][0] for k in kinds)
         return res if many else res[0]
 
-    def _alloc_yuv_outs(self, n, t, h, w, mask, layout, dev):
-        """-> {'f32' | 'u8' | 'yuv': (the (n,...) tensor returned, what the launch writes per clip)} for the bits of mask"""
+    def _alloc_yuv_outs(self, n, t, h, w, mask, layout, dev, word_dtype=torch.int16):
+        """-> {'f32' | 'u8' | 'yuv': (the (n,...) tensor returned, what the launch writes per clip)} for the bits of mask; word_dtype:
+        the dtype of a 16-bit planes buffer"""
         s = 4 if self.vsr else 1
         outs = {}
         if mask & _native.OUT_F32:
@@ -617,45 +650,55 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
             x = torch.empty((n, t, h * s, w * s, 3), device=dev, dtype=torch.uint8)
             outs['u8'] = (x, list(x))
         if mask & _native.OUT_YUV420:
-            buf, views = ops.empty_yuv420((n, t), h * s, w * s, layout, dev)
-            outs['yuv'] = (buf, ops._yuv_clips(views, 'out')[0])
+            if layout in ops.YUV16_LAYOUTS:
+                buf, views = ops.empty_yuv420p16((n, t), h * s, w * s, layout, dev, word_dtype)
+            else:
+                buf, views = ops.empty_yuv420((n, t), h * s, w * s, layout, dev)
+            outs['yuv'] = (buf, ops._any_yuv_clips(views, 'out')[0])
         return outs
 
     def _launch_clips_yuv(self, clips, mvs, par, side, outs, ws, t, h, w, std):
-        """One pnp_generator_forward_clips_yuv call on torch's current stream: per-clip plane views, nothing copied or concatenated."""
+        """One pnp_generator_forward_clips_yuv call (Yuv420Frames16 clips: pnp_generator_forward_clips_yuv16) on torch's current stream:
+        per-clip plane views, nothing copied or concatenated."""
         n = len(clips)
-        arr = (_native.ClipYuv * n)()
+        sixteen = isinstance(clips[0], ops.Yuv420Frames16)
+        Clip, Planes = (_native.ClipYuv16, _native.Yuv420Planes16) if sixteen else (_native.ClipYuv, _native.Yuv420Planes)
+        entry = 'pnp_generator_forward_clips_yuv16' if sixteen else 'pnp_generator_forward_clips_yuv'
+        arr = (Clip * n)()
         mask = 0
         for kind, bit in (('f32', _native.OUT_F32), ('u8', _native.OUT_U8), ('yuv', _native.OUT_YUV420)):
             mask |= bit if kind in outs else 0
         for b in range(n):
-            lq = ops._yuv_clip_desc(clips[b], 'lrs')[0]
-            oy = ops._yuv_clip_desc(outs['yuv'][1][b], 'out')[0] if 'yuv' in outs else _native.Yuv420Planes()
-            arr[b] = _native.ClipYuv(lq, mvs[b].data_ptr(), par[b].data_ptr(), outs['f32'][1][b].data_ptr() if 'f32' in outs else None,
+            lq = ops._any_yuv_clip_desc(clips[b], 'lrs')[0]
+            oy = ops._any_yuv_clip_desc(outs['yuv'][1][b], 'out')[0] if 'yuv' in outs else Planes()
+            if not isinstance(oy, Planes):
+                raise ValueError('the planes output must have the sample size of the input planes')
+            arr[b] = Clip(lq, mvs[b].data_ptr(), par[b].data_ptr(), outs['f32'][1][b].data_ptr() if 'f32' in outs else None,
                                      outs['u8'][1][b].data_ptr() if 'u8' in outs else None, oy)
         fp = ctypes.POINTER(ctypes.c_float)
         base = side.data_ptr()
         P = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
-        rc = _native.lib().pnp_generator_forward_clips_yuv(
+        rc = getattr(_native.lib(), entry)(
             self._handle, P(self._flat), P(self._packed), ctypes.cast(arr, ctypes.c_void_p), n, std, mask, ctypes.cast(base, fp),
             ctypes.cast(base + 4 * n * t, fp), ctypes.cast(base + 8 * n * t, fp), P(ws), ws.numel(), t, h, w,
             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, 'pnp_generator_forward_clips_yuv')
+        _native.check(rc, entry)
 
     def _forward_yuv_graphed(self, clips, mvs_c, par_c, side, std, mask, layout, shape):
         """use_graphs at the 4:2:0 boundary: the planes are copied into static planes of their own (1.5 B per pixel), the outputs out"""
         n, t, h, w = shape
         dev = mvs_c.device
+        c0 = clips[0]
         key = ('yuv', n, t, h, w, str(dev), side.numpy().tobytes(), self._packed.data_ptr(), self._packed_floats, self.max_resident_features,
-               std, mask, layout)
+               std, mask, layout, c0.y.dtype, tuple(c0[3:]))
         ent = self._graphs.get(key)
-        fill = lambda e: [dst.copy_(src) for b in range(n) for dst, src in zip(e['clips'][b], clips[b])]      # noqa: E731
+        fill = lambda e: [dst.copy_(src) for b in range(n) for dst, src in zip(e['clips'][b][:3], clips[b][:3])]      # noqa: E731
         if ent is None:
-            mk = lambda hh, ww: torch.empty((n, t, hh, ww), device=dev, dtype=torch.uint8)      # noqa: E731
-            static = ops.Yuv420Frames(mk(h, w), mk(h // 2, w // 2), mk(h // 2, w // 2))
-            ent = dict(clips=ops._yuv_clips(static, 'lrs')[0], mvs=torch.empty_like(mvs_c), par=torch.empty_like(par_c), side=side.clone(),
+            mk = lambda hh, ww: torch.empty((n, t, hh, ww), device=dev, dtype=c0.y.dtype)      # noqa: E731
+            static = type(c0)(mk(h, w), mk(h // 2, w // 2), mk(h // 2, w // 2), *c0[3:])
+            ent = dict(clips=ops._any_yuv_clips(static, 'lrs')[0], mvs=torch.empty_like(mvs_c), par=torch.empty_like(par_c), side=side.clone(),
                        ws=torch.empty(self._workspace_bytes(t, h, w, 'yuv', mask) * self._contexts(n, h, w), device=dev, dtype=torch.uint8),
-                       outs=self._alloc_yuv_outs(n, t, h, w, mask, layout, dev))
+                       outs=self._alloc_yuv_outs(n, t, h, w, mask, layout, dev, c0.y.dtype))
             run = lambda: self._launch_clips_yuv(ent['clips'], list(ent['mvs']), list(ent['par']), ent['side'], ent['outs'], ent['ws'],      # noqa: E731
                                                  t, h, w, std)
             fill(ent)
@@ -687,13 +730,18 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         if self.sparse_val and not self.training and len(clips) != 1:
             raise NotImplementedError('sparse_val=True evaluates one clip at a time: the reference reads feature[0] '
                                       'only (sr_backbone_utils.py:262-275)')
+        lrs0 = clips[0][0]
+        via8, run_dtype = self._yuv_out_route(lrs0, kinds, layout)
+        if via8:
+            res = [self._yuv8_of_16(r, kinds, via8, std) for r in self._forward_clips_yuv(clips, run_dtype, yuv_standard)]
+            return res if many else [r[0] for r in res]
         ys, cbs, crs, mv_l, par_l, sides, first = [], [], [], [], [], [], None
         for lrs, QPs, slices, mvs, base_QPs, par_map in clips:
-            one, lead = ops._yuv_clips(lrs, 'lrs')
+            one, lead = ops._any_yuv_clips(lrs, 'lrs')
             if len(one) != 1:
                 raise ValueError('a clip of forward_clips is one sample: Yuv420Frames of (t,...) or (1,t,...) views')
-            _, t, h, w = ops._yuv_clip_desc(one[0], 'lrs')
-            sig = (t, h, w, lrs.y.device)
+            _, t, h, w = ops._any_yuv_clip_desc(one[0], 'lrs')
+            sig = (t, h, w, lrs.y.device) + ((type(lrs), lrs.y.dtype) + tuple(lrs[3:]) if isinstance(lrs0, ops.Yuv420Frames16) else ())
             if first is None:
                 first = sig
             elif sig != first:
@@ -708,7 +756,7 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
             mv_l.append(mvs_c)
             par_l.append(par_c)
             sides.append(self._yuv_side(t, QPs, slices, base_QPs))
-        t, h, w, dev = first
+        t, h, w, dev = first[:4]
         self._check_resident(t)
         with torch.cuda.device(dev):
             self._ensure_packed(dev)
@@ -717,23 +765,31 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
                 if self.get_option(_native.OPT_SPARSE_EVAL) != sparse_now:
                     self.set_option(_native.OPT_SPARSE_EVAL, sparse_now)
             side = torch.stack(sides, dim=1).cpu().contiguous()
-            flat = torch.ops.pnpvcve.generator_forward_clips_yuv(self._op_handle, ys, cbs, crs, mv_l, par_l, side, std, mask,
-                                                                 ops.YUV_LAYOUTS.index(layout) if layout else -1)
+            if isinstance(lrs0, ops.Yuv420Frames16):
+                names = sorted(ops.YUV16_LAYOUTS)
+                flat = torch.ops.pnpvcve.generator_forward_clips_yuv16(self._op_handle, ys, cbs, crs, int(lrs0.bit_depth), bool(lrs0.msb_aligned),
+                                                                       mv_l, par_l, side, std, mask, names.index(layout) if layout else -1)
+            else:
+                flat = torch.ops.pnpvcve.generator_forward_clips_yuv(self._op_handle, ys, cbs, crs, mv_l, par_l, side, std, mask,
+                                                                     ops.YUV_LAYOUTS.index(layout) if layout else -1)
         n = len(ys)
         order = [k for k in ('f32', 'u8', 'yuv') if k in kinds]
         per = {k: flat[j * n:(j + 1) * n] for j, k in enumerate(order)}
         res = [tuple(per[k][i][None] for k in kinds) for i in range(n)]
         return res if many else [r[0] for r in res]
 
-    def _forward_clips_yuv_native(self, ys, cbs, crs, mvs, par, side, std, mask, layout):
+    def _forward_clips_yuv_native(self, ys, cbs, crs, mvs, par, side, std, mask, layout, bit_depth=8, msb_aligned=False):
         """Body of torch.ops.pnpvcve.generator_forward_clips_yuv: per-clip plane views -> the fp32 outputs (mask & 1), then the uint8
         ones (mask & 2), then the packed 4:2:0 buffers (mask & 4), one freshly allocated tensor per clip."""
         n = len(ys)
-        clips = [ops.Yuv420Frames(ys[b], cbs[b], crs[b]) for b in range(n)]
+        if bit_depth == 8:
+            clips = [ops.Yuv420Frames(ys[b], cbs[b], crs[b]) for b in range(n)]
+        else:      # (torch.ops.pnpvcve.generator_forward_clips_yuv16)
+            clips = [ops.Yuv420Frames16(ys[b], cbs[b], crs[b], bit_depth, msb_aligned) for b in range(n)]
         t, h, w = ys[0].shape
         dev = ys[0].device
         with torch.cuda.device(dev):
-            per = [self._alloc_yuv_outs(1, t, h, w, mask, layout, dev) for _ in range(n)]
+            per = [self._alloc_yuv_outs(1, t, h, w, mask, layout, dev, ys[0].dtype) for _ in range(n)]
             outs = {k: (None, [p[k][1][0] for p in per]) for k in per[0]}
             ws = self._get_workspace(n, t, h, w, dev, 'yuv', mask)
             self._launch_clips_yuv(clips, mvs, par, side, outs, ws, t, h, w, std)

@@ -853,11 +853,16 @@ _PLANE_BITS = {'y': _native.PLANE_Y, 'u': _native.PLANE_CB, 'v': _native.PLANE_C
 
 def _yuv_metric_pair(a, b, crop_border):
     """two Yuv420Frames that show the same frames, (n,t,...) or (t,...), each in a layout of its own -> (per-clip descriptor pairs,
-    lead shape, t, h, w, crop); every refusal a ValueError / TypeError raised before any GPU work"""
-    clips_a, lead_a = _yuv_clips(a, 'a')
-    clips_b, lead_b = _yuv_clips(b, 'b')
-    da = [_yuv_clip_desc(c, 'a') for c in clips_a]
-    db = [_yuv_clip_desc(c, 'b') for c in clips_b]
+    lead shape, t, h, w, crop); every refusal a ValueError / TypeError raised before any GPU work.  Two Yuv420Frames16 of one bit
+    depth (each in a container of its own) are scored at that depth; an 8-bit clip against a 16-bit one is refused."""
+    if isinstance(a, Yuv420Frames16) != isinstance(b, Yuv420Frames16):
+        raise ValueError('a and b must both be 8-bit (Yuv420Frames) or both 16-bit (Yuv420Frames16) clips')
+    if isinstance(a, Yuv420Frames16) and _bit_depth(a.bit_depth) != _bit_depth(b.bit_depth):
+        raise ValueError(f'the two clips differ in bit depth: {a.bit_depth} and {b.bit_depth}')
+    clips_a, lead_a = _any_yuv_clips(a, 'a')
+    clips_b, lead_b = _any_yuv_clips(b, 'b')
+    da = [_any_yuv_clip_desc(c, 'a') for c in clips_a]
+    db = [_any_yuv_clip_desc(c, 'b') for c in clips_b]
     t, h, w = da[0][1:]
     if lead_a != lead_b or any(d[1:] != (t, h, w) for d in da + db):
         raise ValueError(f'the two clips differ in shape: {tuple(a.y.shape)} and {tuple(b.y.shape)}')
@@ -875,15 +880,16 @@ def _yuv_metric_pair(a, b, crop_border):
 
 def psnr_sse_yuv420(a, b, crop_border=0):
     """The statistic behind psnr_yuv420: the exact sum of squared byte differences of the cropped Y, Cb and Cr planes of every frame, an
-    int64 CPU tensor lead + (3,) (pnp_psnr_sse_yuv420: integer, the same bits every run)."""
+    int64 CPU tensor lead + (3,) (pnp_psnr_sse_yuv420: integer, the same bits every run).  Two Yuv420Frames16: the sample values'
+    differences (pnp_psnr_sse_yuv420p16)."""
     pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border)
+    entry = 'pnp_psnr_sse_yuv420p16' if isinstance(a, Yuv420Frames16) else 'pnp_psnr_sse_yuv420'
     dev = a.y.device
     with torch.cuda.device(dev):
         sse = torch.empty((len(pairs), t, 3), dtype=torch.int64, device=dev)
         for i, (da, db) in enumerate(pairs):
             if t:
-                _native.check(_native.lib().pnp_psnr_sse_yuv420(ctypes.byref(da), ctypes.byref(db), _ptr(sse[i]), t, h, w, crop, _stream()),
-                              'pnp_psnr_sse_yuv420')
+                _native.check(getattr(_native.lib(), entry)(ctypes.byref(da), ctypes.byref(db), _ptr(sse[i]), t, h, w, crop, _stream()), entry)
     return sse.cpu().reshape(lead + (3,))
 
 
@@ -891,14 +897,16 @@ def psnr_yuv420(a, b, crop_border=0):
     """Per-frame plane PSNR of two 8-bit 4:2:0 clips, read from the planes where they lie (1.5 B per pixel and clip).
     a, b: Yuv420Frames (n,t,...) or (t,...) of one shape, each in its own layout (NV12 output against an I420 ground truth); the Y
     plane is cropped by crop_border (even), the chroma planes by crop_border / 2.  Returns a float64 CPU tensor lead + (3,) = Y, U, V:
-    PSNR_p = 10 log10(255^2 N_p / SSE_p) with N_p the samples of the cropped plane, inf where the planes are equal."""
+    PSNR_p = 10 log10(255^2 N_p / SSE_p) with N_p the samples of the cropped plane, inf where the planes are equal.  Two
+    Yuv420Frames16 of one bit depth d are scored on their sample values with the peak 2^d - 1 in place of 255."""
     import numpy as np
     sse = psnr_sse_yuv420(a, b, crop_border).numpy().astype(np.float64)
     h, w = a.y.shape[-2:]
     crop = int(crop_border)
     n_y, n_c = (h - 2 * crop) * (w - 2 * crop), (h // 2 - crop) * (w // 2 - crop)
     with np.errstate(divide='ignore'):
-        out = 10.0 * np.log10(255.0 ** 2 * np.array([n_y, n_c, n_c], np.float64) / sse)
+        peak = float((1 << a.bit_depth) - 1) if isinstance(a, Yuv420Frames16) else 255.0
+        out = 10.0 * np.log10(peak ** 2 * np.array([n_y, n_c, n_c], np.float64) / sse)
     out[sse == 0] = np.inf
     return torch.from_numpy(out)
 
@@ -906,7 +914,8 @@ def psnr_yuv420(a, b, crop_border=0):
 def ssim_yuv420(a, b, crop_border=0, planes='y'):
     """Per-frame plane SSIM of two 8-bit 4:2:0 clips (pnp_ssim_partials_yuv420: ssim_frames' window and fp64 arithmetic on the bytes of a
     plane).  planes: any of 'y', 'u', 'v' in any order ('yuv', 'u', 'vy', ...); returns a float64 CPU tensor lead + (len(planes),) in
-    that order.  Crop as psnr_yuv420."""
+    that order.  Crop as psnr_yuv420.  Two Yuv420Frames16 of one bit depth d: the same on the sample values, L = 2^d - 1
+    (pnp_ssim_partials_yuv420p16)."""
     if not isinstance(planes, str) or not planes or len(set(planes.lower())) != len(planes) or any(p not in _PLANE_BITS for p in planes.lower()):
         raise ValueError(f"planes must name each of 'y', 'u', 'v' at most once, got {planes!r}")
     planes = planes.lower()
@@ -924,8 +933,8 @@ def ssim_yuv420(a, b, crop_border=0, planes='y'):
             if not t:
                 continue
             part = torch.empty(t * sum(nb.values()), dtype=torch.float64, device=dev)
-            _native.check(L.pnp_ssim_partials_yuv420(ctypes.byref(da), ctypes.byref(db), mask, _ptr(part), t, h, w, crop, _stream()),
-                          'pnp_ssim_partials_yuv420')
+            entry = 'pnp_ssim_partials_yuv420p16' if isinstance(a, Yuv420Frames16) else 'pnp_ssim_partials_yuv420'
+            _native.check(getattr(L, entry)(ctypes.byref(da), ctypes.byref(db), mask, _ptr(part), t, h, w, crop, _stream()), entry)
             off = 0
             for p in order:
                 rows, cols, c = (h, w, crop) if p == 'y' else (h // 2, w // 2, crop // 2)
@@ -933,3 +942,203 @@ def ssim_yuv420(a, b, crop_border=0, planes='y'):
                 res[i, :, planes.index(p)] = (part[off:off + t * nb[p]].reshape(t, nb[p]).sum(dim=1) / n).cpu()
                 off += t * nb[p]
     return res.reshape(lead + (len(planes),))
+
+
+# ---------------------------------------------------------------- 10 / 12-bit 4:2:0 frames (include/pnpvcve.h: pnp_yuv420_planes16)
+_Yuv420Base16 = collections.namedtuple('Yuv420Frames16', ['y', 'cb', 'cr', 'bit_depth', 'msb_aligned'], defaults=(10, False))
+
+
+class Yuv420Frames16(_Yuv420Base16):
+    """10 / 12-bit 4:2:0 frames as three CUDA VIEWS of 16-bit words (torch.int16, or torch.uint16 where torch has it: the same bits)
+    of wherever the decoder wrote them: y (n,t,h,w), cb and cr (n,t,h/2,w/2), or without the batch dimension.  bit_depth 10 | 12;
+    msb_aligned: the value sits in the high bits of the word (P010 / P012) instead of the low ones (yuv420p10le / yuv420p12le).
+    Strides are in samples: the last-dimension stride is 1 for y and 1 (planar) or 2 (interleaved: cb and cr one sample apart in one
+    buffer) for chroma.  Nothing is copied; yuv420p16_views builds the views of a packed buffer."""
+    __slots__ = ()
+
+
+# name -> (the 8-bit layout with the same plane order, bit depth, msb_aligned)
+YUV16_LAYOUTS = {'p010': ('nv12', 10, True), 'p012': ('nv12', 12, True), 'yuv420p10le': ('i420', 10, False), 'yuv420p12le': ('i420', 12, False)}
+_WORD_DTYPES = tuple(d for d in (torch.int16, getattr(torch, 'uint16', None)) if d is not None)
+
+
+def _yuv16_layout(layout):
+    """a layout name of YUV16_LAYOUTS or ('nv12' | 'nv21' | 'i420', bit_depth, msb_aligned) -> (order, bit_depth, msb_aligned)"""
+    if isinstance(layout, str):
+        if layout not in YUV16_LAYOUTS:
+            raise ValueError(f'layout must be one of {sorted(YUV16_LAYOUTS)} or (order, bit_depth, msb_aligned), got {layout!r}')
+        return YUV16_LAYOUTS[layout]
+    if not isinstance(layout, (tuple, list)) or len(layout) != 3 or layout[0] not in YUV_LAYOUTS:
+        raise ValueError(f'layout must be one of {sorted(YUV16_LAYOUTS)} or ({YUV_LAYOUTS}, bit_depth, msb_aligned), got {layout!r}')
+    return layout[0], _bit_depth(layout[1]), bool(layout[2])
+
+
+def _bit_depth(d):
+    if isinstance(d, bool) or d not in (10, 12):
+        raise ValueError(f'bit_depth must be 10 or 12, got {d!r}')
+    return int(d)
+
+
+def yuv420p16_views(buf, h, w, layout='yuv420p10le'):
+    """A packed buffer of 16-bit words (..., 3h/2, pitch) -- or flat (..., 3hw/2) for planar layouts -- -> Yuv420Frames16 of views
+    into it (no copy): yuv420_views' rules with samples for bytes.  layout: 'p010' | 'p012' (Y, then interleaved Cb Cr, value in the
+    high bits) | 'yuv420p10le' | 'yuv420p12le' (Y, Cb, Cr planes, value in the low bits), or ('nv12' | 'nv21' | 'i420', bit_depth,
+    msb_aligned)."""
+    order, depth, msb = _yuv16_layout(layout)
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise ValueError(f'4:2:0 frames need an even height and width, got {h} x {w}')
+    if not isinstance(buf, torch.Tensor) or buf.dtype not in _WORD_DTYPES:
+        raise TypeError(f'buf must be a tensor of 16-bit words (torch.int16 / torch.uint16), got {getattr(buf, "dtype", type(buf))}')
+    if buf.dim() >= 2 and buf.shape[-2] == h * 3 // 2 and buf.shape[-1] >= w and buf.stride(-1) == 1:
+        pitch = buf.shape[-1]
+        y = buf[..., :h, :w]
+        if order != 'i420':
+            c = buf[..., h:, :w]
+            a, b = c[..., 0::2], c[..., 1::2]
+            return Yuv420Frames16(y, a, b, depth, msb) if order == 'nv12' else Yuv420Frames16(y, b, a, depth, msb)
+        if pitch % 2 or buf.stride(-2) != pitch:
+            raise ValueError('a planar buffer needs an even pitch and whole rows: its chroma rows are half a luma row long')
+        flat = buf.flatten(-2)          # (a view: the two last dimensions are contiguous)
+        n = (h // 2) * (pitch // 2)
+        cb = flat[..., h * pitch:h * pitch + n].unflatten(-1, (h // 2, pitch // 2))[..., :w // 2]
+        cr = flat[..., h * pitch + n:h * pitch + 2 * n].unflatten(-1, (h // 2, pitch // 2))[..., :w // 2]
+        return Yuv420Frames16(y, cb, cr, depth, msb)
+    if order == 'i420' and buf.dim() >= 1 and buf.shape[-1] == h * w * 3 // 2 and buf.stride(-1) == 1:
+        return yuv420p16_views(buf.unflatten(-1, (h * 3 // 2, w)), h, w, (order, depth, msb))
+    raise ValueError(f'buf must be (..., {h * 3 // 2}, pitch >= {w}) 16-bit words with a unit last stride, got {tuple(buf.shape)}')
+
+
+def _yuv16_clip_desc(frames, what='frames'):
+    """Yuv420Frames16 of (t,h,w) / (t,h/2,w/2) views -> (_native.Yuv420Planes16, t, h, w); every refusal a ValueError / TypeError
+    raised before any GPU work"""
+    if not isinstance(frames, Yuv420Frames16):
+        raise TypeError(f'{what} must be ops.Yuv420Frames16(y, cb, cr, bit_depth, msb_aligned)')
+    y, cb, cr, depth, msb = frames
+    depth = _bit_depth(depth)
+    for name, x in (('y', y), ('cb', cb), ('cr', cr)):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise RuntimeError(f'{what}.{name} must be a CUDA/HIP tensor: the PnP-VCVE hot path has no CPU fallback')
+        if x.dtype not in _WORD_DTYPES:
+            raise TypeError(f'{what}.{name} must be int16 or uint16, got {x.dtype}')
+        if x.dim() != 3:
+            raise ValueError(f'{what}.{name} must be (t,rows,cols) per clip, got {tuple(x.shape)}')
+    t, h, w = y.shape
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise ValueError(f'4:2:0 frames need an even height and width, got {h} x {w}')
+    if tuple(cb.shape) != (t, h // 2, w // 2) or tuple(cr.shape) != (t, h // 2, w // 2):
+        raise ValueError(f'cb and cr must be (t,h/2,w/2) = {(t, h // 2, w // 2)}, got {tuple(cb.shape)} and {tuple(cr.shape)}')
+    if y.stride(2) != 1:
+        raise ValueError(f'{what}.y must have a unit last stride, got {y.stride(2)}')
+    if cb.stride() != cr.stride() or cb.stride(2) not in (1, 2):
+        raise ValueError(f'{what}.cb and .cr must share their strides, with a last stride of 1 or 2: got {cb.stride()} and {cr.stride()}')
+    step = cb.stride(2)
+    if step == 2 and abs(cb.data_ptr() - cr.data_ptr()) != 2:
+        raise ValueError('chroma with a step of 2 must be interleaved: cb and cr one sample apart (P010 / P012)')
+    if y.stride(1) < w or cb.stride(1) < step * (w // 2) or (t > 1 and (y.stride(0) < 0 or cb.stride(0) < 0)):
+        raise ValueError(f'{what}: a pitch below the row\'s samples (strides {y.stride()}, {cb.stride()})')
+    if (y.data_ptr() | cb.data_ptr() | cr.data_ptr()) & 1:
+        raise ValueError(f'{what}: 16-bit planes must lie at even addresses')
+    d = _native.Yuv420Planes16(y.data_ptr(), cb.data_ptr(), cr.data_ptr(), 2 * y.stride(1), 2 * cb.stride(1), 2 * y.stride(0) if t > 1 else 0,
+                               2 * cb.stride(0) if t > 1 else 0, step, depth, int(bool(msb)))
+    return d, t, h, w
+
+
+def _yuv16_clips(frames, what='frames'):
+    """Yuv420Frames16 with or without the batch dimension -> (list of per-clip Yuv420Frames16, lead shape)"""
+    if not isinstance(frames, Yuv420Frames16):
+        raise TypeError(f'{what} must be ops.Yuv420Frames16(y, cb, cr, bit_depth, msb_aligned)')
+    if any(not isinstance(x, torch.Tensor) for x in frames[:3]):
+        raise TypeError(f'{what}: y, cb and cr must be tensors')
+    d = frames.y.dim()
+    if d not in (3, 4) or frames.cb.dim() != d or frames.cr.dim() != d:
+        raise ValueError(f'{what}: y, cb, cr must all be (n,t,rows,cols) or all (t,rows,cols), got {tuple(frames.y.shape)}, '
+                         f'{tuple(frames.cb.shape)}, {tuple(frames.cr.shape)}')
+    if d == 3:
+        return [frames], ()
+    n = frames.y.shape[0]
+    if frames.cb.shape[0] != n or frames.cr.shape[0] != n:
+        raise ValueError(f'{what}: y, cb and cr disagree in the batch size')
+    return [Yuv420Frames16(frames.y[b], frames.cb[b], frames.cr[b], frames.bit_depth, frames.msb_aligned) for b in range(n)], (n,)
+
+
+def is_yuv(frames):
+    """frames are 4:2:0 planes of either sample size"""
+    return isinstance(frames, (Yuv420Frames, Yuv420Frames16))
+
+
+def _any_yuv_clips(frames, what='frames'):
+    """_yuv_clips / _yuv16_clips by the type of `frames`"""
+    return _yuv16_clips(frames, what) if isinstance(frames, Yuv420Frames16) else _yuv_clips(frames, what)
+
+
+def _any_yuv_clip_desc(frames, what='frames'):
+    """_yuv_clip_desc / _yuv16_clip_desc by the type of `frames`"""
+    return _yuv16_clip_desc(frames, what) if isinstance(frames, Yuv420Frames16) else _yuv_clip_desc(frames, what)
+
+
+def frames_from_yuv420p16(frames, standard='bt601-limited'):
+    """Yuv420Frames16 (n,t,...) or (t,...) -> (n,t,3,h,w) / (t,3,h,w) fp32 RGB planes, clamped to [0,1], chroma replicated: the
+    arithmetic of include/pnpvcve.h at the frames' depth, bit-equal to tests/yuv16_ref.py.  What generator.forward(Yuv420Frames16)
+    computes on, without this fp32 clip."""
+    std = _yuv_standard(standard)
+    clips, lead = _yuv16_clips(frames)
+    descs = [_yuv16_clip_desc(c) for c in clips]
+    _, t, h, w = descs[0]
+    if any(d[1:] != (t, h, w) for d in descs):
+        raise ValueError('the clips of a batch must agree in shape')
+    dev = frames.y.device
+    with torch.cuda.device(dev):
+        out = torch.empty((len(clips), t, 3, h, w), device=dev, dtype=torch.float32)
+        for b, (d, _, _, _) in enumerate(descs):
+            if t:
+                _native.check(_native.lib().pnp_frames_from_yuv420p16(ctypes.byref(d), std, _ptr(out[b]), t, h, w, _stream()),
+                              'pnp_frames_from_yuv420p16')
+    return out if lead else out[0]
+
+
+def empty_yuv420p16(lead, h, w, layout, device, dtype=torch.int16):
+    """-> (packed buffer of 16-bit words lead + (3h/2, w), its Yuv420Frames16 views)"""
+    buf = torch.empty(tuple(lead) + (h * 3 // 2, w), device=device, dtype=dtype)
+    return buf, yuv420p16_views(buf, h, w, layout)
+
+
+def frames_to_yuv420p16(planes, standard='bt601-limited', layout='yuv420p10le', out=None, dtype=torch.int16):
+    """(n,t,3,h,w) or (t,3,h,w) fp32 CUDA planes -> (packed buffer of 16-bit words (...,3h/2,w) in `layout`, its Yuv420Frames16
+    views): clamp, luma, box-mean chroma, round half to even to [0, 2^d - 1], the bits outside the value zero (include/pnpvcve.h).
+    out: Yuv420Frames16 views to write instead of a fresh buffer (any pitch, any even address; returns (None, out)); the depth and
+    container are then out's."""
+    std = _yuv_standard(standard)
+    planes = _chk(planes, 'planes')
+    if planes.dim() not in (4, 5) or planes.shape[-3] != 3:
+        raise ValueError(f'planes must be (n,t,3,h,w) or (t,3,h,w), got {tuple(planes.shape)}')
+    h, w = planes.shape[-2:]
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise ValueError(f'4:2:0 frames need an even height and width, got {h} x {w}')
+    lead = tuple(planes.shape[:-3])
+    with torch.cuda.device(planes.device):
+        buf = None
+        if out is None:
+            buf, out = empty_yuv420p16(lead, h, w, layout, planes.device, dtype)
+        clips, olead = _yuv16_clips(out, 'out')
+        src = planes if planes.dim() == 5 else planes[None]
+        if len(clips) != src.shape[0]:
+            raise ValueError('out and planes disagree in the batch size')
+        for b, c in enumerate(clips):
+            d, t, oh, ow = _yuv16_clip_desc(c, 'out')
+            if (t, oh, ow) != (src.shape[1], h, w):
+                raise ValueError(f'out is {(t, oh, ow)}, planes are {(src.shape[1], h, w)}')
+            if t:
+                _native.check(_native.lib().pnp_frames_to_yuv420p16(_ptr(src[b]), ctypes.byref(d), std, t, h, w, _stream()),
+                              'pnp_frames_to_yuv420p16')
+    return buf, out
+
+
+def pack_lr_yuv420p16(frames, standard='bt601-limited', general=False):
+    """(include/pnpvcve_debug.h) one clip's Yuv420Frames16 (t,...) -> the (t,h,w,4) fp32 RGB0 conv source the forward unpacks them
+    into; general: the 2-byte-load form whatever the alignment"""
+    d, t, h, w = _yuv16_clip_desc(frames)
+    with torch.cuda.device(frames.y.device):
+        out = torch.empty((t, h, w, 4), device=frames.y.device, dtype=torch.float32)
+        _native.check(_native.lib().pnp_debug_pack_lr_yuv420p16(ctypes.byref(d), _yuv_standard(standard), _ptr(out), t, h, w, int(bool(general)),
+                                                                _stream()), 'pnp_debug_pack_lr_yuv420p16')
+    return out

@@ -99,12 +99,15 @@ class BasicVSR(nn.Module):
         ssim_yuv420): 'PSNR' / 'SSIM' score the Y plane, and in this mode only 'PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V' and 'PSNR_YUV'
         = (6 PSNR_Y + PSNR_U + PSNR_V) / 8 per frame are accepted too; every value is the mean over frames.  crop_border (even) crops
         the Y plane, half of it the chroma planes.  test_cfg.convert_to may be None or 'y' and both mean the same here: the decoder's
-        Y' plane IS the luma -- it is NOT the BT.601 Y that convert_to='y' derives from RGB bytes, so the two modes' numbers differ."""
-        from .ops import Yuv420Frames
-        if isinstance(output, Yuv420Frames) or isinstance(gt, Yuv420Frames):
-            if not (isinstance(output, Yuv420Frames) and isinstance(gt, Yuv420Frames)):
+        Y' plane IS the luma -- it is NOT the BT.601 Y that convert_to='y' derives from RGB bytes, so the two modes' numbers differ.
+        Two ops.Yuv420Frames16 of one bit depth d are scored the same way on their sample values, with the peak 2^d - 1."""
+        from .ops import Yuv420Frames, Yuv420Frames16, is_yuv
+        if is_yuv(output) or is_yuv(gt):
+            if not ((isinstance(output, Yuv420Frames) and isinstance(gt, Yuv420Frames)) or
+                    (isinstance(output, Yuv420Frames16) and isinstance(gt, Yuv420Frames16))):
                 raise ValueError('plane metrics compare two 4:2:0 clips: output and gt must both be ops.Yuv420Frames '
-                                 "(ask the generator for out_dtype='i420' / 'nv12', or convert with ops.frames_to_yuv420)")
+                                 "(ask the generator for out_dtype='i420' / 'nv12', or convert with ops.frames_to_yuv420), or both "
+                                 'ops.Yuv420Frames16 of one bit depth')
             return self._evaluate_yuv(output, gt)
         crop_border = self.test_cfg['crop_border']
         convert_to = self.test_cfg.get('convert_to', None)
@@ -146,12 +149,12 @@ class BasicVSR(nn.Module):
                                                                    convert_to=convert_to)
         return eval_result
 
-    YUV_OUT_LAYOUTS = ('nv12', 'i420')      # the packed 4:2:0 layouts generator.forward writes
+    YUV_OUT_LAYOUTS = ('nv12', 'i420', 'p010', 'p012', 'yuv420p10le', 'yuv420p12le')      # the packed 4:2:0 layouts generator.forward writes
     YUV_METRICS = ('PSNR', 'SSIM', 'PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V', 'PSNR_YUV')
 
     def _evaluate_yuv(self, output, gt):
-        """evaluate() of two ops.Yuv420Frames clips: plane PSNR / SSIM on the device, means over the clip's frames"""
-        from .ops import Yuv420Frames, psnr_yuv420, ssim_yuv420
+        """evaluate() of two ops.Yuv420Frames (or two ops.Yuv420Frames16) clips: plane PSNR / SSIM on the device, means over the clip's frames"""
+        from .ops import psnr_yuv420, ssim_yuv420
         crop_border = self.test_cfg['crop_border']
         convert_to = self.test_cfg.get('convert_to', None)
         if not (convert_to is None or (isinstance(convert_to, str) and convert_to.lower() == 'y')):
@@ -165,11 +168,11 @@ class BasicVSR(nn.Module):
             if x.y.dim() == 4:
                 if x.y.size(0) != 1:
                     raise ValueError(f'evaluate() expects one clip per call (samples_per_gpu=1), got a batch of {x.y.size(0)}')
-                return Yuv420Frames(x.y[0], x.cb[0], x.cr[0])
+                return type(x)(x.y[0], x.cb[0], x.cr[0], *x[3:])
             return x
 
         output, gt = one_clip(output, 'output'), one_clip(gt, 'gt')
-        gt = Yuv420Frames(*[p.to(output.y.device) for p in gt])
+        gt = type(gt)(*[p.to(output.y.device) for p in gt[:3]], *gt[3:])
         eval_result = dict()
         psnr = psnr_yuv420(output, gt, crop_border) if any(m.startswith('PSNR') for m in metrics) else None      # (t, 3)
         col = {'SSIM': 'y', 'SSIM_U': 'u', 'SSIM_V': 'v'}
@@ -197,11 +200,12 @@ class BasicVSR(nn.Module):
         4:2:0 frames (not in the reference): `lq` may be ops.Yuv420Frames in the colour standard `yuv_standard`, and with
         out_dtype = 'i420' | 'nv12' the generator writes packed 4:2:0 only (`precomputed_output`: that packed buffer): the
         metrics are then evaluate()'s plane metrics against a Yuv420Frames `gt`, and save_image writes <save_path>/<clip>.yuv -- the
-        buffer's bytes, frames in order, one FrameWriter job per clip."""
+        buffer's bytes, frames in order, one FrameWriter job per clip.  ops.Yuv420Frames16 `lq` (10 / 12 bit) likewise, with the four
+        16-bit layout names beside them: the buffer is then 16-bit little-endian words, 3 B per pixel in the file."""
         from . import ops
-        yuv_in = isinstance(lq, ops.Yuv420Frames)
+        yuv_in = ops.is_yuv(lq)
         yuv_layout = out_dtype if (yuv_in and isinstance(out_dtype, str) and out_dtype in self.YUV_OUT_LAYOUTS) else None
-        if isinstance(gt, ops.Yuv420Frames) and yuv_layout is None:
+        if ops.is_yuv(gt) and yuv_layout is None:
             raise ValueError("a 4:2:0 ground truth is compared with 4:2:0 output: lq must be ops.Yuv420Frames and out_dtype one of "
                              f'{self.YUV_OUT_LAYOUTS}')
         if yuv_layout is not None:
@@ -240,7 +244,7 @@ class BasicVSR(nn.Module):
         else:
             lq_planes = lq
             if yuv_in:
-                lq_planes = ops.frames_from_yuv420(lq, yuv_standard)
+                lq_planes = (ops.frames_from_yuv420p16 if isinstance(lq, ops.Yuv420Frames16) else ops.frames_from_yuv420)(lq, yuv_standard)
             elif lq.dtype == torch.uint8 and lq.ndim == 5 and lq.is_cuda:       # byte frames: hand back the planes the caller knows
                 from .ops import frames_from_rgb8
                 lq_planes = frames_from_rgb8(lq)
@@ -275,8 +279,8 @@ class BasicVSR(nn.Module):
                           layout, yuv_standard):
         """forward_test with 4:2:0 planes in and packed 4:2:0 out: the generator's (n,t,3H/2,W) uint8 buffer is all that exists of the output"""
         from . import ops
-        if gt is not None and not isinstance(gt, ops.Yuv420Frames):
-            raise ValueError('4:2:0 output is scored against a 4:2:0 ground truth (ops.Yuv420Frames); the centre-frame case and RGB ground '
+        if gt is not None and not ops.is_yuv(gt):
+            raise ValueError('4:2:0 output is scored against a 4:2:0 ground truth (ops.Yuv420Frames / Yuv420Frames16); the centre-frame case and RGB ground '
                              'truths read the fp32 planes')
         if precomputed_output is not None:
             buf = precomputed_output
@@ -289,17 +293,19 @@ class BasicVSR(nn.Module):
                 buf = self.generator(lq, QPs, slices, mvs, base_QPs, par_map, out_dtype=layout, yuv_standard=yuv_standard)
                 torch.cuda.synchronize()
                 self.last_forward_seconds = time.time() - begin
-        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.dim() != 4 or buf.shape[-2] % 3:
-            raise ValueError('the 4:2:0 output is the packed (n,t,3H/2,W) uint8 buffer the generator returns')
+        wide = layout in ops.YUV16_LAYOUTS
+        if not isinstance(buf, torch.Tensor) or (buf.dtype == torch.uint8) == wide or buf.dim() != 4 or buf.shape[-2] % 3:
+            raise ValueError('the 4:2:0 output is the packed (n,t,3H/2,W) buffer the generator returns: uint8, or 16-bit words for a 10 / 12-bit layout')
         H, W = buf.shape[-2] * 2 // 3, buf.shape[-1]
-        output = ops.yuv420_views(buf, H, W, layout)
+        output = ops.yuv420p16_views(buf, H, W, layout) if wide else ops.yuv420_views(buf, H, W, layout)
         if self.test_cfg is not None and self.test_cfg.get('metrics', None):
             assert gt is not None, 'evaluation with metrics must have gt images.'
             results = dict(eval_result=self.evaluate(output, gt))
         else:
-            results = dict(lq=ops.frames_from_yuv420(lq, yuv_standard).cpu(), output=buf.cpu())
+            from_planes = ops.frames_from_yuv420p16 if isinstance(lq, ops.Yuv420Frames16) else ops.frames_from_yuv420
+            results = dict(lq=from_planes(lq, yuv_standard).cpu(), output=buf.cpu())
             if gt is not None:
-                results['gt'] = ops.Yuv420Frames(*[p.cpu() for p in gt])
+                results['gt'] = type(gt)(*[p.cpu() for p in gt[:3]], *gt[3:])
         if save_image:
             from .io_async import FrameWriter
             writer = getattr(self, 'frame_writer', None)
@@ -309,7 +315,8 @@ class BasicVSR(nn.Module):
             try:
                 clip = meta[0]['key'].split('/')[0]
                 name = f'{clip}.yuv' if iteration is None else f'{clip}-{iteration + 1:06d}.yuv'
-                writer.submit_bytes(osp.join(save_path, name), buf[0].contiguous().cpu().numpy())
+                # (16-bit words leave as their bytes, little-endian: the host's and the file's order)
+                writer.submit_bytes(osp.join(save_path, name), buf[0].contiguous().cpu().view(torch.uint8).numpy())
             finally:
                 if own:
                     writer.close()

@@ -17,6 +17,9 @@ package).
     torch.ops.pnpvcve.generator_forward_clips_yuv(handle, y[], cb[], cr[], mvs[], par[], side, standard, out_mask, layout)
                                                                 the same forward on 8-bit 4:2:0 plane views (NV12 / NV21 / I420); fp32
                                                                 planes, uint8 HWC frames and / or packed 4:2:0 buffers out (out_mask 1..7)
+    torch.ops.pnpvcve.generator_forward_clips_yuv16(handle, y[], cb[], cr[], bit_depth, msb_aligned, mvs[], par[], side, standard, out_mask, layout)
+                                                                the same on 10 / 12-bit plane views (16-bit words); layout indexes
+                                                                sorted(ops.YUV16_LAYOUTS)
     torch.ops.pnpvcve.frames_from_yuv420(y, cb, cr, standard)   4:2:0 planes -> fp32 RGB planes (include/pnpvcve.h states the arithmetic)
 
     torch.ops.pnpvcve.conv3x3(srcs, packed_w, bias, gamma, packed_w1x1, par, residual, act)
@@ -211,3 +214,31 @@ def pixel_shuffle_conv(x: torch.Tensor, packed: torch.Tensor, act: int) -> torch
 def _(x, packed, act):
     h, w, c = x.shape
     return x.new_empty((2 * h, 2 * w, c))
+
+
+@torch.library.custom_op('pnpvcve::generator_forward_clips_yuv16', mutates_args=())
+def generator_forward_clips_yuv16(handle: int, y: list[torch.Tensor], cb: list[torch.Tensor], cr: list[torch.Tensor], bit_depth: int,
+                                  msb_aligned: bool, mvs: list[torch.Tensor], par: list[torch.Tensor], side: torch.Tensor, standard: int,
+                                  out_mask: int, layout: int) -> list[torch.Tensor]:
+    """generator_forward_clips_yuv on views of 16-bit words (int16 / uint16) holding bit_depth-bit samples in the low (msb_aligned False)
+    or high bits; the packed (t,3H/2,W) 4:2:0 buffers (& 4) are 16-bit words of y's dtype in layout sorted(ops.YUV16_LAYOUTS)[layout]"""
+    m = _GENERATORS.get(handle)
+    if m is None:
+        raise RuntimeError(f'pnpvcve::generator_forward_clips_yuv16: unknown generator handle {handle}')
+    return m._forward_clips_yuv_native(list(y), list(cb), list(cr), list(mvs), list(par), side, int(standard), int(out_mask),
+                                       sorted(ops.YUV16_LAYOUTS)[layout] if layout >= 0 else None, int(bit_depth), bool(msb_aligned))
+
+
+@generator_forward_clips_yuv16.register_fake
+def _(handle, y, cb, cr, bit_depth, msb_aligned, mvs, par, side, standard, out_mask, layout):
+    m = _GENERATORS.get(handle)
+    s = 4 if (m is not None and m.vsr) else 1
+    outs = []
+    for bit in (1, 2, 4):
+        for x in y:
+            if not out_mask & bit:
+                continue
+            t, h, w = x.shape
+            shape = {1: (t, 3, h * s, w * s), 2: (t, h * s, w * s, 3), 4: (t, h * s * 3 // 2, w * s)}[bit]
+            outs.append(x.new_empty(shape, dtype={1: torch.float32, 2: torch.uint8, 4: x.dtype}[bit]))
+    return outs

@@ -56,9 +56,11 @@ def parse_args():
                    help='raw 4:2:0 evaluation (a Yuv420ClipFolderDataset of .yuv clips): the generator reads the planes and writes packed '
                         '4:2:0 only, the ground truth stays 8-bit planes on the device, PSNR / SSIM are the Y plane\'s (PSNR_U, PSNR_V, '
                         'SSIM_U, SSIM_V and the 6:1:1 PSNR_YUV may be listed in test_cfg.metrics too) and --save-path gets one <clip>.yuv '
-                        'per clip; default off')
-    p.add_argument('--yuv-out-layout', choices=['i420', 'nv12'], default='i420',
-                   help='with --yuv-frames: the layout of the packed 4:2:0 output (and of the written .yuv files); default i420 (yuv420p)')
+                        'per clip; a dataset with bit_depth=10 | 12 (16-bit little-endian .yuv files) goes the same way at its depth; '
+                        'default off')
+    p.add_argument('--yuv-out-layout', choices=['i420', 'nv12', 'p010', 'p012', 'yuv420p10le', 'yuv420p12le'], default='i420',
+                   help='with --yuv-frames: the layout of the packed 4:2:0 output (and of the written .yuv files); default i420 (yuv420p); '
+                        'the 10 / 12-bit layouts for a dataset of that bit depth')
     p.add_argument('--any-size', action='store_true',
                    help='run frames whose height or width is no multiple of 4 (generator.any_size; the same as --cfg-options '
                         'model.generator.any_size=True): the same formulas on the frame as given, no padding.  Default off: such '
