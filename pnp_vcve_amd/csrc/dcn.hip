@@ -66,6 +66,15 @@ __device__ __forceinline__ f32x4 sample_global(const f32x4* __restrict__ x4, flo
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
+// to fp16's finite range.  One v_med3_f32 per element: min(max()) on a value that has crossed the tap loop's hand-over costs a
+// canonicalising v_max_f32 x, x on top (+2.8 % on the fp16 kernel at 720p; this form: no cost, profiles/dcn_edges.txt)
+__device__ __forceinline__ f32x4 sat_h(f32x4 v) {
+    f32x4 r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = __builtin_amdgcn_fmed3f(v[j], -65504.f, 65504.f);
+    return r;
+}
+
 // F16 (PNP_PREC_F16): the gathered samples and the weights are rounded to fp16 as MFMA operands
 // (v_mfma_f32_32x32x16_f16, fp32 accumulation), like every other 64-channel contraction of that mode.  The fp16 matrix
 // pipe is separate from the vector ALUs, so here the partner wave's gather does run under the MFMAs.
@@ -203,7 +212,9 @@ __global__ __launch_bounds__(512) void dcn_window_kernel(const DcnArgs a) {
             const f32x4* bb = sB + lane + grp * (4 * 64);
 #pragma unroll
             for (int sp = 0; sp < 2; ++sp) {
-                const h4 lo = __builtin_convertvector(av[2 * sp], h4), hi = __builtin_convertvector(av[2 * sp + 1], h4);
+                // saturate like every other fp16 operand path (f16_util.h to_h4): an activation above 65504 must not become inf
+                const h4 lo = __builtin_convertvector(sat_h(av[2 * sp]), h4);
+                const h4 hi = __builtin_convertvector(sat_h(av[2 * sp + 1]), h4);
                 const h8 af = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                 const h8 b0 = __builtin_bit_cast(h8, bb[(sp * 2) * 64]), b1 = __builtin_bit_cast(h8, bb[(sp * 2 + 1) * 64]);
                 acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, b0, acc[0], 0, 0, 0);
