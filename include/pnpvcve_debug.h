@@ -116,6 +116,9 @@ int pnp_conv3x3_f16x3_ex(int nsrc, const float* const* srcs_dev, const int* src_
 /* pnp_mv_warp_nhwc_f32 writing its result as an fp16 (h,w,c) map (saturating round-to-nearest-even of the fp32 value). */
 int pnp_mv_warp_nhwc_f16out(const float* feat_dev, const float* flow_x_dev, const float* flow_y_dev, void* out16_dev, int h,
                             int w, int c, void* stream);
+/* ... with pnp_mv_warp_nhwc_mode_f32's `mode` (0 'bilinear', 1 'nearest'): the fp16-output instantiations of both modes. */
+int pnp_mv_warp_nhwc_f16out_mode(const float* feat_dev, const float* flow_x_dev, const float* flow_y_dev, void* out16_dev, int h,
+                                 int w, int c, int mode, void* stream);
 
 #ifdef __cplusplus
 }

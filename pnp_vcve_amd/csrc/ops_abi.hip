@@ -64,6 +64,7 @@ int pnp_mv_warp_nhwc_mode_f32(const float* feat, const float* fx, const float* f
 
 int pnp_mv_warp_nhwc_f32(const float* feat, const float* fx, const float* fy, float* out, int h, int w, int c,
                          void* st) {
+    if (h < 1 || w < 1 || c < 4) return PNP_ERR_BAD_ARG;
     return launch_mv_warp_nhwc(feat, fx, fy, out, h, w, c, (hipStream_t)st);
 }
 
@@ -467,7 +468,14 @@ int pnp_conv3x3_f16_maps(int nsrc, const void* const* srcs, const int* src_chann
 }
 
 int pnp_mv_warp_nhwc_f16out(const float* feat, const float* fx, const float* fy, void* out16, int h, int w, int c, void* st) {
+    if (h < 1 || w < 1 || c < 4) return PNP_ERR_BAD_ARG;
     return launch_mv_warp_nhwc(feat, fx, fy, out16, h, w, c, (hipStream_t)st, true);
+}
+
+int pnp_mv_warp_nhwc_f16out_mode(const float* feat, const float* fx, const float* fy, void* out16, int h, int w, int c, int mode,
+                                 void* st) {
+    if (h < 1 || w < 1 || c < 4 || mode < 0 || mode > 1) return PNP_ERR_BAD_ARG;
+    return launch_mv_warp_nhwc(feat, fx, fy, out16, h, w, c, (hipStream_t)st, true, mode == 1);
 }
 
 }  // extern "C"

@@ -336,13 +336,13 @@ def conv3x3_f16_maps(srcs, packed_w, bias=None, gamma=None, packed_w1x1=None, pa
 
 
 @_on_device_of_first_tensor
-def mv_warp_nhwc_f16(feat, flow_x, flow_y):
+def mv_warp_nhwc_f16(feat, flow_x, flow_y, interpolation='bilinear'):
     """mv_warp_nhwc writing an fp16 (h,w,c) map: saturating round-to-nearest-even of the fp32 result."""
     feat, flow_x, flow_y = _chk(feat, 'feat'), _chk(flow_x, 'flow_x'), _chk(flow_y, 'flow_y')
     h, w, c = feat.shape
     out = torch.empty((h, w, c), device=feat.device, dtype=torch.float16)
-    _native.check(_native.lib().pnp_mv_warp_nhwc_f16out(_ptr(feat), _ptr(flow_x), _ptr(flow_y), _ptr(out), h, w, c, _stream()),
-                  'pnp_mv_warp_nhwc_f16out')
+    _native.check(_native.lib().pnp_mv_warp_nhwc_f16out_mode(_ptr(feat), _ptr(flow_x), _ptr(flow_y), _ptr(out), h, w, c,
+                                                             _WARP_MODES[interpolation], _stream()), 'pnp_mv_warp_nhwc_f16out_mode')
     return out
 
 

@@ -191,6 +191,22 @@ def test_op_level_convs_refuse_maps_beyond_32_bit_offsets_before_touching_memory
     assert lib.pnp_conv3x3_f16x3(0, srcs, chans, w, w, None, None, None, None, None, None, 0, fake, 64, 64, None) == 1001
 
 
+def test_warp_entries_refuse_bad_sizes_before_touching_memory(lib):
+    """every pixel-major warp entry: h < 1, w < 1, c < 4, c % 4 != 0 and a mode other than 0 / 1 are PNP_ERR_BAD_ARG (1001), decided
+    on the host before any launch (runs without a GPU; the pointers are fakes)"""
+    fake = 0x1000
+    entries = {'f32': lambda h, w, c, mode: lib.pnp_mv_warp_nhwc_f32(fake, fake, fake, fake, h, w, c, None),
+               'mode_f32': lambda h, w, c, mode: lib.pnp_mv_warp_nhwc_mode_f32(fake, fake, fake, fake, h, w, c, mode, None),
+               'f16out': lambda h, w, c, mode: lib.pnp_mv_warp_nhwc_f16out(fake, fake, fake, fake, h, w, c, None),
+               'f16out_mode': lambda h, w, c, mode: lib.pnp_mv_warp_nhwc_f16out_mode(fake, fake, fake, fake, h, w, c, mode, None)}
+    for name, call in entries.items():
+        for h, w, c in ((0, 8, 64), (-1, 8, 64), (8, 0, 64), (8, -3, 8), (8, 8, 0), (8, 8, 3), (8, 8, -4), (8, 8, 6), (8, 8, 66),
+                        (0, 0, 0)):
+            assert call(h, w, c, 0) == 1001, (name, h, w, c)
+        if 'mode' in name:
+            assert call(8, 8, 64, 2) == 1001 and call(8, 8, 8, -1) == 1001, name
+
+
 def test_graft_entry_build_runs_and_agrees_with_the_header_on_the_abi_version():
     """__graft_entry__.build() is the driver's "does it build" check: it must pass on a CPU box (hipcc cross-compiles) and its ABI
     assertion must follow include/pnpvcve.h (r04: the header went to 4 while build() still asserted 3)."""
