@@ -583,6 +583,32 @@ int pnp_rasterise_side_info_f32(const float* records_dev, const int* rec_frame_d
                                 const float* slices_host, int t, int h, int w, float* mvs_dev, float* par_dev,
                                 int* scratch_dev, void* stream);
 
+/* Self-ensemble over the 8 flips / transposes of a frame and, optionally, time reversal -- the reference's SpatialTemporalEnsemble
+ * (mmedit/models/common/ensemble.py) with the side information transformed together with the frames, which the reference does not do
+ * (it calls the model with the frames only and cannot run this generator).
+ * A variant is 4 bits v: bit 0 = 'vertical' in the reference's naming, a flip of the WIDTH axis; bit 1 = 'horizontal', a flip of the
+ * HEIGHT axis; bit 2 = transpose; bit 3 = time reversal.  Input views apply bit 0, then bit 1, then bit 2 (the reference's img_list
+ * order); the output inverse applies bit 2, then bit 1, then bit 0; time reversal commutes with all three.  For an original plane X
+ * of h x w, with (h', w') = (w, h) if bit 2 else (h, w) and frame i' = t-1-i if bit 3 else i:
+ *     X'[i', y', x'] = X[i, y, x],  (a, b) = (x', y') if bit 2 else (y', x');  y = h-1-a if bit 1 else a;  x = w-1-b if bit 0 else b.
+ *   Frames (lq: fp32 (t,3,h,w) or uint8 (t,h,w,3)) and partition planes (t,3,h,w) are moved and nothing else: partition classes are
+ *   areas (256, 128 or 64 px), so 16x8 and 8x16 already share a plane.
+ *   Motion vectors (t,4,h,w), channels (fwd x, fwd y, bwd x, bwd y), are moved and then changed in this order: bit 0 negates channels
+ *   0 and 2; bit 1 negates 1 and 3; bit 2 swaps 0 <-> 1 and 2 <-> 3; bit 3 swaps (0,1) <-> (2,3).  A negated zero is -0.0.
+ *   slices, QPs, base_QPs (t) are reversed in time under bit 3 and untouched otherwise (host data: no entry here).
+ * The ensemble's output over the variants V = 0..7 (spatial) or 0..15 (with time reversal) is a sequential fp32 sum in ascending v,
+ * acc = inv_0(G(view_0)); acc = acc + inv_v(G(view_v)) for v = 1, 2, ...; out = acc * (1/|V|), one exact power-of-two scaling.
+ * pnp_ensemble_view: one launch writes variant v's lq', mvs' and par' from the originals.  Each in / out pair may be NULL together.
+ *   No row of a uint8 frame is assumed dword-aligned (w or h odd); all element offsets are 64-bit.
+ * pnp_ensemble_accumulate_f32: x_dev (t,c,H',W') is variant v's output, acc_dev (t,c,H,W) lies in the original orientation and frame
+ *   order; per element s = first ? x : acc + x, then acc = s if scale == 1 else s * scale (plain fp32, no fused operation).
+ * PNP_ERR_BAD_ARG, decided on the host before any HIP call: one side of a pair NULL; variant outside 0..15; t, h, w, c < 1 (H, W
+ *   alike); an unknown format; in == out; scale not finite or <= 0.  PNP_ERR_UNSUPPORTED: more than 2^31 - 1 tiles in one call. */
+int pnp_ensemble_view(const void* lq_dev, const float* mvs_dev, const float* par_dev, void* lq_out_dev, float* mvs_out_dev,
+                      float* par_out_dev, int frames_format, int t, int h, int w, int variant, void* stream);
+int pnp_ensemble_accumulate_f32(const float* x_dev, float* acc_dev, int t, int c, int H, int W, int variant, int first, float scale,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,8 @@ SIGNATURES = {
     'pnp_pack_conv1x1_f32': (c_int, [c_void_p, c_void_p, c_void_p]),
     'pnp_frames_to_rgb8': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'pnp_frames_from_rgb8': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'pnp_ensemble_view': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'pnp_ensemble_accumulate_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     'pnp_psnr_sse_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'pnp_rasterise_side_info_f32': (c_int, [c_void_p, c_void_p, ctypes.c_long, POINTER(c_float), c_int, c_int, c_int,
                                             c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -168,7 +168,10 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
     ops.frames_to_yuv420(fp32 output, standard, layout).  A pair goes through generator.forward_clips by pointer, as under byte_frames.
     A dataset of 10 / 12-bit clips (its samples' meta carry the depth) goes the same way as ops.Yuv420Frames16; yuv_out_layout then
     also takes 'p010' | 'p012' | 'yuv420p10le' | 'yuv420p12le', the ground truth and the output must agree in depth, and the file is
-    ops.frames_to_yuv420p16's words, little-endian."""
+    ops.frames_to_yuv420p16's words, little-endian.
+
+    A model built with ensemble=dict(type='SpatialTemporalEnsemble', ...) runs clip by clip whatever clips_in_flight says (the same
+    metrics); byte_frames / byte_metrics work as above, yuv_frames raises ValueError."""
     import time
     model.eval()
     rank, world = get_dist_info()
@@ -179,6 +182,12 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
     # a sparse_val generator evaluates one sample per call in eval mode (the reference indexes feature[0, ...],
     # sr_backbone_utils.py:262-275; generator.py refuses n != 1): such a model keeps the clip-by-clip loop
     pairs = pairs and not getattr(model.generator, 'sparse_val', False)
+    # a model with a self-ensemble (BasicVSR(ensemble=...)) runs clip by clip: one clip is 8 or 16 generator runs already, which
+    # generator.forward_ensemble sends through forward_clips in groups
+    ensemble = getattr(model, 'forward_ensemble', None) is not None
+    pairs = pairs and not ensemble
+    if ensemble and yuv_frames:
+        raise ValueError('yuv_frames with a self-ensemble model: the ensemble takes fp32 or uint8 RGB frames, not 4:2:0 planes')
 
     byte_frames = (bool(byte_frames) or bool(byte_metrics)) and dev.type == 'cuda' and hasattr(model, 'generator') and not getattr(model, 'psnr_only', False)
     byte_metrics = bool(byte_metrics) and byte_frames

@@ -524,6 +524,68 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         u8 = [o[None] for o in outs[-n:]] if mask & _native.OUT_U8 else None
         return [self._ret(f32[i] if f32 else None, u8[i] if u8 else None, mask) for i in range(n)]
 
+    # ---------------------------------------------------------------- self-ensemble (include/pnpvcve.h, "Self-ensemble")
+    def _ensemble_group_limit(self, h, w):
+        """variants per forward_clips call: what the library runs concurrently (see _contexts); a sparse_val generator in eval mode
+        takes one clip per call"""
+        if self.sparse_val and not self.training:
+            return 1
+        return self.LARGE_FRAME_CONTEXTS if h * w >= self.CONCURRENT_BELOW_PIXELS else self.MAX_CONTEXTS
+
+    def forward_ensemble(self, lrs, QPs=None, slices=None, mvs=None, base_QPs=None, par_map=None, temporal=False, out_dtype=None):
+        """The self-ensemble of forward(): the mean of the outputs over the 8 flips / transposes of the clip (temporal: and their 8
+        time reversals), every variant's side information -- motion vectors, partition planes, slices, QPs -- transformed together
+        with the frames (ops.ensemble_view / ensemble_side; the rule: include/pnpvcve.h), every output taken back through the
+        variant's inverse.  The sum is sequential in fp32 in ascending variant order, scaled once by 1/8 or 1/16
+        (ops.ensemble_accumulate).  Inputs as forward()'s, fp32 or uint8 frames, (n,t,...); samples run one after another, a
+        sample's variants go through forward_clips in groups of one orientation.  out_dtype: None / torch.float32 | torch.uint8 |
+        'both', the bytes being ops.frames_to_rgb8 of the fp32 mean.  4:2:0 frames and deform != 'vos' raise ValueError; the
+        frame-size rules are forward()'s own, for both orientations.  Not replayed from a graph."""
+        if ops.is_yuv(lrs):
+            raise ValueError('the self-ensemble takes fp32 or uint8 RGB frames: where the chroma samples of a flipped 4:2:0 frame lie is '
+                             'not defined here')
+        if self._cfg.deform != _DEFORM['vos']:
+            raise ValueError("the self-ensemble runs deform='vos' generators only: the learned offsets of a DCN aligner are not "
+                             'transformed with the frame')
+        mask = self._out_mask(out_dtype)
+        if not lrs.is_cuda:
+            raise RuntimeError('PnP-VCVE generator: inputs must be CUDA/HIP tensors; this build has no CPU path')
+        byte_in = lrs.dtype == torch.uint8
+        if lrs.dim() != 5 or (byte_in and lrs.shape[-1] != 3):
+            raise ValueError(f'frames must be (n,t,3,h,w) fp32 or (n,t,h,w,3) uint8, got {tuple(lrs.shape)}')
+        n, t = lrs.shape[:2]
+        h, w = lrs.shape[2:4] if byte_in else lrs.shape[3:5]
+        if mvs is None or par_map is None:
+            raise TypeError('mvs (n,t,4,h,w) and par_map (n,t,3,h,w) are required')
+        variants = ops.ENSEMBLE_SPATIAL_TEMPORAL if temporal else ops.ENSEMBLE_SPATIAL
+        limit = self._ensemble_group_limit(h, w)
+        groups = []        # ascending v; a group holds one orientation (a square frame has one)
+        for v in variants:
+            if groups and len(groups[-1]) < limit and (h == w or (groups[-1][-1] ^ v) & 4 == 0):
+                groups[-1].append(v)
+            else:
+                groups.append([v])
+        s = 4 if self.vsr else 1
+        dev = lrs.device
+        with torch.cuda.device(dev):
+            acc = torch.empty((n, t, 3, h * s, w * s), device=dev, dtype=torch.float32)
+            lq_all = lrs.detach().contiguous() if byte_in else lrs.detach().float().contiguous()
+            mv_all, par_all = mvs.detach().float().contiguous(), par_map.detach().float().contiguous()
+            for b in range(n):
+                side = tuple(x[b] if x is not None else None for x in (QPs, slices, base_QPs))
+                for group in groups:
+                    clips = []
+                    for v in group:
+                        lq_v, mv_v, par_v = (lq_all[b], mv_all[b], par_all[b]) if v == 0 else ops.ensemble_view(lq_all[b], mv_all[b], par_all[b], v)
+                        qp_v, sl_v, bq_v = ops.ensemble_side(*side, v)
+                        clips.append((lq_v, qp_v, sl_v, mv_v, bq_v, par_v))
+                    outs = self.forward_clips(clips, out_dtype=torch.float32)
+                    for v, out in zip(group, outs):
+                        ops.ensemble_accumulate(acc[b], out, v, first=v == variants[0], scale=1.0 / len(variants) if v == variants[-1] else 1.0)
+                    del clips, outs
+            u8 = torch.stack([ops.frames_to_rgb8(acc[b]) for b in range(n)]) if mask & _native.OUT_U8 else None
+        return self._ret(acc, u8, mask)
+
     def _forward_clips_native(self, lrs, mvs, par, side, mask):
         """Body of torch.ops.pnpvcve.generator_forward_clips: per-clip contiguous CUDA tensors + the (3, n, t) host side info ->
         the fp32 outputs (mask & 1), then the uint8 ones (mask & 2), one freshly allocated tensor per clip."""

@@ -1142,3 +1142,99 @@ def pack_lr_yuv420p16(frames, standard='bt601-limited', general=False):
         _native.check(_native.lib().pnp_debug_pack_lr_yuv420p16(ctypes.byref(d), _yuv_standard(standard), _ptr(out), t, h, w, int(bool(general)),
                                                                 _stream()), 'pnp_debug_pack_lr_yuv420p16')
     return out
+
+
+# ---------------------------------------------------------------- self-ensemble (include/pnpvcve.h, "Self-ensemble")
+#: variant ids: bit 0 flips the width axis, bit 1 the height axis, bit 2 transposes, bit 3 reverses time
+ENSEMBLE_SPATIAL = tuple(range(8))
+ENSEMBLE_SPATIAL_TEMPORAL = tuple(range(16))
+
+
+def _ensemble_variant(variant):
+    if isinstance(variant, bool) or not isinstance(variant, int) or not 0 <= variant < 16:
+        raise ValueError(f'variant must be an int in 0..15, got {variant!r}')
+    return variant
+
+
+def _ensemble_clip(x, name, byte_ok=False):
+    """one clip tensor of ensemble_view: (t,...) or (1,t,...) -> (the contiguous 4-D tensor, whether it had a batch dimension)"""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError(f'{name} must be a CUDA/HIP tensor: the PnP-VCVE hot path has no CPU fallback')
+    if x.dim() not in (4, 5) or (x.dim() == 5 and x.shape[0] != 1):
+        raise ValueError(f'{name} must be one clip: a 4-D tensor, or a 5-D one with n = 1, got {tuple(x.shape)}')
+    if x.dtype != torch.float32 and not (byte_ok and x.dtype == torch.uint8):
+        raise TypeError(f'{name} must be float32' + (' planes or uint8 (t,h,w,3) frames' if byte_ok else '') + f', got {x.dtype}')
+    return x.reshape(x.shape[-4:]).contiguous(), x.dim() == 5
+
+
+@_on_device_of_first_tensor
+def ensemble_view(lq, mvs, par, variant):
+    """Variant `variant`'s view of a clip's frames and maps, in one launch (pnp_ensemble_view): lq (t,3,h,w) fp32 or (t,h,w,3) uint8,
+    mvs (t,4,h,w), par (t,3,h,w) -- 4-D, or 5-D with n = 1; any of them may be None -> (lq', mvs', par') in the input's rank, None
+    where None was given.  The frames and partition planes are moved; the motion vectors are moved, negated and swapped with them."""
+    v = _ensemble_variant(variant)
+    ins, shape = [], None
+    for x, name, c in ((lq, 'lq', 3), (mvs, 'mvs', 4), (par, 'par', 3)):
+        if x is None:
+            ins.append(None)
+            continue
+        x4, lead = _ensemble_clip(x, name, byte_ok=name == 'lq')
+        if x4.dtype == torch.uint8:
+            if x4.shape[-1] != 3:
+                raise ValueError(f'uint8 frames must be (t,h,w,3), got {tuple(x4.shape)}')
+            thw = (x4.shape[0], x4.shape[1], x4.shape[2])
+        else:
+            if x4.shape[1] != c:
+                raise ValueError(f'{name} must have {c} channels, got {tuple(x4.shape)}')
+            thw = (x4.shape[0], x4.shape[2], x4.shape[3])
+        if shape is None:
+            shape = thw
+        elif thw != shape:
+            raise ValueError(f'lq, mvs and par must agree in (t, h, w): {thw} against {shape}')
+        ins.append((x4, lead))
+    if shape is None:
+        return None, None, None
+    t, h, w = shape
+    ho, wo = (w, h) if v & 4 else (h, w)
+    outs = []
+    for item in ins:
+        if item is None:
+            outs.append(None)
+        elif item[0].dtype == torch.uint8:
+            outs.append(torch.empty((t, ho, wo, 3), device=item[0].device, dtype=torch.uint8))
+        else:
+            outs.append(torch.empty((t, item[0].shape[1], ho, wo), device=item[0].device, dtype=torch.float32))
+    fmt = _native.FRAMES_U8_HWC if (ins[0] is not None and ins[0][0].dtype == torch.uint8) else _native.FRAMES_F32_NCHW
+    P = lambda x: _ptr(x[0] if isinstance(x, tuple) else x)      # noqa: E731
+    _native.check(_native.lib().pnp_ensemble_view(P(ins[0]), P(ins[1]), P(ins[2]), P(outs[0]), P(outs[1]), P(outs[2]), fmt, t, h, w, v,
+                                                  _stream()), 'pnp_ensemble_view')
+    return tuple(None if o is None else (o[None] if item[1] else o) for o, item in zip(outs, ins))
+
+
+def ensemble_side(QPs, slices, base_QPs, variant):
+    """Variant `variant`'s (..., t, 1, 1, 1) side tensors: reversed in time under bit 3, untouched otherwise (plain torch; None stays None)."""
+    v = _ensemble_variant(variant)
+    return tuple(x if (x is None or not v & 8) else x.flip(-4) for x in (QPs, slices, base_QPs))
+
+
+@_on_device_of_first_tensor
+def ensemble_accumulate(acc, x, variant, first, scale=1.0):
+    """In place (pnp_ensemble_accumulate_f32): acc (t,c,H,W), original orientation and frame order, takes variant `variant`'s output
+    x (t,c,H',W') through the variant's inverse -- acc = x if first else acc + x, then times `scale` unless it is 1.  4-D tensors, or
+    5-D with n = 1.  Returns acc."""
+    v = _ensemble_variant(variant)
+    if not isinstance(acc, torch.Tensor) or not acc.is_cuda or not acc.is_contiguous() or acc.dtype != torch.float32:
+        raise RuntimeError('acc must be a contiguous float32 CUDA/HIP tensor (it is written in place)')
+    x4, _ = _ensemble_clip(x, 'x')
+    a4 = acc.reshape(acc.shape[-4:]) if acc.dim() in (4, 5) and (acc.dim() == 4 or acc.shape[0] == 1) else None
+    if a4 is None:
+        raise ValueError(f'acc must be one clip: a 4-D tensor, or a 5-D one with n = 1, got {tuple(acc.shape)}')
+    t, c, H, W = a4.shape
+    if tuple(x4.shape) != ((t, c, W, H) if v & 4 else (t, c, H, W)):
+        raise ValueError(f'x is {tuple(x4.shape)}, acc {tuple(a4.shape)}: not variant {v}\'s output of this clip')
+    scale = float(scale)
+    if not (scale > 0.0) or scale == float('inf'):
+        raise ValueError(f'scale must be finite and > 0, got {scale!r}')
+    _native.check(_native.lib().pnp_ensemble_accumulate_f32(_ptr(x4), _ptr(a4), t, c, H, W, v, int(bool(first)), scale, _stream()),
+                  'pnp_ensemble_accumulate_f32')
+    return acc

@@ -45,9 +45,17 @@ class BasicVSR(nn.Module):
         self.psnr_only = psnr_only
         self.generator = build_backbone(generator)
         self.pixel_loss = build_loss(pixel_loss) if pixel_loss else None
-        if ensemble is not None:
-            raise NotImplementedError('spatial-temporal ensemble is not part of the hot path')
+        # basicvsr.py:52-64.  The reference's SpatialTemporalEnsemble calls the generator with the frames only and cannot run this one;
+        # here the switch selects generator.forward_ensemble, which transforms the side information with the frames
         self.forward_ensemble = None
+        self.is_temporal_ensemble = False
+        if ensemble is not None:
+            if ensemble['type'] == 'SpatialTemporalEnsemble':
+                self.is_temporal_ensemble = bool(ensemble.get('is_temporal_ensemble', False))
+                self.forward_ensemble = self._forward_ensemble
+            else:
+                raise NotImplementedError('Currently support only "SpatialTemporalEnsemble", but got type '
+                                          f'[{ensemble["type"]}]')
         self.fix_iter = train_cfg.get('fix_iter', 0) if train_cfg else 0
         self.is_weight_fixed = False
         self.register_buffer('step_counter', torch.zeros(1))          # basicvsr.py:50
@@ -73,6 +81,9 @@ class BasicVSR(nn.Module):
     @precision.setter
     def precision(self, value):
         self.generator.precision = value
+
+    def _forward_ensemble(self, lq, QPs, slices, mvs, base_QPs, par_map, **kw):
+        return self.generator.forward_ensemble(lq, QPs, slices, mvs, base_QPs, par_map, temporal=self.is_temporal_ensemble, **kw)
 
     def check_if_mirror_extended(self, lrs):
         """basicvsr.py:52-68."""
@@ -201,9 +212,14 @@ class BasicVSR(nn.Module):
         out_dtype = 'i420' | 'nv12' the generator writes packed 4:2:0 only (`precomputed_output`: that packed buffer): the
         metrics are then evaluate()'s plane metrics against a Yuv420Frames `gt`, and save_image writes <save_path>/<clip>.yuv -- the
         buffer's bytes, frames in order, one FrameWriter job per clip.  ops.Yuv420Frames16 `lq` (10 / 12 bit) likewise, with the four
-        16-bit layout names beside them: the buffer is then 16-bit little-endian words, 3 B per pixel in the file."""
+        16-bit layout names beside them: the buffer is then 16-bit little-endian words, 3 B per pixel in the file.
+        Self-ensemble (basicvsr.py:172-173): a model built with ensemble=dict(type='SpatialTemporalEnsemble', ...) runs
+        generator.forward_ensemble where it would run the generator -- fp32 or uint8 frames and out_dtype as above,
+        last_forward_seconds covers the whole ensemble, precomputed_output is taken as it is; 4:2:0 `lq` raises ValueError."""
         from . import ops
         yuv_in = ops.is_yuv(lq)
+        if yuv_in and self.forward_ensemble is not None:
+            raise ValueError('the self-ensemble takes fp32 or uint8 RGB frames, not 4:2:0 planes (generator.forward_ensemble)')
         yuv_layout = out_dtype if (yuv_in and isinstance(out_dtype, str) and out_dtype in self.YUV_OUT_LAYOUTS) else None
         if ops.is_yuv(gt) and yuv_layout is None:
             raise ValueError("a 4:2:0 ground truth is compared with 4:2:0 output: lq must be ops.Yuv420Frames and out_dtype one of "
@@ -220,7 +236,8 @@ class BasicVSR(nn.Module):
                 kw = {} if out_dtype is None else {'out_dtype': out_dtype}
                 if yuv_in:
                     kw['yuv_standard'] = yuv_standard
-                output = self.generator(lq, QPs, slices, mvs, base_QPs, par_map, **kw)
+                run = self.generator if self.forward_ensemble is None else self.forward_ensemble
+                output = run(lq, QPs, slices, mvs, base_QPs, par_map, **kw)
                 torch.cuda.synchronize()
                 self.last_forward_seconds = time.time() - begin
         else:

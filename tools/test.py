@@ -65,6 +65,11 @@ def parse_args():
                    help='run frames whose height or width is no multiple of 4 (generator.any_size; the same as --cfg-options '
                         'model.generator.any_size=True): the same formulas on the frame as given, no padding.  Default off: such '
                         'frames raise ValueError, as in the reference')
+    p.add_argument('--ensemble', choices=['spatial', 'spatial-temporal'], default=None,
+                   help="self-ensemble (sets cfg.model.ensemble = dict(type='SpatialTemporalEnsemble', is_temporal_ensemble=...)): the mean "
+                        'of the outputs over the 8 flips / transposes of every clip, with spatial-temporal also over their 8 time '
+                        'reversals, the motion vectors and partition maps transformed with the frames; 8 or 16 generator runs per '
+                        'clip, clips run one at a time; not with --yuv-frames.  Default off')
     p.add_argument('--local_rank', type=int, default=0)
     a = p.parse_args()
     if 'LOCAL_RANK' not in os.environ:
@@ -97,6 +102,9 @@ def main():
     if args.testdir_gt is not None:
         cfg.merge_from_dict({'data.test.gt_folder': args.testdir_gt})
         print('-------------------- test GT dir :', args.testdir_gt)
+    if args.ensemble is not None:
+        cfg.merge_from_dict({'model.ensemble': dict(_delete_=True, type='SpatialTemporalEnsemble',
+                                                    is_temporal_ensemble=args.ensemble == 'spatial-temporal')})
     dataset = build_dataset(cfg.data.test)
     model = build_model(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)
     if args.checkpoint.lower() != 'none':
