@@ -560,6 +560,52 @@ int pnp_ssim_partials_io(const void* a_dev, int a_format, const void* b_dev, int
                          double* partials_dev, int frames, int c, int h, int w, int crop_border, void* stream);
 int pnp_luma_from_frames(const void* frames_dev, int format, float* out_dev, int nframes, int h, int w, void* stream);
 
+/* Multi-scale SSIM (msssim.hip) on every boundary SSIM is computed on.  This is a definition of the project's OWN: the reference has no
+ * MS-SSIM, and no HM / VTM / libvmaf binary was at hand to compare digits with, so agreement with a particular external tool is
+ * unpinned.  It is pinned by two independent numpy restatements (pnp_vcve_amd/metrics.py::msssim, tests/msssim_ref.py).  This is the
+ * ONE statement of it: Wang, Simoncelli and Bovik 2003, five scales, on one plane of samples (a, b) with peak P.
+ *   Samples and peak: the samples SSIM reads on the same boundary.  pnp_msssim_partials_io: PNP_COLOR_NONE, the byte of every channel
+ *   (to_u8 of an fp32 plane, the byte of a U8_HWC frame as it is), P = 255; PNP_COLOR_Y, the fp32 Y of pnp_luma_from_frames, P = 255.
+ *   pnp_msssim_partials_yuv420: the byte, P = 255.  pnp_msssim_partials_yuv420p16: the word's value as pnp_yuv420_planes16 is read,
+ *   P = 2^d - 1.
+ *   Crop: once, at level 0, as SSIM's: crop_border on RGB / Y planes, half of it on chroma planes, even for 4:2:0.
+ *   Pyramid: level 0 is the cropped plane, h0 x w0.  Level s+1 is floor(h_s / 2) x floor(w_s / 2); its sample (r, c) is
+ *       (float)((((double)x[2r][2c] + x[2r][2c+1]) + ((double)x[2r+1][2c] + x[2r+1][2c+1])) * 0.25), stored as fp32.
+ *   An odd last row or column of a level is dropped.  For integer samples of up to 12 bits every level is exact in fp32 (12 + 8 bits),
+ *   so the fp32 storage IS the fp64 pyramid; for the fp32 Y the expression above is the definition, rounding included.
+ *   Statistics at every level: SSIM's window -- 11 taps, sigma 1.5, normalised, separable, 'valid', fp64.  With C1 = (0.01 P)^2,
+ *   C2 = (0.03 P)^2:  cs = (2 s_ab + C2) / (s_a^2 + s_b^2 + C2),  l = (2 mu_a mu_b + C1) / (mu_a^2 + mu_b^2 + C1).  The device leaves,
+ *   per frame, plane and level, the partial sums of cs and of l * cs over the valid map, one pair per block (16 x 32 tiles of the
+ *   valid map, as pnp_ssim_partials_*); the host adds them in index order (deterministic) and divides by the valid map's size
+ *   (rows_s - 10)(cols_s - 10): the means are CS_s and S_s.
+ *   Value: MS-SSIM = prod_{s=0..3} max(CS_s, 0)^{w_s} * max(S_4, 0)^{w_4}, w = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333) as published
+ *   (sum 1.0001, not renormalised), formed by the host in fp64.  A plane pair whose structure is anticorrelated at some scale scores
+ *   0, not NaN.  Several planes (RGB, PNP_COLOR_NONE) give the mean of the planes' values, with or without a crop (the reference's
+ *   crop quirk belongs to its ssim; it is not carried over to a metric the reference does not have).
+ *   Smallest frame: level 4 must hold one window: min(h0, w0) >= pnp_msssim_min_size() = 176 after the crop, for every plane asked
+ *   for; chroma planes therefore need a 352-line frame.
+ * Sizing (host only, msssim_plan.h), for ONE plane of h x w samples cropped by crop_border on each side (a chroma plane of H x W
+ * frames: h = H/2, w = W/2, crop_border = crop/2): pnp_msssim_level_dims gives the level's rows and columns, pnp_msssim_blocks its
+ * blocks (0 when the plane cannot be scored or the level is not 0..4).  pnp_msssim_workspace_bytes: the fp32 pyramid, levels 1..4 of
+ * both clips, of `planes` such planes a frame (0 when it cannot run); the library owns no device memory, workspace_dev is the
+ * caller's, 4-byte aligned.  The 4:2:0 entries take pnp_msssim_workspace_bytes(frames, planes of the mask, h, w, crop_border) of the
+ * FRAME: every plane of the mask gets a slot of the Y plane's size.
+ * Partials: pnp_msssim_partials_io: partials_dev [frames][planes][B][2] doubles, planes = c (PNP_COLOR_NONE) or 1 (PNP_COLOR_Y), B =
+ * sum over the five levels of pnp_msssim_blocks, level after level; [..][0] the block's sum of cs, [..][1] of l * cs.  The 4:2:0 entries:
+ * for each plane of plane_mask in the order Y, Cb, Cr, [frames][B of that plane][2], one plane after the other.
+ * PNP_ERR_BAD_ARG, decided on the host before any HIP call: whatever pnp_ssim_partials_io / _yuv420 / _yuv420p16 refuse (formats,
+ * colors, descriptors, masks, odd crops, differing depths), a NULL workspace, and a cropped plane asked for below 176 x 176. */
+int pnp_msssim_min_size(void);
+int pnp_msssim_level_dims(int h, int w, int crop_border, int level, int* rows, int* cols);
+int pnp_msssim_blocks(int h, int w, int crop_border, int level);
+int64_t pnp_msssim_workspace_bytes(int frames, int planes, int h, int w, int crop_border);
+int pnp_msssim_partials_io(const void* a_dev, int a_format, const void* b_dev, int b_format, int color, double* partials_dev,
+                           void* workspace_dev, int frames, int c, int h, int w, int crop_border, void* stream);
+int pnp_msssim_partials_yuv420(const pnp_yuv420_planes* a_host_desc, const pnp_yuv420_planes* b_host_desc, int plane_mask,
+                               double* partials_dev, void* workspace_dev, int frames, int h, int w, int crop_border, void* stream);
+int pnp_msssim_partials_yuv420p16(const pnp_yuv420_planes16* a_host_desc, const pnp_yuv420_planes16* b_host_desc, int plane_mask,
+                                  double* partials_dev, void* workspace_dev, int frames, int h, int w, int crop_border, void* stream);
+
 /* Modulated deformable 3x3 conv, 64 -> 64 channels, deform_groups 16 (mmcv.ops.modulated_deform_conv2d as
  * called at mmedit/models/backbones/sr_backbones/iconvsr_mv.py:38-41,81-84; semantics restated, mmcv is not
  * vendored).  x_dev (h,w,64) pixel-major; om_dev (h,w,448): conv_offset[2] output (pre-sigmoid masks) in the

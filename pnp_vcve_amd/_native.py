@@ -137,6 +137,16 @@ SIGNATURES = {
     'pnp_psnr_stat_io': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'pnp_ssim_partials_io': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'pnp_luma_from_frames': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'pnp_msssim_min_size': (c_int, []),
+    'pnp_msssim_level_dims': (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    'pnp_msssim_blocks': (c_int, [c_int, c_int, c_int, c_int]),
+    'pnp_msssim_workspace_bytes': (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    'pnp_msssim_partials_io': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                       c_void_p]),
+    'pnp_msssim_partials_yuv420': (c_int, [POINTER(Yuv420Planes), POINTER(Yuv420Planes), c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                           c_int, c_void_p]),
+    'pnp_msssim_partials_yuv420p16': (c_int, [POINTER(Yuv420Planes16), POINTER(Yuv420Planes16), c_int, c_void_p, c_void_p, c_int, c_int,
+                                              c_int, c_int, c_void_p]),
     'pnp_conv3x3_f32': (c_int, [c_int, POINTER(c_void_p), POINTER(c_int), POINTER(c_void_p), c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     'pnp_bae_block_f32': (c_int, [c_void_p] * 10 + [c_int, c_int, c_void_p]),

@@ -1,0 +1,427 @@
+// Multi-scale SSIM on the device (include/pnpvcve.h, pnp_msssim_*: the ONE statement of the definition): Wang, Simoncelli and Bovik
+// 2003, five scales, per plane, on every boundary SSIM is computed on -- fp32 planes, uint8 RGB frames, the reference's Y, 8-bit and
+// 10 / 12-bit 4:2:0 planes.  The definition is this project's own: the reference has no MS-SSIM and no external tool was at hand to
+// compare digits with; it is pinned by two restatements (pnp_vcve_amd/metrics.py::msssim, tests/msssim_ref.py).
+//
+// Two kernels.  msssim_down_kernel makes level s + 1 of BOTH clips from level s: at s = 0 it reads through the boundary's loaders
+// (metric_src.h, plane_load.h), from s = 1 on it reads the fp32 pyramid; a thread makes two neighbouring output samples of one row
+// from a group of four input samples on two rows, whole samples only, so nothing is divided or accumulated across threads.
+// msssim_level_kernel is ssim_kernel (metrics.hip) -- a 16 x 32 tile of the valid map per block, two 26 x 42 input tiles in LDS, a
+// horizontal pass that leaves five windowed moments of 26 x 32 positions in LDS, a vertical pass -- whose closing pass forms
+// cs = (2 s_ab + C2) / (s_a^2 + s_b^2 + C2) and l * cs and writes the block's TWO partial sums.  ONE launch covers every level of
+// every plane: a plane's blocks are the concatenation of its levels' blocks (msssim_plan.h), the planes of a mask follow each
+// other along the grid's x, so the 1 x 1 valid map of level 4 costs one block and no empty tile is launched.  Four launches of
+// the first kernel and one of the second per call; the host adds a level's partials in index order (deterministic).
+// The library owns no device memory: the pyramid (levels 1..4 of both clips, fp32) lives in the caller's workspace.
+#include "metric_src.h"
+#include "msssim_plan.h"
+
+namespace {
+
+enum { K_RGB = 0, K_Y = 1, K_P8 = 2, K_P16 = 3, K_LEVEL = 4 };      // what a kernel instance reads at level 0 (K_LEVEL: the pyramid only)
+
+// One clip's source of one class of planes (only the member of the instance's kind is read)
+struct MsSrc {
+    FrameSrc fs;            // K_RGB, K_Y
+    PnpPlaneSrc p8;         // K_P8
+    Plane16 p16;            // K_P16
+    int sel;                // K_P8: the plane is the second of an interleaved pair
+};
+
+// Planes of one size and source: the channels of RGB frames, the Y of frames, or one plane of a 4:2:0 mask.  A `unit` (the grid's y)
+// is one plane of one frame: frame * planes + channel (K_RGB), the frame otherwise.
+struct MsClass {
+    MsSrc a, b;
+    PnpMsPlan plan;
+    int H, W, crop;         // the plane before its crop
+    int blk0;               // first block of the class along the level kernel's x
+    long part0;             // first double of the class among the partials
+    float *wa, *wb;         // pyramid slots of unit 0 of the two clips
+};
+
+struct MsArgs {
+    double g[11];
+    MsClass cl[3];
+    int nclass;
+    long slot;              // floats between two units' pyramid slots
+    double* partial;        // [class][unit][level][block][2]
+    double L;               // the peak
+};
+
+// sample `pix` (= y * W + x) of unit `unit` of a clip of frames: the byte SSIM reads, or (Y) the fp32 luma of the pixel
+template <bool Y>
+__device__ __forceinline__ float frame_value(const FrameSrc& s, long unit, long hw, long pix, const double* lt) {
+    if (s.fmt == PNP_FRAMES_U8_HWC) {                                              // three channels
+        const long frame = Y ? unit : unit / 3;
+        const unsigned char* q = static_cast<const unsigned char*>(s.p) + (frame * hw + pix) * 3;
+        if (!Y) return (float)q[unit - frame * 3];
+        return luma_of(lt, (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16));
+    }
+    const float* f = static_cast<const float*>(s.p);
+    if (!Y) return (float)to_u8(f[unit * hw + pix]);
+    f += unit * 3 * hw + pix;
+    return luma_of(lt, px_of_f32(f[0], f[hw], f[2 * hw]));
+}
+
+// v[i][j]: sample crop + 4 gx + j (j < npix = 2 | 4) of row crop + 2 r + i of the unit's level-0 plane
+template <int KIND>
+__device__ __forceinline__ void fetch_2x4(const MsSrc& s, const MsClass& c, long unit, int r, int gx, int npix, const double* lt,
+                                          float v[2][4]) {
+    const int y0 = c.crop + 2 * r, x0 = c.crop + 4 * gx;
+    const long hw = (long)c.H * c.W;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const long p0 = (long)(y0 + i) * c.W + x0;
+        if (KIND == K_P16) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[i][j] = j < npix ? (float)load16(s.p16, unit, y0 + i, x0 + j) : 0.f;
+        } else if (KIND == K_Y) {
+            unsigned px[4];
+            load_px4(s.fs, unit, hw, p0, npix, px);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[i][j] = j < npix ? luma_of(lt, px[j]) : 0.f;
+        } else if (s.fs.fmt == PNP_FRAMES_U8_HWC) {                                // K_RGB, bytes: the pixel group, this unit's channel of it
+            const long frame = unit / 3;
+            const unsigned sh = 8u * (unsigned)(unit - frame * 3);
+            unsigned px[4];
+            load_px4(s.fs, frame, hw, p0, npix, px);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[i][j] = (float)((px[j] >> sh) & 255u);
+        } else {                                                                    // K_RGB, fp32 planes (any number of them a frame)
+            const float* f = static_cast<const float*>(s.fs.p) + unit * hw + p0;
+            if (npix == 4 && (reinterpret_cast<uintptr_t>(f) & 15) == 0) {
+                const f32x4 t = *reinterpret_cast<const f32x4*>(f);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[i][j] = (float)to_u8(t[j]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[i][j] = j < npix ? (float)to_u8(f[j]) : 0.f;
+            }
+        }
+    }
+}
+
+// Level `level` + 1 of both clips from level `level`; KIND: what level 0 is read from (K_LEVEL: level >= 1, the fp32 pyramid).
+// grid (x: groups, y: units, z: classes)
+template <int KIND>
+__global__ __launch_bounds__(256) void msssim_down_kernel(const MsArgs s, const int level) {
+    __shared__ double lt[KIND == K_Y ? 768 : 1];
+    if (KIND == K_Y) stage_luma_table(lt);
+    const MsClass& c = s.cl[blockIdx.z];                                // (read where it lies, in the kernel's argument segment)
+    const long unit = blockIdx.y;
+    const PnpMsLevel &src = c.plan.lv[level], &dst = c.plan.lv[level + 1];
+    const int gpr = (dst.cols + 1) / 2;                                 // groups per output row: two samples each
+    const long groups = (long)dst.rows * gpr;
+    float* oa = c.wa + unit * s.slot + dst.ws_off;
+    float* ob = c.wb + unit * s.slot + dst.ws_off;
+    const float* ia = c.wa + unit * s.slot + src.ws_off;               // (used from level 1 on)
+    const float* ib = c.wb + unit * s.slot + src.ws_off;
+    for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < groups; g += (long)gridDim.x * 256) {
+        const int r = (int)(g / gpr), gx = (int)(g - (long)r * gpr);
+        const int ncol = dst.cols - 2 * gx < 2 ? 1 : 2;
+        float ra[2], rb[2];
+        if constexpr (KIND == K_P8) {
+            pnp_ms_down_plane8(c.a.p8, c.a.sel, unit, c.crop, r, gx, ncol, ra);
+            pnp_ms_down_plane8(c.b.p8, c.b.sel, unit, c.crop, r, gx, ncol, rb);
+        } else {
+            float va[2][4], vb[2][4];
+            if constexpr (KIND == K_LEVEL) {
+                const long p0 = (long)(2 * r) * src.cols + 4 * gx;
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const bool in = j < 2 * ncol;
+                        va[i][j] = in ? ia[p0 + (long)i * src.cols + j] : 0.f;
+                        vb[i][j] = in ? ib[p0 + (long)i * src.cols + j] : 0.f;
+                    }
+            } else {
+                fetch_2x4<KIND>(c.a, c, unit, r, gx, 2 * ncol, lt, va);
+                fetch_2x4<KIND>(c.b, c, unit, r, gx, 2 * ncol, lt, vb);
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                ra[j] = pnp_ms_mean4(va[0][2 * j], va[0][2 * j + 1], va[1][2 * j], va[1][2 * j + 1]);
+                rb[j] = pnp_ms_mean4(vb[0][2 * j], vb[0][2 * j + 1], vb[1][2 * j], vb[1][2 * j + 1]);
+            }
+        }
+        const long o = (long)r * dst.cols + 2 * gx;
+        oa[o] = ra[0];
+        ob[o] = rb[0];
+        if (ncol > 1) {
+            oa[o + 1] = ra[1];
+            ob[o + 1] = rb[1];
+        }
+    }
+}
+
+// ssim_kernel's scheme on one 16 x 32 tile of the valid map of one level of one unit; the block's place along x names the class, the
+// level and the tile.  Level 0 is filled through the loaders of the instance's kind, levels 1..4 from the fp32 pyramid; both passes
+// are one body for all of them.
+template <int KIND>
+__global__ __launch_bounds__(256) void msssim_level_kernel(const MsArgs s) {
+    __shared__ float ta[26 * 42], tb[26 * 42];
+    __shared__ double hm[5][26 * 32];
+    __shared__ double red[4][2];
+    __shared__ double lt[KIND == K_Y ? 768 : 1];
+    if (KIND == K_Y) stage_luma_table(lt);
+    int ci = 0;
+    if (s.nclass > 1 && (int)blockIdx.x >= s.cl[1].blk0) ci = 1;
+    if (s.nclass > 2 && (int)blockIdx.x >= s.cl[2].blk0) ci = 2;
+    const MsClass& c = s.cl[ci];                                        // (read where it lies, in the kernel's argument segment)
+    const int blk = blockIdx.x - c.blk0, t = threadIdx.x;
+    const long unit = blockIdx.y;
+    int level = 0;
+#pragma unroll
+    for (int k = 1; k < PNP_MSSSIM_LEVELS; ++k)
+        if (blk >= c.plan.lv[k].blk0) level = k;
+    const PnpMsLevel& lv = c.plan.lv[level];
+    const int b = blk - lv.blk0;
+    const int ty0 = (b / lv.tiles_x) * 16, tx0 = (b % lv.tiles_x) * 32;            // in valid-map coordinates
+    if (level > 0) {
+        const float* pa = c.wa + unit * s.slot + lv.ws_off;
+        const float* pb = c.wb + unit * s.slot + lv.ws_off;
+        for (int i = t; i < 26 * 42; i += 256) {
+            const int r = i / 42, cx = i - r * 42;
+            const int y = ty0 + r, x = tx0 + cx;
+            const bool in = y < lv.rows && x < lv.cols;                             // absent samples are 0 in both tiles
+            ta[i] = in ? pa[(long)y * lv.cols + x] : 0.f;
+            tb[i] = in ? pb[(long)y * lv.cols + x] : 0.f;
+        }
+    } else if (KIND == K_P8) {
+        for (int i = t; i < 26 * 11; i += 256) {                                   // a row of the tile = 10 groups of four and one of two
+            const int r = i / 11, gc = i - r * 11;
+            const int y = c.crop + ty0 + r, x = c.crop + tx0 + 4 * gc;
+            int npix = 42 - 4 * gc < 4 ? 42 - 4 * gc : 4;
+            if (c.W - c.crop - x < npix) npix = c.W - c.crop - x;
+            unsigned wa[2] = {0, 0}, wb[2] = {0, 0};
+            if (y < c.H - c.crop && npix > 0) {
+                pnp_plane_load4(c.a.p8, unit, y, x, npix, wa);
+                pnp_plane_load4(c.b.p8, unit, y, x, npix, wb);
+            }
+            const unsigned va = c.a.sel ? wa[1] : wa[0], vb = c.b.sel ? wb[1] : wb[0];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (4 * gc + j < 42) {
+                    ta[r * 42 + 4 * gc + j] = (float)((va >> (8 * j)) & 255u);
+                    tb[r * 42 + 4 * gc + j] = (float)((vb >> (8 * j)) & 255u);
+                }
+            }
+        }
+    } else {
+        const long hw = (long)c.H * c.W;
+        for (int i = t; i < 26 * 42; i += 256) {
+            const int r = i / 42, cx = i - r * 42;
+            const int y = c.crop + ty0 + r, x = c.crop + tx0 + cx;
+            float va = 0.f, vb = 0.f;
+            if (y < c.H - c.crop && x < c.W - c.crop) {
+                if (KIND == K_P16) {
+                    va = (float)load16(c.a.p16, unit, y, x);
+                    vb = (float)load16(c.b.p16, unit, y, x);
+                } else {
+                    va = frame_value<KIND == K_Y>(c.a.fs, unit, hw, (long)y * c.W + x, lt);
+                    vb = frame_value<KIND == K_Y>(c.b.fs, unit, hw, (long)y * c.W + x, lt);
+                }
+            }
+            ta[i] = va;
+            tb[i] = vb;
+        }
+    }
+    __syncthreads();
+    for (int i = t; i < 26 * 32; i += 256) {
+        const int r = i >> 5, cx = i & 31;
+        double m1 = 0, m2 = 0, s11 = 0, s22 = 0, s12 = 0;
+#pragma unroll
+        for (int k = 0; k < 11; ++k) {
+            const double x = ta[r * 42 + cx + k], y = tb[r * 42 + cx + k], gk = s.g[k];
+            m1 += gk * x;
+            m2 += gk * y;
+            s11 += gk * x * x;
+            s22 += gk * y * y;
+            s12 += gk * x * y;
+        }
+        hm[0][i] = m1;
+        hm[1][i] = m2;
+        hm[2][i] = s11;
+        hm[3][i] = s22;
+        hm[4][i] = s12;
+    }
+    __syncthreads();
+    const double C1 = (0.01 * s.L) * (0.01 * s.L), C2 = (0.03 * s.L) * (0.03 * s.L);
+    double acc_cs = 0, acc_s = 0;
+    for (int i = t; i < 16 * 32; i += 256) {
+        const int r = i >> 5, cx = i & 31;
+        if (ty0 + r >= lv.oh || tx0 + cx >= lv.ow) continue;
+        double v[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < 11; ++k)
+#pragma unroll
+            for (int q = 0; q < 5; ++q) v[q] += s.g[k] * hm[q][(r + k) * 32 + cx];
+        const double mu1 = v[0], mu2 = v[1];
+        const double sg1 = v[2] - mu1 * mu1, sg2 = v[3] - mu2 * mu2, sg12 = v[4] - mu1 * mu2;
+        const double cs = (2 * sg12 + C2) / (sg1 + sg2 + C2);
+        const double l = (2 * mu1 * mu2 + C1) / (mu1 * mu1 + mu2 * mu2 + C1);
+        acc_cs += cs;
+        acc_s += l * cs;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        acc_cs += __shfl_down(acc_cs, off, 64);
+        acc_s += __shfl_down(acc_s, off, 64);
+    }
+    if ((t & 63) == 0) {
+        red[t >> 6][0] = acc_cs;
+        red[t >> 6][1] = acc_s;
+    }
+    __syncthreads();
+    if (t < 2) s.partial[c.part0 + (unit * c.plan.blocks + blk) * 2 + t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
+}
+
+// the five launches of one call: level 1 from the source, levels 2..4 from the pyramid, then every level's statistics
+template <int KIND>
+int launch_all(const MsArgs& s, int units, hipStream_t st) {
+    int blocks = 0;
+    for (int k = 0; k < s.nclass; ++k) blocks += s.cl[k].plan.blocks;
+    for (int level = 0; level + 1 < PNP_MSSSIM_LEVELS; ++level) {
+        long groups = 0;                                                            // of the largest class
+        for (int k = 0; k < s.nclass; ++k) {
+            const PnpMsLevel& d = s.cl[k].plan.lv[level + 1];
+            const long g = (long)d.rows * ((d.cols + 1) / 2);
+            groups = g > groups ? g : groups;
+        }
+        long bx = (groups + 255) / 256;
+        bx = bx < 1 ? 1 : (bx > 4096 ? 4096 : bx);
+        const dim3 grid((unsigned)bx, (unsigned)units, (unsigned)s.nclass);
+        if (level == 0) hipLaunchKernelGGL((msssim_down_kernel<KIND>), grid, dim3(256), 0, st, s, level);
+        else hipLaunchKernelGGL((msssim_down_kernel<K_LEVEL>), grid, dim3(256), 0, st, s, level);
+        const int e = (int)hipGetLastError();
+        if (e) return e;
+    }
+    hipLaunchKernelGGL((msssim_level_kernel<KIND>), dim3((unsigned)blocks, (unsigned)units), dim3(256), 0, st, s);
+    return (int)hipGetLastError();
+}
+
+// the classes' places along the level kernel's x, among the partials and in the workspace: class k's slots follow class k - 1's,
+// clip b's follow clip a's
+void place_classes(MsArgs& s, float* ws, long units_per_class) {
+    int blk0 = 0;
+    long part0 = 0;
+    for (int k = 0; k < s.nclass; ++k) {
+        MsClass& c = s.cl[k];
+        c.blk0 = blk0;
+        c.part0 = part0;
+        c.wa = ws + (long)k * units_per_class * s.slot;
+        c.wb = ws + ((long)s.nclass + k) * units_per_class * s.slot;
+        blk0 += c.plan.blocks;
+        part0 += units_per_class * c.plan.blocks * 2;
+    }
+    for (int k = s.nclass; k < 3; ++k) s.cl[k] = s.cl[0];
+}
+
+// the plane of `plane` (PNP_PLANE_*) of h x w 4:2:0 frames cropped by `crop` on the Y plane
+PnpMsPlan plane_plan(int h, int w, int crop, int plane) {
+    return plane == PNP_PLANE_Y ? pnp_ms_plan(h, w, crop) : pnp_ms_plan(h / 2, w / 2, crop / 2);
+}
+
+}  // namespace
+
+extern "C" int pnp_msssim_min_size(void) { return PNP_MSSSIM_MIN_SIZE; }
+
+extern "C" int pnp_msssim_level_dims(int h, int w, int crop_border, int level, int* rows, int* cols) {
+    const PnpMsPlan p = pnp_ms_plan(h, w, crop_border);
+    if (!p.ok || level < 0 || level >= PNP_MSSSIM_LEVELS || !rows || !cols) return PNP_ERR_BAD_ARG;
+    *rows = p.lv[level].rows;
+    *cols = p.lv[level].cols;
+    return PNP_OK;
+}
+
+extern "C" int pnp_msssim_blocks(int h, int w, int crop_border, int level) {
+    const PnpMsPlan p = pnp_ms_plan(h, w, crop_border);
+    if (!p.ok || level < 0 || level >= PNP_MSSSIM_LEVELS) return 0;
+    return p.lv[level].blocks;
+}
+
+extern "C" int64_t pnp_msssim_workspace_bytes(int frames, int planes, int h, int w, int crop_border) {
+    const PnpMsPlan p = pnp_ms_plan(h, w, crop_border);
+    if (!p.ok || frames < 1 || planes < 1) return 0;
+    return 2 * (int64_t)frames * planes * p.ws_floats * (int64_t)sizeof(float);
+}
+
+extern "C" int pnp_msssim_partials_io(const void* a, int a_format, const void* b, int b_format, int color, double* partials,
+                                      void* workspace, int frames, int c, int h, int w, int crop_border, void* stream) {
+    if (!io_args_ok(a, a_format, b, b_format, color, partials, frames, c, h, w, crop_border) || !workspace) return PNP_ERR_BAD_ARG;
+    MsArgs s;
+    MsClass& k = s.cl[0];
+    k.plan = pnp_ms_plan(h, w, crop_border);
+    if (!k.plan.ok) return PNP_ERR_BAD_ARG;
+    k.a = k.b = MsSrc{};
+    k.a.fs = frame_src(a, a_format, frames, h, w);
+    k.b.fs = frame_src(b, b_format, frames, h, w);
+    k.H = h, k.W = w, k.crop = crop_border;
+    const int planes = color == PNP_COLOR_Y ? 1 : c;
+    s.nclass = 1;
+    s.slot = k.plan.ws_floats;
+    s.partial = partials;
+    s.L = 255.0;
+    ssim_window(s.g);
+    place_classes(s, static_cast<float*>(workspace), (long)frames * planes);
+    if (color == PNP_COLOR_Y) return launch_all<K_Y>(s, frames, (hipStream_t)stream);
+    return launch_all<K_RGB>(s, frames * planes, (hipStream_t)stream);
+}
+
+extern "C" int pnp_msssim_partials_yuv420(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, int plane_mask, double* partials,
+                                          void* workspace, int frames, int h, int w, int crop_border, void* stream) {
+    if (!planes_args_ok(a, b, partials, frames, h, w, crop_border) || !workspace || plane_mask < 1 || plane_mask > 7) return PNP_ERR_BAD_ARG;
+    MsArgs s;
+    s.nclass = 0;
+    const ChromaSrc ac = chroma_src(*a, h, w), bc = chroma_src(*b, h, w);
+    for (int bit = 1; bit < 8; bit <<= 1) {
+        if (!(plane_mask & bit)) continue;
+        MsClass& k = s.cl[s.nclass++];
+        k.plan = plane_plan(h, w, crop_border, bit);
+        if (!k.plan.ok) return PNP_ERR_BAD_ARG;                                     // a cropped plane of the mask below 176
+        k.a = k.b = MsSrc{};
+        if (bit == PNP_PLANE_Y) {
+            k.a.p8 = luma_src(*a, h, w);
+            k.b.p8 = luma_src(*b, h, w);
+            k.H = h, k.W = w, k.crop = crop_border;
+        } else {
+            const int cr = bit == PNP_PLANE_CR;
+            k.a.p8 = ac.c[cr];
+            k.b.p8 = bc.c[cr];
+            k.a.sel = ac.paired && cr != ac.cr_first;                                // the plane one byte behind the pair's first
+            k.b.sel = bc.paired && cr != bc.cr_first;
+            k.H = h / 2, k.W = w / 2, k.crop = crop_border / 2;
+        }
+    }
+    s.slot = pnp_ms_plan(h, w, crop_border).ws_floats;
+    s.partial = partials;
+    s.L = 255.0;
+    ssim_window(s.g);
+    place_classes(s, static_cast<float*>(workspace), frames);
+    return launch_all<K_P8>(s, frames, (hipStream_t)stream);
+}
+
+extern "C" int pnp_msssim_partials_yuv420p16(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, int plane_mask, double* partials,
+                                             void* workspace, int frames, int h, int w, int crop_border, void* stream) {
+    if (!planes16_args_ok(a, b, partials, frames, h, w, crop_border) || !workspace || plane_mask < 1 || plane_mask > 7) return PNP_ERR_BAD_ARG;
+    MsArgs s;
+    s.nclass = 0;
+    for (int p = 0; p < 3; ++p) {
+        const int bit = 1 << p;
+        if (!(plane_mask & bit)) continue;
+        MsClass& k = s.cl[s.nclass++];
+        k.plan = plane_plan(h, w, crop_border, bit);
+        if (!k.plan.ok) return PNP_ERR_BAD_ARG;                                     // a cropped plane of the mask below 176
+        k.a = k.b = MsSrc{};
+        k.a.p16 = plane16(*a, p);
+        k.b.p16 = plane16(*b, p);
+        if (p == 0) k.H = h, k.W = w, k.crop = crop_border;
+        else k.H = h / 2, k.W = w / 2, k.crop = crop_border / 2;
+    }
+    s.slot = pnp_ms_plan(h, w, crop_border).ws_floats;
+    s.partial = partials;
+    s.L = (double)((1 << a->bit_depth) - 1);
+    ssim_window(s.g);
+    place_classes(s, static_cast<float*>(workspace), frames);
+    return launch_all<K_P16>(s, frames, (hipStream_t)stream);
+}

@@ -2,38 +2,9 @@
 // metrics.hip read from the decoder's planes where they lie -- NV12 / NV21 / I420, any address and pitch, each of the two clips
 // described on its own -- 1.5 B per pixel and clip, no RGB and no fp32 copy in between.  What a codec-enhancement result is scored by:
 // Y, Cb and Cr on their own (and the 6:1:1 mean the host forms).  plane_load.h fetches; the statistics are metrics.hip's.
-#include "plane_load.h"
-#include "prep.h"
-#include "yuv.h"
-#include "yuv16.h"
-#include <cmath>
+#include "metric_src.h"
 
 namespace {
-
-// The chroma of one clip: paired (NV12 / NV21: one load gives both planes; c[0] is the pair at the lower address and cr_first says
-// which plane that is) or two planes of their own (I420; c[0] = Cb, c[1] = Cr).
-struct ChromaSrc {
-    PnpPlaneSrc c[2];
-    int paired, cr_first;
-};
-
-PnpPlaneSrc luma_src(const pnp_yuv420_planes& p, int h, int w) { return PnpPlaneSrc{p.y, p.y_pitch, p.y_frame, 1, h, w}; }
-
-ChromaSrc chroma_src(const pnp_yuv420_planes& p, int h, int w) {
-    ChromaSrc s;
-    const int rows = h / 2, cols = w / 2;
-    const uintptr_t cb = reinterpret_cast<uintptr_t>(p.cb), cr = reinterpret_cast<uintptr_t>(p.cr);
-    s.paired = p.c_step == 2 && (cb > cr ? cb - cr : cr - cb) == 1;
-    s.cr_first = cr < cb;
-    if (s.paired) {
-        s.c[0] = s.c[1] = PnpPlaneSrc{s.cr_first ? p.cr : p.cb, p.c_pitch, p.c_frame, 2, rows, 2 * cols};
-    } else {
-        const int rowbytes = p.c_step * (cols - 1) + 1;
-        s.c[0] = PnpPlaneSrc{p.cb, p.c_pitch, p.c_frame, p.c_step, rows, rowbytes};
-        s.c[1] = PnpPlaneSrc{p.cr, p.c_pitch, p.c_frame, p.c_step, rows, rowbytes};
-    }
-    return s;
-}
 
 // sum over the four bytes of (x_j - y_j)^2; absent samples are 0 in both words
 __device__ __forceinline__ unsigned sq4(unsigned x, unsigned y) {
@@ -117,24 +88,6 @@ __global__ __launch_bounds__(256) void psnr_yuv420_kernel(const PsnrYuvArgs s) {
 // ssim_kernel (metrics.hip) with the plane loader in front: tiling, LDS layout and both passes are ssim_kernel's, statement for
 // statement, so a plane gives the partials of its (frames,1,rows,cols) fp32 plane byte / 255.0f bit for bit (to_u8 of that value is
 // the byte).  One launch serves every plane of the mask: blocks [blk0, blk0 + blocks) of the grid's x are plane k's.
-// One plane of a 10 / 12-bit clip (pnp_yuv420_planes16): 2-byte loads, sample (row, col) of frame f is the word at
-// p + f * frame + row * pitch (bytes) + col * step (samples), read as (word >> shift) & mask.
-struct Plane16 {
-    const unsigned short* p;
-    long pitch, frame;
-    int step;
-    unsigned shift, mask;
-};
-__device__ __forceinline__ unsigned load16(const Plane16& s, long f, int row, int col) {
-    const unsigned short* q = reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(s.p) + f * s.frame + (long)row * s.pitch);
-    return ((unsigned)q[(long)col * s.step] >> s.shift) & s.mask;
-}
-Plane16 plane16(const pnp_yuv420_planes16& p, int plane) {      // plane: 0 Y | 1 Cb | 2 Cr
-    const unsigned shift = p.msb_aligned ? 16u - (unsigned)p.bit_depth : 0u, mask = (1u << p.bit_depth) - 1u;
-    if (plane == 0) return Plane16{p.y, p.y_pitch, p.y_frame, 1, shift, mask};
-    return Plane16{plane == 1 ? p.cb : p.cr, p.c_pitch, p.c_frame, p.c_step, shift, mask};
-}
-
 struct SsimPlane {
     PnpPlaneSrc a, b;
     Plane16 a16, b16;       // the 16-bit sample path's planes (ssim_yuv420_kernel<true>)
@@ -230,28 +183,6 @@ __global__ __launch_bounds__(256) void ssim_yuv420_kernel(const SsimYuvArgs s) {
     if ((t & 63) == 0) red[t >> 6] = acc;
     __syncthreads();
     if (t == 0) s.partial[p.out0 + frame * p.blocks + blk] = red[0] + red[1] + red[2] + red[3];
-}
-
-// what both entries refuse before they look at their statistic
-bool planes_args_ok(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, const void* out, int frames, int h, int w, int crop) {
-    if (!a || !b || !out || frames < 1 || h < 2 || w < 2 || (h & 1) || (w & 1)) return false;
-    if (crop < 0 || (crop & 1) || 2 * crop >= h || 2 * crop >= w) return false;
-    return yuv_planes_ok(*a, w) && yuv_planes_ok(*b, w);
-}
-
-bool planes16_args_ok(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, const void* out, int frames, int h, int w, int crop) {
-    if (!a || !b || !out || frames < 1 || h < 2 || w < 2 || (h & 1) || (w & 1)) return false;
-    if (crop < 0 || (crop & 1) || 2 * crop >= h || 2 * crop >= w) return false;
-    return yuv16_planes_ok(*a, w) && yuv16_planes_ok(*b, w) && a->bit_depth == b->bit_depth;
-}
-
-void ssim_window(double* g) {                            // cv2.getGaussianKernel(11, 1.5)
-    double sum = 0;
-    for (int i = 0; i < 11; ++i) {
-        g[i] = exp(-((i - 5.0) * (i - 5.0)) / (2 * 1.5 * 1.5));
-        sum += g[i];
-    }
-    for (int i = 0; i < 11; ++i) g[i] /= sum;
 }
 
 // The exact integer SSE of the three planes of two 16-bit clips in one launch: psnr_yuv420_kernel's walk (a wave a row, first the Y

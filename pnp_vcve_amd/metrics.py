@@ -114,4 +114,69 @@ def ssim(img1, img2, crop_border=0, input_order='HWC', convert_to=None):
     return float(np.mean([_ssim_channel(img1[..., i], img2[..., i]) for i in range(img1.shape[2])]))
 
 
-ALLOWED_METRICS = {'PSNR': psnr, 'SSIM': ssim}
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # Wang, Simoncelli, Bovik 2003, as published (sum 1.0001)
+MSSSIM_MIN_SIZE = 176                                            # level 4 must hold one 11 x 11 window: 11 << 4
+
+
+def _msssim_down(x):
+    """the next level of the pyramid: 2 x 2 means formed in float64 and stored as float32, an odd last row / column dropped"""
+    h, w = x.shape[0] // 2, x.shape[1] // 2
+    x = x[:2 * h, :2 * w].astype(np.float64)
+    return (((x[0::2, 0::2] + x[0::2, 1::2]) + (x[1::2, 0::2] + x[1::2, 1::2])) * 0.25).astype(np.float32)
+
+
+def msssim_plane_scales(a, b, peak=255.0):
+    """(5, 2) float64: the raw (CS_s, S_s) of one plane pair -- the means over the valid map of cs and of l * cs at the five levels"""
+    C1, C2 = (0.01 * peak) ** 2, (0.03 * peak) ** 2
+    g = np.exp(-((np.arange(11) - 5.0) ** 2) / (2 * 1.5 ** 2))
+    g /= g.sum()
+    a, b = a.astype(np.float32), b.astype(np.float32)
+    out = np.zeros((5, 2), np.float64)
+    for s in range(5):
+        if s:
+            a, b = _msssim_down(a), _msssim_down(b)
+        x, y = a.astype(np.float64), b.astype(np.float64)
+        mu1, mu2 = _gauss_valid(x, g), _gauss_valid(y, g)
+        s1 = _gauss_valid(x * x, g) - mu1 ** 2
+        s2 = _gauss_valid(y * y, g) - mu2 ** 2
+        s12 = _gauss_valid(x * y, g) - mu1 * mu2
+        cs = (2 * s12 + C2) / (s1 + s2 + C2)
+        lum = (2 * mu1 * mu2 + C1) / (mu1 ** 2 + mu2 ** 2 + C1)
+        out[s] = cs.mean(), (lum * cs).mean()
+    return out
+
+
+def msssim_from_scales(scales):
+    """(..., 5, 2) raw (CS_s, S_s) -> (...) MS-SSIM = prod_{s<4} max(CS_s, 0)^w_s * max(S_4, 0)^w_4 in float64"""
+    scales = np.asarray(scales, np.float64)
+    w = np.array(MSSSIM_WEIGHTS, np.float64)
+    f = np.concatenate([scales[..., :4, 0], scales[..., 4:, 1]], axis=-1)
+    return np.prod(np.maximum(f, 0.0) ** w, axis=-1)
+
+
+def msssim(img1, img2, crop_border=0, input_order='HWC', convert_to=None):
+    """Multi-scale SSIM (Wang, Simoncelli, Bovik 2003; five scales) of two uint8 BGR images, the definition of include/pnpvcve.h
+    (pnp_msssim_*).  It is this project's own: the reference has no MS-SSIM and neither cv2 nor an HM / VTM / libvmaf build is available
+    here, so parity with a particular external tool is unpinned; it is checked against the independent scipy restatement
+    tests/msssim_ref.py.  Every level uses ssim()'s window; level s+1 is the 2 x 2 mean of level s.  convert_to='y': one plane, the
+    float32 Y of ssim().  Several channels give the mean of the channels' values, with or without a crop (ssim()'s crop quirk is the
+    reference's and is not carried over).  The cropped image must be at least 176 x 176."""
+    assert img1.shape == img2.shape, f'Image shapes are different: {img1.shape}, {img2.shape}.'
+    if input_order == 'CHW':
+        img1, img2 = img1.transpose(1, 2, 0), img2.transpose(1, 2, 0)
+    if _is_y(convert_to, ''):
+        img1, img2 = img1.astype(np.float32), img2.astype(np.float32)
+        img1, img2 = bgr2y(img1 / 255.) * 255., bgr2y(img2 / 255.) * 255.
+    if img1.ndim == 2:
+        img1, img2 = img1[..., None], img2[..., None]
+    if crop_border != 0:
+        img1 = img1[crop_border:-crop_border, crop_border:-crop_border]
+        img2 = img2[crop_border:-crop_border, crop_border:-crop_border]
+    if min(img1.shape[:2]) < MSSSIM_MIN_SIZE:
+        raise ValueError(f'MS-SSIM needs {MSSSIM_MIN_SIZE} x {MSSSIM_MIN_SIZE} samples after the crop (level 4 must hold one 11 x 11 '
+                         f'window), got {img1.shape[0]} x {img1.shape[1]}')
+    scales = np.stack([msssim_plane_scales(img1[..., i], img2[..., i]) for i in range(img1.shape[2])])
+    return float(np.mean(msssim_from_scales(scales)))
+
+
+ALLOWED_METRICS = {'PSNR': psnr, 'SSIM': ssim, 'MS-SSIM': msssim}

@@ -638,6 +638,77 @@ def ssim_frames(a, b, crop_border=0, convert_to=None):
     return per_plane.mean(dim=1).cpu().reshape(lead)
 
 
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # Wang, Simoncelli, Bovik 2003, as published (sum 1.0001)
+
+
+def _msssim_plan(h, w, crop):
+    """one plane of h x w samples cropped by `crop` -> (blocks per level, valid-map sizes per level), or None when it cannot be
+    scored (pnp_msssim_blocks / pnp_msssim_level_dims: a cropped plane below 176 x 176)"""
+    L = _native.lib()
+    blocks = [int(L.pnp_msssim_blocks(h, w, crop, s)) for s in range(5)]
+    if min(blocks) < 1:
+        return None
+    sizes = []
+    for s in range(5):
+        r, c = ctypes.c_int(0), ctypes.c_int(0)
+        _native.check(L.pnp_msssim_level_dims(h, w, crop, s, ctypes.byref(r), ctypes.byref(c)), 'pnp_msssim_level_dims')
+        sizes.append((r.value - 10) * (c.value - 10))
+    return blocks, sizes
+
+
+def _msssim_scales(part, blocks, sizes):
+    """partials (units, sum(blocks), 2) of planes of one plan -> (units, 5, 2) float64 CPU: a level's partials added in index order,
+    divided by the level's valid-map size: the raw (CS_s, S_s)"""
+    import numpy as np
+    p = part.cpu().numpy()
+    out = np.empty((p.shape[0], 5, 2), np.float64)
+    off = 0
+    for s in range(5):
+        out[:, s] = p[:, off:off + blocks[s]].cumsum(axis=1)[:, -1] / sizes[s]
+        off += blocks[s]
+    return torch.from_numpy(out)
+
+
+def _msssim_value(scales):
+    """(..., 5, 2) raw (CS_s, S_s) -> (...): prod_{s<4} max(CS_s, 0)^w_s * max(S_4, 0)^w_4 in float64"""
+    f = torch.cat([scales[..., :4, 0], scales[..., 4:, 1]], dim=-1).clamp(min=0.0)
+    return (f ** torch.tensor(MSSSIM_WEIGHTS, dtype=torch.float64)).prod(dim=-1)
+
+
+def _msssim_too_small(what):
+    n = int(_native.lib().pnp_msssim_min_size())
+    return ValueError(f'MS-SSIM needs {n} x {n} samples of {what} after the crop: level 4 of the pyramid must hold one 11 x 11 window')
+
+
+@_on_device_of_first_tensor
+def msssim_frames(a, b, crop_border=0, convert_to=None, scales=False):
+    """Per-frame multi-scale SSIM (include/pnpvcve.h, pnp_msssim_partials_io: five scales, ssim_frames' window at each, 2 x 2 mean
+    pyramid), computed on the GPU in fp64.  Inputs as ssim_frames: a, b, each on its own, fp32 (..., c, h, w) planes or uint8
+    (..., h, w, 3) RGB frames; convert_to None (the mean over the channels' values, with or without a crop) | 'y' / 'Y' (one plane,
+    the fp32 Y).  Returns a float64 CPU tensor of the leading shape; with scales=True also the raw, unclamped per-level means, a
+    float64 CPU tensor lead + (planes, 5, 2) = (CS_s, S_s).  The cropped frames must be at least 176 x 176."""
+    a, fa, b, fb, color, lead, frames, c, h, w = _metric_pair(a, b, convert_to)
+    crop_border = int(crop_border)
+    if crop_border < 0 or 2 * crop_border >= h or 2 * crop_border >= w:
+        raise ValueError(f'a crop of {crop_border} leaves nothing of {h} x {w} frames')
+    plan = _msssim_plan(h, w, crop_border)
+    if plan is None:
+        raise _msssim_too_small('every frame')
+    blocks, sizes = plan
+    L = _native.lib()
+    planes = 1 if color == _native.COLOR_Y else c
+    if not frames:
+        res, sc = torch.empty(lead, dtype=torch.float64), torch.empty(lead + (planes, 5, 2), dtype=torch.float64)
+        return (res, sc) if scales else res
+    part = torch.empty((frames * planes, sum(blocks), 2), dtype=torch.float64, device=a.device)
+    ws = torch.empty(int(L.pnp_msssim_workspace_bytes(frames, planes, h, w, crop_border)) // 4, dtype=torch.float32, device=a.device)
+    _native.check(L.pnp_msssim_partials_io(_ptr(a), fa, _ptr(b), fb, color, _ptr(part), _ptr(ws), frames, c, h, w, crop_border, _stream()),
+                  'pnp_msssim_partials_io')
+    sc = _msssim_scales(part, blocks, sizes).reshape(frames, planes, 5, 2)
+    res = _msssim_value(sc).mean(dim=1).reshape(lead)
+    return (res, sc.reshape(lead + (planes, 5, 2))) if scales else res
+
+
 @_on_device_of_first_tensor
 def bae_block(x, w2_packed, b2, gamma, w1x1_packed, par, w1_packed, b1):
     """One BAE block (ResidualBlockNoBNDynamic_drt.forward, sr_backbone_utils.py:305-313,329), pnp_bae_block_f32.
@@ -942,6 +1013,47 @@ def ssim_yuv420(a, b, crop_border=0, planes='y'):
                 res[i, :, planes.index(p)] = (part[off:off + t * nb[p]].reshape(t, nb[p]).sum(dim=1) / n).cpu()
                 off += t * nb[p]
     return res.reshape(lead + (len(planes),))
+
+
+def msssim_yuv420(a, b, crop_border=0, planes='y', scales=False):
+    """Per-frame plane MS-SSIM of two 4:2:0 clips (pnp_msssim_partials_yuv420 / _yuv420p16: msssim_frames' definition on the samples of
+    a plane, peak 255 or 2^d - 1).  a, b, planes and the crop as ssim_yuv420: two Yuv420Frames, or two Yuv420Frames16 of one depth,
+    each in a layout of its own; returns a float64 CPU tensor lead + (len(planes),) in the order of `planes`, with scales=True also the
+    raw per-level means lead + (len(planes), 5, 2) = (CS_s, S_s).  Every cropped plane asked for must be at least 176 x 176: chroma
+    planes need 352-line frames."""
+    if not isinstance(planes, str) or not planes or len(set(planes.lower())) != len(planes) or any(p not in _PLANE_BITS for p in planes.lower()):
+        raise ValueError(f"planes must name each of 'y', 'u', 'v' at most once, got {planes!r}")
+    planes = planes.lower()
+    pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border)
+    L = _native.lib()
+    mask = sum(_PLANE_BITS[p] for p in planes)
+    order = [p for p in 'yuv' if p in planes]                      # the order the library writes
+    plans = {}
+    for p in order:
+        plans[p] = _msssim_plan(h, w, crop) if p == 'y' else _msssim_plan(h // 2, w // 2, crop // 2)
+        if plans[p] is None:
+            raise _msssim_too_small(f'plane {p!r}')
+    dev = a.y.device
+    res = torch.empty((len(pairs), t, len(planes)), dtype=torch.float64)
+    sc = torch.empty((len(pairs), t, len(planes), 5, 2), dtype=torch.float64)
+    entry = 'pnp_msssim_partials_yuv420p16' if isinstance(a, Yuv420Frames16) else 'pnp_msssim_partials_yuv420'
+    with torch.cuda.device(dev):
+        for i, (da, db) in enumerate(pairs):
+            if not t:
+                continue
+            part = torch.empty(t * sum(sum(plans[p][0]) for p in order) * 2, dtype=torch.float64, device=dev)
+            ws = torch.empty(int(L.pnp_msssim_workspace_bytes(t, len(order), h, w, crop)) // 4, dtype=torch.float32, device=dev)
+            _native.check(getattr(L, entry)(ctypes.byref(da), ctypes.byref(db), mask, _ptr(part), _ptr(ws), t, h, w, crop, _stream()), entry)
+            off = 0
+            for p in order:
+                blocks, sizes = plans[p]
+                n = t * sum(blocks) * 2
+                s = _msssim_scales(part[off:off + n].reshape(t, sum(blocks), 2), blocks, sizes)
+                sc[i, :, planes.index(p)] = s
+                res[i, :, planes.index(p)] = _msssim_value(s)
+                off += n
+    res = res.reshape(lead + (len(planes),))
+    return (res, sc.reshape(lead + (len(planes), 5, 2))) if scales else res
 
 
 # ---------------------------------------------------------------- 10 / 12-bit 4:2:0 frames (include/pnpvcve.h: pnp_yuv420_planes16)

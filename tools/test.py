@@ -49,13 +49,14 @@ def parse_args():
                         '(fp32 planes only for the metrics); a pair of clips goes in by pointer instead of concatenated.  Same '
                         'metrics and PNG bytes; default off')
     p.add_argument('--byte-metrics', action='store_true',
-                   help='implies --byte-frames; PSNR / SSIM read bytes too: the ground truth stays uint8 on the device and the generator '
+                   help='implies --byte-frames; PSNR / SSIM / MS-SSIM read bytes too: the ground truth stays uint8 on the device and the generator '
                         'writes display bytes only, with or without --save-path (6 B per pixel into the metrics instead of 24).  Same '
                         'metrics; default off')
     p.add_argument('--yuv-frames', action='store_true',
                    help='raw 4:2:0 evaluation (a Yuv420ClipFolderDataset of .yuv clips): the generator reads the planes and writes packed '
                         '4:2:0 only, the ground truth stays 8-bit planes on the device, PSNR / SSIM are the Y plane\'s (PSNR_U, PSNR_V, '
-                        'SSIM_U, SSIM_V and the 6:1:1 PSNR_YUV may be listed in test_cfg.metrics too) and --save-path gets one <clip>.yuv '
+                        'SSIM_U, SSIM_V, the 6:1:1 PSNR_YUV and MS-SSIM, MS-SSIM_U, MS-SSIM_V -- five scales, planes of 176 x 176 or more -- '
+                        'may be listed in test_cfg.metrics too) and --save-path gets one <clip>.yuv '
                         'per clip; a dataset with bit_depth=10 | 12 (16-bit little-endian .yuv files) goes the same way at its depth; '
                         'default off')
     p.add_argument('--yuv-out-layout', choices=['i420', 'nv12', 'p010', 'p012', 'yuv420p10le', 'yuv420p12le'], default='i420',
@@ -137,7 +138,10 @@ def main():
         stats = dataset.evaluate(outputs)
         for k, v in stats.items():
             print(f'Eval-{k}: {v}')
-        print('{:.4f}/{:.4f}'.format(float(stats.get('PSNR', float('nan'))), float(stats.get('SSIM', float('nan')))))
+        line = '{:.4f}/{:.4f}'.format(float(stats.get('PSNR', float('nan'))), float(stats.get('SSIM', float('nan'))))
+        if 'MS-SSIM' in (cfg.test_cfg.get('metrics', None) or ()):      # a third field only when the config lists it
+            line += '/{:.4f}'.format(float(stats.get('MS-SSIM', float('nan'))))
+        print(line)
         fps = [o['frames_per_s'] for o in outputs]
         import torch.distributed as dist
         backend = dist.get_backend() if dist.is_available() and dist.is_initialized() else 'none'
