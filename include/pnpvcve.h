@@ -606,6 +606,56 @@ int pnp_msssim_partials_yuv420(const pnp_yuv420_planes* a_host_desc, const pnp_y
 int pnp_msssim_partials_yuv420p16(const pnp_yuv420_planes16* a_host_desc, const pnp_yuv420_planes16* b_host_desc, int plane_mask,
                                   double* partials_dev, void* workspace_dev, int frames, int h, int w, int crop_border, void* stream);
 
+/* XPSNR (xpsnr.hip): a PSNR whose squared error is weighted block by block with the inverse of the ORIGINAL's spatio-temporal activity
+ * (Helmrich et al., ICASSP 2020; ITU-T HSTP-VID-WPOM), of 4:2:0 planes at 8, 10 or 12 bit.  No ffmpeg, VTM or vvenc build was at hand
+ * to compare digits with, so agreement with a particular external tool is UNPINNED; the definition follows the published scheme as
+ * closely as it could be stated without one, and a deviation found later against a real tool is a bug in THIS statement, the one
+ * statement of it.  It is pinned by two independent numpy restatements (pnp_vcve_amd/metrics.py::xpsnr, tests/xpsnr_ref.py).
+ *   Inputs: the original clip o (b: the ground truth, whose activity sets the weights) and the test clip r (a), 4:2:0 planes of one bit
+ *   depth d in {8, 10, 12}, T frames, luma h x w (even); an integer fps >= 1.  The crop (even; half of it on chroma) is applied first:
+ *   H, W and the block grid below refer to the cropped planes and no sample outside the crop is used (16-bit samples are fetched one
+ *   by one; bytes as the aligned dwords that cover a group of four where those lie inside the plane's rows -- the reading rule of
+ *   the other plane metrics).  Samples are the integers the other plane metrics read (the byte; the word's value as
+ *   pnp_yuv420_planes16 is read).  P = 2^d - 1.
+ *   Block grid: N = max(4, 4 * floor(32 * sqrt(W H / (3840 * 2160)) + 0.5)) -- 44 at 1280 x 720, 64 at 1920 x 1080, 128 at 3840 x 2160, 4
+ *   on small frames (the library decides the rounding in integers: the largest k with (2k - 1)^2 * 3840 * 2160 <= 4096 W H).  Luma
+ *   blocks k are the ceil(H / N) x ceil(W / N) tiles [y0, y1) x [x0, x1), clipped at the plane's edge, in row-major order; the chroma
+ *   block of k is [y0/2, y1/2) x [x0/2, x1/2) of the chroma plane (all bounds are even).
+ *   Activity region of block k (luma of o, frame t): border b = 2 if W H > 2048 * 1152, else 1.  R_k is rows [y0 > 0 ? y0 : b,
+ *   y1 < H ? y1 : H - b) and columns likewise: the filters read across block edges, never across the picture's edge.  area_k = rows *
+ *   columns of R_k; if R_k is empty, sa = ta = 0 and the activity is the floor.
+ *   Spatial activity, b = 1: sa_k = sum over (y, x) in R_k of |12 o[y][x] - 2 (o[y][x-1] + o[y][x+1] + o[y-1][x] + o[y+1][x]) - (the four
+ *   diagonal neighbours)|.  b = 2: the positions are every second row and column of R_k starting at its first; at each, |sum of
+ *   K6 * o[y-2 .. y+3][x-2 .. x+3]| with the zero-sum kernel K6, rows -2 .. +3:
+ *        0 -1 -1 -1 -1  0 / -1 -2 -3 -3 -2 -1 / -1 -3 12 12 -3 -1 / -1 -3 12 12 -3 -1 / -1 -2 -3 -3 -2 -1 / 0 -1 -1 -1 -1  0
+ *   (reads stay inside the plane for every block: positions are even and below H - 2, W - 2).
+ *   Temporal activity, same positions: s_t is the sample (b = 1) or the sum of the 2 x 2 samples at the position (b = 2).  Second order
+ *   when fps >= 32 and t >= 2: ta_k = sum |s_t - 2 s_{t-1} + s_{t-2}|, factor f = 1.  First order otherwise (fps < 32, or t = 1): ta_k =
+ *   sum |s_t - s_{t-1}|, f = 2.  At t = 0: ta_k = 0.
+ *   Weights (host, fp64): act_k = max((sa_k + f ta_k) / area_k, 2^(d-6)); a_k = act_k^2; minimum smoothing a^_k = max(a_k, min of a_j over
+ *   the existing 8 neighbour blocks) (a block with no neighbour keeps a_k); A = sqrt(16 * 2^(2d-9) * sqrt(3840 * 2160 / (W H)));
+ *   w_k = A / sqrt(a^_k).
+ *   Error: sse_{p,k}, the exact integer squared error of plane p in {Y, U, V} over block k (chroma: over its chroma block).
+ *   Value: wsse_p(t) = sum_k w_k sse_{p,k}, added in block index order.  Per frame XPSNR_p(t) = 10 log10(P^2 H_p W_p / wsse_p(t)); per
+ *   clip -- the metric's own convention, the log of the mean, not the mean of the logs -- XPSNR_p = 10 log10(P^2 H_p W_p T / sum_t
+ *   wsse_p(t)); +inf when the sum is 0.
+ * The device part is integers only.  pnp_xpsnr_block_size: N of h x w frames cropped by crop_border (0 when they cannot be scored);
+ * pnp_xpsnr_grid: the rows and columns of the block grid (host only, xpsnr_plan.h).  pnp_xpsnr_sums_yuv420 / _yuv420p16: a is the test
+ * clip, b the original, each described on its own (any pitch and address, interleaved or planar chroma, low- or high-aligned words);
+ * sums_dev [frames][rows * cols][5] uint64 = sse_y, sse_u, sse_v, sa, ta of every frame and block, all of it written by ONE launch,
+ * without atomics, the same bits on every run.  plane_mask (PNP_PLANE_*) selects the planes whose error is formed -- only they are read,
+ * the others' sums are 0 -- and the Y plane of b, the activity's source, is read whatever the mask.  sa and ta are the raw sums: f is
+ * applied by the host.
+ * PNP_ERR_BAD_ARG, decided on the host before any HIP call: NULL descriptors, planes (b's Y among them) or sums, frames < 1, odd or
+ * too small frames, odd, negative or too large crops, bad descriptors, differing depths (as pnp_ssim_partials_yuv420 / _yuv420p16), a
+ * mask outside 1..7, fps < 1. */
+int pnp_xpsnr_block_size(int h, int w, int crop_border);
+int pnp_xpsnr_grid(int h, int w, int crop_border, int* rows, int* cols);
+int pnp_xpsnr_sums_yuv420(const pnp_yuv420_planes* a_host_desc, const pnp_yuv420_planes* b_host_desc, int plane_mask,
+                          unsigned long long* sums_dev, int frames, int h, int w, int crop_border, int fps, void* stream);
+int pnp_xpsnr_sums_yuv420p16(const pnp_yuv420_planes16* a_host_desc, const pnp_yuv420_planes16* b_host_desc, int plane_mask,
+                             unsigned long long* sums_dev, int frames, int h, int w, int crop_border, int fps, void* stream);
+
 /* Modulated deformable 3x3 conv, 64 -> 64 channels, deform_groups 16 (mmcv.ops.modulated_deform_conv2d as
  * called at mmedit/models/backbones/sr_backbones/iconvsr_mv.py:38-41,81-84; semantics restated, mmcv is not
  * vendored).  x_dev (h,w,64) pixel-major; om_dev (h,w,448): conv_offset[2] output (pre-sigmoid masks) in the

@@ -147,6 +147,12 @@ SIGNATURES = {
                                            c_int, c_void_p]),
     'pnp_msssim_partials_yuv420p16': (c_int, [POINTER(Yuv420Planes16), POINTER(Yuv420Planes16), c_int, c_void_p, c_void_p, c_int, c_int,
                                               c_int, c_int, c_void_p]),
+    'pnp_xpsnr_block_size': (c_int, [c_int, c_int, c_int]),
+    'pnp_xpsnr_grid': (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    'pnp_xpsnr_sums_yuv420': (c_int, [POINTER(Yuv420Planes), POINTER(Yuv420Planes), c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                      c_void_p]),
+    'pnp_xpsnr_sums_yuv420p16': (c_int, [POINTER(Yuv420Planes16), POINTER(Yuv420Planes16), c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                         c_int, c_void_p]),
     'pnp_conv3x3_f32': (c_int, [c_int, POINTER(c_void_p), POINTER(c_int), POINTER(c_void_p), c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     'pnp_bae_block_f32': (c_int, [c_void_p] * 10 + [c_int, c_int, c_void_p]),

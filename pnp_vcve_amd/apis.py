@@ -164,7 +164,7 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
     yuv_frames (default off; a dataset of raw 4:2:0 clips, Yuv420ClipFolderDataset): the generator reads the decoder's planes and is
     asked for packed 4:2:0 in `yuv_out_layout` ('i420' | 'nv12') ONLY, the ground truth stays 8-bit planes on the device, the metrics
     are the plane metrics of BasicVSR.evaluate (ops.psnr_yuv420 / ssim_yuv420: 'PSNR' / 'SSIM' score the Y plane; 'PSNR_U', 'PSNR_V',
-    'SSIM_U', 'SSIM_V', 'PSNR_YUV' are accepted too), and save_image writes <save_path>/<clip>.yuv -- exactly the bytes of
+    'SSIM_U', 'SSIM_V', 'PSNR_YUV', the 'MS-SSIM' and the 'XPSNR' names are accepted too), and save_image writes <save_path>/<clip>.yuv -- exactly the bytes of
     ops.frames_to_yuv420(fp32 output, standard, layout).  A pair goes through generator.forward_clips by pointer, as under byte_frames.
     A dataset of 10 / 12-bit clips (its samples' meta carry the depth) goes the same way as ops.Yuv420Frames16; yuv_out_layout then
     also takes 'p010' | 'p012' | 'yuv420p10le' | 'yuv420p12le', the ground truth and the output must agree in depth, and the file is

@@ -180,3 +180,156 @@ def msssim(img1, img2, crop_border=0, input_order='HWC', convert_to=None):
 
 
 ALLOWED_METRICS = {'PSNR': psnr, 'SSIM': ssim, 'MS-SSIM': msssim}
+
+
+# ---------------------------------------------------------------- XPSNR (include/pnpvcve.h, pnp_xpsnr_*: the one statement of the definition)
+# A plane metric of 4:2:0 clips: it is not in ALLOWED_METRICS (RGB / Y clips refuse the name as they refuse any unknown one).  The
+# functions below are the host path: integer sums from numpy planes (xpsnr_sums), and the fp64 part -- weights, weighted sums, decibels
+# -- which ops.xpsnr_yuv420 calls on the device's sums too (xpsnr_weights, xpsnr_values): that part exists once.
+XPSNR_K6 = ((0, -1, -1, -1, -1, 0), (-1, -2, -3, -3, -2, -1), (-1, -3, 12, 12, -3, -1),
+            (-1, -3, 12, 12, -3, -1), (-1, -2, -3, -3, -2, -1), (0, -1, -1, -1, -1, 0))
+
+
+def xpsnr_plan(h, w):
+    """(N, rows, cols, b) of a cropped h x w luma plane: the block size, the block grid and the border of the activity filters"""
+    n = max(4, 4 * int(np.floor(32.0 * np.sqrt(w * h / (3840.0 * 2160.0)) + 0.5)))
+    return n, -(-h // n), -(-w // n), (2 if w * h > 2048 * 1152 else 1)
+
+
+def xpsnr_regions(h, w):
+    """the activity regions of every block: (ry0, ry1) of the block rows and (rx0, rx1) of the block columns, int64 arrays"""
+    n, rows, cols, b = xpsnr_plan(h, w)
+
+    def axis(size, count):
+        lo = np.arange(count, dtype=np.int64) * n
+        hi = np.minimum(lo + n, size)
+        return np.where(lo > 0, lo, b), np.where(hi < size, hi, size - b)
+
+    return axis(h, rows), axis(w, cols)
+
+
+def xpsnr_areas(h, w):
+    """(rows, cols) int64: area_k, 0 for an empty region"""
+    (y0, y1), (x0, x1) = xpsnr_regions(h, w)
+    return np.maximum(y1 - y0, 0)[:, None] * np.maximum(x1 - x0, 0)[None, :]
+
+
+def _xpsnr_block_sums(x, n):
+    """(..., h, w) integers -> (..., rows, cols): the sums over the N x N tiles, the last ones clipped at the edge"""
+    h, w = x.shape[-2:]
+    return np.add.reduceat(np.add.reduceat(x, np.arange(0, h, n), axis=-2), np.arange(0, w, n), axis=-1)
+
+
+def xpsnr_sums(o, r, fps=30, planes='yuv'):
+    """The integer part on the host: o (the original) and r (the test clip) as (y, u, v) triples of (T, rows, cols) integer arrays of
+    sample values, already cropped -> (T, rows * cols, 5) int64 = sse_y, sse_u, sse_v, sa, ta of every frame and block, what
+    pnp_xpsnr_sums_yuv420 leaves.  Only the planes named in `planes` are compared, the others' sums are 0.  Vectorised: the filters
+    run over the whole picture's positions (the union of the regions is the picture without its border), the blocks add them up."""
+    oy = np.asarray(o[0]).astype(np.int64)
+    t, h, w = oy.shape
+    n, rows, cols, b = xpsnr_plan(h, w)
+    out = np.zeros((t, rows, cols, 5), np.int64)
+    for k, name in enumerate('yuv'):
+        if name in planes:
+            d = np.asarray(o[k]).astype(np.int64) - np.asarray(r[k]).astype(np.int64)
+            out[..., k] = _xpsnr_block_sums(d * d, n if k == 0 else n // 2)
+    sa, ta = np.zeros((t, h, w), np.int64), np.zeros((t, h, w), np.int64)
+    if h > 2 * b and w > 2 * b:
+        if b == 1:
+            c = oy[:, 1:-1, 1:-1]
+            e = 12 * c - 2 * (oy[:, 1:-1, :-2] + oy[:, 1:-1, 2:] + oy[:, :-2, 1:-1] + oy[:, 2:, 1:-1]) \
+                - (oy[:, :-2, :-2] + oy[:, :-2, 2:] + oy[:, 2:, :-2] + oy[:, 2:, 2:])
+            sa[:, 1:-1, 1:-1] = np.abs(e)
+            s, where = c, (slice(None), slice(1, -1), slice(1, -1))
+        else:       # positions: the even rows and columns of [2, h - 2) x [2, w - 2)
+            py, px = (h - 4) // 2, (w - 4) // 2
+            e = np.zeros((t, py, px), np.int64)
+            for q in range(6):
+                for c in range(6):
+                    if XPSNR_K6[q][c]:
+                        e += XPSNR_K6[q][c] * oy[:, q:q + 2 * py:2, c:c + 2 * px:2]
+            sa[:, 2:h - 2:2, 2:w - 2:2] = np.abs(e)
+            s = oy[:, 2:h - 2:2, 2:w - 2:2] + oy[:, 2:h - 2:2, 3:w - 1:2] + oy[:, 3:h - 1:2, 2:w - 2:2] + oy[:, 3:h - 1:2, 3:w - 1:2]
+            where = (slice(None), slice(2, h - 2, 2), slice(2, w - 2, 2))
+        d = np.zeros_like(s)
+        for i in range(1, t):
+            d[i] = s[i] - 2 * s[i - 1] + s[i - 2] if (fps >= 32 and i >= 2) else s[i] - s[i - 1]
+        ta[where] = np.abs(d)
+    out[..., 3] = _xpsnr_block_sums(sa, n)
+    out[..., 4] = _xpsnr_block_sums(ta, n)
+    return out.reshape(t, rows * cols, 5)
+
+
+def xpsnr_weights(sa, ta, area, t, fps, d, h, w):
+    """The weights w_k of frame t, fp64: sa, ta, area are (rows, cols) arrays of the frame's block sums and region areas, d the bit
+    depth, h x w the cropped luma plane.  act = max((sa + f ta) / area, 2^(d-6)) (the floor for an empty region), a = act^2, the
+    minimum smoothing over the existing 8 neighbours, w = A / sqrt(a^)."""
+    sa, ta, area = (np.asarray(x, np.float64) for x in (sa, ta, area))
+    f = 1.0 if (fps >= 32 and t >= 2) else 2.0
+    floor = 2.0 ** (d - 6)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        act = np.where(area > 0, (sa + f * ta) / area, floor)
+    a = np.maximum(act, floor) ** 2
+    rows, cols = a.shape
+    pad = np.full((rows + 2, cols + 2), np.inf)
+    pad[1:-1, 1:-1] = a
+    nb = np.full((rows, cols), np.inf)
+    for dy in range(3):
+        for dx in range(3):
+            if (dy, dx) != (1, 1):
+                nb = np.minimum(nb, pad[dy:dy + rows, dx:dx + cols])
+    smoothed = np.where(np.isfinite(nb), np.maximum(a, nb), a)      # (a block with no neighbour keeps a)
+    big_a = np.sqrt(16.0 * 2.0 ** (2 * d - 9) * np.sqrt(3840.0 * 2160.0 / (w * h)))
+    return big_a / np.sqrt(smoothed)
+
+
+def xpsnr_values(sums, d, fps, h, w, planes='yuv'):
+    """(T, rows * cols, 5) integer sums of a cropped h x w clip of depth d -> (wsse (T, len(planes)), per-frame dB (T, len(planes)), the
+    clip's dB (len(planes),)), fp64: wsse_p(t) = sum_k w_k sse_{p,k} added in block index order; XPSNR_p(t) = 10 log10(P^2 H_p W_p /
+    wsse_p(t)); the clip's value is the log of the mean, 10 log10(P^2 H_p W_p T / sum_t wsse_p(t)); +inf where the sum is 0."""
+    sums = np.asarray(sums)
+    n, rows, cols, _ = xpsnr_plan(h, w)
+    t = sums.shape[0]
+    assert sums.shape == (t, rows * cols, 5), (sums.shape, rows, cols)
+    area = xpsnr_areas(h, w)
+    wsse = np.zeros((t, len(planes)), np.float64)
+    for i in range(t):
+        g = sums[i].reshape(rows, cols, 5)
+        wk = xpsnr_weights(g[..., 3], g[..., 4], area, i, fps, d, h, w).reshape(-1)
+        for j, p in enumerate(planes):
+            terms = wk * sums[i, :, 'yuv'.index(p)].astype(np.float64)
+            wsse[i, j] = np.cumsum(terms)[-1]                       # sequential: block index order
+    peak2 = float((1 << d) - 1) ** 2
+    size = np.array([float(h * w) if p == 'y' else float((h // 2) * (w // 2)) for p in planes])
+    total = np.cumsum(wsse, axis=0)[-1]
+    with np.errstate(divide='ignore'):
+        frames = np.where(wsse > 0, 10.0 * np.log10(peak2 * size / wsse), np.inf)
+        clip = np.where(total > 0, 10.0 * np.log10(peak2 * size * t / total), np.inf)
+    return wsse, frames, clip
+
+
+def xpsnr(o, r, d, fps=30, crop_border=0):
+    """XPSNR of a test clip r against the original o on the host: (y, u, v) triples of (T, rows, cols) integer arrays of sample values
+    at bit depth d, the luma cropped by crop_border (even) and the chroma by half of it -> dict(sums (T, blocks, 5) int64, wsse and
+    frames (T, 3) fp64 -- the weighted squared error and the dB of every frame, columns Y, U, V --, clip (3,) fp64: the metric).  The
+    definition is include/pnpvcve.h's; what ops.xpsnr_yuv420 returns from the device's sums goes through the same xpsnr_values."""
+    if crop_border < 0 or crop_border % 2:
+        raise ValueError(f'crop_border must be even and >= 0 (the chroma planes are cropped by half of it), got {crop_border}')
+    if d not in (8, 10, 12) or int(fps) != fps or fps < 1:
+        raise ValueError(f'XPSNR takes a bit depth of 8, 10 or 12 and an integer fps >= 1, got {d} and {fps}')
+
+    def cut(planes):
+        out = []
+        for k, p in enumerate(planes):
+            c = crop_border if k == 0 else crop_border // 2
+            p = np.asarray(p)
+            out.append(p[:, c:p.shape[1] - c, c:p.shape[2] - c])
+        return out
+
+    o, r = cut(o), cut(r)
+    t, h, w = o[0].shape
+    if h < 2 or w < 2 or h % 2 or w % 2 or any(x.shape != (t, h // 2, w // 2) for x in o[1:]) or [x.shape for x in o] != [x.shape for x in r]:
+        raise ValueError(f'XPSNR compares two 4:2:0 clips of one even size, got {[x.shape for x in o]} and {[x.shape for x in r]}')
+    sums = xpsnr_sums(o, r, fps)
+    wsse, frames, clip = xpsnr_values(sums, d, fps, h, w)
+    return dict(sums=sums, wsse=wsse, frames=frames, clip=clip)

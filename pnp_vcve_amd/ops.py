@@ -1056,6 +1056,66 @@ def msssim_yuv420(a, b, crop_border=0, planes='y', scales=False):
     return (res, sc.reshape(lead + (len(planes), 5, 2))) if scales else res
 
 
+def _xpsnr_args(planes, fps):
+    if not isinstance(planes, str) or not planes or len(set(planes.lower())) != len(planes) or any(p not in _PLANE_BITS for p in planes.lower()):
+        raise ValueError(f"planes must name each of 'y', 'u', 'v' at most once, got {planes!r}")
+    if isinstance(fps, bool) or not isinstance(fps, int) or fps < 1:
+        raise ValueError(f'fps must be an integer >= 1 (it chooses the order of the temporal activity), got {fps!r}')
+    return planes.lower(), int(fps)
+
+
+def xpsnr_sums_yuv420(a, b, crop_border=0, planes='y', fps=30):
+    """The statistic behind xpsnr_yuv420 (pnp_xpsnr_sums_yuv420 / _yuv420p16; include/pnpvcve.h states the metric): a is the test clip, b
+    the ORIGINAL, two Yuv420Frames or two Yuv420Frames16 of one depth, (n,t,...) or (t,...), each in a layout of its own.  Returns an
+    int64 CPU tensor lead + (rows * cols, 5): per frame and block of the XPSNR grid of the cropped frame the exact sse_y, sse_u, sse_v
+    (0 for planes not named in `planes`) and the spatial and temporal activity sums sa, ta of b's luma.  Integer, the same bits every
+    run; a clip's frames are one call, since frame t reads the original's frames t - 1 and t - 2."""
+    planes, fps = _xpsnr_args(planes, fps)
+    pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border)
+    L = _native.lib()
+    rows, cols = ctypes.c_int(0), ctypes.c_int(0)
+    _native.check(L.pnp_xpsnr_grid(h, w, crop, ctypes.byref(rows), ctypes.byref(cols)), 'pnp_xpsnr_grid')
+    nblk = rows.value * cols.value
+    mask = sum(_PLANE_BITS[p] for p in planes)
+    entry = 'pnp_xpsnr_sums_yuv420p16' if isinstance(a, Yuv420Frames16) else 'pnp_xpsnr_sums_yuv420'
+    dev = a.y.device
+    with torch.cuda.device(dev):
+        sums = torch.empty((len(pairs), t, nblk, 5), dtype=torch.int64, device=dev)
+        for i, (da, db) in enumerate(pairs):
+            if t:
+                _native.check(getattr(L, entry)(ctypes.byref(da), ctypes.byref(db), mask, _ptr(sums[i]), t, h, w, crop, fps, _stream()), entry)
+    return sums.cpu().reshape(lead + (nblk, 5))
+
+
+def xpsnr_yuv420(a, b, crop_border=0, planes='y', fps=30, clip=False):
+    """XPSNR of two 4:2:0 clips (include/pnpvcve.h: a PSNR whose squared error is weighted block by block with the inverse of the
+    original's spatio-temporal activity).  a: the test clip, b: the ORIGINAL; two Yuv420Frames, or two Yuv420Frames16 of one depth,
+    each in a layout of its own; crop as psnr_yuv420; planes as ssim_yuv420; fps >= 1 (from 32 on the temporal activity is of second
+    order).  Returns (wsse, dB): float64 CPU tensors lead + (len(planes),), the weighted squared error and XPSNR of every frame, in the
+    order of `planes`; with clip=True also the clip's value lead[:-1] + (len(planes),), 10 log10 of the MEAN weighted error over the
+    frames (the metric's convention, not the mean of the frames' dB).  The integers are the device's (xpsnr_sums_yuv420); the fp64 part
+    is metrics.xpsnr_values, the host path's own."""
+    from . import metrics
+    planes, fps = _xpsnr_args(planes, fps)
+    sums = xpsnr_sums_yuv420(a, b, crop_border, planes, fps)
+    t = sums.shape[-3]
+    crop = int(crop_border)
+    h, w = a.y.shape[-2] - 2 * crop, a.y.shape[-1] - 2 * crop
+    d = a.bit_depth if isinstance(a, Yuv420Frames16) else 8
+    flat = sums.reshape((-1,) + tuple(sums.shape[-3:])).numpy()
+    if not t:
+        raise ValueError('XPSNR needs at least one frame')
+    vals = [metrics.xpsnr_values(s, d, fps, h, w, planes) for s in flat]
+    lead = tuple(sums.shape[:-2])
+
+    def gather(k, shape):
+        import numpy as np
+        return torch.from_numpy(np.ascontiguousarray(np.stack([v[k] for v in vals]), dtype=np.float64)).reshape(shape)
+
+    wsse, db = gather(0, lead + (len(planes),)), gather(1, lead + (len(planes),))
+    return (wsse, db, gather(2, lead[:-1] + (len(planes),))) if clip else (wsse, db)
+
+
 # ---------------------------------------------------------------- 10 / 12-bit 4:2:0 frames (include/pnpvcve.h: pnp_yuv420_planes16)
 _Yuv420Base16 = collections.namedtuple('Yuv420Frames16', ['y', 'cb', 'cr', 'bit_depth', 'msb_aligned'], defaults=(10, False))
 

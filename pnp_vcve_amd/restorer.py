@@ -109,9 +109,11 @@ class BasicVSR(nn.Module):
         each in a layout of its own -- the metrics are PLANE metrics read from the 8-bit planes on the device (ops.psnr_yuv420 /
         ssim_yuv420 / msssim_yuv420): 'PSNR' / 'SSIM' / 'MS-SSIM' score the Y plane, and in this mode only 'PSNR_U', 'PSNR_V', 'SSIM_U',
         'SSIM_V', 'MS-SSIM_U', 'MS-SSIM_V' and 'PSNR_YUV' = (6 PSNR_Y + PSNR_U + PSNR_V) / 8 per frame are accepted too; every value is
-        the mean over frames.  'MS-SSIM' (five scales; include/pnpvcve.h) is served on the device path of RGB / Y clips too and needs
-        176 x 176 samples of every plane it scores after the crop.  crop_border (even) crops
-        the Y plane, half of it the chroma planes.  test_cfg.convert_to may be None or 'y' and both mean the same here: the decoder's
+        the mean over frames.  'XPSNR', 'XPSNR_U', 'XPSNR_V' (this mode only; include/pnpvcve.h) are the activity-weighted PSNR of the
+        planes with `gt` as the original and test_cfg.get('xpsnr_fps', 30) frames per second; their value is the CLIP's, the log of the
+        mean weighted error over the frames, not the mean of the frames' dB.  'MS-SSIM' (five scales; include/pnpvcve.h) is served on
+        the device path of RGB / Y clips too and needs 176 x 176 samples of every plane it scores after the crop.  crop_border (even)
+        crops the Y plane, half of it the chroma planes.  test_cfg.convert_to may be None or 'y' and both mean the same here: the decoder's
         Y' plane IS the luma -- it is NOT the BT.601 Y that convert_to='y' derives from RGB bytes, so the two modes' numbers differ.
         Two ops.Yuv420Frames16 of one bit depth d are scored the same way on their sample values, with the peak 2^d - 1."""
         from .ops import Yuv420Frames, Yuv420Frames16, is_yuv
@@ -168,11 +170,12 @@ class BasicVSR(nn.Module):
         return eval_result
 
     YUV_OUT_LAYOUTS = ('nv12', 'i420', 'p010', 'p012', 'yuv420p10le', 'yuv420p12le')      # the packed 4:2:0 layouts generator.forward writes
-    YUV_METRICS = ('PSNR', 'SSIM', 'PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V', 'PSNR_YUV', 'MS-SSIM', 'MS-SSIM_U', 'MS-SSIM_V')
+    YUV_METRICS = ('PSNR', 'SSIM', 'PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V', 'PSNR_YUV', 'MS-SSIM', 'MS-SSIM_U', 'MS-SSIM_V', 'XPSNR', 'XPSNR_U',
+                   'XPSNR_V')
 
     def _evaluate_yuv(self, output, gt):
         """evaluate() of two ops.Yuv420Frames (or two ops.Yuv420Frames16) clips: plane PSNR / SSIM on the device, means over the clip's frames"""
-        from .ops import msssim_yuv420, psnr_yuv420, ssim_yuv420
+        from .ops import msssim_yuv420, psnr_yuv420, ssim_yuv420, xpsnr_yuv420
         crop_border = self.test_cfg['crop_border']
         convert_to = self.test_cfg.get('convert_to', None)
         if not (convert_to is None or (isinstance(convert_to, str) and convert_to.lower() == 'y')):
@@ -199,9 +202,15 @@ class BasicVSR(nn.Module):
         ms_col = {'MS-SSIM': 'y', 'MS-SSIM_U': 'u', 'MS-SSIM_V': 'v'}
         ms_planes = ''.join(dict.fromkeys(ms_col[m] for m in metrics if m in ms_col))
         msssim = msssim_yuv420(output, gt, crop_border, ms_planes) if ms_planes else None                          # (t, len(ms_planes))
+        xp_col = {'XPSNR': 'y', 'XPSNR_U': 'u', 'XPSNR_V': 'v'}
+        xp_planes = ''.join(dict.fromkeys(xp_col[m] for m in metrics if m in xp_col))
+        # gt is the original, whose activity sets the weights; the value is the CLIP's (the log of the mean weighted error): (len(xp_planes),)
+        xpsnr = xpsnr_yuv420(output, gt, crop_border, xp_planes, self.test_cfg.get('xpsnr_fps', 30), clip=True)[2] if xp_planes else None
         for metric in metrics:
             if metric in col:
                 eval_result[metric] = float(ssim[:, planes.index(col[metric])].mean())
+            elif metric in xp_col:
+                eval_result[metric] = float(xpsnr[xp_planes.index(xp_col[metric])])
             elif metric in ms_col:
                 eval_result[metric] = float(msssim[:, ms_planes.index(ms_col[metric])].mean())
             elif metric == 'PSNR_YUV':

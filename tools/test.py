@@ -55,7 +55,8 @@ def parse_args():
     p.add_argument('--yuv-frames', action='store_true',
                    help='raw 4:2:0 evaluation (a Yuv420ClipFolderDataset of .yuv clips): the generator reads the planes and writes packed '
                         '4:2:0 only, the ground truth stays 8-bit planes on the device, PSNR / SSIM are the Y plane\'s (PSNR_U, PSNR_V, '
-                        'SSIM_U, SSIM_V, the 6:1:1 PSNR_YUV and MS-SSIM, MS-SSIM_U, MS-SSIM_V -- five scales, planes of 176 x 176 or more -- '
+                        'SSIM_U, SSIM_V, the 6:1:1 PSNR_YUV, MS-SSIM, MS-SSIM_U, MS-SSIM_V -- five scales, planes of 176 x 176 or more -- and the '
+                        'activity-weighted XPSNR, XPSNR_U, XPSNR_V -- the ground truth is the original, test_cfg.xpsnr_fps (30) its frame rate -- '
                         'may be listed in test_cfg.metrics too) and --save-path gets one <clip>.yuv '
                         'per clip; a dataset with bit_depth=10 | 12 (16-bit little-endian .yuv files) goes the same way at its depth; '
                         'default off')
@@ -141,6 +142,8 @@ def main():
         line = '{:.4f}/{:.4f}'.format(float(stats.get('PSNR', float('nan'))), float(stats.get('SSIM', float('nan'))))
         if 'MS-SSIM' in (cfg.test_cfg.get('metrics', None) or ()):      # a third field only when the config lists it
             line += '/{:.4f}'.format(float(stats.get('MS-SSIM', float('nan'))))
+        if 'XPSNR' in (cfg.test_cfg.get('metrics', None) or ()):        # and an XPSNR field only when the config lists it
+            line += '/{:.4f}'.format(float(stats.get('XPSNR', float('nan'))))
         print(line)
         fps = [o['frames_per_s'] for o in outputs]
         import torch.distributed as dist
