@@ -302,7 +302,7 @@ int pnp_ssim_blocks_yuv420(int h, int w, int crop_border, int plane);
 int pnp_ssim_partials_yuv420(const pnp_yuv420_planes* a_host_desc, const pnp_yuv420_planes* b_host_desc, int plane_mask,
                              double* partials_dev, int frames, int h, int w, int crop_border, void* stream);
 
-/* 10 / 12-bit 4:2:0 boundary (yuv16.hip): the same boundary on the planes HEVC Main10 / VVC decoders and reference software write.
+/* 10 / 12-bit 4:2:0 boundary (yuv.hip): the same boundary on the planes HEVC Main10 / VVC decoders and reference software write.
  * The reference has no such path; tests/yuv16_ref.py restates the arithmetic below in numpy.  This is the ONE statement of it.
  *   Containers: bit depth d = 10 | 12, a sample in a 16-bit little-endian word; LOW-aligned (yuv420p10le / yuv420p12le: the value in
  *   the low d bits, msb_aligned = 0) or HIGH-aligned (P010 / P012: the value in the high d bits, msb_aligned = 1).  Reading is total

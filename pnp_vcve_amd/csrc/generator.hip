@@ -28,11 +28,9 @@
 #include "warp.h"
 #include "dcn.h"
 #include "yuv.h"
-#include "yuv16.h"
 #ifdef PNP_HOST_STUB
 #include "host_stub/io_stub.h"   // recording stand-ins for the byte-frame launchers (prep.h, conv_mfma.h) of the host-only scheduler tests
 #include "host_stub/yuv_stub.h"  // ... and for the 4:2:0 launchers (yuv.h)
-#include "host_stub/yuv16_stub.h"  // ... and their 10 / 12-bit forms (yuv16.h)
 #include "host_stub/fold_stub.h" // ... and for the fold table's launcher (conv_mfma.h)
 #endif
 
@@ -931,6 +929,14 @@ struct BandChain {
     }
 };
 
+// A 4:2:0 clip of either public kind (pnp_clip_yuv | pnp_clip_yuv16): its planes in and out, and the pointers the two kinds share
+struct YuvClip {
+    YuvPlanes lq, out;
+    const float *mvs_dev, *par_dev;
+    float* out_f32_dev;
+    unsigned char* out_u8_dev;
+};
+
 // One sample (clip) of the batch on one stream with one workspace context: what the run needs to know, and its launches phase by phase.
 struct ClipRun {
     const pnp_generator* const g;
@@ -943,12 +949,10 @@ struct ClipRun {
     const float* const lr_b; const unsigned char* const lq8;
     float* const out_b; unsigned char* const out8;
     const float *const mv_b, *const par_in, *const sl, *const qp, *const bq;
-    // ... or the frames and / or one more output as 4:2:0 planes (nullptr: not), with the standard's constants
-    const pnp_yuv420_planes *const lqy, *const outy;
-    YuvCoef yk{};
-    // ... or as 10 / 12-bit planes (pnp_generator_forward_clips_yuv16): the input's constants and container, and the output's
-    const pnp_yuv420_planes16 *const lqy16, *const outy16;
-    YuvCoef16 yk16_in{}, yk16_out{};
+    // ... or the frames and / or one more output as 4:2:0 planes of either sample size (nullptr: not), with the standard's constants
+    // at the input's depth and container, and at the output's
+    const YuvPlanes *const lqy, *const outy;
+    YuvCoef yk_in{}, yk_out{};
     const bool staged, alone;      // alone: the only workspace context in flight
     const int64_t hw = (int64_t)h * w, fm = hw * 64;
     const int E = c.num_experts, cfg_lr = conv_pick_cfg(h, w), os = c.vsr ? 4 : 1;
@@ -973,18 +977,15 @@ struct ClipRun {
 
     ClipRun(const pnp_generator* g_, const float* flat_, const float* packed_, const pnp_clip_io& io, int lq_format, int out_mask,
             const float* sl_, const float* qp_, const float* bq_, const Workspace& W_, int t_, int h_, int w_, hipStream_t st_, bool alone_,
-            const pnp_clip_yuv* yuv = nullptr, int yuv_standard = 0, const pnp_clip_yuv16* yuv16 = nullptr)
+            const YuvClip* yuv = nullptr, int yuv_standard = 0)
         : g(g_), c(g_->cfg), flat(flat_), packed(packed_), W(W_), t(t_), h(h_), w(w_), st(st_),
           lr_b(lq_format == PNP_FRAMES_F32_NCHW ? static_cast<const float*>(io.lq_dev) : nullptr),
           lq8(lq_format == PNP_FRAMES_U8_HWC ? static_cast<const unsigned char*>(io.lq_dev) : nullptr),
           out_b((out_mask & PNP_OUT_F32) ? io.out_f32_dev : nullptr), out8((out_mask & PNP_OUT_U8) ? io.out_u8_dev : nullptr),
           mv_b(io.mvs_dev), par_in(io.par_dev), sl(sl_), qp(qp_), bq(bq_), lqy(yuv ? &yuv->lq : nullptr),
-          outy((yuv && (out_mask & PNP_OUT_YUV420)) ? &yuv->out_yuv : nullptr), lqy16(yuv16 ? &yuv16->lq : nullptr),
-          outy16((yuv16 && (out_mask & PNP_OUT_YUV420)) ? &yuv16->out_yuv16 : nullptr), staged((lq8 || out8 || lqy || lqy16) && io_staged(g_)),
-          alone(alone_) {
-        if (yuv) (void)yuv_coef(yuv_standard, &yk);
-        if (lqy16) (void)yuv_coef16(yuv_standard, lqy16->bit_depth, lqy16->msb_aligned, &yk16_in);
-        if (outy16) (void)yuv_coef16(yuv_standard, outy16->bit_depth, outy16->msb_aligned, &yk16_out);
+          outy((yuv && (out_mask & PNP_OUT_YUV420)) ? &yuv->out : nullptr), staged((lq8 || out8 || lqy) && io_staged(g_)), alone(alone_) {
+        if (lqy) (void)yuv_coef(yuv_standard, *lqy, &yk_in);
+        if (outy) (void)yuv_coef(yuv_standard, *outy, &yk_out);
     }
 
     // fp16 mirror of a weight image that lives in `packed` or in the per-clip expert mixtures
@@ -1095,8 +1096,7 @@ struct ClipRun {
             const int rc = launch_fill(reinterpret_cast<float*>(W.queue), 0.0f, 16, st);
             if (rc) return rc;
         }
-        if (lqy) return launch_pack_lr_yuv420(*lqy, yk, W.lr4, t, h, w, false, st);
-        if (lqy16) return launch_pack_lr_yuv420p16(*lqy16, yk16_in, W.lr4, t, h, w, false, st);
+        if (lqy) return launch_pack_lr_yuv420(*lqy, yk_in, W.lr4, t, h, w, false, st);
         if (!lq8) return launch_pack_lr(lr_b, W.lr4, t, h, w, st);
         // any_size: a clip that is not whole 12-byte groups on a 4-aligned address takes the kernel with a head and a tail; every
         // other clip the one it always took
@@ -1351,16 +1351,15 @@ struct ClipRun {
         }
         // a 4:2:0 clip: the frame conv_last adds is the RGB0 frame the pack launch left in the workspace, or (fp32 interface) its planes
         const float* lr0_i = nullptr;
-        if ((lqy || lqy16) && staged) {
-            rc = lqy ? launch_frames_from_yuv420(yuv_frame(*lqy, i), yk, W.lr1, 1, h, w, st)
-                     : launch_frames_from_yuv420p16(yuv16_frame(*lqy16, i), yk16_in, W.lr1, 1, h, w, st);
+        if (lqy && staged) {
+            rc = launch_frames_from_yuv420(yuv_frame(*lqy, i), yk_in, W.lr1, 1, h, w, st);
             untimed(g);
             if (rc) return rc;
             lr_i = W.lr1;
-        } else if (lqy || lqy16) {
+        } else if (lqy) {
             lr0_i = W.lr4 + (int64_t)i * hw * 4;
         }
-        if (((staged && out8_i) || outy || outy16) && !out_i) out_i = W.out1;
+        if (((staged && out8_i) || outy) && !out_i) out_i = W.out1;
         rc = conv(ConvCall(H, Wd, CONV_CFG_RGB).source(top, 64, packed + g->last_img).bias(packed + g->last_bias)
                       .mode(c.vsr ? 3 : 2).rgb(lr_i, hw, packed + g->last_valu).rgb8(lr8_i, staged ? nullptr : out8_i).rgb0(lr0_i).to(out_i).f16_map(s16));
         if (rc) return rc;
@@ -1369,10 +1368,9 @@ struct ClipRun {
             rc = launch_frames_to_rgb8(out_i, out8_i, 1, H, Wd, st);
             if (rc) return rc;
         }
-        if (!outy && !outy16) return rc;
+        if (!outy) return rc;
         untimed(g);
-        if (outy16) return launch_frames_to_yuv420p16(out_i, yuv16_frame(*outy16, i), yk16_out, 1, H, Wd, st);
-        return launch_frames_to_yuv420(out_i, yuv_frame(*outy, i), yk, 1, H, Wd, st);
+        return launch_frames_to_yuv420(out_i, yuv_frame(*outy, i), yk_out, 1, H, Wd, st);
     }
 
     // one branch run of the schedule (recomputed runs of the bounded schedule are steps like any other) and, forward, the frame's head
@@ -1466,8 +1464,7 @@ int forward_check(const pnp_generator* g, int n, int t, int h, int w, int lq_for
 // The batch loop behind both entry points: n clips, each named by a descriptor, `lq_format` / `out_mask` for all of them.
 int forward_batch(const pnp_generator* g, const float* flat, const float* packed, const pnp_clip_io* clips, int n, int lq_format,
                   int out_mask, const float* slices, const float* qps, const float* base_qps, void* workspace, int64_t workspace_bytes,
-                  int t, int h, int w, hipStream_t st, const pnp_clip_yuv* yclips = nullptr, int yuv_standard = 0,
-                  const pnp_clip_yuv16* y16clips = nullptr) {
+                  int t, int h, int w, hipStream_t st, const YuvClip* yclips = nullptr, int yuv_standard = 0) {
     const int bad = forward_check(g, n, t, h, w, lq_format, out_mask, workspace, workspace_bytes);
     if (bad) return bad;
     const int64_t ctx_bytes = carve(g, nullptr, t, h, w, lq_format, out_mask).bytes;
@@ -1501,12 +1498,9 @@ int forward_batch(const pnp_generator* g, const float* flat, const float* packed
         const int k = b % nctx;
         const Workspace W = carve(g, (char*)workspace + (int64_t)k * ctx_bytes, t, h, w, lq_format, out_mask);
         // (a 4:2:0 batch comes as its own descriptors: the pointers the two kinds share, then the planes)
-        const pnp_clip_io io = yclips     ? pnp_clip_io{nullptr, yclips[b].mvs_dev, yclips[b].par_dev, yclips[b].out_f32_dev, yclips[b].out_u8_dev}
-                               : y16clips ? pnp_clip_io{nullptr, y16clips[b].mvs_dev, y16clips[b].par_dev, y16clips[b].out_f32_dev, y16clips[b].out_u8_dev}
-                                          : clips[b];
+        const pnp_clip_io io = yclips ? pnp_clip_io{nullptr, yclips[b].mvs_dev, yclips[b].par_dev, yclips[b].out_f32_dev, yclips[b].out_u8_dev} : clips[b];
         rc = ClipRun(g, flat, packed, io, lq_format, out_mask, slices + (int64_t)b * t, qps + (int64_t)b * t, base_qps + (int64_t)b * t,
-                     W, t, h, w, nctx > 1 ? g->side_streams[k] : st, nctx == 1, yclips ? yclips + b : nullptr, yuv_standard,
-                     y16clips ? y16clips + b : nullptr).run();
+                     W, t, h, w, nctx > 1 ? g->side_streams[k] : st, nctx == 1, yclips ? yclips + b : nullptr, yuv_standard).run();
     }
     if (nctx > 1) {      // join even after an error: the caller's stream must not run ahead of what was launched
         for (int k = 0; k < nctx; ++k) {
@@ -1516,6 +1510,26 @@ int forward_batch(const pnp_generator* g, const float* flat, const float* packed
         }
     }
     return rc;
+}
+
+// The body behind the two 4:2:0 entries (the scheduler's 4:2:0 frame format: the workspace holds fp32 frames only, so its layout does
+// not know the sample size): what only these entries can get wrong, in front of everything else (no HIP call has been made).
+int forward_clips_yuv(const pnp_generator* g, const float* flat, const float* packed, const std::vector<YuvClip>& clips, int yuv_standard,
+                      int out_mask, const float* slices, const float* qps, const float* base_qps, void* workspace, int64_t workspace_bytes, int t,
+                      int h, int w, hipStream_t st) {
+    YuvCoef k;
+    if (!g || !yuv_coef(yuv_standard, 8, 0, &k) || out_mask < 1 || out_mask > (PNP_OUT_F32 | PNP_OUT_U8 | PNP_OUT_YUV420)) return PNP_ERR_BAD_ARG;
+    if (h < 2 || w < 2 || (h & 1) || (w & 1)) return PNP_ERR_BAD_ARG;
+    const int os = g->cfg.vsr ? 4 : 1;
+    for (const YuvClip& c : clips) {
+        if (!yuv_planes_ok(c.lq, w) || !c.mvs_dev || !c.par_dev) return PNP_ERR_BAD_ARG;
+        if ((out_mask & PNP_OUT_F32) && !c.out_f32_dev) return PNP_ERR_BAD_ARG;
+        const uintptr_t amask = g->any_size ? 0 : 3;      // (the byte output's rule of pnp_generator_forward_clips)
+        if ((out_mask & PNP_OUT_U8) && (!c.out_u8_dev || (reinterpret_cast<uintptr_t>(c.out_u8_dev) & amask))) return PNP_ERR_BAD_ARG;
+        if ((out_mask & PNP_OUT_YUV420) && !yuv_planes_ok(c.out, w * os)) return PNP_ERR_BAD_ARG;
+    }
+    return forward_batch(g, flat, packed, nullptr, (int)clips.size(), FRAMES_YUV420, out_mask, slices, qps, base_qps, workspace, workspace_bytes, t, h,
+                         w, st, clips.data(), yuv_standard);
 }
 
 }  // namespace
@@ -1574,42 +1588,25 @@ int64_t pnp_generator_workspace_bytes_yuv(const pnp_generator* g, int t, int h, 
 int pnp_generator_forward_clips_yuv(const pnp_generator* g, const float* flat, const float* packed, const pnp_clip_yuv* clips, int n,
                                     int yuv_standard, int out_mask, const float* slices, const float* qps, const float* base_qps,
                                     void* workspace, int64_t workspace_bytes, int t, int h, int w, void* stream_) {
-    // what only this entry can get wrong, in front of everything else (no HIP call has been made)
-    YuvCoef k;
-    if (!g || !clips || n < 1 || !yuv_coef(yuv_standard, &k) || out_mask < 1 || out_mask > (PNP_OUT_F32 | PNP_OUT_U8 | PNP_OUT_YUV420)) return PNP_ERR_BAD_ARG;
-    if (h < 2 || w < 2 || (h & 1) || (w & 1)) return PNP_ERR_BAD_ARG;
-    const int os = g->cfg.vsr ? 4 : 1;
+    if (!clips || n < 1) return PNP_ERR_BAD_ARG;      // (what the conversion itself needs; everything else is forward_clips_yuv's to refuse)
+    std::vector<YuvClip> y(n);
     for (int b = 0; b < n; ++b) {
         const pnp_clip_yuv& c = clips[b];
-        if (!yuv_planes_ok(c.lq, w) || !c.mvs_dev || !c.par_dev) return PNP_ERR_BAD_ARG;
-        if ((out_mask & PNP_OUT_F32) && !c.out_f32_dev) return PNP_ERR_BAD_ARG;
-        const uintptr_t amask = g->any_size ? 0 : 3;      // (the byte output's rule of pnp_generator_forward_clips)
-        if ((out_mask & PNP_OUT_U8) && (!c.out_u8_dev || (reinterpret_cast<uintptr_t>(c.out_u8_dev) & amask))) return PNP_ERR_BAD_ARG;
-        if ((out_mask & PNP_OUT_YUV420) && !yuv_planes_ok(c.out_yuv, w * os)) return PNP_ERR_BAD_ARG;
+        y[b] = YuvClip{yuv_planes(c.lq), yuv_planes(c.out_yuv), c.mvs_dev, c.par_dev, c.out_f32_dev, c.out_u8_dev};
     }
-    return forward_batch(g, flat, packed, nullptr, n, FRAMES_YUV420, out_mask, slices, qps, base_qps, workspace, workspace_bytes, t, h, w,
-                         (hipStream_t)stream_, clips, yuv_standard);
+    return forward_clips_yuv(g, flat, packed, y, yuv_standard, out_mask, slices, qps, base_qps, workspace, workspace_bytes, t, h, w, (hipStream_t)stream_);
 }
 
 int pnp_generator_forward_clips_yuv16(const pnp_generator* g, const float* flat, const float* packed, const pnp_clip_yuv16* clips, int n,
                                       int yuv_standard, int out_mask, const float* slices, const float* qps, const float* base_qps,
                                       void* workspace, int64_t workspace_bytes, int t, int h, int w, void* stream_) {
-    // what only this entry can get wrong, in front of everything else (no HIP call has been made)
-    YuvCoef k;
-    if (!g || !clips || n < 1 || !yuv_coef(yuv_standard, &k) || out_mask < 1 || out_mask > (PNP_OUT_F32 | PNP_OUT_U8 | PNP_OUT_YUV420)) return PNP_ERR_BAD_ARG;
-    if (h < 2 || w < 2 || (h & 1) || (w & 1)) return PNP_ERR_BAD_ARG;
-    const int os = g->cfg.vsr ? 4 : 1;
+    if (!clips || n < 1) return PNP_ERR_BAD_ARG;      // (what the conversion itself needs; everything else is forward_clips_yuv's to refuse)
+    std::vector<YuvClip> y(n);
     for (int b = 0; b < n; ++b) {
         const pnp_clip_yuv16& c = clips[b];
-        if (!yuv16_planes_ok(c.lq, w) || !c.mvs_dev || !c.par_dev) return PNP_ERR_BAD_ARG;
-        if ((out_mask & PNP_OUT_F32) && !c.out_f32_dev) return PNP_ERR_BAD_ARG;
-        const uintptr_t amask = g->any_size ? 0 : 3;      // (the byte output's rule of pnp_generator_forward_clips)
-        if ((out_mask & PNP_OUT_U8) && (!c.out_u8_dev || (reinterpret_cast<uintptr_t>(c.out_u8_dev) & amask))) return PNP_ERR_BAD_ARG;
-        if ((out_mask & PNP_OUT_YUV420) && !yuv16_planes_ok(c.out_yuv16, w * os)) return PNP_ERR_BAD_ARG;
+        y[b] = YuvClip{yuv_planes(c.lq), yuv_planes(c.out_yuv16), c.mvs_dev, c.par_dev, c.out_f32_dev, c.out_u8_dev};
     }
-    // (the scheduler's 4:2:0 frame format: the workspace holds fp32 frames only, so its layout is the 8-bit boundary's)
-    return forward_batch(g, flat, packed, nullptr, n, FRAMES_YUV420, out_mask, slices, qps, base_qps, workspace, workspace_bytes, t, h, w,
-                         (hipStream_t)stream_, nullptr, yuv_standard, clips);
+    return forward_clips_yuv(g, flat, packed, y, yuv_standard, out_mask, slices, qps, base_qps, workspace, workspace_bytes, t, h, w, (hipStream_t)stream_);
 }
 
 int pnp_generator_profile(pnp_generator* g, int enable) {

@@ -6,7 +6,6 @@
 #include "plane_load.h"
 #include "prep.h"
 #include "yuv.h"
-#include "yuv16.h"
 #include <cmath>
 
 namespace {
@@ -184,7 +183,7 @@ inline bool planes_args_ok(const pnp_yuv420_planes* a, const pnp_yuv420_planes* 
 inline bool planes16_args_ok(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, const void* out, int frames, int h, int w, int crop) {
     if (!a || !b || !out || frames < 1 || h < 2 || w < 2 || (h & 1) || (w & 1)) return false;
     if (crop < 0 || (crop & 1) || 2 * crop >= h || 2 * crop >= w) return false;
-    return yuv16_planes_ok(*a, w) && yuv16_planes_ok(*b, w) && a->bit_depth == b->bit_depth;
+    return yuv_planes_ok(*a, w) && yuv_planes_ok(*b, w) && a->bit_depth == b->bit_depth;
 }
 
 inline void ssim_window(double* g) {                     // cv2.getGaussianKernel(11, 1.5)

@@ -663,10 +663,10 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
     def _forward_yuv(self, frames, QPs, slices, mvs, base_QPs, par_map, out_dtype, yuv_standard):
         std = ops._yuv_standard(yuv_standard)
         kinds, mask, layout, many = self._yuv_outs(out_dtype)
-        clips, lead = ops._any_yuv_clips(frames, 'lrs')
+        clips, lead = ops._yuv_clips(frames, 'lrs')
         if not lead:
             raise ValueError('forward() takes a batch: Yuv420Frames of (n,t,rows,cols) views')
-        descs = [ops._any_yuv_clip_desc(c, 'lrs') for c in clips]      # (every refusal before any GPU work)
+        descs = [ops._yuv_clip_desc(c, 'lrs') for c in clips]      # (every refusal before any GPU work)
         via8, run_dtype = self._yuv_out_route(frames, kinds, layout)
         if via8:
             res = self._yuv8_of_16(self._forward_yuv(frames, QPs, slices, mvs, base_QPs, par_map, run_dtype, yuv_standard), kinds, via8, std)
@@ -716,7 +716,7 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
                 buf, views = ops.empty_yuv420p16((n, t), h * s, w * s, layout, dev, word_dtype)
             else:
                 buf, views = ops.empty_yuv420((n, t), h * s, w * s, layout, dev)
-            outs['yuv'] = (buf, ops._any_yuv_clips(views, 'out')[0])
+            outs['yuv'] = (buf, ops._yuv_clips(views, 'out')[0])
         return outs
 
     def _launch_clips_yuv(self, clips, mvs, par, side, outs, ws, t, h, w, std):
@@ -731,8 +731,8 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         for kind, bit in (('f32', _native.OUT_F32), ('u8', _native.OUT_U8), ('yuv', _native.OUT_YUV420)):
             mask |= bit if kind in outs else 0
         for b in range(n):
-            lq = ops._any_yuv_clip_desc(clips[b], 'lrs')[0]
-            oy = ops._any_yuv_clip_desc(outs['yuv'][1][b], 'out')[0] if 'yuv' in outs else Planes()
+            lq = ops._yuv_clip_desc(clips[b], 'lrs')[0]
+            oy = ops._yuv_clip_desc(outs['yuv'][1][b], 'out')[0] if 'yuv' in outs else Planes()
             if not isinstance(oy, Planes):
                 raise ValueError('the planes output must have the sample size of the input planes')
             arr[b] = Clip(lq, mvs[b].data_ptr(), par[b].data_ptr(), outs['f32'][1][b].data_ptr() if 'f32' in outs else None,
@@ -758,7 +758,7 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         if ent is None:
             mk = lambda hh, ww: torch.empty((n, t, hh, ww), device=dev, dtype=c0.y.dtype)      # noqa: E731
             static = type(c0)(mk(h, w), mk(h // 2, w // 2), mk(h // 2, w // 2), *c0[3:])
-            ent = dict(clips=ops._any_yuv_clips(static, 'lrs')[0], mvs=torch.empty_like(mvs_c), par=torch.empty_like(par_c), side=side.clone(),
+            ent = dict(clips=ops._yuv_clips(static, 'lrs')[0], mvs=torch.empty_like(mvs_c), par=torch.empty_like(par_c), side=side.clone(),
                        ws=torch.empty(self._workspace_bytes(t, h, w, 'yuv', mask) * self._contexts(n, h, w), device=dev, dtype=torch.uint8),
                        outs=self._alloc_yuv_outs(n, t, h, w, mask, layout, dev, c0.y.dtype))
             run = lambda: self._launch_clips_yuv(ent['clips'], list(ent['mvs']), list(ent['par']), ent['side'], ent['outs'], ent['ws'],      # noqa: E731
@@ -799,10 +799,10 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
             return res if many else [r[0] for r in res]
         ys, cbs, crs, mv_l, par_l, sides, first = [], [], [], [], [], [], None
         for lrs, QPs, slices, mvs, base_QPs, par_map in clips:
-            one, lead = ops._any_yuv_clips(lrs, 'lrs')
+            one, lead = ops._yuv_clips(lrs, 'lrs')
             if len(one) != 1:
                 raise ValueError('a clip of forward_clips is one sample: Yuv420Frames of (t,...) or (1,t,...) views')
-            _, t, h, w = ops._any_yuv_clip_desc(one[0], 'lrs')
+            _, t, h, w = ops._yuv_clip_desc(one[0], 'lrs')
             sig = (t, h, w, lrs.y.device) + ((type(lrs), lrs.y.dtype) + tuple(lrs[3:]) if isinstance(lrs0, ops.Yuv420Frames16) else ())
             if first is None:
                 first = sig

@@ -749,7 +749,10 @@ def pixel_shuffle_conv(x, packed, act=0):
 
 
 # ---------------------------------------------------------------- Y'CbCr 4:2:0 frames (include/pnpvcve.h states the arithmetic)
+# 8-bit planes (Yuv420Frames: bytes) and 10 / 12-bit planes (Yuv420Frames16: 16-bit words) share every helper below; the sample's size
+# is the tensors' element_size(), and a function named for one sample size refuses frames of the other.
 _Yuv420Base = collections.namedtuple('Yuv420Frames', ['y', 'cb', 'cr'])
+_Yuv420Base16 = collections.namedtuple('Yuv420Frames16', ['y', 'cb', 'cr', 'bit_depth', 'msb_aligned'], defaults=(10, False))
 
 
 class Yuv420Frames(_Yuv420Base):
@@ -760,7 +763,24 @@ class Yuv420Frames(_Yuv420Base):
     __slots__ = ()
 
 
+class Yuv420Frames16(_Yuv420Base16):
+    """10 / 12-bit 4:2:0 frames as three CUDA VIEWS of 16-bit words (torch.int16, or torch.uint16 where torch has it: the same bits)
+    of wherever the decoder wrote them: y (n,t,h,w), cb and cr (n,t,h/2,w/2), or without the batch dimension.  bit_depth 10 | 12;
+    msb_aligned: the value sits in the high bits of the word (P010 / P012) instead of the low ones (yuv420p10le / yuv420p12le).
+    Strides are in samples: the last-dimension stride is 1 for y and 1 (planar) or 2 (interleaved: cb and cr one sample apart in one
+    buffer) for chroma.  Nothing is copied; yuv420p16_views builds the views of a packed buffer."""
+    __slots__ = ()
+
+
 YUV_LAYOUTS = ('nv12', 'nv21', 'i420')
+# name -> (the 8-bit layout with the same plane order, bit depth, msb_aligned)
+YUV16_LAYOUTS = {'p010': ('nv12', 10, True), 'p012': ('nv12', 12, True), 'yuv420p10le': ('i420', 10, False), 'yuv420p12le': ('i420', 12, False)}
+_WORD_DTYPES = tuple(d for d in (torch.int16, getattr(torch, 'uint16', None)) if d is not None)
+
+
+def is_yuv(frames):
+    """frames are 4:2:0 planes of either sample size"""
+    return isinstance(frames, (Yuv420Frames, Yuv420Frames16))
 
 
 def _yuv_standard(standard):
@@ -773,46 +793,102 @@ def _yuv_standard(standard):
     return int(standard)
 
 
+def _yuv16_layout(layout):
+    """a layout name of YUV16_LAYOUTS or ('nv12' | 'nv21' | 'i420', bit_depth, msb_aligned) -> (order, bit_depth, msb_aligned)"""
+    if isinstance(layout, str):
+        if layout not in YUV16_LAYOUTS:
+            raise ValueError(f'layout must be one of {sorted(YUV16_LAYOUTS)} or (order, bit_depth, msb_aligned), got {layout!r}')
+        return YUV16_LAYOUTS[layout]
+    if not isinstance(layout, (tuple, list)) or len(layout) != 3 or layout[0] not in YUV_LAYOUTS:
+        raise ValueError(f'layout must be one of {sorted(YUV16_LAYOUTS)} or ({YUV_LAYOUTS}, bit_depth, msb_aligned), got {layout!r}')
+    return layout[0], _bit_depth(layout[1]), bool(layout[2])
+
+
+def _bit_depth(d):
+    if isinstance(d, bool) or d not in (10, 12):
+        raise ValueError(f'bit_depth must be 10 or 12, got {d!r}')
+    return int(d)
+
+
+def _yuv_expect(frames, what, cls=None):
+    """TypeError unless frames are `cls` (Yuv420Frames | Yuv420Frames16; None: either, anything else is told what 8-bit frames are)
+    -> frames are 16-bit"""
+    if cls is Yuv420Frames16 or (cls is None and isinstance(frames, Yuv420Frames16)):
+        if not isinstance(frames, Yuv420Frames16):
+            raise TypeError(f'{what} must be ops.Yuv420Frames16(y, cb, cr, bit_depth, msb_aligned)')
+        return True
+    if not isinstance(frames, Yuv420Frames):
+        raise TypeError(f'{what} must be ops.Yuv420Frames(y, cb, cr)')
+    return False
+
+
+def _yuv_entry(name, frames):
+    """the C entry `name` for the frames' sample size"""
+    return name + ('p16' if isinstance(frames, Yuv420Frames16) else '')
+
+
+def _yuv_views(buf, h, w, order, tail=()):
+    """yuv420_views / yuv420p16_views: tail () -> Yuv420Frames of a uint8 buffer, (bit_depth, msb_aligned) -> Yuv420Frames16 of 16-bit
+    words; order 'nv12' | 'nv21' | 'i420'"""
+    cls, words, planar = (Yuv420Frames16, '16-bit words', 'a planar') if tail else (Yuv420Frames, 'uint8', 'an I420')
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise ValueError(f'4:2:0 frames need an even height and width, got {h} x {w}')
+    if tail and (not isinstance(buf, torch.Tensor) or buf.dtype not in _WORD_DTYPES):
+        raise TypeError(f'buf must be a tensor of 16-bit words (torch.int16 / torch.uint16), got {getattr(buf, "dtype", type(buf))}')
+    if not tail and buf.dtype != torch.uint8:
+        raise TypeError(f'buf must be uint8, got {buf.dtype}')
+    if buf.dim() >= 2 and buf.shape[-2] == h * 3 // 2 and buf.shape[-1] >= w and buf.stride(-1) == 1:
+        pitch = buf.shape[-1]
+        y = buf[..., :h, :w]
+        if order != 'i420':
+            c = buf[..., h:, :w]
+            a, b = c[..., 0::2], c[..., 1::2]
+            return cls(y, a, b, *tail) if order == 'nv12' else cls(y, b, a, *tail)
+        if pitch % 2 or buf.stride(-2) != pitch:
+            raise ValueError(f'{planar} buffer needs an even pitch and whole rows: its chroma rows are half a luma row long')
+        flat = buf.flatten(-2)          # (a view: the two last dimensions are contiguous)
+        n = (h // 2) * (pitch // 2)
+        cb = flat[..., h * pitch:h * pitch + n].unflatten(-1, (h // 2, pitch // 2))[..., :w // 2]
+        cr = flat[..., h * pitch + n:h * pitch + 2 * n].unflatten(-1, (h // 2, pitch // 2))[..., :w // 2]
+        return cls(y, cb, cr, *tail)
+    if order == 'i420' and buf.dim() >= 1 and buf.shape[-1] == h * w * 3 // 2 and buf.stride(-1) == 1:
+        return _yuv_views(buf.unflatten(-1, (h * 3 // 2, w)), h, w, order, tail)
+    raise ValueError(f'buf must be (..., {h * 3 // 2}, pitch >= {w}) {words} with a unit last stride, got {tuple(buf.shape)}')
+
+
 def yuv420_views(buf, h, w, layout='nv12'):
     """A packed uint8 buffer (..., 3h/2, pitch) -- or flat (..., nbytes) for I420 whose chroma rows are pitch/2 = w/2 apart -- ->
     Yuv420Frames of views into it (no copy).  NV12 / NV21: h rows of Y, then h/2 rows of interleaved chroma pairs, all `pitch`
     bytes apart.  I420: the Y plane, then the Cb plane and the Cr plane with rows pitch/2 apart (pitch even)."""
     if layout not in YUV_LAYOUTS:
         raise ValueError(f'layout must be one of {YUV_LAYOUTS}, got {layout!r}')
-    if h < 2 or w < 2 or h % 2 or w % 2:
-        raise ValueError(f'4:2:0 frames need an even height and width, got {h} x {w}')
-    if buf.dtype != torch.uint8:
-        raise TypeError(f'buf must be uint8, got {buf.dtype}')
-    if buf.dim() >= 2 and buf.shape[-2] == h * 3 // 2 and buf.shape[-1] >= w and buf.stride(-1) == 1:
-        pitch = buf.shape[-1]
-        y = buf[..., :h, :w]
-        if layout != 'i420':
-            c = buf[..., h:, :w]
-            a, b = c[..., 0::2], c[..., 1::2]
-            return Yuv420Frames(y, a, b) if layout == 'nv12' else Yuv420Frames(y, b, a)
-        if pitch % 2 or buf.stride(-2) != pitch:
-            raise ValueError('an I420 buffer needs an even pitch and whole rows: its chroma rows are half a luma row long')
-        flat = buf.flatten(-2)          # (a view: the two last dimensions are contiguous)
-        n = (h // 2) * (pitch // 2)
-        cb = flat[..., h * pitch:h * pitch + n].unflatten(-1, (h // 2, pitch // 2))[..., :w // 2]
-        cr = flat[..., h * pitch + n:h * pitch + 2 * n].unflatten(-1, (h // 2, pitch // 2))[..., :w // 2]
-        return Yuv420Frames(y, cb, cr)
-    if layout == 'i420' and buf.dim() >= 1 and buf.shape[-1] == h * w * 3 // 2 and buf.stride(-1) == 1:
-        return yuv420_views(buf.unflatten(-1, (h * 3 // 2, w)), h, w, layout)
-    raise ValueError(f'buf must be (..., {h * 3 // 2}, pitch >= {w}) uint8 with a unit last stride, got {tuple(buf.shape)}')
+    return _yuv_views(buf, h, w, layout)
 
 
-def _yuv_clip_desc(frames, what='frames'):
-    """Yuv420Frames of (t,h,w) / (t,h/2,w/2) views -> (_native.Yuv420Planes, t, h, w); every refusal a ValueError / TypeError raised
-    before any GPU work"""
-    if not isinstance(frames, Yuv420Frames):
-        raise TypeError(f'{what} must be ops.Yuv420Frames(y, cb, cr)')
-    y, cb, cr = frames
+def yuv420p16_views(buf, h, w, layout='yuv420p10le'):
+    """A packed buffer of 16-bit words (..., 3h/2, pitch) -- or flat (..., 3hw/2) for planar layouts -- -> Yuv420Frames16 of views
+    into it (no copy): yuv420_views' rules with samples for bytes.  layout: 'p010' | 'p012' (Y, then interleaved Cb Cr, value in the
+    high bits) | 'yuv420p10le' | 'yuv420p12le' (Y, Cb, Cr planes, value in the low bits), or ('nv12' | 'nv21' | 'i420', bit_depth,
+    msb_aligned)."""
+    order, depth, msb = _yuv16_layout(layout)
+    return _yuv_views(buf, h, w, order, (depth, msb))
+
+
+def _yuv_clip_desc(frames, what='frames', cls=None):
+    """Yuv420Frames / Yuv420Frames16 of (t,h,w) / (t,h/2,w/2) views -> (_native.Yuv420Planes / Yuv420Planes16, t, h, w): pointers,
+    pitches and frame strides in BYTES, the chroma step in samples; every refusal a ValueError / TypeError raised before any GPU
+    work.  cls: as _yuv_expect"""
+    sixteen = _yuv_expect(frames, what, cls)
+    y, cb, cr = frames[:3]
+    if sixteen:
+        depth = _bit_depth(frames.bit_depth)
+    dtypes, named, apart, unit = ((_WORD_DTYPES, 'int16 or uint16', 'sample apart (P010 / P012)', 'samples') if sixteen else
+                                  ((torch.uint8,), 'uint8', 'byte apart (NV12 / NV21)', 'bytes'))
     for name, x in (('y', y), ('cb', cb), ('cr', cr)):
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise RuntimeError(f'{what}.{name} must be a CUDA/HIP tensor: the PnP-VCVE hot path has no CPU fallback')
-        if x.dtype != torch.uint8:
-            raise TypeError(f'{what}.{name} must be uint8, got {x.dtype}')
+        if x.dtype not in dtypes:
+            raise TypeError(f'{what}.{name} must be {named}, got {x.dtype}')
         if x.dim() != 3:
             raise ValueError(f'{what}.{name} must be (t,rows,cols) per clip, got {tuple(x.shape)}')
     t, h, w = y.shape
@@ -824,21 +900,24 @@ def _yuv_clip_desc(frames, what='frames'):
         raise ValueError(f'{what}.y must have a unit last stride, got {y.stride(2)}')
     if cb.stride() != cr.stride() or cb.stride(2) not in (1, 2):
         raise ValueError(f'{what}.cb and .cr must share their strides, with a last stride of 1 or 2: got {cb.stride()} and {cr.stride()}')
-    step = cb.stride(2)
-    if step == 2 and abs(cb.data_ptr() - cr.data_ptr()) != 1:
-        raise ValueError('chroma with a step of 2 must be interleaved: cb and cr one byte apart (NV12 / NV21)')
+    step, size = cb.stride(2), y.element_size()
+    if step == 2 and abs(cb.data_ptr() - cr.data_ptr()) != size:
+        raise ValueError(f'chroma with a step of 2 must be interleaved: cb and cr one {apart}')
     if y.stride(1) < w or cb.stride(1) < step * (w // 2) or (t > 1 and (y.stride(0) < 0 or cb.stride(0) < 0)):
-        raise ValueError(f'{what}: a pitch below the row\'s bytes (strides {y.stride()}, {cb.stride()})')
-    d = _native.Yuv420Planes(y.data_ptr(), cb.data_ptr(), cr.data_ptr(), y.stride(1), cb.stride(1), y.stride(0) if t > 1 else 0,
-                             cb.stride(0) if t > 1 else 0, step)
+        raise ValueError(f'{what}: a pitch below the row\'s {unit} (strides {y.stride()}, {cb.stride()})')
+    if size == 2 and (y.data_ptr() | cb.data_ptr() | cr.data_ptr()) & 1:
+        raise ValueError(f'{what}: 16-bit planes must lie at even addresses')
+    args = (y.data_ptr(), cb.data_ptr(), cr.data_ptr(), size * y.stride(1), size * cb.stride(1), size * y.stride(0) if t > 1 else 0,
+            size * cb.stride(0) if t > 1 else 0, step)
+    d = _native.Yuv420Planes16(*args, depth, int(bool(frames.msb_aligned))) if sixteen else _native.Yuv420Planes(*args)
     return d, t, h, w
 
 
-def _yuv_clips(frames, what='frames'):
-    """Yuv420Frames with or without the batch dimension -> (list of per-clip Yuv420Frames, lead shape)"""
-    if not isinstance(frames, Yuv420Frames):
-        raise TypeError(f'{what} must be ops.Yuv420Frames(y, cb, cr)')
-    if any(not isinstance(x, torch.Tensor) for x in frames):
+def _yuv_clips(frames, what='frames', cls=None):
+    """Yuv420Frames / Yuv420Frames16 with or without the batch dimension -> (list of per-clip frames of the same kind, lead shape).
+    cls: as _yuv_expect"""
+    _yuv_expect(frames, what, cls)
+    if any(not isinstance(x, torch.Tensor) for x in frames[:3]):
         raise TypeError(f'{what}: y, cb and cr must be tensors')
     d = frames.y.dim()
     if d not in (3, 4) or frames.cb.dim() != d or frames.cr.dim() != d:
@@ -849,39 +928,30 @@ def _yuv_clips(frames, what='frames'):
     n = frames.y.shape[0]
     if frames.cb.shape[0] != n or frames.cr.shape[0] != n:
         raise ValueError(f'{what}: y, cb and cr disagree in the batch size')
-    return [Yuv420Frames(frames.y[b], frames.cb[b], frames.cr[b]) for b in range(n)], (n,)
+    kind = Yuv420Frames16 if isinstance(frames, Yuv420Frames16) else Yuv420Frames
+    return [kind(frames.y[b], frames.cb[b], frames.cr[b], *frames[3:]) for b in range(n)], (n,)
 
 
-def frames_from_yuv420(frames, standard='bt601-limited'):
-    """Yuv420Frames (n,t,...) or (t,...) -> (n,t,3,h,w) / (t,3,h,w) fp32 RGB planes, clamped to [0,1], chroma replicated: the
-    arithmetic of include/pnpvcve.h, bit-equal to tests/yuv_ref.py.  What generator.forward(Yuv420Frames) computes on, without this
-    fp32 clip."""
+def _frames_from_yuv(frames, standard, cls=None):
+    """frames_from_yuv420 / frames_from_yuv420p16 (cls: as _yuv_expect; None: by the frames' type)"""
     std = _yuv_standard(standard)
-    clips, lead = _yuv_clips(frames)
+    clips, lead = _yuv_clips(frames, 'frames', cls)
     descs = [_yuv_clip_desc(c) for c in clips]
     _, t, h, w = descs[0]
     if any(d[1:] != (t, h, w) for d in descs):
         raise ValueError('the clips of a batch must agree in shape')
+    entry = _yuv_entry('pnp_frames_from_yuv420', frames)
     dev = frames.y.device
     with torch.cuda.device(dev):
         out = torch.empty((len(clips), t, 3, h, w), device=dev, dtype=torch.float32)
         for b, (d, _, _, _) in enumerate(descs):
             if t:
-                _native.check(_native.lib().pnp_frames_from_yuv420(ctypes.byref(d), std, _ptr(out[b]), t, h, w, _stream()),
-                              'pnp_frames_from_yuv420')
+                _native.check(getattr(_native.lib(), entry)(ctypes.byref(d), std, _ptr(out[b]), t, h, w, _stream()), entry)
     return out if lead else out[0]
 
 
-def empty_yuv420(lead, h, w, layout, device):
-    """-> (packed uint8 buffer lead + (3h/2, w), its Yuv420Frames views)"""
-    buf = torch.empty(tuple(lead) + (h * 3 // 2, w), device=device, dtype=torch.uint8)
-    return buf, yuv420_views(buf, h, w, layout)
-
-
-def frames_to_yuv420(planes, standard='bt601-limited', layout='nv12', out=None):
-    """(n,t,3,h,w) or (t,3,h,w) fp32 CUDA planes -> (packed uint8 buffer (...,3h/2,w) in `layout`, its Yuv420Frames views): clamp,
-    luma, box-mean chroma, round half to even (include/pnpvcve.h).  out: Yuv420Frames views to write instead of a fresh buffer
-    (any pitch and address; returns (None, out))."""
+def _frames_to_yuv(planes, standard, out, cls, empty):
+    """frames_to_yuv420 / frames_to_yuv420p16; empty(lead, h, w, device) -> (a fresh packed buffer, its views) where out is None"""
     std = _yuv_standard(standard)
     planes = _chk(planes, 'planes')
     if planes.dim() not in (4, 5) or planes.shape[-3] != 3:
@@ -893,33 +963,93 @@ def frames_to_yuv420(planes, standard='bt601-limited', layout='nv12', out=None):
     with torch.cuda.device(planes.device):
         buf = None
         if out is None:
-            buf, out = empty_yuv420(lead, h, w, layout, planes.device)
-        clips, olead = _yuv_clips(out, 'out')
+            buf, out = empty(lead, h, w, planes.device)
+        clips, olead = _yuv_clips(out, 'out', cls)
         src = planes if planes.dim() == 5 else planes[None]
         if len(clips) != src.shape[0]:
             raise ValueError('out and planes disagree in the batch size')
+        entry = _yuv_entry('pnp_frames_to_yuv420', out)
         for b, c in enumerate(clips):
             d, t, oh, ow = _yuv_clip_desc(c, 'out')
             if (t, oh, ow) != (src.shape[1], h, w):
                 raise ValueError(f'out is {(t, oh, ow)}, planes are {(src.shape[1], h, w)}')
             if t:
-                _native.check(_native.lib().pnp_frames_to_yuv420(_ptr(src[b]), ctypes.byref(d), std, t, h, w, _stream()), 'pnp_frames_to_yuv420')
+                _native.check(getattr(_native.lib(), entry)(_ptr(src[b]), ctypes.byref(d), std, t, h, w, _stream()), entry)
     return buf, out
+
+
+def _pack_lr_yuv(frames, standard, general, cls):
+    """pack_lr_yuv420 / pack_lr_yuv420p16"""
+    d, t, h, w = _yuv_clip_desc(frames, 'frames', cls)
+    entry = _yuv_entry('pnp_debug_pack_lr_yuv420', frames)
+    with torch.cuda.device(frames.y.device):
+        out = torch.empty((t, h, w, 4), device=frames.y.device, dtype=torch.float32)
+        _native.check(getattr(_native.lib(), entry)(ctypes.byref(d), _yuv_standard(standard), _ptr(out), t, h, w, int(bool(general)), _stream()), entry)
+    return out
+
+
+def frames_from_yuv420(frames, standard='bt601-limited'):
+    """Yuv420Frames (n,t,...) or (t,...) -> (n,t,3,h,w) / (t,3,h,w) fp32 RGB planes, clamped to [0,1], chroma replicated: the
+    arithmetic of include/pnpvcve.h, bit-equal to tests/yuv_ref.py.  What generator.forward(Yuv420Frames) computes on, without this
+    fp32 clip."""
+    return _frames_from_yuv(frames, standard, Yuv420Frames)
+
+
+def frames_from_yuv420p16(frames, standard='bt601-limited'):
+    """Yuv420Frames16 (n,t,...) or (t,...) -> (n,t,3,h,w) / (t,3,h,w) fp32 RGB planes, clamped to [0,1], chroma replicated: the
+    arithmetic of include/pnpvcve.h at the frames' depth, bit-equal to tests/yuv16_ref.py.  What generator.forward(Yuv420Frames16)
+    computes on, without this fp32 clip."""
+    return _frames_from_yuv(frames, standard, Yuv420Frames16)
+
+
+def empty_yuv420(lead, h, w, layout, device):
+    """-> (packed uint8 buffer lead + (3h/2, w), its Yuv420Frames views)"""
+    buf = torch.empty(tuple(lead) + (h * 3 // 2, w), device=device, dtype=torch.uint8)
+    return buf, yuv420_views(buf, h, w, layout)
+
+
+def empty_yuv420p16(lead, h, w, layout, device, dtype=torch.int16):
+    """-> (packed buffer of 16-bit words lead + (3h/2, w), its Yuv420Frames16 views)"""
+    buf = torch.empty(tuple(lead) + (h * 3 // 2, w), device=device, dtype=dtype)
+    return buf, yuv420p16_views(buf, h, w, layout)
+
+
+def frames_to_yuv420(planes, standard='bt601-limited', layout='nv12', out=None):
+    """(n,t,3,h,w) or (t,3,h,w) fp32 CUDA planes -> (packed uint8 buffer (...,3h/2,w) in `layout`, its Yuv420Frames views): clamp,
+    luma, box-mean chroma, round half to even (include/pnpvcve.h).  out: Yuv420Frames views to write instead of a fresh buffer
+    (any pitch and address; returns (None, out))."""
+    return _frames_to_yuv(planes, standard, out, Yuv420Frames, lambda lead, h, w, dev: empty_yuv420(lead, h, w, layout, dev))
+
+
+def frames_to_yuv420p16(planes, standard='bt601-limited', layout='yuv420p10le', out=None, dtype=torch.int16):
+    """(n,t,3,h,w) or (t,3,h,w) fp32 CUDA planes -> (packed buffer of 16-bit words (...,3h/2,w) in `layout`, its Yuv420Frames16
+    views): clamp, luma, box-mean chroma, round half to even to [0, 2^d - 1], the bits outside the value zero (include/pnpvcve.h).
+    out: Yuv420Frames16 views to write instead of a fresh buffer (any pitch, any even address; returns (None, out)); the depth and
+    container are then out's."""
+    return _frames_to_yuv(planes, standard, out, Yuv420Frames16, lambda lead, h, w, dev: empty_yuv420p16(lead, h, w, layout, dev, dtype))
 
 
 def pack_lr_yuv420(frames, standard='bt601-limited', general=False):
     """(include/pnpvcve_debug.h) one clip's Yuv420Frames (t,...) -> the (t,h,w,4) fp32 RGB0 conv source the forward unpacks them into;
     general: the byte-load form whatever the alignment"""
-    d, t, h, w = _yuv_clip_desc(frames)
-    with torch.cuda.device(frames.y.device):
-        out = torch.empty((t, h, w, 4), device=frames.y.device, dtype=torch.float32)
-        _native.check(_native.lib().pnp_debug_pack_lr_yuv420(ctypes.byref(d), _yuv_standard(standard), _ptr(out), t, h, w, int(bool(general)),
-                                                             _stream()), 'pnp_debug_pack_lr_yuv420')
-    return out
+    return _pack_lr_yuv(frames, standard, general, Yuv420Frames)
+
+
+def pack_lr_yuv420p16(frames, standard='bt601-limited', general=False):
+    """(include/pnpvcve_debug.h) one clip's Yuv420Frames16 (t,...) -> the (t,h,w,4) fp32 RGB0 conv source the forward unpacks them
+    into; general: the 2-byte-load form whatever the alignment"""
+    return _pack_lr_yuv(frames, standard, general, Yuv420Frames16)
 
 
 # ---------------------------------------------------------------- plane metrics of 4:2:0 clips (include/pnpvcve.h states the arithmetic)
 _PLANE_BITS = {'y': _native.PLANE_Y, 'u': _native.PLANE_CB, 'v': _native.PLANE_CR}
+
+
+def _metric_planes(planes):
+    """planes of a 4:2:0 metric: any of 'y', 'u', 'v' in any order, each at most once -> in lower case"""
+    if not isinstance(planes, str) or not planes or len(set(planes.lower())) != len(planes) or any(p not in _PLANE_BITS for p in planes.lower()):
+        raise ValueError(f"planes must name each of 'y', 'u', 'v' at most once, got {planes!r}")
+    return planes.lower()
 
 
 def _yuv_metric_pair(a, b, crop_border):
@@ -930,10 +1060,10 @@ def _yuv_metric_pair(a, b, crop_border):
         raise ValueError('a and b must both be 8-bit (Yuv420Frames) or both 16-bit (Yuv420Frames16) clips')
     if isinstance(a, Yuv420Frames16) and _bit_depth(a.bit_depth) != _bit_depth(b.bit_depth):
         raise ValueError(f'the two clips differ in bit depth: {a.bit_depth} and {b.bit_depth}')
-    clips_a, lead_a = _any_yuv_clips(a, 'a')
-    clips_b, lead_b = _any_yuv_clips(b, 'b')
-    da = [_any_yuv_clip_desc(c, 'a') for c in clips_a]
-    db = [_any_yuv_clip_desc(c, 'b') for c in clips_b]
+    clips_a, lead_a = _yuv_clips(a, 'a')
+    clips_b, lead_b = _yuv_clips(b, 'b')
+    da = [_yuv_clip_desc(c, 'a') for c in clips_a]
+    db = [_yuv_clip_desc(c, 'b') for c in clips_b]
     t, h, w = da[0][1:]
     if lead_a != lead_b or any(d[1:] != (t, h, w) for d in da + db):
         raise ValueError(f'the two clips differ in shape: {tuple(a.y.shape)} and {tuple(b.y.shape)}')
@@ -987,9 +1117,7 @@ def ssim_yuv420(a, b, crop_border=0, planes='y'):
     plane).  planes: any of 'y', 'u', 'v' in any order ('yuv', 'u', 'vy', ...); returns a float64 CPU tensor lead + (len(planes),) in
     that order.  Crop as psnr_yuv420.  Two Yuv420Frames16 of one bit depth d: the same on the sample values, L = 2^d - 1
     (pnp_ssim_partials_yuv420p16)."""
-    if not isinstance(planes, str) or not planes or len(set(planes.lower())) != len(planes) or any(p not in _PLANE_BITS for p in planes.lower()):
-        raise ValueError(f"planes must name each of 'y', 'u', 'v' at most once, got {planes!r}")
-    planes = planes.lower()
+    planes = _metric_planes(planes)
     pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border)
     L = _native.lib()
     mask = sum(_PLANE_BITS[p] for p in planes)
@@ -1021,9 +1149,7 @@ def msssim_yuv420(a, b, crop_border=0, planes='y', scales=False):
     each in a layout of its own; returns a float64 CPU tensor lead + (len(planes),) in the order of `planes`, with scales=True also the
     raw per-level means lead + (len(planes), 5, 2) = (CS_s, S_s).  Every cropped plane asked for must be at least 176 x 176: chroma
     planes need 352-line frames."""
-    if not isinstance(planes, str) or not planes or len(set(planes.lower())) != len(planes) or any(p not in _PLANE_BITS for p in planes.lower()):
-        raise ValueError(f"planes must name each of 'y', 'u', 'v' at most once, got {planes!r}")
-    planes = planes.lower()
+    planes = _metric_planes(planes)
     pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border)
     L = _native.lib()
     mask = sum(_PLANE_BITS[p] for p in planes)
@@ -1057,11 +1183,10 @@ def msssim_yuv420(a, b, crop_border=0, planes='y', scales=False):
 
 
 def _xpsnr_args(planes, fps):
-    if not isinstance(planes, str) or not planes or len(set(planes.lower())) != len(planes) or any(p not in _PLANE_BITS for p in planes.lower()):
-        raise ValueError(f"planes must name each of 'y', 'u', 'v' at most once, got {planes!r}")
+    planes = _metric_planes(planes)
     if isinstance(fps, bool) or not isinstance(fps, int) or fps < 1:
         raise ValueError(f'fps must be an integer >= 1 (it chooses the order of the temporal activity), got {fps!r}')
-    return planes.lower(), int(fps)
+    return planes, int(fps)
 
 
 def xpsnr_sums_yuv420(a, b, crop_border=0, planes='y', fps=30):
@@ -1114,206 +1239,6 @@ def xpsnr_yuv420(a, b, crop_border=0, planes='y', fps=30, clip=False):
 
     wsse, db = gather(0, lead + (len(planes),)), gather(1, lead + (len(planes),))
     return (wsse, db, gather(2, lead[:-1] + (len(planes),))) if clip else (wsse, db)
-
-
-# ---------------------------------------------------------------- 10 / 12-bit 4:2:0 frames (include/pnpvcve.h: pnp_yuv420_planes16)
-_Yuv420Base16 = collections.namedtuple('Yuv420Frames16', ['y', 'cb', 'cr', 'bit_depth', 'msb_aligned'], defaults=(10, False))
-
-
-class Yuv420Frames16(_Yuv420Base16):
-    """10 / 12-bit 4:2:0 frames as three CUDA VIEWS of 16-bit words (torch.int16, or torch.uint16 where torch has it: the same bits)
-    of wherever the decoder wrote them: y (n,t,h,w), cb and cr (n,t,h/2,w/2), or without the batch dimension.  bit_depth 10 | 12;
-    msb_aligned: the value sits in the high bits of the word (P010 / P012) instead of the low ones (yuv420p10le / yuv420p12le).
-    Strides are in samples: the last-dimension stride is 1 for y and 1 (planar) or 2 (interleaved: cb and cr one sample apart in one
-    buffer) for chroma.  Nothing is copied; yuv420p16_views builds the views of a packed buffer."""
-    __slots__ = ()
-
-
-# name -> (the 8-bit layout with the same plane order, bit depth, msb_aligned)
-YUV16_LAYOUTS = {'p010': ('nv12', 10, True), 'p012': ('nv12', 12, True), 'yuv420p10le': ('i420', 10, False), 'yuv420p12le': ('i420', 12, False)}
-_WORD_DTYPES = tuple(d for d in (torch.int16, getattr(torch, 'uint16', None)) if d is not None)
-
-
-def _yuv16_layout(layout):
-    """a layout name of YUV16_LAYOUTS or ('nv12' | 'nv21' | 'i420', bit_depth, msb_aligned) -> (order, bit_depth, msb_aligned)"""
-    if isinstance(layout, str):
-        if layout not in YUV16_LAYOUTS:
-            raise ValueError(f'layout must be one of {sorted(YUV16_LAYOUTS)} or (order, bit_depth, msb_aligned), got {layout!r}')
-        return YUV16_LAYOUTS[layout]
-    if not isinstance(layout, (tuple, list)) or len(layout) != 3 or layout[0] not in YUV_LAYOUTS:
-        raise ValueError(f'layout must be one of {sorted(YUV16_LAYOUTS)} or ({YUV_LAYOUTS}, bit_depth, msb_aligned), got {layout!r}')
-    return layout[0], _bit_depth(layout[1]), bool(layout[2])
-
-
-def _bit_depth(d):
-    if isinstance(d, bool) or d not in (10, 12):
-        raise ValueError(f'bit_depth must be 10 or 12, got {d!r}')
-    return int(d)
-
-
-def yuv420p16_views(buf, h, w, layout='yuv420p10le'):
-    """A packed buffer of 16-bit words (..., 3h/2, pitch) -- or flat (..., 3hw/2) for planar layouts -- -> Yuv420Frames16 of views
-    into it (no copy): yuv420_views' rules with samples for bytes.  layout: 'p010' | 'p012' (Y, then interleaved Cb Cr, value in the
-    high bits) | 'yuv420p10le' | 'yuv420p12le' (Y, Cb, Cr planes, value in the low bits), or ('nv12' | 'nv21' | 'i420', bit_depth,
-    msb_aligned)."""
-    order, depth, msb = _yuv16_layout(layout)
-    if h < 2 or w < 2 or h % 2 or w % 2:
-        raise ValueError(f'4:2:0 frames need an even height and width, got {h} x {w}')
-    if not isinstance(buf, torch.Tensor) or buf.dtype not in _WORD_DTYPES:
-        raise TypeError(f'buf must be a tensor of 16-bit words (torch.int16 / torch.uint16), got {getattr(buf, "dtype", type(buf))}')
-    if buf.dim() >= 2 and buf.shape[-2] == h * 3 // 2 and buf.shape[-1] >= w and buf.stride(-1) == 1:
-        pitch = buf.shape[-1]
-        y = buf[..., :h, :w]
-        if order != 'i420':
-            c = buf[..., h:, :w]
-            a, b = c[..., 0::2], c[..., 1::2]
-            return Yuv420Frames16(y, a, b, depth, msb) if order == 'nv12' else Yuv420Frames16(y, b, a, depth, msb)
-        if pitch % 2 or buf.stride(-2) != pitch:
-            raise ValueError('a planar buffer needs an even pitch and whole rows: its chroma rows are half a luma row long')
-        flat = buf.flatten(-2)          # (a view: the two last dimensions are contiguous)
-        n = (h // 2) * (pitch // 2)
-        cb = flat[..., h * pitch:h * pitch + n].unflatten(-1, (h // 2, pitch // 2))[..., :w // 2]
-        cr = flat[..., h * pitch + n:h * pitch + 2 * n].unflatten(-1, (h // 2, pitch // 2))[..., :w // 2]
-        return Yuv420Frames16(y, cb, cr, depth, msb)
-    if order == 'i420' and buf.dim() >= 1 and buf.shape[-1] == h * w * 3 // 2 and buf.stride(-1) == 1:
-        return yuv420p16_views(buf.unflatten(-1, (h * 3 // 2, w)), h, w, (order, depth, msb))
-    raise ValueError(f'buf must be (..., {h * 3 // 2}, pitch >= {w}) 16-bit words with a unit last stride, got {tuple(buf.shape)}')
-
-
-def _yuv16_clip_desc(frames, what='frames'):
-    """Yuv420Frames16 of (t,h,w) / (t,h/2,w/2) views -> (_native.Yuv420Planes16, t, h, w); every refusal a ValueError / TypeError
-    raised before any GPU work"""
-    if not isinstance(frames, Yuv420Frames16):
-        raise TypeError(f'{what} must be ops.Yuv420Frames16(y, cb, cr, bit_depth, msb_aligned)')
-    y, cb, cr, depth, msb = frames
-    depth = _bit_depth(depth)
-    for name, x in (('y', y), ('cb', cb), ('cr', cr)):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise RuntimeError(f'{what}.{name} must be a CUDA/HIP tensor: the PnP-VCVE hot path has no CPU fallback')
-        if x.dtype not in _WORD_DTYPES:
-            raise TypeError(f'{what}.{name} must be int16 or uint16, got {x.dtype}')
-        if x.dim() != 3:
-            raise ValueError(f'{what}.{name} must be (t,rows,cols) per clip, got {tuple(x.shape)}')
-    t, h, w = y.shape
-    if h < 2 or w < 2 or h % 2 or w % 2:
-        raise ValueError(f'4:2:0 frames need an even height and width, got {h} x {w}')
-    if tuple(cb.shape) != (t, h // 2, w // 2) or tuple(cr.shape) != (t, h // 2, w // 2):
-        raise ValueError(f'cb and cr must be (t,h/2,w/2) = {(t, h // 2, w // 2)}, got {tuple(cb.shape)} and {tuple(cr.shape)}')
-    if y.stride(2) != 1:
-        raise ValueError(f'{what}.y must have a unit last stride, got {y.stride(2)}')
-    if cb.stride() != cr.stride() or cb.stride(2) not in (1, 2):
-        raise ValueError(f'{what}.cb and .cr must share their strides, with a last stride of 1 or 2: got {cb.stride()} and {cr.stride()}')
-    step = cb.stride(2)
-    if step == 2 and abs(cb.data_ptr() - cr.data_ptr()) != 2:
-        raise ValueError('chroma with a step of 2 must be interleaved: cb and cr one sample apart (P010 / P012)')
-    if y.stride(1) < w or cb.stride(1) < step * (w // 2) or (t > 1 and (y.stride(0) < 0 or cb.stride(0) < 0)):
-        raise ValueError(f'{what}: a pitch below the row\'s samples (strides {y.stride()}, {cb.stride()})')
-    if (y.data_ptr() | cb.data_ptr() | cr.data_ptr()) & 1:
-        raise ValueError(f'{what}: 16-bit planes must lie at even addresses')
-    d = _native.Yuv420Planes16(y.data_ptr(), cb.data_ptr(), cr.data_ptr(), 2 * y.stride(1), 2 * cb.stride(1), 2 * y.stride(0) if t > 1 else 0,
-                               2 * cb.stride(0) if t > 1 else 0, step, depth, int(bool(msb)))
-    return d, t, h, w
-
-
-def _yuv16_clips(frames, what='frames'):
-    """Yuv420Frames16 with or without the batch dimension -> (list of per-clip Yuv420Frames16, lead shape)"""
-    if not isinstance(frames, Yuv420Frames16):
-        raise TypeError(f'{what} must be ops.Yuv420Frames16(y, cb, cr, bit_depth, msb_aligned)')
-    if any(not isinstance(x, torch.Tensor) for x in frames[:3]):
-        raise TypeError(f'{what}: y, cb and cr must be tensors')
-    d = frames.y.dim()
-    if d not in (3, 4) or frames.cb.dim() != d or frames.cr.dim() != d:
-        raise ValueError(f'{what}: y, cb, cr must all be (n,t,rows,cols) or all (t,rows,cols), got {tuple(frames.y.shape)}, '
-                         f'{tuple(frames.cb.shape)}, {tuple(frames.cr.shape)}')
-    if d == 3:
-        return [frames], ()
-    n = frames.y.shape[0]
-    if frames.cb.shape[0] != n or frames.cr.shape[0] != n:
-        raise ValueError(f'{what}: y, cb and cr disagree in the batch size')
-    return [Yuv420Frames16(frames.y[b], frames.cb[b], frames.cr[b], frames.bit_depth, frames.msb_aligned) for b in range(n)], (n,)
-
-
-def is_yuv(frames):
-    """frames are 4:2:0 planes of either sample size"""
-    return isinstance(frames, (Yuv420Frames, Yuv420Frames16))
-
-
-def _any_yuv_clips(frames, what='frames'):
-    """_yuv_clips / _yuv16_clips by the type of `frames`"""
-    return _yuv16_clips(frames, what) if isinstance(frames, Yuv420Frames16) else _yuv_clips(frames, what)
-
-
-def _any_yuv_clip_desc(frames, what='frames'):
-    """_yuv_clip_desc / _yuv16_clip_desc by the type of `frames`"""
-    return _yuv16_clip_desc(frames, what) if isinstance(frames, Yuv420Frames16) else _yuv_clip_desc(frames, what)
-
-
-def frames_from_yuv420p16(frames, standard='bt601-limited'):
-    """Yuv420Frames16 (n,t,...) or (t,...) -> (n,t,3,h,w) / (t,3,h,w) fp32 RGB planes, clamped to [0,1], chroma replicated: the
-    arithmetic of include/pnpvcve.h at the frames' depth, bit-equal to tests/yuv16_ref.py.  What generator.forward(Yuv420Frames16)
-    computes on, without this fp32 clip."""
-    std = _yuv_standard(standard)
-    clips, lead = _yuv16_clips(frames)
-    descs = [_yuv16_clip_desc(c) for c in clips]
-    _, t, h, w = descs[0]
-    if any(d[1:] != (t, h, w) for d in descs):
-        raise ValueError('the clips of a batch must agree in shape')
-    dev = frames.y.device
-    with torch.cuda.device(dev):
-        out = torch.empty((len(clips), t, 3, h, w), device=dev, dtype=torch.float32)
-        for b, (d, _, _, _) in enumerate(descs):
-            if t:
-                _native.check(_native.lib().pnp_frames_from_yuv420p16(ctypes.byref(d), std, _ptr(out[b]), t, h, w, _stream()),
-                              'pnp_frames_from_yuv420p16')
-    return out if lead else out[0]
-
-
-def empty_yuv420p16(lead, h, w, layout, device, dtype=torch.int16):
-    """-> (packed buffer of 16-bit words lead + (3h/2, w), its Yuv420Frames16 views)"""
-    buf = torch.empty(tuple(lead) + (h * 3 // 2, w), device=device, dtype=dtype)
-    return buf, yuv420p16_views(buf, h, w, layout)
-
-
-def frames_to_yuv420p16(planes, standard='bt601-limited', layout='yuv420p10le', out=None, dtype=torch.int16):
-    """(n,t,3,h,w) or (t,3,h,w) fp32 CUDA planes -> (packed buffer of 16-bit words (...,3h/2,w) in `layout`, its Yuv420Frames16
-    views): clamp, luma, box-mean chroma, round half to even to [0, 2^d - 1], the bits outside the value zero (include/pnpvcve.h).
-    out: Yuv420Frames16 views to write instead of a fresh buffer (any pitch, any even address; returns (None, out)); the depth and
-    container are then out's."""
-    std = _yuv_standard(standard)
-    planes = _chk(planes, 'planes')
-    if planes.dim() not in (4, 5) or planes.shape[-3] != 3:
-        raise ValueError(f'planes must be (n,t,3,h,w) or (t,3,h,w), got {tuple(planes.shape)}')
-    h, w = planes.shape[-2:]
-    if h < 2 or w < 2 or h % 2 or w % 2:
-        raise ValueError(f'4:2:0 frames need an even height and width, got {h} x {w}')
-    lead = tuple(planes.shape[:-3])
-    with torch.cuda.device(planes.device):
-        buf = None
-        if out is None:
-            buf, out = empty_yuv420p16(lead, h, w, layout, planes.device, dtype)
-        clips, olead = _yuv16_clips(out, 'out')
-        src = planes if planes.dim() == 5 else planes[None]
-        if len(clips) != src.shape[0]:
-            raise ValueError('out and planes disagree in the batch size')
-        for b, c in enumerate(clips):
-            d, t, oh, ow = _yuv16_clip_desc(c, 'out')
-            if (t, oh, ow) != (src.shape[1], h, w):
-                raise ValueError(f'out is {(t, oh, ow)}, planes are {(src.shape[1], h, w)}')
-            if t:
-                _native.check(_native.lib().pnp_frames_to_yuv420p16(_ptr(src[b]), ctypes.byref(d), std, t, h, w, _stream()),
-                              'pnp_frames_to_yuv420p16')
-    return buf, out
-
-
-def pack_lr_yuv420p16(frames, standard='bt601-limited', general=False):
-    """(include/pnpvcve_debug.h) one clip's Yuv420Frames16 (t,...) -> the (t,h,w,4) fp32 RGB0 conv source the forward unpacks them
-    into; general: the 2-byte-load form whatever the alignment"""
-    d, t, h, w = _yuv16_clip_desc(frames)
-    with torch.cuda.device(frames.y.device):
-        out = torch.empty((t, h, w, 4), device=frames.y.device, dtype=torch.float32)
-        _native.check(_native.lib().pnp_debug_pack_lr_yuv420p16(ctypes.byref(d), _yuv_standard(standard), _ptr(out), t, h, w, int(bool(general)),
-                                                                _stream()), 'pnp_debug_pack_lr_yuv420p16')
-    return out
 
 
 # ---------------------------------------------------------------- self-ensemble (include/pnpvcve.h, "Self-ensemble")

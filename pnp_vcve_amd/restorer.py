@@ -282,7 +282,7 @@ class BasicVSR(nn.Module):
         else:
             lq_planes = lq
             if yuv_in:
-                lq_planes = (ops.frames_from_yuv420p16 if isinstance(lq, ops.Yuv420Frames16) else ops.frames_from_yuv420)(lq, yuv_standard)
+                lq_planes = ops._frames_from_yuv(lq, yuv_standard)
             elif lq.dtype == torch.uint8 and lq.ndim == 5 and lq.is_cuda:       # byte frames: hand back the planes the caller knows
                 from .ops import frames_from_rgb8
                 lq_planes = frames_from_rgb8(lq)
@@ -340,7 +340,7 @@ class BasicVSR(nn.Module):
             assert gt is not None, 'evaluation with metrics must have gt images.'
             results = dict(eval_result=self.evaluate(output, gt))
         else:
-            from_planes = ops.frames_from_yuv420p16 if isinstance(lq, ops.Yuv420Frames16) else ops.frames_from_yuv420
+            from_planes = ops._frames_from_yuv
             results = dict(lq=from_planes(lq, yuv_standard).cpu(), output=buf.cpu())
             if gt is not None:
                 results['gt'] = type(gt)(*[p.cpu() for p in gt[:3]], *gt[3:])

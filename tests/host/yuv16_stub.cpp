@@ -4,8 +4,9 @@
 //     g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DPNP_HOST_STUB -Dmain=sched_stub_main
 //         -x c++ tests/host/yuv16_stub.cpp
 // It reuses tests/host/sched_stub.cpp unchanged (recording launchers over csrc/generator.hip; its driver is renamed away).  The
-// launchers of the two 4:2:0 boundaries are recorded by csrc/host_stub/yuv_stub.h and yuv16_stub.h; the hooks below give them, and
-// conv_last's launch behind a 4:2:0 clip, the range bookkeeping the other launchers have.  One JSON object per scenario:
+// launchers of the 4:2:0 boundary are recorded by csrc/host_stub/yuv_stub.h, one record type whose sample_bytes tells the 8-bit run
+// from the 16-bit one; the hooks below give them, and conv_last's launch behind a 4:2:0 clip, the range bookkeeping the other
+// launchers have.  One JSON object per scenario:
 //   * every plane of every 16-bit clip is a heap block of its own that ends with the last sample of its last row (ASan's red zone
 //     behind it) and starts 10 bytes into the block behind 8 poisoned bytes: even addresses that are not 4-byte aligned, pitches of
 //     a row plus 2 or 6 bytes.  Only the samples inside a row's width count as written, so a launch that reads a row's padding, or
@@ -18,6 +19,7 @@
 #include <unordered_map>
 
 #include "sched_stub.cpp"
+#include "yuv_common.h"      // each_row, Block, any_written
 
 namespace {
 
@@ -27,30 +29,10 @@ int n_pack = 0, n_pack_fast = 0, n_from = 0, n_to = 0, n_to8 = 0, n_last_io = 0,
 bool count_writes = false;
 std::unordered_map<uintptr_t, int> out_writes;      // byte address -> times a 16-bit output launch wrote it
 
-// the bytes of `frames` frames of h x w a launch touches: each row's samples, nothing of the padding.  S: bytes of a sample;
-// pitches and frame strides are bytes in both descriptors, c_step is samples
-template <int S, class P, class F>
-void each_row(const P& p, int frames, int h, int w, F f) {
-    auto at = [](auto* q, int64_t bytes) { return (unsigned char*)q + bytes; };
-    for (int i = 0; i < frames; ++i) {
-        for (int r = 0; r < h; ++r) f("a row of the Y plane", at(p.y, (int64_t)i * p.y_frame + (int64_t)r * p.y_pitch), (size_t)w * S);
-        for (int r = 0; r < h / 2; ++r) {
-            const int64_t o = (int64_t)i * p.c_frame + (int64_t)r * p.c_pitch;
-            if (p.c_step == 2) {
-                f("a row of interleaved chroma", at(p.cb < p.cr ? p.cb : p.cr, o), (size_t)w * S);
-            } else {
-                f("a row of the Cb plane", at(p.cb, o), (size_t)w / 2 * S);
-                f("a row of the Cr plane", at(p.cr, o), (size_t)w / 2 * S);
-            }
-        }
-    }
-}
+// (the 8- and the 16-bit run go through the same three launchers)
+const char* const names[3] = {"launch_pack_lr_yuv420", "launch_frames_from_yuv420", "launch_frames_to_yuv420"};
 
-const char* const names8[3] = {"launch_pack_lr_yuv420", "launch_frames_from_yuv420", "launch_frames_to_yuv420"};
-const char* const names16[3] = {"launch_pack_lr_yuv420p16", "launch_frames_from_yuv420p16", "launch_frames_to_yuv420p16"};
-
-template <int S, class R>
-void yuv_launch(const R& r, const char* const* names) {
+void yuv_launch(const PnpStubYuvLaunch& r) {
     Tr(names[r.kind], r.stream).p("y", r.planes.y).p("cb", r.planes.cb).p("cr", r.planes.cr).p("in", r.in).p("out", r.out).i("frames", r.frames)
         .i("H", r.h).i("W", r.w);
     note_launch(r.stream);
@@ -63,32 +45,31 @@ void yuv_launch(const R& r, const char* const* names) {
     };
     switch (r.kind) {
         case PNP_STUB_YUV_PACK:
-            each_row<S>(r.planes, r.frames, r.h, r.w, rd);
+            each_row(r.planes, r.frames, r.h, r.w, rd);
             WR("the packed RGB0 frames", r.out, px * 16);
             break;
         case PNP_STUB_YUV_FROM:
             if (r.frames != 1) fail("a staged conversion of more than one frame");
-            each_row<S>(r.planes, r.frames, r.h, r.w, rd);
+            each_row(r.planes, r.frames, r.h, r.w, rd);
             WR("a frame of fp32 planes", r.out, px * 12);
             break;
         default:
             if (r.frames != 1) fail("an output conversion of more than one frame");
             RD("a frame of fp32 planes", r.in, px * 12);
-            each_row<S>(r.planes, r.frames, r.h, r.w, wr);
+            each_row(r.planes, r.frames, r.h, r.w, wr);
     }
 }
 
-void yuv8_hook(const PnpStubYuvLaunch& r) {
-    ++n8;
-    yuv_launch<1>(r, names8);
-}
-
-void yuv16_hook(const PnpStubYuv16Launch& r) {
-    n_pack += r.kind == PNP_STUB_YUV_PACK;
-    n_pack_fast += r.kind == PNP_STUB_YUV_PACK && r.fast;
-    n_from += r.kind == PNP_STUB_YUV_FROM;
-    n_to += r.kind == PNP_STUB_YUV_TO;
-    yuv_launch<2>(r, names16);
+void yuv_hook(const PnpStubYuvLaunch& r) {
+    if (r.planes.sample_bytes == 1) {
+        ++n8;
+    } else {
+        n_pack += r.kind == PNP_STUB_YUV_PACK;
+        n_pack_fast += r.kind == PNP_STUB_YUV_PACK && r.fast;
+        n_from += r.kind == PNP_STUB_YUV_FROM;
+        n_to += r.kind == PNP_STUB_YUV_TO;
+    }
+    yuv_launch(r);
 }
 
 void io_hook(const PnpStubIoLaunch& r) {
@@ -126,33 +107,10 @@ void reset() {
     mixes.clear();
     pnp_stub_io_log.clear();
     pnp_stub_yuv_log.clear();
-    pnp_stub_yuv16_log.clear();
     out_writes.clear();
     dcn_calls = 0;
     n_pack = n_pack_fast = n_from = n_to = n_to8 = n_last_io = n8 = 0;
 }
-
-// One plane (or one interleaved chroma pair) of a clip: a heap block whose first 8 bytes are poisoned, the plane `lead` bytes in, the
-// block ending with the last sample of the last row.
-struct Block {
-    unsigned char *base = nullptr, *p = nullptr;
-    size_t bytes = 0;
-    void make(int t, int rows, int64_t pitch, int64_t frame, int64_t row_bytes, int lead) {
-        bytes = (size_t)((t - 1) * frame + (rows - 1) * pitch + row_bytes);
-        base = (unsigned char*)malloc(lead + bytes);      // (malloc: 16-byte aligned)
-        p = base + lead;
-#if PNP_HAVE_ASAN
-        ASAN_POISON_MEMORY_REGION(base, 8);
-#endif
-    }
-    void release() {
-#if PNP_HAVE_ASAN
-        if (base) ASAN_UNPOISON_MEMORY_REGION(base, 8);
-#endif
-        free(base);
-        base = p = nullptr;
-    }
-};
 
 // S = 1: pnp_yuv420_planes (D), bytes; S = 2: pnp_yuv420_planes16, 16-bit words.  layout 0: Y + interleaved Cb Cr | 1: Cr Cb | 2: planar.
 // ragged: planes 10 bytes into their blocks, pitches of a row plus 2 (Y) or 6 (chroma) bytes; otherwise 16 bytes in, pitches rounded
@@ -196,13 +154,6 @@ struct Scenario16 {
     pnp_generator_cfg cfg;
     int prec, n, t, h, w, contexts, layout, depth, msb, out_depth, out_msb, out_mask, last_valu, any_size, ragged;
 };
-
-bool any_written(const void* p, size_t n) {
-    const uintptr_t lo = (uintptr_t)p, hi = lo + n;
-    for (const auto& iv : written)
-        if (iv.first < hi && iv.second > lo) return true;
-    return false;
-}
 
 // what the comparison of the two traces leaves out: the pack launch, the staged conversion and the output conversion
 std::vector<std::string> comparable(const std::vector<std::string>& tr) {
@@ -248,8 +199,7 @@ int run(const Scenario16& sc) {
     pnp_stub_stream caller{0};
     const int prc = pnp_generator_pack(g, flat, packed, &caller);
     pnp_stub_io_hook = io_hook;
-    pnp_stub_yuv_hook = yuv8_hook;
-    pnp_stub_yuv16_hook = yuv16_hook;
+    pnp_stub_yuv_hook = yuv_hook;
     std::vector<pnp_clip_yuv> clips8(n);
     std::vector<pnp_clip_yuv16> clips16(n);
     std::vector<ClipPlanes<1>> in8(n), out8(n);
@@ -280,8 +230,8 @@ int run(const Scenario16& sc) {
             mark(clips8[b].mvs_dev, (size_t)t * 4 * hw * 4);
             mark(clips8[b].par_dev, (size_t)t * 3 * hw * 4);
             auto mk = [](const char*, const unsigned char* p, size_t k) { mark(p, k); };      // (a row's samples, not its padding)
-            each_row<1>(clips8[b].lq, t, sc.h, sc.w, mk);
-            each_row<2>(clips16[b].lq, t, sc.h, sc.w, mk);
+            each_row(yuv_planes(clips8[b].lq), t, sc.h, sc.w, mk);
+            each_row(yuv_planes(clips16[b].lq), t, sc.h, sc.w, mk);
         }
     };
     // the 8-bit 4:2:0 boundary on the same handle, workspace and outputs: once to make its streams and events, once for the trace
@@ -330,7 +280,7 @@ int run(const Scenario16& sc) {
         if ((sc.out_mask & PNP_OUT_F32) ? !f_w : any_written(clips16[b].out_f32_dev, out_px * 4)) fail("the fp32 output is not what the mask asks for");
         if ((sc.out_mask & PNP_OUT_U8) ? !u_w : any_written(clips16[b].out_u8_dev, out_px)) fail("the uint8 output is not what the mask asks for");
         if (sc.out_mask & PNP_OUT_YUV420)
-            each_row<2>(clips16[b].out_yuv16, t, H, W, [&](const char* what, const unsigned char* p, size_t k) {
+            each_row(yuv_planes(clips16[b].out_yuv16), t, H, W, [&](const char* what, const unsigned char* p, size_t k) {
                 for (size_t j = 0; j < k; ++j) {
                     const auto it = out_writes.find((uintptr_t)p + j);
                     if (it == out_writes.end() || it->second != 1) return fail(std::string("a sample of ") + what + " of the output was not written exactly once");
@@ -340,10 +290,14 @@ int run(const Scenario16& sc) {
     }
     if (rc16 == 0 && out_writes.size() != expect_writes) fail("a 16-bit output launch wrote bytes that are no sample of a requested output plane");
     const bool staged = io_staged(g);
-    for (const PnpStubYuv16Launch& r : pnp_stub_yuv16_log) {
+    for (const PnpStubYuvLaunch& r : pnp_stub_yuv_log) {      // (the log was reset behind the 8-bit run)
+        if (r.planes.sample_bytes != 2) {
+            fail("a launch at the 16-bit boundary does not name 16-bit words");
+            continue;
+        }
         if (r.kind == PNP_STUB_YUV_PACK) {
             bool own = false;
-            for (int b = 0; b < n; ++b) own = own || r.planes.y == clips16[b].lq.y;
+            for (int b = 0; b < n; ++b) own = own || r.planes.y == (unsigned char*)clips16[b].lq.y;
             if (!own || r.frames != t || r.h != sc.h || r.w != sc.w) fail("a pack launch does not read one clip's t frames");
             if (r.fast != !sc.ragged) fail("the pack launch's form does not follow the planes' alignment");
         }
@@ -353,7 +307,6 @@ int run(const Scenario16& sc) {
     }
     pnp_stub_io_hook = nullptr;
     pnp_stub_yuv_hook = nullptr;
-    pnp_stub_yuv16_hook = nullptr;
     std::vector<int> streams_used = launch_streams;
     std::sort(streams_used.begin(), streams_used.end());
     streams_used.erase(std::unique(streams_used.begin(), streams_used.end()), streams_used.end());

@@ -16,6 +16,7 @@
 #include <unordered_map>
 
 #include "sched_stub.cpp"
+#include "yuv_common.h"      // each_row, Block, any_written
 
 namespace {
 
@@ -23,23 +24,6 @@ using namespace stub;
 
 int n_pack = 0, n_pack_fast = 0, n_from = 0, n_to = 0, n_to8 = 0, n_last_io = 0, n_last_rgb0 = 0;
 std::unordered_map<uintptr_t, int> out_writes;      // byte address -> times a 4:2:0 output launch wrote it
-
-// the bytes of `frames` frames of h x w a launch touches: each row's samples, nothing of the padding
-template <class F>
-void each_row(const pnp_yuv420_planes& p, int frames, int h, int w, F f) {
-    for (int i = 0; i < frames; ++i) {
-        for (int r = 0; r < h; ++r) f("a row of the Y plane", p.y + (int64_t)i * p.y_frame + (int64_t)r * p.y_pitch, (size_t)w);
-        for (int r = 0; r < h / 2; ++r) {
-            const int64_t o = (int64_t)i * p.c_frame + (int64_t)r * p.c_pitch;
-            if (p.c_step == 2) {
-                f("a row of interleaved chroma", (p.cb < p.cr ? p.cb : p.cr) + o, (size_t)w);
-            } else {
-                f("a row of the Cb plane", p.cb + o, (size_t)w / 2);
-                f("a row of the Cr plane", p.cr + o, (size_t)w / 2);
-            }
-        }
-    }
-}
 
 void trace_yuv(const PnpStubYuvLaunch& r) {
     static const char* const names[3] = {"launch_pack_lr_yuv420", "launch_frames_from_yuv420", "launch_frames_to_yuv420"};
@@ -123,45 +107,23 @@ void reset() {
     n_pack = n_pack_fast = n_from = n_to = n_to8 = n_last_io = n_last_rgb0 = 0;
 }
 
-// One plane (or one interleaved chroma pair) of a clip: a heap block whose first 8 bytes are poisoned, the plane 9 bytes in, the block
-// ending with the last sample of the last row.
-struct Block {
-    unsigned char *base = nullptr, *p = nullptr;
-    size_t bytes = 0;
-    void make(int t, int rows, int64_t pitch, int64_t frame, int row_bytes) {
-        bytes = (size_t)((t - 1) * frame + (rows - 1) * pitch + row_bytes);
-        base = (unsigned char*)malloc(9 + bytes);
-        p = base + 9;
-#if PNP_HAVE_ASAN
-        ASAN_POISON_MEMORY_REGION(base, 8);
-#endif
-    }
-    void release() {
-#if PNP_HAVE_ASAN
-        if (base) ASAN_UNPOISON_MEMORY_REGION(base, 8);
-#endif
-        free(base);
-        base = p = nullptr;
-    }
-};
-
 struct ClipPlanes {
     Block y, c0, c1;
     pnp_yuv420_planes d;
-    // layout 0 nv12 | 1 nv21 | 2 i420; pitches odd: w + 7 for Y, for chroma w + 5 (interleaved) or w/2 + 3
+    // planes 9 bytes into their blocks; layout 0 nv12 | 1 nv21 | 2 i420; pitches odd: w + 7 for Y, for chroma w + 5 (interleaved) or w/2 + 3
     void make(const std::string& name, int layout, int t, int h, int w) {
         const int64_t yp = w + 7, cp = layout == 2 ? w / 2 + 3 : w + 5;
         const int64_t yf = yp * h + 3, cf = cp * (h / 2) + 5;
-        y.make(t, h, yp, yf, w);
+        y.make(t, h, yp, yf, w, 9);
         region(name + ".y", y.p, y.bytes);
         if (layout == 2) {
-            c0.make(t, h / 2, cp, cf, w / 2);
-            c1.make(t, h / 2, cp, cf, w / 2);
+            c0.make(t, h / 2, cp, cf, w / 2, 9);
+            c1.make(t, h / 2, cp, cf, w / 2, 9);
             region(name + ".cb", c0.p, c0.bytes);
             region(name + ".cr", c1.p, c1.bytes);
             d = pnp_yuv420_planes{y.p, c0.p, c1.p, yp, cp, yf, cf, 1};
         } else {
-            c0.make(t, h / 2, cp, cf, w);
+            c0.make(t, h / 2, cp, cf, w, 9);
             region(name + ".c", c0.p, c0.bytes);
             d = pnp_yuv420_planes{y.p, layout == 0 ? c0.p : c0.p + 1, layout == 0 ? c0.p + 1 : c0.p, yp, cp, yf, cf, 2};
         }
@@ -174,13 +136,6 @@ struct YuvScenario {
     pnp_generator_cfg cfg;
     int prec, n, t, h, w, contexts, layout, out_mask, last_valu, max_resident, any_size;
 };
-
-bool any_written(const void* p, size_t n) {
-    const uintptr_t lo = (uintptr_t)p, hi = lo + n;
-    for (const auto& iv : written)
-        if (iv.first < hi && iv.second > lo) return true;
-    return false;
-}
 
 // what the comparison of the two traces leaves out: the pack launch and the converters go, a conv_last launch becomes one token
 std::vector<std::string> comparable(const std::vector<std::string>& tr) {
@@ -258,7 +213,7 @@ int run_yuv(YuvScenario sc) {
             mark(fclips[b].lq_dev, (size_t)t * 3 * hw * 4);
             mark(fclips[b].mvs_dev, (size_t)t * 4 * hw * 4);
             mark(fclips[b].par_dev, (size_t)t * 3 * hw * 4);
-            each_row(in[b].d, t, sc.h, sc.w, [](const char*, const unsigned char* p, size_t k) { mark(p, k); });      // (a row's samples, not its padding)
+            each_row(yuv_planes(in[b].d), t, sc.h, sc.w, [](const char*, const unsigned char* p, size_t k) { mark(p, k); });      // (a row's samples, not its padding)
         }
     };
     // the fp32 boundary on the same handle: once to make its streams and events, once for the trace
@@ -308,7 +263,7 @@ int run_yuv(YuvScenario sc) {
         if ((sc.out_mask & PNP_OUT_F32) ? !f_w : any_written(yclips[b].out_f32_dev, out_px * 4)) fail("the fp32 output is not what the mask asks for");
         if ((sc.out_mask & PNP_OUT_U8) ? !u_w : any_written(yclips[b].out_u8_dev, out_px)) fail("the uint8 output is not what the mask asks for");
         if (sc.out_mask & PNP_OUT_YUV420)
-            each_row(out[b].d, t, H, W, [&](const char* what, const unsigned char* p, size_t k) {
+            each_row(yuv_planes(out[b].d), t, H, W, [&](const char* what, const unsigned char* p, size_t k) {
                 for (size_t j = 0; j < k; ++j) {
                     const auto it = out_writes.find((uintptr_t)p + j);
                     if (it == out_writes.end() || it->second != 1) return fail(std::string("a sample of ") + what + " of the output was not written exactly once");
@@ -329,6 +284,7 @@ int run_yuv(YuvScenario sc) {
             fail("a conversion of more than one frame");
         }
         if (r.kind == PNP_STUB_YUV_FROM && !staged) fail("a frame was converted to fp32 planes in front of a last conv that reads RGB0");
+        if (r.planes.sample_bytes != 1 || r.planes.bit_depth != 8 || r.planes.msb_aligned) fail("a launch at the 8-bit boundary does not name bytes");
     }
     int rgb_heads = 0;
     for (const ConvRec& cr : convs)
