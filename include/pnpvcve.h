@@ -228,8 +228,35 @@ int64_t pnp_generator_workspace_bytes_io(const pnp_generator* g, int t, int h, i
  *   RGB -> bytes: r, g, b clamped to [0, 1]; yl = (Kr * r + Kg * g) + Kb * b; Y = clamp(rint(float(yoff) + sy * yl), 0, 255), rint
  *   rounding half to even; per pixel pb = (b - yl) * (0.5 / (1 - Kb)), pr = (r - yl) * (0.5 / (1 - Kr)); the chroma sample of a 2x2
  *   block is the BOX MEAN ((p00 + p01) + (p10 + p11)) * 0.25 (rows top then bottom, columns left then right) and
- *   Cb = clamp(rint(128 + sc * mean_pb), 0, 255), Cr likewise.  Box-down and replicate-up are consistent (centre siting); other
- *   sitings and filters, 4:2:2 and 4:4:4 are not offered (10 and 12 bit: pnp_yuv420_planes16 below).  Limited-range white (235,128,128) gives 0.99999994, not 1.
+ *   Cb = clamp(rint(128 + sc * mean_pb), 0, 255), Cr likewise.  Box-down and replicate-up are consistent (centre siting) and are the
+ *   DEFAULT chroma mode; the other modes are stated below.  4:2:2 and 4:4:4 are not offered (10 and 12 bit: pnp_yuv420_planes16
+ *   below).  Limited-range white (235,128,128) gives 0.99999994, not 1.
+ * Chroma modes (siting and filters; opt-in, at every depth; tests/yuv_chroma_ref.py restates them in numpy).  This is the ONE statement
+ * of them; like the rest of this boundary, and like MS-SSIM's and XPSNR's arithmetic below, the definition is the project's own: no
+ * external tool's digits are pinned.  Every entry that takes yuv_standard takes PNP_YUV_CODE(standard, chroma): the standard 0..3 in
+ * bits 0..7, the mode in bits 8..11, so a bare standard is mode 0 and what it always was.  A mode selects BOTH directions:
+ *     mode                          chroma sample (j, i) lies at luma (row, column)   planes -> RGB   RGB -> planes
+ *     0 PNP_YUV_CHROMA_REPLICATE    (2j + 1/2, 2i + 1/2)                              replication     box mean       (the default, above)
+ *     1 PNP_YUV_CHROMA_CENTER       (2j + 1/2, 2i + 1/2)                              bilinear        box mean
+ *     2 PNP_YUV_CHROMA_LEFT         (2j + 1/2, 2i)     H.264 / HEVC / VVC type 0      bilinear        [1 2 1] / 4 across, box down
+ *     3 PNP_YUV_CHROMA_TOPLEFT      (2j,       2i)     BT.2020 / UHD type 2           bilinear        [1 2 1] / 4 both ways
+ *   An axis is CO-SITED where chroma lies on the even luma indices (x for LEFT; x and y for TOPLEFT) and MIDWAY otherwise.
+ *   Planes -> RGB, modes 1..3: per axis, luma index k with i = k >> 1 takes two chroma indices with weights in quarters, n the chroma
+ *   plane's extent on that axis:
+ *       co-sited axis:  even k: (i: 4)                        odd k: (i: 2, min(i + 1, n - 1): 2)
+ *       midway axis:    even k: (i: 3, max(i - 1, 0): 1)      odd k: (i: 3, min(i + 1, n - 1): 1)
+ *   Indices clamp; nothing outside the plane is read.  The interpolated chroma is an exact integer, u16 = sum of wy * wx * (Cb[a][b] -
+ *   mid) over the two rows a and the two columns b (the weights sum to 16; mid = 128, or 2^(d-1)), and u = float(u16) * 0.0625f, v
+ *   likewise from Cr.  |u16| < 2^16 at 12 bit, so the fp32 value is exact and there is no summation order to pin.  From u, v on, the
+ *   formulas, constants, clamp and the rule of no contraction are the ones above, word for word; Y is untouched.  The limited-range
+ *   identity of the 16-bit statement carries over: u16 scales by s exactly.
+ *   RGB -> planes, modes 2 and 3: pb, pr per pixel are the ones above; every operation below is one fp32 operation rounded on its own.
+ *   On a co-sited axis the sample at 2i takes the taps L = max(2i - 1, 0), C = 2i, R = 2i + 1 as ((pL + pR) + (pC + pC)) * 0.25; on a
+ *   midway axis it takes (p0 + p1) * 0.5 of 2i and 2i + 1.  LEFT: each of the rows 2j and 2j + 1 is filtered across first, then the two
+ *   are combined.  TOPLEFT: the rows max(2j - 1, 0), 2j, 2j + 1 are filtered across, then combined with the three-tap form.  Modes 0
+ *   and 1 keep the box mean's expression.  Rounding and clamping to samples are unchanged; so is Y.
+ *   A chroma ramp C[i] = a + b i therefore upsamples to a + b (x - off) / 2 exactly away from the clamped edges, off = 0 on a
+ *   co-sited axis and 1/2 on a midway one.  A mode above 3, any bit from 12 up and a low byte above 3 are PNP_ERR_BAD_ARG.
  * A plane pointer may sit at ANY byte address and a pitch may be any value that holds a row, odd ones too.  No byte outside
  * [plane, plane + rows * pitch) of a plane is read or written, and inside it the bytes of a row beyond the frame's width are never
  * written.  Planes and pitches that are 4-byte aligned take a faster form of the unpacking (same values).
@@ -247,6 +274,11 @@ int64_t pnp_generator_workspace_bytes_io(const pnp_generator* g, int t, int h, i
 #define PNP_YUV_BT601_FULL 1
 #define PNP_YUV_BT709_LIMITED 2
 #define PNP_YUV_BT709_FULL 3
+#define PNP_YUV_CHROMA_REPLICATE 0
+#define PNP_YUV_CHROMA_CENTER 1
+#define PNP_YUV_CHROMA_LEFT 2
+#define PNP_YUV_CHROMA_TOPLEFT 3
+#define PNP_YUV_CODE(standard, chroma) ((standard) | ((chroma) << 8))
 #define PNP_OUT_YUV420 4
 typedef struct pnp_yuv420_planes {      /* t frames of h x w, 8 bit, 4:2:0 */
     unsigned char *y, *cb, *cr;         /* first frame's planes; NV12: cr == cb + 1, c_step 2; NV21: cb == cr + 1; I420: c_step 1 */
@@ -310,8 +342,8 @@ int pnp_ssim_partials_yuv420(const pnp_yuv420_planes* a_host_desc, const pnp_yuv
  *   value to zero.
  *   Range constants, with s = 2^(d-8): limited range yoff = 16 s, sy = 219 s, sc = 224 s; full range yoff = 0, sy = sc = 2^d - 1; the
  *   chroma midpoint is 2^(d-1) in both (it takes the place of 128).
- *   Kr, Kb, the formulas, the clamp to [0, 1], replicated chroma on the way in and the box mean on the way out are those of the 8-bit
- *   statement above, word for word, with these constants; rounding is rint, half to even, clamped to [0, 2^d - 1].  Every constant
+ *   Kr, Kb, the formulas, the clamp to [0, 1], replicated chroma on the way in and the box mean on the way out (and the other chroma
+ *   modes, PNP_YUV_CODE) are those of the 8-bit statement above, word for word, with these constants; rounding is rint, half to even, clamped to [0, 2^d - 1].  Every constant
  *   is evaluated in double and rounded to fp32 ONCE; every later product and sum is an fp32 operation of its own, no contraction.
  *   The limited-range identity: in limited range every constant is the 8-bit one times an exact power of two (cy, crv, ... divided by
  *   s; yoff, sy, sc and the midpoint times s), and float(s Y - 16 s) = s float(Y - 16) exactly.  So planes whose samples are s

@@ -58,7 +58,8 @@ int pnp_debug_pack_lr_u8(const unsigned char* lq_dev, float* lr4_dev, int t, int
 
 /* The 4:2:0 unpacking in front of pnp_generator_forward_clips_yuv's convs, alone: t frames of planes -> lr4_dev (t,h,w,4) fp32 RGB0,
  * the values of pnp_frames_from_yuv420.  general = 0: the form the forward picks (the aligned one where planes and pitches are 4-byte
- * aligned and w is a multiple of 4); 1: the byte-load form whatever the alignment.  Same values either way. */
+ * aligned and w is a multiple of 4); 1: the byte-load form whatever the alignment.  Same values either way.  yuv_standard takes
+ * PNP_YUV_CODE(standard, chroma) as every 4:2:0 entry does: a chroma mode other than 0 runs the sited forms of the two kernels. */
 int pnp_debug_pack_lr_yuv420(const pnp_yuv420_planes* in_host_desc, int yuv_standard, float* lr4_dev, int t, int h, int w,
                              int general, void* stream);
 /* The same for 10 / 12-bit planes (pnp_generator_forward_clips_yuv16): the values of pnp_frames_from_yuv420p16.  general = 0: the

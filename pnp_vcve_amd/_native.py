@@ -52,6 +52,7 @@ class ClipYuv16(ctypes.Structure):
 FRAMES_F32_NCHW, FRAMES_U8_HWC = 0, 1        # PNP_FRAMES_*
 OUT_F32, OUT_U8, OUT_YUV420 = 1, 2, 4        # PNP_OUT_* (a mask; OUT_YUV420 on pnp_generator_forward_clips_yuv only)
 YUV_STANDARDS = {'bt601-limited': 0, 'bt601-full': 1, 'bt709-limited': 2, 'bt709-full': 3}      # PNP_YUV_*
+YUV_CHROMA = {'replicate': 0, 'center': 1, 'left': 2, 'topleft': 3}      # PNP_YUV_CHROMA_*: bits 8..11 of PNP_YUV_CODE(standard, chroma)
 COLOR_NONE, COLOR_Y = 0, 1                   # PNP_COLOR_* (the metrics' convert_to)
 PLANE_Y, PLANE_CB, PLANE_CR = 1, 2, 4        # PNP_PLANE_* (a mask: the planes pnp_ssim_partials_yuv420 scores)
 

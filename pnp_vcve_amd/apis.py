@@ -166,6 +166,8 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
     are the plane metrics of BasicVSR.evaluate (ops.psnr_yuv420 / ssim_yuv420: 'PSNR' / 'SSIM' score the Y plane; 'PSNR_U', 'PSNR_V',
     'SSIM_U', 'SSIM_V', 'PSNR_YUV', the 'MS-SSIM' and the 'XPSNR' names are accepted too), and save_image writes <save_path>/<clip>.yuv -- exactly the bytes of
     ops.frames_to_yuv420(fp32 output, standard, layout).  A pair goes through generator.forward_clips by pointer, as under byte_frames.
+    The dataset's `chroma` ('replicate' unless it says otherwise: where its clips' chroma samples lie, include/pnpvcve.h) is the
+    chroma mode of every generator call and of the planes written; the generator is told only when it is not 'replicate'.
     A dataset of 10 / 12-bit clips (its samples' meta carry the depth) goes the same way as ops.Yuv420Frames16; yuv_out_layout then
     also takes 'p010' | 'p012' | 'yuv420p10le' | 'yuv420p12le', the ground truth and the output must agree in depth, and the file is
     ops.frames_to_yuv420p16's words, little-endian.
@@ -206,6 +208,8 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
             raise ValueError(f'yuv_out_layout {yuv_out_layout!r} does not have the dataset\'s bit depth ({depth}): the output is scored '
                              f'against the ground truth at one depth')
     yuv_standard = getattr(dataset, 'yuv_standard', 'bt601-limited')
+    chroma = getattr(dataset, 'chroma', 'replicate')
+    yuv_kw = {'yuv_standard': yuv_standard} if chroma == 'replicate' else {'yuv_standard': yuv_standard, 'chroma': chroma}
     out_dtype = None
     if yuv_frames:
         out_dtype = yuv_out_layout
@@ -222,7 +226,7 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
             if byte_frames or yuv_frames:
                 kw['out_dtype'] = out_dtype
             if yuv_frames:
-                kw['yuv_standard'] = yuv_standard
+                kw.update(yuv_kw)
             res = model(test_mode=True, save_image=save_image, save_path=save_path, **kw, **data)
         if fps is None:
             fps = _frames(data['lq']) / model.last_forward_seconds if getattr(model, 'last_forward_seconds', None) else 0.0
@@ -244,7 +248,7 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
             with torch.no_grad():
                 torch.cuda.synchronize()
                 t0 = time.time()
-                kw = {'yuv_standard': yuv_standard} if yuv_frames else {}
+                kw = dict(yuv_kw) if yuv_frames else {}
                 outs = model.generator.forward_clips([tuple(c[k] for k in GENERATOR_INPUTS) for c in (held, data)], out_dtype=out_dtype, **kw)
                 torch.cuda.synchronize()
                 dt = time.time() - t0

@@ -16,13 +16,18 @@ struct YuvCoef {
     float vmax;                         // 2^d - 1
     unsigned shift;                     // 0 (low-aligned) | 16 - d (high-aligned)
     unsigned vmask;                     // 2^d - 1
+    int chroma;                         // PNP_YUV_CHROMA_*: the siting and filters of both directions (bits 8..11 of the code)
 };
 // depth 8 (low-aligned only: the sample is the byte), or 10 | 12 in a 16-bit word, low- or high-aligned
 static inline bool yuv_depth_ok(int bit_depth, int msb_aligned) {
     return bit_depth == 8 ? msb_aligned == 0 : (bit_depth == 10 || bit_depth == 12) && (msb_aligned == 0 || msb_aligned == 1);
 }
-static inline bool yuv_coef(int standard, int bit_depth, int msb_aligned, YuvCoef* k) {
-    if (standard < PNP_YUV_BT601_LIMITED || standard > PNP_YUV_BT709_FULL || !yuv_depth_ok(bit_depth, msb_aligned)) return false;
+// `code` is what every entry takes as yuv_standard: PNP_YUV_CODE(standard, chroma), the standard 0..3 in bits 0..7 and the chroma mode
+// 0..3 in bits 8..11; any other bit set (a mode above 3, a low byte above 3, bits from 12 up, a negative value) is refused
+static inline bool yuv_coef(int code, int bit_depth, int msb_aligned, YuvCoef* k) {
+    if ((code & ~0x303) || !yuv_depth_ok(bit_depth, msb_aligned)) return false;
+    const int standard = code & 0xff;
+    k->chroma = (code >> 8) & 0xf;
     const bool bt709 = standard >= PNP_YUV_BT709_LIMITED, full = (standard & 1) != 0;
     const double Kr = bt709 ? 0.2126 : 0.299, Kb = bt709 ? 0.0722 : 0.114, Kg = 1.0 - Kr - Kb;
     const double s = (double)(1 << (bit_depth - 8)), top = (double)((1 << bit_depth) - 1);
@@ -58,7 +63,7 @@ static inline YuvPlanes yuv_planes(const pnp_yuv420_planes16& p) {
     return YuvPlanes{reinterpret_cast<unsigned char*>(p.y), reinterpret_cast<unsigned char*>(p.cb), reinterpret_cast<unsigned char*>(p.cr),
                      p.y_pitch, p.c_pitch, p.y_frame, p.c_frame, p.c_step, 2, p.bit_depth, p.msb_aligned};
 }
-static inline bool yuv_coef(int standard, const YuvPlanes& p, YuvCoef* k) { return yuv_coef(standard, p.bit_depth, p.msb_aligned, k); }
+static inline bool yuv_coef(int code, const YuvPlanes& p, YuvCoef* k) { return yuv_coef(code, p.bit_depth, p.msb_aligned, k); }
 
 // What a descriptor must satisfy for h x w frames (h, w even): planes present, a depth and container of its sample size, c_step
 // 1 | 2, pitches that hold a row; with 2-byte samples even pointers, pitches and strides (bytes: any address and pitch, odd ones too).
@@ -93,7 +98,8 @@ static inline YuvPlanes yuv_frame(const YuvPlanes& p, int64_t i) {
 }
 
 // T frames of planes -> the (T,H,W,4) RGB0 conv source (clamped fp32 RGB, 4th channel zero).  1.5 samples read + 16 B written per
-// pixel.  force_general: the single-sample-load form even where the aligned one applies (same values; tests)
+// pixel.  force_general: the single-sample-load form even where the aligned one applies (same values; tests).  k.chroma selects the
+// kernels here and in the two launchers below: PNP_YUV_CHROMA_REPLICATE the replicate / box ones, every other mode the sited ones
 int launch_pack_lr_yuv420(const YuvPlanes& in, const YuvCoef& k, float* lr4, int T, int H, int W, bool force_general, hipStream_t stream);
 // n frames of planes <-> (n,3,H,W) fp32 planes; any address and pitch yuv_planes_ok admits, bytes beyond a row's width are neither
 // read nor written

@@ -4,8 +4,11 @@
 // pnp_frames_to_yuv420, pnp_yuv420_planes16): constants of the depth rounded to fp32 once on the host (yuv.h), every product and sum
 // after that an fp32 operation rounded on its own -- contraction is off in every function that computes.  Chroma is replicated on the
 // way in (pixel (y, x) reads sample (y >> 1, x >> 1)) and box-averaged on the way out, so a thread owns whole 2x2 blocks and reads
-// each chroma pair once.  Every kernel is a template on the sample type S (unsigned char | unsigned short); pitches and frame strides
-// are bytes, c_step is samples, and only the loads, the extraction of a sample from a load and the store know S.
+// each chroma pair once.  The other chroma modes of the header (PNP_YUV_CHROMA_CENTER / _LEFT / _TOPLEFT: bilinear chroma at its true
+// position on the way in, [1 2 1] / 4 on the co-sited axes on the way out) have kernels of their own below (the *_sited_* ones): a
+// thread still owns whole 2x2 blocks and reads the clamped neighbours it needs beside them.  Every kernel is a template on the sample
+// type S (unsigned char | unsigned short); pitches and frame strides are bytes, c_step is samples, and only the loads, the extraction
+// of a sample from a load and the store know S.
 #include <type_traits>
 
 #include "yuv.h"
@@ -151,6 +154,147 @@ __global__ __launch_bounds__(256) void frames_from_yuv420_kernel(const YuvPlanes
     }
 }
 
+// ---- sited chroma on the way in (PNP_YUV_CHROMA_CENTER | _LEFT | _TOPLEFT).  One axis, weights in quarters: the even and the odd
+// luma index of chroma index i, from the samples m, c, p at max(i - 1, 0), i, min(i + 1, n - 1).  CO: the axis is co-sited (even: c
+// alone; odd: halfway to p), else midway (3 : 1 towards the nearer neighbour).  Both axes together weigh 16 and the sum is an integer.
+template <bool CO> __device__ __forceinline__ int tap_even(int m, int c) { return CO ? 4 * c : 3 * c + m; }
+template <bool CO> __device__ __forceinline__ int tap_odd(int c, int p) { return CO ? 2 * c + 2 * p : 3 * c + p; }
+
+// the chroma terms of ONE pixel from its weighted sums of 16 (exact in fp32: below 2^16 at 12 bit)
+__device__ __forceinline__ ChromaTerms chroma_terms16(const YuvCoef& k, int cb16, int cr16) {
+#pragma clang fp contract(off)
+    const float u = (float)(cb16 - 16 * k.cmid) * 0.0625f, v = (float)(cr16 - 16 * k.cmid) * 0.0625f;
+    return ChromaTerms{k.crv * v, k.cgu * u, k.cgv * v, k.cbu * u};
+}
+
+// The chroma terms of the four pixels (00, 01, 10, 11) of block (by, bx) of frame f: single-sample loads of the clamped 3x3
+// neighbourhood (a co-sited axis has no tap at index - 1: its loads fold into the centre's), at any address, pitch and c_step.
+template <class S, bool XCO, bool YCO>
+__device__ __forceinline__ void sited_terms(const YuvPlanes& p, const YuvCoef& k, long f, int by, int bx, int bh, int bw, ChromaTerms (&c)[4]) {
+    const int rows[3] = {YCO ? by : max(by - 1, 0), by, min(by + 1, bh - 1)};
+    const long cols[3] = {(long)(XCO ? bx : max(bx - 1, 0)) * p.c_step, (long)bx * p.c_step, (long)min(bx + 1, bw - 1) * p.c_step};
+    int be[3], bo[3], re[3], ro[3];     // each row across: the even and the odd column, cb and cr
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const long co = f * p.c_frame + (long)rows[r] * p.c_pitch;
+        const S *b = at<S>(p.cb, co), *q = at<S>(p.cr, co);
+        const int bm = (int)val<S>(k, b[cols[0]]), bc = (int)val<S>(k, b[cols[1]]), bp = (int)val<S>(k, b[cols[2]]);
+        const int rm = (int)val<S>(k, q[cols[0]]), rc = (int)val<S>(k, q[cols[1]]), rp = (int)val<S>(k, q[cols[2]]);
+        be[r] = tap_even<XCO>(bm, bc), bo[r] = tap_odd<XCO>(bc, bp);
+        re[r] = tap_even<XCO>(rm, rc), ro[r] = tap_odd<XCO>(rc, rp);
+    }
+    c[0] = chroma_terms16(k, tap_even<YCO>(be[0], be[1]), tap_even<YCO>(re[0], re[1]));
+    c[1] = chroma_terms16(k, tap_even<YCO>(bo[0], bo[1]), tap_even<YCO>(ro[0], ro[1]));
+    c[2] = chroma_terms16(k, tap_odd<YCO>(be[1], be[2]), tap_odd<YCO>(re[1], re[2]));
+    c[3] = chroma_terms16(k, tap_odd<YCO>(bo[1], bo[2]), tap_odd<YCO>(ro[1], ro[2]));
+}
+
+// General sited form: pack_lr_yuv420_kernel's thread, loads of Y and stores, with sited_terms' chroma
+template <class S, bool XCO, bool YCO>
+__global__ __launch_bounds__(256) void pack_lr_yuv420_sited_kernel(const YuvPlanes p, const YuvCoef k, float* __restrict__ lr4, int H, int W, long total) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int bw = W >> 1, bh = H >> 1;
+    const int bx = (int)(i % bw);
+    const long r = i / bw;
+    const int by = (int)(r % bh);
+    const long f = r / bh;
+    const S* y0 = at<S>(p.y, f * p.y_frame + (long)(2 * by) * p.y_pitch) + 2 * bx;
+    const S* y1 = at<S>(reinterpret_cast<const unsigned char*>(y0), p.y_pitch);
+    ChromaTerms c[4];
+    sited_terms<S, XCO, YCO>(p, k, f, by, bx, bh, bw, c);
+    f32x4* d = reinterpret_cast<f32x4*>(lr4) + (f * H + 2 * by) * W + 2 * bx;
+    const unsigned y00 = y0[0], y01 = y0[1], y10 = y1[0], y11 = y1[1];
+    d[0] = rgb0_of(k, val<S>(k, y00), c[0]);
+    d[1] = rgb0_of(k, val<S>(k, y01), c[1]);
+    d[W] = rgb0_of(k, val<S>(k, y10), c[2]);
+    d[W + 1] = rgb0_of(k, val<S>(k, y11), c[3]);
+}
+
+// Aligned sited form (yuv_planes_fast): pack_lr_yuv420_fast_kernel's thread -- two four-sample loads of Y, eight 16-byte stores, 64
+// contiguous bytes per row -- with the chroma of its two columns loaded as there, once per row of the clamped rows by - 1, by, by + 1
+// (a pitch that is aligned keeps every row's load aligned), and the clamped columns 2 gx - 1 and 2 gx + 2 beside them as single
+// samples.  The same integers as the general form, so the same values.
+template <class S, int STEP, bool XCO, bool YCO>
+__global__ __launch_bounds__(256) void pack_lr_yuv420_sited_fast_kernel(const YuvPlanes p, const YuvCoef k, float* __restrict__ lr4, int H, int W,
+                                                                        int cr_first, long total) {
+    using L = Load<S>;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int gw = W >> 2, bh = H >> 1, bw = W >> 1;
+    const int gx = (int)(i % gw);
+    const long r = i / gw;
+    const int by = (int)(r % bh);
+    const long f = r / bh;
+    const unsigned char* yp = p.y + f * p.y_frame + (long)(2 * by) * p.y_pitch + (long)sizeof(S) * (4 * gx);
+    const typename L::Four ya = *at<typename L::Four>(yp, 0), yb = *at<typename L::Four>(yp, p.y_pitch);
+    const int rows[3] = {YCO ? by : max(by - 1, 0), by, min(by + 1, bh - 1)};
+    const long xl = (long)(XCO ? 2 * gx : max(2 * gx - 1, 0)) * STEP, xr = (long)min(2 * gx + 2, bw - 1) * STEP;
+    int hb[3][4], hr[3][4];             // each row across: the thread's four columns, cb and cr
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const long co = f * p.c_frame + (long)rows[j] * p.c_pitch;
+        unsigned cb0, cr0, cb1, cr1;
+        if (STEP == 2) {
+            const typename L::Four q = *at<typename L::Four>(cr_first ? p.cr : p.cb, co + (long)sizeof(S) * (4 * gx));
+            const unsigned a0 = L::get(q, 0), b0 = L::get(q, 1), a1 = L::get(q, 2), b1 = L::get(q, 3);
+            cb0 = cr_first ? b0 : a0, cr0 = cr_first ? a0 : b0;
+            cb1 = cr_first ? b1 : a1, cr1 = cr_first ? a1 : b1;
+        } else {
+            const long cx = co + (long)sizeof(S) * (2 * gx);
+            const unsigned qb = *at<typename L::Two>(p.cb, cx), qr = *at<typename L::Two>(p.cr, cx);
+            cb0 = L::get2(qb, 0), cb1 = L::get2(qb, 1), cr0 = L::get2(qr, 0), cr1 = L::get2(qr, 1);
+        }
+        const S *b = at<S>(p.cb, co), *q = at<S>(p.cr, co);
+        const int bA = (int)val<S>(k, cb0), bB = (int)val<S>(k, cb1), rA = (int)val<S>(k, cr0), rB = (int)val<S>(k, cr1);
+        const int bL = XCO ? bA : (int)val<S>(k, b[xl]), rL = XCO ? rA : (int)val<S>(k, q[xl]);
+        const int bR = (int)val<S>(k, b[xr]), rR = (int)val<S>(k, q[xr]);
+        hb[j][0] = tap_even<XCO>(bL, bA), hb[j][1] = tap_odd<XCO>(bA, bB), hb[j][2] = tap_even<XCO>(bA, bB), hb[j][3] = tap_odd<XCO>(bB, bR);
+        hr[j][0] = tap_even<XCO>(rL, rA), hr[j][1] = tap_odd<XCO>(rA, rB), hr[j][2] = tap_even<XCO>(rA, rB), hr[j][3] = tap_odd<XCO>(rB, rR);
+    }
+    f32x4* d = reinterpret_cast<f32x4*>(lr4) + (f * H + 2 * by) * W + 4 * gx;
+    f32x4 t[4], u[4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+        t[x] = rgb0_of(k, val<S>(k, L::get(ya, x)), chroma_terms16(k, tap_even<YCO>(hb[0][x], hb[1][x]), tap_even<YCO>(hr[0][x], hr[1][x])));
+        u[x] = rgb0_of(k, val<S>(k, L::get(yb, x)), chroma_terms16(k, tap_odd<YCO>(hb[1][x], hb[2][x]), tap_odd<YCO>(hr[1][x], hr[2][x])));
+    }
+    d[0] = t[0];
+    d[1] = t[1];
+    d[2] = t[2];
+    d[3] = t[3];
+    d[W] = u[0];
+    d[W + 1] = u[1];
+    d[W + 2] = u[2];
+    d[W + 3] = u[3];
+}
+
+// planes -> (n,3,H,W) fp32 planes with sited chroma: frames_from_yuv420_kernel's thread and stores, the general sited form's values
+template <class S, bool XCO, bool YCO>
+__global__ __launch_bounds__(256) void frames_from_yuv420_sited_kernel(const YuvPlanes p, const YuvCoef k, float* __restrict__ out, int H, int W, long total) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int bw = W >> 1, bh = H >> 1;
+    const int bx = (int)(i % bw);
+    const long r = i / bw;
+    const int by = (int)(r % bh);
+    const long f = r / bh;
+    const long yo = f * p.y_frame + (long)(2 * by) * p.y_pitch;
+    ChromaTerms c[4];
+    sited_terms<S, XCO, YCO>(p, k, f, by, bx, bh, bw, c);
+    const long hw = (long)H * W;
+    float* d = out + f * 3 * hw + (long)(2 * by) * W + 2 * bx;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int dy = j >> 1, dx = j & 1;
+        const f32x4 v = rgb0_of(k, val<S>(k, at<S>(p.y, yo + dy * p.y_pitch)[2 * bx + dx]), c[j]);
+        float* q = d + dy * W + dx;
+        q[0] = v[0];
+        q[hw] = v[1];
+        q[2 * hw] = v[2];
+    }
+}
+
 // clamp(rint(x), 0, 2^d - 1), rint rounding half to even, as it is stored: a byte, or a word with the bits outside the value zero
 template <class S>
 __device__ __forceinline__ S sample_of(const YuvCoef& k, float x) {
@@ -192,6 +336,52 @@ __global__ __launch_bounds__(256) void frames_to_yuv420_kernel(const float* __re
     at<S>(p.cr, co)[cx] = sample_of<S>(k, (float)k.cmid + k.sc * mr);
 }
 
+// (n,3,H,W) fp32 planes -> planes with chroma co-sited with the even luma columns (PNP_YUV_CHROMA_LEFT; YCO: and with the even luma
+// rows, PNP_YUV_CHROMA_TOPLEFT).  frames_to_yuv420_kernel's thread and stores; the chroma sample takes pb, pr of the columns
+// max(2 bx - 1, 0), 2 bx, 2 bx + 1 as ((pL + pR) + (pC + pC)) * 0.25 in each of its rows -- 2 by and 2 by + 1, combined as
+// (a0 + a1) * 0.5, or max(2 by - 1, 0), 2 by, 2 by + 1, combined with the three-tap form -- so a thread evaluates the pixels beside
+// its block once more (the same fp32 operations: the same values) and reads nothing outside the frame.
+template <class S, bool YCO>
+__global__ __launch_bounds__(256) void frames_to_yuv420_sited_kernel(const float* __restrict__ in, const YuvPlanes p, const YuvCoef k, int H, int W, long total) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int bw = W >> 1, bh = H >> 1;
+    const int bx = (int)(i % bw);
+    const long r = i / bw;
+    const int by = (int)(r % bh);
+    const long f = r / bh;
+    const long hw = (long)H * W;
+    const float* s = in + f * 3 * hw;
+    constexpr int NR = YCO ? 3 : 2;
+    const int cols[3] = {max(2 * bx - 1, 0), 2 * bx, 2 * bx + 1};
+    float ab[NR], ar[NR];               // each row across
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+        const int dy = YCO ? j - 1 : j;                 // the row's place in the block: -1 (above it), 0, 1
+        const int row = max(2 * by + dy, 0);
+        float pb[3], pr[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float* q = s + (long)row * W + cols[c];
+            const float rr = fminf(fmaxf(q[0], 0.f), 1.f), gg = fminf(fmaxf(q[hw], 0.f), 1.f), bb = fminf(fmaxf(q[2 * hw], 0.f), 1.f);
+            const float yl = (k.kr * rr + k.kg * gg) + k.kb * bb;
+            if (dy >= 0 && c >= 1) at<S>(p.y, f * p.y_frame + (long)row * p.y_pitch)[cols[c]] = sample_of<S>(k, (float)k.yoff + k.sy * yl);
+            pb[c] = (bb - yl) * k.ipb;
+            pr[c] = (rr - yl) * k.ipr;
+        }
+        ab[j] = ((pb[0] + pb[2]) + (pb[1] + pb[1])) * 0.25f;
+        ar[j] = ((pr[0] + pr[2]) + (pr[1] + pr[1])) * 0.25f;
+    }
+    float mb, mr;
+    if constexpr (YCO) mb = ((ab[0] + ab[2]) + (ab[1] + ab[1])) * 0.25f, mr = ((ar[0] + ar[2]) + (ar[1] + ar[1])) * 0.25f;
+    else mb = (ab[0] + ab[1]) * 0.5f, mr = (ar[0] + ar[1]) * 0.5f;
+    const long co = f * p.c_frame + (long)by * p.c_pitch;
+    const long cx = (long)bx * p.c_step;
+    at<S>(p.cb, co)[cx] = sample_of<S>(k, (float)k.cmid + k.sc * mb);
+    at<S>(p.cr, co)[cx] = sample_of<S>(k, (float)k.cmid + k.sc * mr);
+}
+
 unsigned blocks_of(long total) { return (unsigned)((total + 255) / 256); }
 
 bool frame_ok(int n, int H, int W) { return n >= 1 && H >= 2 && W >= 2 && !(H & 1) && !(W & 1); }
@@ -210,17 +400,55 @@ int pack_lr(const YuvPlanes& in, const YuvCoef& k, float* lr4, int T, int H, int
     return (int)hipGetLastError();
 }
 
+// the sited forms: XCO, YCO are the co-sited axes of k.chroma (CENTER: none; LEFT: x; TOPLEFT: both)
+template <class S, bool XCO, bool YCO>
+int pack_lr_sited(const YuvPlanes& in, const YuvCoef& k, float* lr4, int T, int H, int W, bool fast, hipStream_t stream) {
+    if (fast) {
+        const long total = (long)T * (H / 2) * (W / 4);
+        const int cr_first = in.cr < in.cb ? 1 : 0;
+        if (in.c_step == 2)
+            hipLaunchKernelGGL((pack_lr_yuv420_sited_fast_kernel<S, 2, XCO, YCO>), dim3(blocks_of(total)), dim3(256), 0, stream, in, k, lr4, H, W, cr_first, total);
+        else
+            hipLaunchKernelGGL((pack_lr_yuv420_sited_fast_kernel<S, 1, XCO, YCO>), dim3(blocks_of(total)), dim3(256), 0, stream, in, k, lr4, H, W, cr_first, total);
+        return (int)hipGetLastError();
+    }
+    const long total = (long)T * (H / 2) * (W / 2);
+    hipLaunchKernelGGL((pack_lr_yuv420_sited_kernel<S, XCO, YCO>), dim3(blocks_of(total)), dim3(256), 0, stream, in, k, lr4, H, W, total);
+    return (int)hipGetLastError();
+}
+template <class S, bool XCO, bool YCO>
+int frames_from_sited(const YuvPlanes& in, const YuvCoef& k, float* out, int H, int W, long total, hipStream_t stream) {
+    hipLaunchKernelGGL((frames_from_yuv420_sited_kernel<S, XCO, YCO>), dim3(blocks_of(total)), dim3(256), 0, stream, in, k, out, H, W, total);
+    return (int)hipGetLastError();
+}
+template <class S, bool YCO>
+int frames_to_sited(const float* in, const YuvPlanes& out, const YuvCoef& k, int H, int W, long total, hipStream_t stream) {
+    hipLaunchKernelGGL((frames_to_yuv420_sited_kernel<S, YCO>), dim3(blocks_of(total)), dim3(256), 0, stream, in, out, k, H, W, total);
+    return (int)hipGetLastError();
+}
+
+// f<S, XCO, YCO>(args...) for the sample size and the sited mode (CENTER | LEFT | TOPLEFT)
+#define YUV_SITED(f, bytes, mode, ...)                                                                                  \
+    ((bytes) == 1 ? ((mode) == PNP_YUV_CHROMA_CENTER ? f<unsigned char, false, false>(__VA_ARGS__)                      \
+                     : (mode) == PNP_YUV_CHROMA_LEFT ? f<unsigned char, true, false>(__VA_ARGS__)                       \
+                                                     : f<unsigned char, true, true>(__VA_ARGS__))                       \
+                  : ((mode) == PNP_YUV_CHROMA_CENTER ? f<unsigned short, false, false>(__VA_ARGS__)                     \
+                     : (mode) == PNP_YUV_CHROMA_LEFT ? f<unsigned short, true, false>(__VA_ARGS__)                      \
+                                                     : f<unsigned short, true, true>(__VA_ARGS__)))
+
 }  // namespace
 
 int launch_pack_lr_yuv420(const YuvPlanes& in, const YuvCoef& k, float* lr4, int T, int H, int W, bool force_general, hipStream_t stream) {
     if (!frame_ok(T, H, W) || !lr4 || !yuv_planes_ok(in, W)) return PNP_ERR_BAD_ARG;
     const bool fast = !force_general && yuv_planes_fast(in, W);
+    if (k.chroma != PNP_YUV_CHROMA_REPLICATE) return YUV_SITED(pack_lr_sited, in.sample_bytes, k.chroma, in, k, lr4, T, H, W, fast, stream);
     return in.sample_bytes == 1 ? pack_lr<unsigned char>(in, k, lr4, T, H, W, fast, stream) : pack_lr<unsigned short>(in, k, lr4, T, H, W, fast, stream);
 }
 
 int launch_frames_from_yuv420(const YuvPlanes& in, const YuvCoef& k, float* out, int nframes, int H, int W, hipStream_t stream) {
     if (!frame_ok(nframes, H, W) || !out || !yuv_planes_ok(in, W)) return PNP_ERR_BAD_ARG;
     const long total = (long)nframes * (H / 2) * (W / 2);
+    if (k.chroma != PNP_YUV_CHROMA_REPLICATE) return YUV_SITED(frames_from_sited, in.sample_bytes, k.chroma, in, k, out, H, W, total, stream);
     if (in.sample_bytes == 1) hipLaunchKernelGGL(frames_from_yuv420_kernel<unsigned char>, dim3(blocks_of(total)), dim3(256), 0, stream, in, k, out, H, W, total);
     else hipLaunchKernelGGL(frames_from_yuv420_kernel<unsigned short>, dim3(blocks_of(total)), dim3(256), 0, stream, in, k, out, H, W, total);
     return (int)hipGetLastError();
@@ -229,6 +457,11 @@ int launch_frames_from_yuv420(const YuvPlanes& in, const YuvCoef& k, float* out,
 int launch_frames_to_yuv420(const float* in, const YuvPlanes& out, const YuvCoef& k, int nframes, int H, int W, hipStream_t stream) {
     if (!frame_ok(nframes, H, W) || !in || !yuv_planes_ok(out, W)) return PNP_ERR_BAD_ARG;
     const long total = (long)nframes * (H / 2) * (W / 2);
+    if (k.chroma == PNP_YUV_CHROMA_LEFT || k.chroma == PNP_YUV_CHROMA_TOPLEFT) {        // (CENTER writes the box mean, as REPLICATE)
+        const bool yco = k.chroma == PNP_YUV_CHROMA_TOPLEFT;
+        if (out.sample_bytes == 1) return yco ? frames_to_sited<unsigned char, true>(in, out, k, H, W, total, stream) : frames_to_sited<unsigned char, false>(in, out, k, H, W, total, stream);
+        return yco ? frames_to_sited<unsigned short, true>(in, out, k, H, W, total, stream) : frames_to_sited<unsigned short, false>(in, out, k, H, W, total, stream);
+    }
     if (out.sample_bytes == 1) hipLaunchKernelGGL(frames_to_yuv420_kernel<unsigned char>, dim3(blocks_of(total)), dim3(256), 0, stream, in, out, k, H, W, total);
     else hipLaunchKernelGGL(frames_to_yuv420_kernel<unsigned short>, dim3(blocks_of(total)), dim3(256), 0, stream, in, out, k, H, W, total);
     return (int)hipGetLastError();

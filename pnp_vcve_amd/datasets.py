@@ -185,14 +185,15 @@ class Yuv420ClipFolderDataset(_EvalMixin, torch.utils.data.Dataset):
     height, width: the frame size of the lq clips (a raw file does not carry it).  mv_folder defaults to lq_folder with its last
     'yuv' path component replaced by 'mv'; the base QP comes from the crfNN path component, as in CompressedClipFolderDataset.
     A sample carries lq_yuv / gt_yuv, packed uint8 (T, 3h/2, w) buffers as on disk, the side info and MV records of the PNG dataset,
-    and meta with `layout` and `yuv_standard`.
+    and meta with `layout`, `yuv_standard` and `chroma` -- where the clips' chroma samples lie: 'replicate' (default) | 'center' |
+    'left' (H.264 / HEVC / VVC streams) | 'topleft' (BT.2020 / UHD), the chroma modes of include/pnpvcve.h.
     bit_depth 10 | 12: the files hold 16-bit little-endian samples (`-pix_fmt yuv420p10le` / `yuv420p12le`, VTM / HM output; with
     msb_aligned the value sits in the word's high bits, as in P010 / P012 with layout 'nv12'), a frame is 3 h w bytes, the buffers are
     int16 (T, 3h/2, w) -- the words as they are, uploaded as they are -- and meta carries `bit_depth` and `msb_aligned`."""
 
     def __init__(self, lq_folder, gt_folder, height, width, layout='i420', yuv_standard='bt601-limited', mv_folder=None,
                  num_input_frames=100, scale=1, repeat=1, qp_slice_file=None, replace_qp_withIPB=False, pipeline=None, test_mode=True,
-                 bit_depth=8, msb_aligned=False, **unused):
+                 bit_depth=8, msb_aligned=False, chroma='replicate', **unused):
         import json
         import os
         if not isinstance(repeat, int):
@@ -201,6 +202,9 @@ class Yuv420ClipFolderDataset(_EvalMixin, torch.utils.data.Dataset):
             raise ValueError(f"layout must be 'i420', 'nv12' or 'nv21', got {layout!r}")
         if yuv_standard not in ('bt601-limited', 'bt601-full', 'bt709-limited', 'bt709-full'):
             raise ValueError(f'unknown yuv_standard {yuv_standard!r}')
+        if chroma not in ('replicate', 'center', 'left', 'topleft'):
+            raise ValueError(f"chroma must be 'replicate', 'center', 'left' or 'topleft', got {chroma!r}")
+        self.chroma = chroma
         if isinstance(bit_depth, bool) or bit_depth not in (8, 10, 12):
             raise ValueError(f'bit_depth must be 8, 10 or 12, got {bit_depth!r}')
         if msb_aligned and bit_depth == 8:
@@ -279,7 +283,7 @@ class Yuv420ClipFolderDataset(_EvalMixin, torch.utils.data.Dataset):
                     base_QPs=torch.full((T, 1, 1, 1), base_qp / 255.0, dtype=torch.float32),
                     mv_records=torch.from_numpy(np.concatenate(recs)), rec_frame=torch.from_numpy(np.concatenate(rec_frame)),
                     meta=dict(key=f'{key}/{0:08d}', lq_path=lq_path, gt_path=gt_path, layout=self.layout, yuv_standard=self.yuv_standard,
-                              bit_depth=self.bit_depth, msb_aligned=self.msb_aligned))
+                              bit_depth=self.bit_depth, msb_aligned=self.msb_aligned, chroma=self.chroma))
 
 
 def collate(batch):

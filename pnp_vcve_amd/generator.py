@@ -329,7 +329,8 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
             return _native.OUT_F32 | _native.OUT_U8
         raise ValueError(f"out_dtype must be None, torch.float32, torch.uint8 or 'both', got {out_dtype!r}")
 
-    def forward(self, lrs, QPs=None, slices=None, mvs=None, base_QPs=None, par_map=None, out_dtype=None, yuv_standard='bt601-limited'):
+    def forward(self, lrs, QPs=None, slices=None, mvs=None, base_QPs=None, par_map=None, out_dtype=None, yuv_standard='bt601-limited',
+                chroma='replicate'):
         """iconvsr_ipb_par.py:44-149.  lrs (n,t,3,h,w); QPs/slices/base_QPs (n,t,1,1,1);
         mvs (n,t,4,h,w); par_map (n,t,3,h,w).  Returns (n,t,3,h,w) (x4 spatial when vsr).
 
@@ -342,14 +343,17 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         colour standard `yuv_standard` ('bt601-limited' | 'bt601-full' | 'bt709-limited' | 'bt709-full') -- bit-identical to
         forward(ops.frames_from_yuv420(lrs, yuv_standard), ...), without the fp32 clip.  out_dtype then also takes 'nv12' / 'i420'
         (a packed uint8 (n,t,3H/2,W) buffer, ops.frames_to_yuv420's arithmetic on the same fp32 values) and a tuple or list of
-        dtypes (several outputs, returned as a tuple in that order).
+        dtypes (several outputs, returned as a tuple in that order).  chroma: 'replicate' (the default: replicated on the way in, box
+        mean on the way out) | 'center' | 'left' (H.264 / HEVC / VVC streams) | 'topleft' (BT.2020 / UHD), the chroma modes of
+        include/pnpvcve.h -- where the chroma samples lie, bilinear on the way in and the matching filter on the way out; the two
+        identities above hold with the same `chroma` passed to ops.frames_from_yuv420 / ops.frames_to_yuv420.
 
         10 / 12-bit 4:2:0 frames: an ops.Yuv420Frames16 `lrs` (P010 / P012 / yuv420p10le / yuv420p12le views) -- bit-identical to
         forward(ops.frames_from_yuv420p16(lrs, yuv_standard), ...).  out_dtype then also takes 'p010' | 'p012' | 'yuv420p10le' |
         'yuv420p12le' (a packed (n,t,3H/2,W) buffer of 16-bit words of lrs' dtype, ops.frames_to_yuv420p16's arithmetic; its depth and
         container need not be the input's) beside 'nv12' / 'i420'.  16-bit planes out of 8-bit planes in are refused."""
         if ops.is_yuv(lrs):
-            return self._forward_yuv(lrs, QPs, slices, mvs, base_QPs, par_map, out_dtype, yuv_standard)
+            return self._forward_yuv(lrs, QPs, slices, mvs, base_QPs, par_map, out_dtype, yuv_standard, chroma)
         if not lrs.is_cuda:
             raise RuntimeError('PnP-VCVE generator: inputs must be CUDA/HIP tensors; this build has no CPU path '
                                '(the CPU restatement under oracle/ is test infrastructure only)')
@@ -450,18 +454,18 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         _native.check(rc, 'pnp_generator_forward_clips')
 
-    def forward_clips(self, clips, out_dtype=None, yuv_standard='bt601-limited'):
+    def forward_clips(self, clips, out_dtype=None, yuv_standard='bt601-limited', chroma='replicate'):
         """A batch as a sequence of clips, each where it lives: clips[i] = (lrs, QPs, slices, mvs, base_QPs, par_map) with the tensors
         of forward() for n = 1 (or without the batch dimension).  All clips go to the library in ONE call as pointers -- nothing is
         concatenated -- and run like a batch (large frames two at a time on two streams, small ones up to eight).  Returns a list of
         per-clip outputs, each what forward(..., out_dtype) returns for that clip (with the batch dimension, n = 1).  The clips must
         agree in shape and in the dtype class of lrs (uint8 or floating point): ValueError otherwise.  Not replayed from a graph
         (use_graphs concerns forward()): a graph's static buffers would be the copies this call exists to avoid.
-        Clips whose lrs are ops.Yuv420Frames (each clip's planes in allocations of their own) take yuv_standard and the out_dtype
-        values of forward()'s 4:2:0 boundary."""
+        Clips whose lrs are ops.Yuv420Frames (each clip's planes in allocations of their own) take yuv_standard, chroma and the
+        out_dtype values of forward()'s 4:2:0 boundary."""
         clips = list(clips)
         if clips and ops.is_yuv(clips[0][0]):
-            return self._forward_clips_yuv(clips, out_dtype, yuv_standard)
+            return self._forward_clips_yuv(clips, out_dtype, yuv_standard, chroma)
         mask = self._out_mask(out_dtype)
         if not clips:
             raise ValueError('forward_clips needs at least one clip')
@@ -642,10 +646,12 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
 
     @staticmethod
     def _yuv8_of_16(res, kinds, layout, std):
-        """the outputs `kinds` asks for, from a run of _yuv_out_route's out_dtype: the 8-bit planes are ops.frames_to_yuv420 of the fp32 output"""
+        """the outputs `kinds` asks for, from a run of _yuv_out_route's out_dtype: the 8-bit planes are ops.frames_to_yuv420 of the fp32
+        output; std: the code of ops._yuv_code"""
         ran = [k for k in kinds if k != 'yuv'] + ([] if 'f32' in kinds else ['f32'])
         got = dict(zip(ran, res))
-        got['yuv'] = ops.frames_to_yuv420(got['f32'], std, layout)[0]
+        standard, chroma = ops._yuv_code_split(std)
+        got['yuv'] = ops.frames_to_yuv420(got['f32'], standard, layout, chroma=chroma)[0]
         return tuple(got[k] for k in kinds)
 
     def _yuv_side(self, t, QPs, slices, base_QPs):
@@ -660,8 +666,8 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         return torch.stack([slices.reshape(t).float(), QPs.reshape(t).float() if QPs is not None else zero,
                             base_QPs.reshape(t).float() if base_QPs is not None else zero])
 
-    def _forward_yuv(self, frames, QPs, slices, mvs, base_QPs, par_map, out_dtype, yuv_standard):
-        std = ops._yuv_standard(yuv_standard)
+    def _forward_yuv(self, frames, QPs, slices, mvs, base_QPs, par_map, out_dtype, yuv_standard, chroma='replicate'):
+        std = ops._yuv_code(yuv_standard, chroma)      # (what the library takes as yuv_standard; part of a graph's key)
         kinds, mask, layout, many = self._yuv_outs(out_dtype)
         clips, lead = ops._yuv_clips(frames, 'lrs')
         if not lead:
@@ -669,7 +675,7 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         descs = [ops._yuv_clip_desc(c, 'lrs') for c in clips]      # (every refusal before any GPU work)
         via8, run_dtype = self._yuv_out_route(frames, kinds, layout)
         if via8:
-            res = self._yuv8_of_16(self._forward_yuv(frames, QPs, slices, mvs, base_QPs, par_map, run_dtype, yuv_standard), kinds, via8, std)
+            res = self._yuv8_of_16(self._forward_yuv(frames, QPs, slices, mvs, base_QPs, par_map, run_dtype, yuv_standard, chroma), kinds, via8, std)
             return res if many else res[0]
         n, (_, t, h, w) = len(clips), descs[0]
         assert h >= 64 and w >= 64, f'The height and width of inputs should be at least 64, but got {h} and {w}.'
@@ -786,8 +792,8 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         ent['graph'].replay()
         return {k: (v[0].clone(), None) for k, v in ent['outs'].items()}
 
-    def _forward_clips_yuv(self, clips, out_dtype, yuv_standard):
-        std = ops._yuv_standard(yuv_standard)
+    def _forward_clips_yuv(self, clips, out_dtype, yuv_standard, chroma='replicate'):
+        std = ops._yuv_code(yuv_standard, chroma)
         kinds, mask, layout, many = self._yuv_outs(out_dtype)
         if self.sparse_val and not self.training and len(clips) != 1:
             raise NotImplementedError('sparse_val=True evaluates one clip at a time: the reference reads feature[0] '
@@ -795,7 +801,7 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         lrs0 = clips[0][0]
         via8, run_dtype = self._yuv_out_route(lrs0, kinds, layout)
         if via8:
-            res = [self._yuv8_of_16(r, kinds, via8, std) for r in self._forward_clips_yuv(clips, run_dtype, yuv_standard)]
+            res = [self._yuv8_of_16(r, kinds, via8, std) for r in self._forward_clips_yuv(clips, run_dtype, yuv_standard, chroma)]
             return res if many else [r[0] for r in res]
         ys, cbs, crs, mv_l, par_l, sides, first = [], [], [], [], [], [], None
         for lrs, QPs, slices, mvs, base_QPs, par_map in clips:

@@ -793,6 +793,25 @@ def _yuv_standard(standard):
     return int(standard)
 
 
+YUV_CHROMA = tuple(sorted(_native.YUV_CHROMA, key=_native.YUV_CHROMA.get))      # the chroma modes by name, in the order of their codes
+
+
+def _yuv_code(standard, chroma='replicate'):
+    """PNP_YUV_CODE(standard, chroma), what every 4:2:0 entry of the library takes as yuv_standard: the standard (a name or 0..3) in
+    bits 0..7, the chroma mode (a name of YUV_CHROMA) in bits 8..11; 'replicate' leaves the bare standard"""
+    if not isinstance(chroma, str) or chroma not in _native.YUV_CHROMA:
+        raise ValueError(f'chroma must be one of {YUV_CHROMA}, got {chroma!r}')
+    return _yuv_standard(standard) | _native.YUV_CHROMA[chroma] << 8
+
+
+def _yuv_code_split(code):
+    """a code of _yuv_code (as a custom op's `standard` integer carries it) -> (standard 0..3, chroma name)"""
+    code = int(code)
+    if code < 0 or code >> 8 >= len(YUV_CHROMA):
+        raise ValueError(f'not a code of a yuv_standard and a chroma mode: {code!r}')
+    return _yuv_standard(code & 255), YUV_CHROMA[code >> 8]
+
+
 def _yuv16_layout(layout):
     """a layout name of YUV16_LAYOUTS or ('nv12' | 'nv21' | 'i420', bit_depth, msb_aligned) -> (order, bit_depth, msb_aligned)"""
     if isinstance(layout, str):
@@ -932,9 +951,9 @@ def _yuv_clips(frames, what='frames', cls=None):
     return [kind(frames.y[b], frames.cb[b], frames.cr[b], *frames[3:]) for b in range(n)], (n,)
 
 
-def _frames_from_yuv(frames, standard, cls=None):
+def _frames_from_yuv(frames, standard, cls=None, chroma='replicate'):
     """frames_from_yuv420 / frames_from_yuv420p16 (cls: as _yuv_expect; None: by the frames' type)"""
-    std = _yuv_standard(standard)
+    std = _yuv_code(standard, chroma)
     clips, lead = _yuv_clips(frames, 'frames', cls)
     descs = [_yuv_clip_desc(c) for c in clips]
     _, t, h, w = descs[0]
@@ -950,9 +969,9 @@ def _frames_from_yuv(frames, standard, cls=None):
     return out if lead else out[0]
 
 
-def _frames_to_yuv(planes, standard, out, cls, empty):
+def _frames_to_yuv(planes, standard, out, cls, empty, chroma='replicate'):
     """frames_to_yuv420 / frames_to_yuv420p16; empty(lead, h, w, device) -> (a fresh packed buffer, its views) where out is None"""
-    std = _yuv_standard(standard)
+    std = _yuv_code(standard, chroma)
     planes = _chk(planes, 'planes')
     if planes.dim() not in (4, 5) or planes.shape[-3] != 3:
         raise ValueError(f'planes must be (n,t,3,h,w) or (t,3,h,w), got {tuple(planes.shape)}')
@@ -978,28 +997,30 @@ def _frames_to_yuv(planes, standard, out, cls, empty):
     return buf, out
 
 
-def _pack_lr_yuv(frames, standard, general, cls):
+def _pack_lr_yuv(frames, standard, general, cls, chroma='replicate'):
     """pack_lr_yuv420 / pack_lr_yuv420p16"""
+    std = _yuv_code(standard, chroma)
     d, t, h, w = _yuv_clip_desc(frames, 'frames', cls)
     entry = _yuv_entry('pnp_debug_pack_lr_yuv420', frames)
     with torch.cuda.device(frames.y.device):
         out = torch.empty((t, h, w, 4), device=frames.y.device, dtype=torch.float32)
-        _native.check(getattr(_native.lib(), entry)(ctypes.byref(d), _yuv_standard(standard), _ptr(out), t, h, w, int(bool(general)), _stream()), entry)
+        _native.check(getattr(_native.lib(), entry)(ctypes.byref(d), std, _ptr(out), t, h, w, int(bool(general)), _stream()), entry)
     return out
 
 
-def frames_from_yuv420(frames, standard='bt601-limited'):
+def frames_from_yuv420(frames, standard='bt601-limited', chroma='replicate'):
     """Yuv420Frames (n,t,...) or (t,...) -> (n,t,3,h,w) / (t,3,h,w) fp32 RGB planes, clamped to [0,1], chroma replicated: the
     arithmetic of include/pnpvcve.h, bit-equal to tests/yuv_ref.py.  What generator.forward(Yuv420Frames) computes on, without this
-    fp32 clip."""
-    return _frames_from_yuv(frames, standard, Yuv420Frames)
+    fp32 clip.  chroma: 'replicate' | 'center' | 'left' | 'topleft', the header's chroma modes (the siting of the chroma samples;
+    every mode but the first interpolates them bilinearly; bit-equal to tests/yuv_chroma_ref.py)."""
+    return _frames_from_yuv(frames, standard, Yuv420Frames, chroma)
 
 
-def frames_from_yuv420p16(frames, standard='bt601-limited'):
+def frames_from_yuv420p16(frames, standard='bt601-limited', chroma='replicate'):
     """Yuv420Frames16 (n,t,...) or (t,...) -> (n,t,3,h,w) / (t,3,h,w) fp32 RGB planes, clamped to [0,1], chroma replicated: the
     arithmetic of include/pnpvcve.h at the frames' depth, bit-equal to tests/yuv16_ref.py.  What generator.forward(Yuv420Frames16)
-    computes on, without this fp32 clip."""
-    return _frames_from_yuv(frames, standard, Yuv420Frames16)
+    computes on, without this fp32 clip.  chroma: as frames_from_yuv420."""
+    return _frames_from_yuv(frames, standard, Yuv420Frames16, chroma)
 
 
 def empty_yuv420(lead, h, w, layout, device):
@@ -1014,31 +1035,32 @@ def empty_yuv420p16(lead, h, w, layout, device, dtype=torch.int16):
     return buf, yuv420p16_views(buf, h, w, layout)
 
 
-def frames_to_yuv420(planes, standard='bt601-limited', layout='nv12', out=None):
+def frames_to_yuv420(planes, standard='bt601-limited', layout='nv12', out=None, chroma='replicate'):
     """(n,t,3,h,w) or (t,3,h,w) fp32 CUDA planes -> (packed uint8 buffer (...,3h/2,w) in `layout`, its Yuv420Frames views): clamp,
     luma, box-mean chroma, round half to even (include/pnpvcve.h).  out: Yuv420Frames views to write instead of a fresh buffer
-    (any pitch and address; returns (None, out))."""
-    return _frames_to_yuv(planes, standard, out, Yuv420Frames, lambda lead, h, w, dev: empty_yuv420(lead, h, w, layout, dev))
+    (any pitch and address; returns (None, out)).  chroma: the header's chroma mode; 'left' and 'topleft' filter [1 2 1] / 4 on
+    their co-sited axes where the other two take the box mean."""
+    return _frames_to_yuv(planes, standard, out, Yuv420Frames, lambda lead, h, w, dev: empty_yuv420(lead, h, w, layout, dev), chroma)
 
 
-def frames_to_yuv420p16(planes, standard='bt601-limited', layout='yuv420p10le', out=None, dtype=torch.int16):
+def frames_to_yuv420p16(planes, standard='bt601-limited', layout='yuv420p10le', out=None, dtype=torch.int16, chroma='replicate'):
     """(n,t,3,h,w) or (t,3,h,w) fp32 CUDA planes -> (packed buffer of 16-bit words (...,3h/2,w) in `layout`, its Yuv420Frames16
     views): clamp, luma, box-mean chroma, round half to even to [0, 2^d - 1], the bits outside the value zero (include/pnpvcve.h).
     out: Yuv420Frames16 views to write instead of a fresh buffer (any pitch, any even address; returns (None, out)); the depth and
-    container are then out's."""
-    return _frames_to_yuv(planes, standard, out, Yuv420Frames16, lambda lead, h, w, dev: empty_yuv420p16(lead, h, w, layout, dev, dtype))
+    container are then out's.  chroma: as frames_to_yuv420."""
+    return _frames_to_yuv(planes, standard, out, Yuv420Frames16, lambda lead, h, w, dev: empty_yuv420p16(lead, h, w, layout, dev, dtype), chroma)
 
 
-def pack_lr_yuv420(frames, standard='bt601-limited', general=False):
+def pack_lr_yuv420(frames, standard='bt601-limited', general=False, chroma='replicate'):
     """(include/pnpvcve_debug.h) one clip's Yuv420Frames (t,...) -> the (t,h,w,4) fp32 RGB0 conv source the forward unpacks them into;
-    general: the byte-load form whatever the alignment"""
-    return _pack_lr_yuv(frames, standard, general, Yuv420Frames)
+    general: the byte-load form whatever the alignment; chroma: the header's chroma mode"""
+    return _pack_lr_yuv(frames, standard, general, Yuv420Frames, chroma)
 
 
-def pack_lr_yuv420p16(frames, standard='bt601-limited', general=False):
+def pack_lr_yuv420p16(frames, standard='bt601-limited', general=False, chroma='replicate'):
     """(include/pnpvcve_debug.h) one clip's Yuv420Frames16 (t,...) -> the (t,h,w,4) fp32 RGB0 conv source the forward unpacks them
-    into; general: the 2-byte-load form whatever the alignment"""
-    return _pack_lr_yuv(frames, standard, general, Yuv420Frames16)
+    into; general: the 2-byte-load form whatever the alignment; chroma: the header's chroma mode"""
+    return _pack_lr_yuv(frames, standard, general, Yuv420Frames16, chroma)
 
 
 # ---------------------------------------------------------------- plane metrics of 4:2:0 clips (include/pnpvcve.h states the arithmetic)

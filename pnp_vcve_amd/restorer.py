@@ -221,7 +221,7 @@ class BasicVSR(nn.Module):
 
     def forward_test(self, lq, gt=None, QPs=None, slices=None, mvs=None, base_QPs=None, par_map=None, meta=None,
                      save_image=False, save_path=None, iteration=None, precomputed_output=None, out_dtype=None,
-                     yuv_standard='bt601-limited'):
+                     yuv_standard='bt601-limited', chroma='replicate'):
         """basicvsr.py:155-233.  `precomputed_output` (not in the reference): this clip's enhanced frames when the caller has
         already run the generator -- apis.multi_gpu_test does so for two clips at a time, which the generator interleaves on two
         streams; evaluation and saving then proceed clip by clip exactly as below.
@@ -233,7 +233,8 @@ class BasicVSR(nn.Module):
         out_dtype = 'i420' | 'nv12' the generator writes packed 4:2:0 only (`precomputed_output`: that packed buffer): the
         metrics are then evaluate()'s plane metrics against a Yuv420Frames `gt`, and save_image writes <save_path>/<clip>.yuv -- the
         buffer's bytes, frames in order, one FrameWriter job per clip.  ops.Yuv420Frames16 `lq` (10 / 12 bit) likewise, with the four
-        16-bit layout names beside them: the buffer is then 16-bit little-endian words, 3 B per pixel in the file.
+        16-bit layout names beside them: the buffer is then 16-bit little-endian words, 3 B per pixel in the file.  `chroma`
+        ('replicate' | 'center' | 'left' | 'topleft'): the chroma mode of generator.forward, for the planes in and the planes out.
         Self-ensemble (basicvsr.py:172-173): a model built with ensemble=dict(type='SpatialTemporalEnsemble', ...) runs
         generator.forward_ensemble where it would run the generator -- fp32 or uint8 frames and out_dtype as above,
         last_forward_seconds covers the whole ensemble, precomputed_output is taken as it is; 4:2:0 `lq` raises ValueError."""
@@ -247,7 +248,7 @@ class BasicVSR(nn.Module):
                              f'{self.YUV_OUT_LAYOUTS}')
         if yuv_layout is not None:
             return self._forward_test_yuv(lq, gt, QPs, slices, mvs, base_QPs, par_map, meta, save_image, save_path, iteration,
-                                          precomputed_output, yuv_layout, yuv_standard)
+                                          precomputed_output, yuv_layout, yuv_standard, chroma)
         if precomputed_output is not None:
             output = precomputed_output
         elif not self.psnr_only:
@@ -257,6 +258,8 @@ class BasicVSR(nn.Module):
                 kw = {} if out_dtype is None else {'out_dtype': out_dtype}
                 if yuv_in:
                     kw['yuv_standard'] = yuv_standard
+                    if chroma != 'replicate':
+                        kw['chroma'] = chroma
                 run = self.generator if self.forward_ensemble is None else self.forward_ensemble
                 output = run(lq, QPs, slices, mvs, base_QPs, par_map, **kw)
                 torch.cuda.synchronize()
@@ -282,7 +285,7 @@ class BasicVSR(nn.Module):
         else:
             lq_planes = lq
             if yuv_in:
-                lq_planes = ops._frames_from_yuv(lq, yuv_standard)
+                lq_planes = ops._frames_from_yuv(lq, yuv_standard, chroma=chroma)
             elif lq.dtype == torch.uint8 and lq.ndim == 5 and lq.is_cuda:       # byte frames: hand back the planes the caller knows
                 from .ops import frames_from_rgb8
                 lq_planes = frames_from_rgb8(lq)
@@ -314,7 +317,7 @@ class BasicVSR(nn.Module):
         return results
 
     def _forward_test_yuv(self, lq, gt, QPs, slices, mvs, base_QPs, par_map, meta, save_image, save_path, iteration, precomputed_output,
-                          layout, yuv_standard):
+                          layout, yuv_standard, chroma='replicate'):
         """forward_test with 4:2:0 planes in and packed 4:2:0 out: the generator's (n,t,3H/2,W) uint8 buffer is all that exists of the output"""
         from . import ops
         if gt is not None and not ops.is_yuv(gt):
@@ -328,7 +331,8 @@ class BasicVSR(nn.Module):
             with torch.no_grad():
                 torch.cuda.synchronize()
                 begin = time.time()
-                buf = self.generator(lq, QPs, slices, mvs, base_QPs, par_map, out_dtype=layout, yuv_standard=yuv_standard)
+                kw = {} if chroma == 'replicate' else {'chroma': chroma}
+                buf = self.generator(lq, QPs, slices, mvs, base_QPs, par_map, out_dtype=layout, yuv_standard=yuv_standard, **kw)
                 torch.cuda.synchronize()
                 self.last_forward_seconds = time.time() - begin
         wide = layout in ops.YUV16_LAYOUTS
@@ -341,7 +345,7 @@ class BasicVSR(nn.Module):
             results = dict(eval_result=self.evaluate(output, gt))
         else:
             from_planes = ops._frames_from_yuv
-            results = dict(lq=from_planes(lq, yuv_standard).cpu(), output=buf.cpu())
+            results = dict(lq=from_planes(lq, yuv_standard, chroma=chroma).cpu(), output=buf.cpu())
             if gt is not None:
                 results['gt'] = type(gt)(*[p.cpu() for p in gt[:3]], *gt[3:])
         if save_image:

@@ -21,6 +21,8 @@ package).
                                                                 the same on 10 / 12-bit plane views (16-bit words); layout indexes
                                                                 sorted(ops.YUV16_LAYOUTS)
     torch.ops.pnpvcve.frames_from_yuv420(y, cb, cr, standard)   4:2:0 planes -> fp32 RGB planes (include/pnpvcve.h states the arithmetic)
+                                                                `standard` of the three 4:2:0 ops: PNP_YUV_* (0..3), or with a chroma mode
+                                                                PNP_YUV_CODE(standard, chroma) = standard | mode << 8 (ops._yuv_code)
 
     torch.ops.pnpvcve.conv3x3(srcs, packed_w, bias, gamma, packed_w1x1, par, residual, act)
                                                                 basicvsr_net.py:484, sr_backbone_utils.py:304-333 halves, iconvsr.py:365
@@ -133,8 +135,10 @@ def _(handle, lrs, mvs, par, side, out_mask):
 
 @torch.library.custom_op('pnpvcve::frames_from_yuv420', mutates_args=())
 def frames_from_yuv420(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, standard: int) -> torch.Tensor:
-    """uint8 views y (...,h,w), cb / cr (...,h/2,w/2) with 3 or 4 dimensions -> (...,3,h,w) fp32 RGB; standard = PNP_YUV_*"""
-    return ops.frames_from_yuv420(ops.Yuv420Frames(y, cb, cr), int(standard))
+    """uint8 views y (...,h,w), cb / cr (...,h/2,w/2) with 3 or 4 dimensions -> (...,3,h,w) fp32 RGB; standard = PNP_YUV_*, or
+    PNP_YUV_CODE(standard, chroma) (ops._yuv_code)"""
+    std, chroma = ops._yuv_code_split(standard)
+    return ops.frames_from_yuv420(ops.Yuv420Frames(y, cb, cr), std, chroma)
 
 
 @frames_from_yuv420.register_fake

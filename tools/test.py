@@ -63,6 +63,11 @@ def parse_args():
     p.add_argument('--yuv-out-layout', choices=['i420', 'nv12', 'p010', 'p012', 'yuv420p10le', 'yuv420p12le'], default='i420',
                    help='with --yuv-frames: the layout of the packed 4:2:0 output (and of the written .yuv files); default i420 (yuv420p); '
                         'the 10 / 12-bit layouts for a dataset of that bit depth')
+    p.add_argument('--yuv-chroma', choices=['replicate', 'center', 'left', 'topleft'], default=None,
+                   help='with --yuv-frames: where the clips\' chroma samples lie (sets data.test.chroma; include/pnpvcve.h states the modes): '
+                        'replicate -- replicated in, box mean out, the default; center -- the same position, bilinear in; left -- H.264 / '
+                        'HEVC / VVC streams (chroma_sample_loc_type 0); topleft -- BT.2020 / UHD (type 2).  The written planes use the '
+                        'same mode')
     p.add_argument('--any-size', action='store_true',
                    help='run frames whose height or width is no multiple of 4 (generator.any_size; the same as --cfg-options '
                         'model.generator.any_size=True): the same formulas on the frame as given, no padding.  Default off: such '
@@ -104,6 +109,10 @@ def main():
     if args.testdir_gt is not None:
         cfg.merge_from_dict({'data.test.gt_folder': args.testdir_gt})
         print('-------------------- test GT dir :', args.testdir_gt)
+    if args.yuv_chroma is not None:
+        if not args.yuv_frames:
+            raise SystemExit('tools/test.py: --yuv-chroma describes the clips of --yuv-frames')
+        cfg.merge_from_dict({'data.test.chroma': args.yuv_chroma})
     if args.ensemble is not None:
         cfg.merge_from_dict({'model.ensemble': dict(_delete_=True, type='SpatialTemporalEnsemble',
                                                     is_temporal_ensemble=args.ensemble == 'spatial-temporal')})
