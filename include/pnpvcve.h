@@ -688,6 +688,60 @@ int pnp_xpsnr_sums_yuv420(const pnp_yuv420_planes* a_host_desc, const pnp_yuv420
 int pnp_xpsnr_sums_yuv420p16(const pnp_yuv420_planes16* a_host_desc, const pnp_yuv420_planes16* b_host_desc, int plane_mask,
                              unsigned long long* sums_dev, int frames, int h, int w, int crop_border, int fps, void* stream);
 
+/* PSNR-B (psnrb.hip): PSNR with a blocking effect factor (BEF) added to the mean squared error (Yim and Bovik, "Quality assessment of
+ * deblocked images", IEEE TIP 2011), the artifact-specific score of the compression-artifact-reduction literature, on every boundary
+ * PSNR is served on.  No external tool's digits could be compared, so agreement with a particular public port is UNPINNED; this is the
+ * ONE statement of the definition and it is pinned by two independent numpy restatements (pnp_vcve_amd/metrics.py::psnrb, which slices,
+ * and tests/psnrb_ref.py, which enumerates pairs).  Two points are stated on purpose: the BEF is taken from the TEST clip a (the
+ * enhanced frames), as in the paper -- some public ports take it from their first argument, whichever that is -- and the pair counts
+ * are the pairs that really exist -- the popular ports assume sizes that are multiples of the block.
+ * For one plane of the test clip a and of the reference b:
+ *   Dimensions and crop: the plane has rows x cols samples and peak P; the crop is c (crop_border; crop_border / 2 on the chroma planes
+ *   of 4:2:0, crop_border even there).
+ *   Block size: Bp = block on RGB channels, on the Y of RGB clips and on the Y plane; block / 2 on Cb / Cr of 4:2:0 (coded chroma blocks
+ *   are half size).  block is one of 4, 8, 16, 32, 64; the default of every caller is 8.
+ *   Region: rows [y0, y1) = [c, rows - c), columns [x0, x1) = [c, cols - c), h = y1 - y0, w = x1 - x0; every plane asked for needs
+ *   min(h, w) >= Bp.  The block grid is anchored at the UNCROPPED plane's origin, which is the coded picture's: a crop does not move it.
+ *   Pairs: a horizontal pair is (y, x), (y, x + 1) with both samples in the region; it is a BOUNDARY pair iff (x + 1) mod Bp == 0.  A
+ *   vertical pair is (y, x), (y + 1, x); it is a boundary pair iff (y + 1) mod Bp == 0.
+ *   Sums, five per frame and plane: sse = sum (a - b)^2 over the region; sbh, snh = sum of (a[y][x] - a[y][x+1])^2 over the boundary /
+ *   the other horizontal pairs; sbv, snv likewise over the vertical pairs.  Only a enters the four pair sums.
+ *   Counts (host, closed form): kx = floor((x1 - 1) / Bp) - floor(x0 / Bp), ky likewise; NBh = h kx, NNh = h (w - 1 - kx), NBv = w ky,
+ *   NNv = w (h - 1 - ky).
+ *   Value (host, fp64): D_B = (sbh + sbv) / (NBh + NBv), 0 when there is no boundary pair; D_N = (snh + snv) / (NNh + NNv);
+ *   eta = log2(Bp) / log2(min(h, w)); BEF = eta (D_B - D_N) if D_B > D_N, else 0; MSE = sse / (h w);
+ *   PSNR-B = 10 log10(P^2 / (MSE + BEF)), +inf when the denominator is 0.
+ *   Aggregation: a clip's value is aggregated over frames exactly as PSNR's is on the same boundary; three RGB channels give the mean of
+ *   the three channels' values per frame (MS-SSIM's convention here for several planes).
+ *   Samples and peaks are those PSNR reads on the same boundary: to_u8 of an fp32 channel or the byte of a U8_HWC frame, P = 255; the
+ *   byte of 8-bit planes; the word's value as pnp_yuv420_planes16 is read, P = 2^d - 1; PNP_COLOR_Y: the fp32 Y of pnp_luma_from_frames,
+ *   P = 255, where every difference is one fp32 subtraction, squared as (double)d * d.
+ *   Magnitudes: a squared difference reaches 2^24 at 12 bit; every sum of a 3840 x 2160 plane stays below 2^63.
+ * pnp_psnrb_counts: counts[4] = NBh, NNh, NBv, NNv of a plane of rows x cols samples cropped by `crop` with blocks of plane_block (Bp: a
+ * power of two, 2 .. 64); pnp_psnrb_luma_blocks: the partials per frame of PNP_COLOR_Y below, 0 when nothing can be scored.  Both host only
+ * (psnrb_plan.h, the one copy of the rules the launcher and the kernel use too).
+ * pnp_psnrb_sums_io: frames as pnp_psnr_stat_io takes them, each input in its own format.  PNP_COLOR_NONE: out_dev [frames][c][5] uint64 =
+ * sse, sbh, snh, sbv, snv of every frame and channel, exact, the same bits on every run (integer atomics into a buffer the entry
+ * zeroes).  PNP_COLOR_Y: out_dev [frames][pnp_psnrb_luma_blocks(h, w, crop_border)][5] doubles, one partial of the five sums per thread
+ * block, each written by one thread; the host adds them in index order (no floating-point atomics).
+ * pnp_psnrb_sums_yuv420 / _yuv420p16: the planes as pnp_psnr_sse_yuv420 / _yuv420p16 take them, each clip described on its own (any
+ * address, any pitch that holds a row, interleaved or planar chroma, low- or high-aligned words; no byte outside [plane, plane + rows *
+ * pitch) is read); sums_dev [frames][3][5] uint64 in the order Y, Cb, Cr.  plane_mask (PNP_PLANE_*) selects the planes: only they are
+ * read, the others' sums are written as 0.
+ * The no-reference form: b (b_dev / the b descriptor) may be NULL; sse is then 0 and nothing of b is read (b_format is ignored) -- the
+ * four pair sums are the blockiness of a alone.
+ * PNP_ERR_BAD_ARG, decided on the host before any HIP call: whatever pnp_psnr_stat_io / pnp_psnr_sse_yuv420 / _yuv420p16 refuse (with
+ * a in b's place when b is NULL), a mask outside 1..7, a block outside the five values, a plane asked for with min(h, w) < Bp, a NULL
+ * a or output. */
+int pnp_psnrb_counts(int rows, int cols, int crop, int plane_block, int64_t counts[4]);
+int pnp_psnrb_luma_blocks(int h, int w, int crop_border);
+int pnp_psnrb_sums_io(const void* a_dev, int a_format, const void* b_dev, int b_format, int color, void* out_dev, int frames, int c, int h,
+                      int w, int crop_border, int block, void* stream);
+int pnp_psnrb_sums_yuv420(const pnp_yuv420_planes* a_host_desc, const pnp_yuv420_planes* b_host_desc, int plane_mask,
+                          unsigned long long* sums_dev, int frames, int h, int w, int crop_border, int block, void* stream);
+int pnp_psnrb_sums_yuv420p16(const pnp_yuv420_planes16* a_host_desc, const pnp_yuv420_planes16* b_host_desc, int plane_mask,
+                             unsigned long long* sums_dev, int frames, int h, int w, int crop_border, int block, void* stream);
+
 /* Modulated deformable 3x3 conv, 64 -> 64 channels, deform_groups 16 (mmcv.ops.modulated_deform_conv2d as
  * called at mmedit/models/backbones/sr_backbones/iconvsr_mv.py:38-41,81-84; semantics restated, mmcv is not
  * vendored).  x_dev (h,w,64) pixel-major; om_dev (h,w,448): conv_offset[2] output (pre-sigmoid masks) in the

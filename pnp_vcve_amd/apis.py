@@ -164,7 +164,7 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
     yuv_frames (default off; a dataset of raw 4:2:0 clips, Yuv420ClipFolderDataset): the generator reads the decoder's planes and is
     asked for packed 4:2:0 in `yuv_out_layout` ('i420' | 'nv12') ONLY, the ground truth stays 8-bit planes on the device, the metrics
     are the plane metrics of BasicVSR.evaluate (ops.psnr_yuv420 / ssim_yuv420: 'PSNR' / 'SSIM' score the Y plane; 'PSNR_U', 'PSNR_V',
-    'SSIM_U', 'SSIM_V', 'PSNR_YUV', the 'MS-SSIM' and the 'XPSNR' names are accepted too), and save_image writes <save_path>/<clip>.yuv -- exactly the bytes of
+    'SSIM_U', 'SSIM_V', 'PSNR_YUV', the 'MS-SSIM', the 'XPSNR' and the 'PSNR-B' names are accepted too), and save_image writes <save_path>/<clip>.yuv -- exactly the bytes of
     ops.frames_to_yuv420(fp32 output, standard, layout).  A pair goes through generator.forward_clips by pointer, as under byte_frames.
     The dataset's `chroma` ('replicate' unless it says otherwise: where its clips' chroma samples lie, include/pnpvcve.h) is the
     chroma mode of every generator call and of the planes written; the generator is told only when it is not 'replicate'.

@@ -179,7 +179,115 @@ def msssim(img1, img2, crop_border=0, input_order='HWC', convert_to=None):
     return float(np.mean(msssim_from_scales(scales)))
 
 
-ALLOWED_METRICS = {'PSNR': psnr, 'SSIM': ssim, 'MS-SSIM': msssim}
+# ---------------------------------------------------------------- PSNR-B (include/pnpvcve.h, pnp_psnrb_*: the one statement of the definition)
+# The host path: the five sums of a plane by slicing (psnrb_plane_sums), the pair counts in closed form (psnrb_counts) and the fp64 part
+# (psnrb_values), which ops.psnrb_* call on the device's sums too: that part exists once.
+PSNRB_BLOCKS = (4, 8, 16, 32, 64)
+
+
+def psnrb_block(block, chroma=False):
+    """the block size of a plane: `block` (one of PSNRB_BLOCKS), half of it on the chroma planes of 4:2:0"""
+    if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or int(block) not in PSNRB_BLOCKS:
+        raise ValueError(f'block must be one of {PSNRB_BLOCKS}, got {block!r}')
+    return int(block) // 2 if chroma else int(block)
+
+
+def psnrb_counts(rows, cols, crop=0, plane_block=8):
+    """(NBh, NNh, NBv, NNv): the horizontal boundary / other and the vertical boundary / other neighbour pairs inside the crop of a plane of
+    rows x cols samples with blocks of plane_block (the plane's own: a power of two, 2 .. 64), the grid anchored at the uncropped origin"""
+    bp = int(plane_block)
+    if bp < 2 or bp > 64 or bp & (bp - 1):
+        raise ValueError(f'a plane block is a power of two from 2 to 64, got {plane_block!r}')
+    if rows < 1 or cols < 1 or crop < 0 or 2 * crop >= rows or 2 * crop >= cols:
+        raise ValueError(f'a crop of {crop} leaves nothing of a {rows} x {cols} plane')
+    h, w = rows - 2 * crop, cols - 2 * crop
+    if min(h, w) < bp:
+        raise ValueError(f'PSNR-B with blocks of {bp} needs {bp} x {bp} samples after the crop, got {h} x {w}')
+    kx = (cols - crop - 1) // bp - crop // bp
+    ky = (rows - crop - 1) // bp - crop // bp
+    return h * kx, h * (w - 1 - kx), w * ky, w * (h - 1 - ky)
+
+
+def psnrb_plane_sums(a, b, crop=0, plane_block=8):
+    """(5,) sse, sbh, snh, sbv, snv of one plane of the test clip a against the reference b (None: sse = 0).  Integer planes give exact
+    int64 sums; float32 planes (the Y of convert_to='y') are subtracted in float32, squared and added in float64."""
+    psnrb_counts(a.shape[0], a.shape[1], crop, plane_block)
+    y0, y1, x0, x1 = crop, a.shape[0] - crop, crop, a.shape[1] - crop
+    exact = np.issubdtype(a.dtype, np.integer)
+    wide = np.int64 if exact else np.float64
+
+    def sq(d):
+        d = d.astype(wide)
+        return d * d
+
+    a = a[y0:y1, x0:x1].astype(np.int64 if exact else np.float32)
+    out = np.zeros(5, wide)
+    if b is not None:
+        out[0] = sq(a - b[y0:y1, x0:x1].astype(a.dtype)).sum()
+    dh, dv = sq(a[:, :-1] - a[:, 1:]), sq(a[:-1, :] - a[1:, :])
+    bh = (np.arange(x0, x1 - 1) + 1) % plane_block == 0
+    bv = (np.arange(y0, y1 - 1) + 1) % plane_block == 0
+    out[1], out[2] = dh[:, bh].sum(), dh[:, ~bh].sum()
+    out[3], out[4] = dv[bv, :].sum(), dv[~bv, :].sum()
+    return out
+
+
+def psnrb_values(sums, counts, block, dims, peak):
+    """The fp64 part.  sums (..., 5) = sse, sbh, snh, sbv, snv of a plane; counts = psnrb_counts of it; block: the PLANE's block size;
+    dims = (h, w) of the region; peak P.  -> (PSNR-B, BEF), float64 arrays (...): D_B = (sbh + sbv) / (NBh + NBv), 0 without a boundary
+    pair; D_N = (snh + snv) / (NNh + NNv); BEF = log2(block) / log2(min(h, w)) * (D_B - D_N) where D_B > D_N, else 0; PSNR-B = 10 log10(P^2
+    / (sse / (h w) + BEF)), inf where the denominator is 0."""
+    s = np.asarray(sums).astype(np.float64)
+    nbh, nnh, nbv, nnv = (int(x) for x in counts)
+    h, w = int(dims[0]), int(dims[1])
+    zero = np.zeros(s.shape[:-1], np.float64)
+    d_b = (s[..., 1] + s[..., 3]) / float(nbh + nbv) if nbh + nbv else zero
+    d_n = (s[..., 2] + s[..., 4]) / float(nnh + nnv) if nnh + nnv else zero
+    eta = np.log2(float(block)) / np.log2(float(min(h, w)))
+    bef = np.where(d_b > d_n, eta * (d_b - d_n), 0.0)
+    den = s[..., 0] / float(h * w) + bef
+    with np.errstate(divide='ignore'):
+        val = 10.0 * np.log10(float(peak) ** 2 / den)
+    return np.where(den == 0, np.inf, val), bef
+
+
+def _psnrb_planes(img, input_order, convert_to):
+    if input_order == 'CHW':
+        img = img.transpose(1, 2, 0)
+    if _is_y(convert_to, '.'):
+        return [bgr2y(img.astype(np.float32) / 255.) * 255.]
+    if img.ndim == 2:
+        img = img[..., None]
+    return [img[..., i] for i in range(img.shape[2])]
+
+
+def psnrb(img1, img2, crop_border=0, input_order='HWC', convert_to=None, block=8):
+    """PSNR-B (Yim and Bovik 2011) of the test image img1 against the reference img2, two uint8 BGR images as psnr() takes them: PSNR
+    with the blocking effect factor of img1 added to the mean squared error, the definition of include/pnpvcve.h (pnp_psnrb_*).  It is
+    unpinned against any external port; it is checked against the independent pair-by-pair restatement tests/psnrb_ref.py.  The block
+    grid is anchored at the uncropped image's origin.  convert_to='y': one plane, the float32 Y of psnr().  Several channels give the
+    mean of the channels' values."""
+    assert img1.shape == img2.shape, f'Image shapes are different: {img1.shape}, {img2.shape}.'
+    bp = psnrb_block(block)
+    pa, pb = _psnrb_planes(img1, input_order, convert_to), _psnrb_planes(img2, input_order, convert_to)
+    rows, cols = pa[0].shape
+    counts = psnrb_counts(rows, cols, crop_border, bp)
+    dims = (rows - 2 * crop_border, cols - 2 * crop_border)
+    sums = np.stack([psnrb_plane_sums(x, y, crop_border, bp) for x, y in zip(pa, pb)])
+    return float(np.mean(psnrb_values(sums, counts, bp, dims, 255.0)[0]))
+
+
+def bef(img, crop_border=0, input_order='HWC', convert_to=None, block=8):
+    """The blocking effect factor of one image alone (the BEF of psnrb(): a no-reference blockiness figure), the mean over its channels"""
+    bp = psnrb_block(block)
+    pa = _psnrb_planes(img, input_order, convert_to)
+    rows, cols = pa[0].shape
+    counts = psnrb_counts(rows, cols, crop_border, bp)
+    sums = np.stack([psnrb_plane_sums(x, None, crop_border, bp) for x in pa])
+    return float(np.mean(psnrb_values(sums, counts, bp, (rows - 2 * crop_border, cols - 2 * crop_border), 255.0)[1]))
+
+
+ALLOWED_METRICS = {'PSNR': psnr, 'SSIM': ssim, 'MS-SSIM': msssim, 'PSNR-B': psnrb}
 
 
 # ---------------------------------------------------------------- XPSNR (include/pnpvcve.h, pnp_xpsnr_*: the one statement of the definition)

@@ -500,14 +500,18 @@ def _metric_frames(t, name):
     return t.contiguous(), _native.FRAMES_F32_NCHW, tuple(t.shape[:-3]), int(c), int(h), int(w)
 
 
+def _metric_color(convert_to):
+    """convert_to None | 'y' / 'Y' -> PNP_COLOR_*"""
+    if isinstance(convert_to, str) and convert_to.lower() == 'y':
+        return _native.COLOR_Y
+    if convert_to is None:
+        return _native.COLOR_NONE
+    raise ValueError('Wrong color model. Supported values are "Y" and None.')
+
+
 def _metric_pair(a, b, convert_to):
     """-> (a, a_format, b, b_format, PNP_COLOR_*, leading shape, frames, c, h, w) of two clips that show the same frames"""
-    if isinstance(convert_to, str) and convert_to.lower() == 'y':
-        color = _native.COLOR_Y
-    elif convert_to is None:
-        color = _native.COLOR_NONE
-    else:
-        raise ValueError('Wrong color model. Supported values are "Y" and None.')
+    color = _metric_color(convert_to)
     a, fa, lead_a, ca, ha, wa = _metric_frames(a, 'a')
     b, fb, lead_b, cb, hb, wb = _metric_frames(b, 'b')
     if (lead_a, ca, ha, wa) != (lead_b, cb, hb, wb):
@@ -1261,6 +1265,128 @@ def xpsnr_yuv420(a, b, crop_border=0, planes='y', fps=30, clip=False):
 
     wsse, db = gather(0, lead + (len(planes),)), gather(1, lead + (len(planes),))
     return (wsse, db, gather(2, lead[:-1] + (len(planes),))) if clip else (wsse, db)
+
+
+# ---------------------------------------------------------------- PSNR-B (include/pnpvcve.h, pnp_psnrb_*)
+def _psnrb_values(sums, plane_dims, block, peak, chroma):
+    """sums (..., planes, 5) -> (PSNR-B, BEF) float64 tensors (..., planes): metrics.psnrb_values, the host path's own fp64 part, on each
+    plane.  plane_dims[k] = (rows, cols, crop) of plane k, chroma[k] whether it is a chroma plane of 4:2:0 (half the block)."""
+    import numpy as np
+    from . import metrics
+    s = sums.numpy()
+    val, bef = np.empty(s.shape[:-1], np.float64), np.empty(s.shape[:-1], np.float64)
+    for k, (rows, cols, crop) in enumerate(plane_dims):
+        bp = metrics.psnrb_block(block, chroma[k])
+        counts = metrics.psnrb_counts(rows, cols, crop, bp)
+        val[..., k], bef[..., k] = metrics.psnrb_values(s[..., k, :], counts, bp, (rows - 2 * crop, cols - 2 * crop), peak)
+    return torch.from_numpy(val), torch.from_numpy(bef)
+
+
+@_on_device_of_first_tensor
+def psnrb_sums_frames(a, b, crop_border=0, convert_to=None, block=8):
+    """The statistic behind psnrb_frames (pnp_psnrb_sums_io; include/pnpvcve.h states the metric).  a: the TEST clip, whose block edges
+    are measured; b: the reference, or None (the no-reference form: sse = 0, b is not read); each on its own fp32 (...,c,h,w) planes or
+    uint8 (...,h,w,3) RGB frames.  convert_to None: an int64 CPU tensor lead + (c, 5) = sse, sbh, snh, sbv, snv of every frame and channel,
+    exact, the same bits every run.  'y': a float64 CPU tensor lead + (1, 5), the sums over the fp32 Y (a frame's per-block partials
+    added in index order)."""
+    from . import metrics
+    if b is None:
+        color = _metric_color(convert_to)
+        a, fa, lead, c, h, w = _metric_frames(a, 'a')
+        if color == _native.COLOR_Y and c != 3:
+            raise ValueError('a must have 3 channels')
+        frames = 1
+        for d in lead:
+            frames *= d
+        fb = fa
+    else:
+        a, fa, b, fb, color, lead, frames, c, h, w = _metric_pair(a, b, convert_to)
+    crop = int(crop_border)
+    metrics.psnrb_counts(h, w, crop, metrics.psnrb_block(block))         # every refusal a ValueError raised before any GPU work
+    L = _native.lib()
+    if color == _native.COLOR_Y:
+        nb = int(L.pnp_psnrb_luma_blocks(h, w, crop))
+        out = torch.empty((frames, nb, 5), dtype=torch.float64, device=a.device)
+    else:
+        out = torch.empty((frames, c, 5), dtype=torch.int64, device=a.device)
+    if frames:
+        _native.check(L.pnp_psnrb_sums_io(_ptr(a), fa, None if b is None else _ptr(b), fb, color, _ptr(out), frames, c, h, w, crop, int(block),
+                                          _stream()), 'pnp_psnrb_sums_io')
+    if color == _native.COLOR_Y:
+        import numpy as np
+        part = out.cpu().numpy()
+        sums = part.cumsum(axis=1)[:, -1].copy() if frames else np.zeros((0, 5), np.float64)      # index order
+        return torch.from_numpy(sums).reshape(lead + (1, 5))
+    return out.cpu().reshape(lead + (c, 5))
+
+
+def _psnrb_frames(a, b, crop_border, convert_to, block):
+    sums = psnrb_sums_frames(a, b, crop_border, convert_to, block)
+    h, w = (a.shape[-3:-1] if a.dtype == torch.uint8 else a.shape[-2:])
+    planes = sums.shape[-2]
+    return _psnrb_values(sums, [(int(h), int(w), int(crop_border))] * planes, block, 255.0, [False] * planes)
+
+
+def psnrb_frames(a, b, crop_border=0, convert_to=None, block=8):
+    """Per-frame PSNR-B (Yim and Bovik 2011; include/pnpvcve.h) of the test clip a against the reference b on the GPU: PSNR with the
+    blocking effect factor of a's `block` x `block` grid (4, 8, 16, 32 or 64; anchored at the uncropped frame's origin) added to the mean
+    squared error.  a, b, crop_border and convert_to as psnr_frames; several channels give the mean of the channels' values.  Returns a
+    float64 CPU tensor of the leading shape.  The sums are the device's (psnrb_sums_frames); the fp64 part is metrics.psnrb_values."""
+    import numpy as np
+    return torch.from_numpy(np.asarray(_psnrb_frames(a, b, crop_border, convert_to, block)[0].numpy().mean(axis=-1)))
+
+
+def bef_frames(a, crop_border=0, convert_to=None, block=8):
+    """The blocking effect factor of a clip alone, per frame (the BEF of psnrb_frames, the mean over the channels): a no-reference
+    blockiness figure in squared sample units.  Nothing but `a` is read."""
+    import numpy as np
+    return torch.from_numpy(np.asarray(_psnrb_frames(a, None, crop_border, convert_to, block)[1].numpy().mean(axis=-1)))
+
+
+def psnrb_sums_yuv420(a, b, crop_border=0, planes='y', block=8):
+    """The statistic behind psnrb_yuv420 (pnp_psnrb_sums_yuv420 / _yuv420p16): a is the TEST clip, b the reference or None (sse = 0, b is
+    not read); two Yuv420Frames or two Yuv420Frames16 of one depth, (n,t,...) or (t,...), each in a layout of its own.  Returns an int64
+    CPU tensor lead + (3, 5): per frame and plane Y, Cb, Cr the exact sse, sbh, snh, sbv, snv, 0 for the planes not named in `planes`
+    (they are not read).  Blocks are `block` on Y and block / 2 on the chroma planes; the crop as psnr_yuv420."""
+    from . import metrics
+    planes = _metric_planes(planes)
+    pairs, lead, t, h, w, crop = _yuv_metric_pair(a, a if b is None else b, crop_border)
+    for p in planes:
+        rows, cols, c = (h, w, crop) if p == 'y' else (h // 2, w // 2, crop // 2)
+        metrics.psnrb_counts(rows, cols, c, metrics.psnrb_block(block, p != 'y'))
+    mask = sum(_PLANE_BITS[p] for p in planes)
+    entry = 'pnp_psnrb_sums_yuv420p16' if isinstance(a, Yuv420Frames16) else 'pnp_psnrb_sums_yuv420'
+    dev = a.y.device
+    with torch.cuda.device(dev):
+        sums = torch.empty((len(pairs), t, 3, 5), dtype=torch.int64, device=dev)
+        for i, (da, db) in enumerate(pairs):
+            if t:
+                _native.check(getattr(_native.lib(), entry)(ctypes.byref(da), None if b is None else ctypes.byref(db), mask, _ptr(sums[i]), t, h,
+                                                            w, crop, int(block), _stream()), entry)
+    return sums.cpu().reshape(lead + (3, 5))
+
+
+def _psnrb_yuv420(a, b, crop_border, planes, block):
+    planes = _metric_planes(planes)
+    sums = psnrb_sums_yuv420(a, b, crop_border, planes, block)
+    h, w = (int(x) for x in a.y.shape[-2:])
+    crop = int(crop_border)
+    idx = ['yuv'.index(p) for p in planes]
+    dims = [(h, w, crop) if p == 'y' else (h // 2, w // 2, crop // 2) for p in planes]
+    peak = float((1 << a.bit_depth) - 1) if isinstance(a, Yuv420Frames16) else 255.0
+    return _psnrb_values(sums[..., idx, :], dims, block, peak, [p != 'y' for p in planes])
+
+
+def psnrb_yuv420(a, b, crop_border=0, planes='y', block=8):
+    """Per-frame plane PSNR-B of two 4:2:0 clips (include/pnpvcve.h): a is the test clip, b the reference; two Yuv420Frames, or two
+    Yuv420Frames16 of one depth d (peak 2^d - 1), each in a layout of its own.  planes as ssim_yuv420; returns a float64 CPU tensor lead +
+    (len(planes),) in that order.  The integers are the device's (psnrb_sums_yuv420); the fp64 part is metrics.psnrb_values."""
+    return _psnrb_yuv420(a, b, crop_border, planes, block)[0]
+
+
+def bef_yuv420(a, crop_border=0, planes='y', block=8):
+    """The blocking effect factor of the planes of one 4:2:0 clip alone, per frame: float64 CPU tensor lead + (len(planes),)"""
+    return _psnrb_yuv420(a, None, crop_border, planes, block)[1]
 
 
 # ---------------------------------------------------------------- self-ensemble (include/pnpvcve.h, "Self-ensemble")

@@ -111,8 +111,10 @@ class BasicVSR(nn.Module):
         'SSIM_V', 'MS-SSIM_U', 'MS-SSIM_V' and 'PSNR_YUV' = (6 PSNR_Y + PSNR_U + PSNR_V) / 8 per frame are accepted too; every value is
         the mean over frames.  'XPSNR', 'XPSNR_U', 'XPSNR_V' (this mode only; include/pnpvcve.h) are the activity-weighted PSNR of the
         planes with `gt` as the original and test_cfg.get('xpsnr_fps', 30) frames per second; their value is the CLIP's, the log of the
-        mean weighted error over the frames, not the mean of the frames' dB.  'MS-SSIM' (five scales; include/pnpvcve.h) is served on
-        the device path of RGB / Y clips too and needs 176 x 176 samples of every plane it scores after the crop.  crop_border (even)
+        mean weighted error over the frames, not the mean of the frames' dB.  'PSNR-B', 'PSNR-B_U', 'PSNR-B_V' (include/pnpvcve.h) are the
+        blocking-aware PSNR of the planes, the output being the test clip, with blocks of test_cfg.get('psnrb_block', 8) on Y and half of
+        that on chroma, the mean over frames; 'PSNR-B' is served on RGB / Y clips too (the `_U` / `_V` names raise KeyError there).
+        'MS-SSIM' (five scales; include/pnpvcve.h) is served on the device path of RGB / Y clips too and needs 176 x 176 samples of every plane it scores after the crop.  crop_border (even)
         crops the Y plane, half of it the chroma planes.  test_cfg.convert_to may be None or 'y' and both mean the same here: the decoder's
         Y' plane IS the luma -- it is NOT the BT.601 Y that convert_to='y' derives from RGB bytes, so the two modes' numbers differ.
         Two ops.Yuv420Frames16 of one bit depth d are scored the same way on their sample values, with the peak 2^d - 1."""
@@ -158,24 +160,30 @@ class BasicVSR(nn.Module):
                 per_frame = msssim_frames(frames_of(output), frames_of(gt), crop_border, convert_to)
                 eval_result[metric] = float(per_frame.mean())
                 continue
+            if metric == 'PSNR-B' and on_device:
+                from .ops import psnrb_frames          # pnp_psnrb_sums_io: the output is the test clip, whose block edges are measured
+                per_frame = psnrb_frames(frames_of(output), frames_of(gt), crop_border, convert_to, self.test_cfg.get('psnrb_block', 8))
+                eval_result[metric] = float(per_frame.mean())
+                continue
+            kw = dict(convert_to=convert_to)
+            if metric == 'PSNR-B':
+                kw['block'] = self.test_cfg.get('psnrb_block', 8)
             if output.ndim == 5:
                 avg = []
                 for i in range(output.size(1)):
-                    avg.append(self.allowed_metrics[metric](tensor2img(output[:, i]), tensor2img(gt[:, i]), crop_border,
-                                                            convert_to=convert_to))
+                    avg.append(self.allowed_metrics[metric](tensor2img(output[:, i]), tensor2img(gt[:, i]), crop_border, **kw))
                 eval_result[metric] = np.mean(avg)
             else:
-                eval_result[metric] = self.allowed_metrics[metric](tensor2img(output), tensor2img(gt), crop_border,
-                                                                   convert_to=convert_to)
+                eval_result[metric] = self.allowed_metrics[metric](tensor2img(output), tensor2img(gt), crop_border, **kw)
         return eval_result
 
     YUV_OUT_LAYOUTS = ('nv12', 'i420', 'p010', 'p012', 'yuv420p10le', 'yuv420p12le')      # the packed 4:2:0 layouts generator.forward writes
     YUV_METRICS = ('PSNR', 'SSIM', 'PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V', 'PSNR_YUV', 'MS-SSIM', 'MS-SSIM_U', 'MS-SSIM_V', 'XPSNR', 'XPSNR_U',
-                   'XPSNR_V')
+                   'XPSNR_V', 'PSNR-B', 'PSNR-B_U', 'PSNR-B_V')
 
     def _evaluate_yuv(self, output, gt):
         """evaluate() of two ops.Yuv420Frames (or two ops.Yuv420Frames16) clips: plane PSNR / SSIM on the device, means over the clip's frames"""
-        from .ops import msssim_yuv420, psnr_yuv420, ssim_yuv420, xpsnr_yuv420
+        from .ops import msssim_yuv420, psnr_yuv420, psnrb_yuv420, ssim_yuv420, xpsnr_yuv420
         crop_border = self.test_cfg['crop_border']
         convert_to = self.test_cfg.get('convert_to', None)
         if not (convert_to is None or (isinstance(convert_to, str) and convert_to.lower() == 'y')):
@@ -195,7 +203,7 @@ class BasicVSR(nn.Module):
         output, gt = one_clip(output, 'output'), one_clip(gt, 'gt')
         gt = type(gt)(*[p.to(output.y.device) for p in gt[:3]], *gt[3:])
         eval_result = dict()
-        psnr = psnr_yuv420(output, gt, crop_border) if any(m.startswith('PSNR') for m in metrics) else None      # (t, 3)
+        psnr = psnr_yuv420(output, gt, crop_border) if any(m in ('PSNR', 'PSNR_U', 'PSNR_V', 'PSNR_YUV') for m in metrics) else None      # (t, 3)
         col = {'SSIM': 'y', 'SSIM_U': 'u', 'SSIM_V': 'v'}
         planes = ''.join(dict.fromkeys(col[m] for m in metrics if m in col))
         ssim = ssim_yuv420(output, gt, crop_border, planes) if planes else None                                    # (t, len(planes))
@@ -206,9 +214,15 @@ class BasicVSR(nn.Module):
         xp_planes = ''.join(dict.fromkeys(xp_col[m] for m in metrics if m in xp_col))
         # gt is the original, whose activity sets the weights; the value is the CLIP's (the log of the mean weighted error): (len(xp_planes),)
         xpsnr = xpsnr_yuv420(output, gt, crop_border, xp_planes, self.test_cfg.get('xpsnr_fps', 30), clip=True)[2] if xp_planes else None
+        pb_col = {'PSNR-B': 'y', 'PSNR-B_U': 'u', 'PSNR-B_V': 'v'}
+        pb_planes = ''.join(dict.fromkeys(pb_col[m] for m in metrics if m in pb_col))
+        # the output is the test clip, whose block edges are measured: (t, len(pb_planes))
+        psnrb = psnrb_yuv420(output, gt, crop_border, pb_planes, self.test_cfg.get('psnrb_block', 8)) if pb_planes else None
         for metric in metrics:
             if metric in col:
                 eval_result[metric] = float(ssim[:, planes.index(col[metric])].mean())
+            elif metric in pb_col:
+                eval_result[metric] = float(psnrb[:, pb_planes.index(pb_col[metric])].mean())
             elif metric in xp_col:
                 eval_result[metric] = float(xpsnr[xp_planes.index(xp_col[metric])])
             elif metric in ms_col:

@@ -49,7 +49,7 @@ def parse_args():
                         '(fp32 planes only for the metrics); a pair of clips goes in by pointer instead of concatenated.  Same '
                         'metrics and PNG bytes; default off')
     p.add_argument('--byte-metrics', action='store_true',
-                   help='implies --byte-frames; PSNR / SSIM / MS-SSIM read bytes too: the ground truth stays uint8 on the device and the generator '
+                   help='implies --byte-frames; PSNR / SSIM / MS-SSIM / PSNR-B read bytes too: the ground truth stays uint8 on the device and the generator '
                         'writes display bytes only, with or without --save-path (6 B per pixel into the metrics instead of 24).  Same '
                         'metrics; default off')
     p.add_argument('--yuv-frames', action='store_true',
@@ -57,6 +57,7 @@ def parse_args():
                         '4:2:0 only, the ground truth stays 8-bit planes on the device, PSNR / SSIM are the Y plane\'s (PSNR_U, PSNR_V, '
                         'SSIM_U, SSIM_V, the 6:1:1 PSNR_YUV, MS-SSIM, MS-SSIM_U, MS-SSIM_V -- five scales, planes of 176 x 176 or more -- and the '
                         'activity-weighted XPSNR, XPSNR_U, XPSNR_V -- the ground truth is the original, test_cfg.xpsnr_fps (30) its frame rate -- '
+                        'and the blocking-aware PSNR-B, PSNR-B_U, PSNR-B_V -- test_cfg.psnrb_block (8) the coded block size -- '
                         'may be listed in test_cfg.metrics too) and --save-path gets one <clip>.yuv '
                         'per clip; a dataset with bit_depth=10 | 12 (16-bit little-endian .yuv files) goes the same way at its depth; '
                         'default off')
@@ -153,6 +154,8 @@ def main():
             line += '/{:.4f}'.format(float(stats.get('MS-SSIM', float('nan'))))
         if 'XPSNR' in (cfg.test_cfg.get('metrics', None) or ()):        # and an XPSNR field only when the config lists it
             line += '/{:.4f}'.format(float(stats.get('XPSNR', float('nan'))))
+        if 'PSNR-B' in (cfg.test_cfg.get('metrics', None) or ()):       # and a PSNR-B field only when the config lists it
+            line += '/{:.4f}'.format(float(stats.get('PSNR-B', float('nan'))))
         print(line)
         fps = [o['frames_per_s'] for o in outputs]
         import torch.distributed as dist
