@@ -229,8 +229,8 @@ int64_t pnp_generator_workspace_bytes_io(const pnp_generator* g, int t, int h, i
  *   rounding half to even; per pixel pb = (b - yl) * (0.5 / (1 - Kb)), pr = (r - yl) * (0.5 / (1 - Kr)); the chroma sample of a 2x2
  *   block is the BOX MEAN ((p00 + p01) + (p10 + p11)) * 0.25 (rows top then bottom, columns left then right) and
  *   Cb = clamp(rint(128 + sc * mean_pb), 0, 255), Cr likewise.  Box-down and replicate-up are consistent (centre siting) and are the
- *   DEFAULT chroma mode; the other modes are stated below.  4:2:2 and 4:4:4 are not offered (10 and 12 bit: pnp_yuv420_planes16
- *   below).  Limited-range white (235,128,128) gives 0.99999994, not 1.
+ *   DEFAULT chroma mode; the other modes are stated below, and so are the 4:2:2 and 4:4:4 chroma formats (10 and 12 bit:
+ *   pnp_yuv420_planes16 below).  Limited-range white (235,128,128) gives 0.99999994, not 1.
  * Chroma modes (siting and filters; opt-in, at every depth; tests/yuv_chroma_ref.py restates them in numpy).  This is the ONE statement
  * of them; like the rest of this boundary, and like MS-SSIM's and XPSNR's arithmetic below, the definition is the project's own: no
  * external tool's digits are pinned.  Every entry that takes yuv_standard takes PNP_YUV_CODE(standard, chroma): the standard 0..3 in
@@ -256,7 +256,29 @@ int64_t pnp_generator_workspace_bytes_io(const pnp_generator* g, int t, int h, i
  *   are combined.  TOPLEFT: the rows max(2j - 1, 0), 2j, 2j + 1 are filtered across, then combined with the three-tap form.  Modes 0
  *   and 1 keep the box mean's expression.  Rounding and clamping to samples are unchanged; so is Y.
  *   A chroma ramp C[i] = a + b i therefore upsamples to a + b (x - off) / 2 exactly away from the clamped edges, off = 0 on a
- *   co-sited axis and 1/2 on a midway one.  A mode above 3, any bit from 12 up and a low byte above 3 are PNP_ERR_BAD_ARG.
+ *   co-sited axis and 1/2 on a midway one.  A mode above 3 and a low byte above 3 are PNP_ERR_BAD_ARG.
+ * Chroma formats (4:2:2 and 4:4:4; at every depth, in every container and chroma mode; tests/yuv_formats_ref.py restates them in
+ * numpy).  This is the ONE statement of them; the definition is the project's own and no external tool's digits are pinned.  A chroma
+ * format is a pair of subsampling factors (sx, sy): PNP_YUV_FORMAT_420 (2, 2), what is stated above; PNP_YUV_FORMAT_422 (2, 1);
+ * PNP_YUV_FORMAT_444 (1, 1).  The chroma planes are (h / sy) x (w / sx); sx must divide w and sy must divide h, so 4:2:2 needs an even
+ * w only and 4:4:4 puts no parity condition on h or w.  The format rides in bits 12..13 of the integer every entry takes as
+ * yuv_standard, PNP_YUV_CODE3(standard, chroma, format): a code with format 0 is every code there was and does what it did; format
+ * value 3 and any bit from 14 up are PNP_ERR_BAD_ARG.  The entries, descriptors and PNP_OUT_YUV420 keep their names: the `420` in
+ * them is historical, and every one of them (the forwards, pnp_frames_from_yuv420 / _to_yuv420 and their p16 forms, the debug pack)
+ * takes every format on the same descriptors, with c_pitch >= c_step * w / sx samples.  A clip's output planes have the input's
+ * format: one code serves both directions.  Standards, depths, containers, constants, rounding and the rule of no contraction are
+ * those of the 4:2:0 statement, word for word; only the chroma geometry changes:
+ *   Planes -> RGB.  PNP_YUV_CHROMA_REPLICATE: pixel (yy, xx) reads chroma sample (yy / sy, xx / sx).  The other modes: the per-axis
+ *   tap table above applies on every axis whose factor is 2; on an axis whose factor is 1, luma index k takes chroma index k with
+ *   weight 4.  The weights still sum to 16; u16, u = float(u16) * 0.0625f and everything after are the expressions above.  So in 4:2:2
+ *   LEFT and TOPLEFT are the same function, in 4:4:4 all four modes are the same function, and no mode is refused for any format.
+ *   RGB -> planes.  Y, pb and pr per pixel are as above.  On an axis with factor 2 the mode's filter of the 4:2:0 statement applies
+ *   on that axis (midway: (p0 + p1) * 0.5; co-sited: ((pL + pR) + (pC + pC)) * 0.25 with the clamped left tap); on an axis with factor
+ *   1 the sample is the pixel's own value, with no operation.  Modes 0 and 1 at 4:2:2 are therefore (p0 + p1) * 0.5 across, and at
+ *   4:4:4 every mode rounds pb and pr of the pixel itself.  Each operation is one fp32 operation rounded on its own.
+ *   The reading and writing rule below carries over with the chroma planes' true rows and columns.
+ *   BT.2020 constants, a conversion between the input's and the output's format, packed formats (YUY2, v210, AYUV) and MS-SSIM,
+ *   XPSNR and PSNR-B on 4:2:2 or 4:4:4 planes are not offered.
  * A plane pointer may sit at ANY byte address and a pitch may be any value that holds a row, odd ones too.  No byte outside
  * [plane, plane + rows * pitch) of a plane is read or written, and inside it the bytes of a row beyond the frame's width are never
  * written.  Planes and pitches that are 4-byte aligned take a faster form of the unpacking (same values).
@@ -264,8 +286,9 @@ int64_t pnp_generator_workspace_bytes_io(const pnp_generator* g, int t, int h, i
  * PNP_OUT_F32 | PNP_OUT_U8 | PNP_OUT_YUV420, each output the one its own call would write: the result is bit-identical to the fp32
  * forward on pnp_frames_from_yuv420 of the planes, and the PNP_OUT_YUV420 bytes are pnp_frames_to_yuv420 of the fp32 output.
  * Errors, decided on the host before any HIP call: PNP_ERR_BAD_ARG for an unknown standard, a mask of 0 or beyond 7, a NULL plane or
- * output the mask needs, c_step not 1 or 2, a pitch below the row's bytes, or odd h or w; then the forward's own, in their order
- * (with pnp_generator_set_any_size every even h, w >= 64 runs).
+ * output the mask needs, c_step not 1 or 2, a pitch below the row's bytes, or odd h or w (4:2:2: odd w; 4:4:4: neither); then the
+ * forward's own, in their order (with pnp_generator_set_any_size every even h, w >= 64 runs; 4:2:2: every h >= 64 with an even
+ * w >= 64; 4:4:4: every h, w >= 64).
  * pnp_generator_workspace_bytes_yuv: bytes of one context (-1: mask, or a bound below the minimum): pnp_generator_workspace_bytes
  * plus ONE frame of fp32 planes (12 h w bytes, 256-aligned) in front of a last conv that keeps its fp32 interface (PNP_PREC_F16,
  * PNP_OPT_CONV_LAST_VALU = 0), plus ONE output frame of fp32 planes (12 H W) where bytes or planes are made of an fp32 frame the
@@ -279,6 +302,10 @@ int64_t pnp_generator_workspace_bytes_io(const pnp_generator* g, int t, int h, i
 #define PNP_YUV_CHROMA_LEFT 2
 #define PNP_YUV_CHROMA_TOPLEFT 3
 #define PNP_YUV_CODE(standard, chroma) ((standard) | ((chroma) << 8))
+#define PNP_YUV_FORMAT_420 0
+#define PNP_YUV_FORMAT_422 1
+#define PNP_YUV_FORMAT_444 2
+#define PNP_YUV_CODE3(standard, chroma, format) ((standard) | ((chroma) << 8) | ((format) << 12))
 #define PNP_OUT_YUV420 4
 typedef struct pnp_yuv420_planes {      /* t frames of h x w, 8 bit, 4:2:0 */
     unsigned char *y, *cb, *cr;         /* first frame's planes; NV12: cr == cb + 1, c_step 2; NV21: cb == cr + 1; I420: c_step 1 */
@@ -333,6 +360,20 @@ int pnp_psnr_sse_yuv420(const pnp_yuv420_planes* a_host_desc, const pnp_yuv420_p
 int pnp_ssim_blocks_yuv420(int h, int w, int crop_border, int plane);
 int pnp_ssim_partials_yuv420(const pnp_yuv420_planes* a_host_desc, const pnp_yuv420_planes* b_host_desc, int plane_mask,
                              double* partials_dev, int frames, int h, int w, int crop_border, void* stream);
+/* The plane metrics of every chroma format ("Chroma formats" above): these entries take chroma_format = PNP_YUV_FORMAT_*, and the
+ * _yuv420 / _yuv420p16 entries are calls of them with PNP_YUV_FORMAT_420, returning what they returned.  Everything above holds with
+ * the chroma planes' true geometry: they are (h / sy) x (w / sx) and are cropped by crop_border / sx across and crop_border / sy down
+ * (the Y plane by crop_border on every side).  crop_border must be even for 4:2:0 and 4:2:2; for 4:4:4 any value >= 0 is accepted.
+ * N_C = (h/sy - 2c/sy)(w/sx - 2c/sx), c = crop_border.  PSNR_YUV keeps the project's 6:1:1 definition (6 PSNR_Y + PSNR_Cb + PSNR_Cr) / 8
+ * for every format, 4:4:4 included, where the three planes have equal sizes: it is a score of this project, not a sample-weighted
+ * mean.  pnp_ssim_blocks_yuv: pnp_ssim_blocks of the cropped plane; with equal crops on both axes the partials are today's, bit for
+ * bit.  PNP_ERR_BAD_ARG (pnp_ssim_blocks_yuv: 0) for a chroma_format outside 0..2, an h or w the format refuses, an odd crop_border at
+ * 4:2:0 or 4:2:2, and whatever the entries above refuse.  The p16 entries: as pnp_psnr_sse_yuv420p16 / pnp_ssim_partials_yuv420p16. */
+int pnp_psnr_sse_yuv(const pnp_yuv420_planes* a_host_desc, const pnp_yuv420_planes* b_host_desc, unsigned long long* sse_dev, int frames,
+                     int h, int w, int crop_border, int chroma_format, void* stream);
+int pnp_ssim_blocks_yuv(int h, int w, int crop_border, int plane, int chroma_format);
+int pnp_ssim_partials_yuv(const pnp_yuv420_planes* a_host_desc, const pnp_yuv420_planes* b_host_desc, int plane_mask,
+                          double* partials_dev, int frames, int h, int w, int crop_border, int chroma_format, void* stream);
 
 /* 10 / 12-bit 4:2:0 boundary (yuv.hip): the same boundary on the planes HEVC Main10 / VVC decoders and reference software write.
  * The reference has no such path; tests/yuv16_ref.py restates the arithmetic below in numpy.  This is the ONE statement of it.
@@ -395,6 +436,10 @@ int pnp_psnr_sse_yuv420p16(const pnp_yuv420_planes16* a_host_desc, const pnp_yuv
                            unsigned long long* sse_dev, int frames, int h, int w, int crop_border, void* stream);
 int pnp_ssim_partials_yuv420p16(const pnp_yuv420_planes16* a_host_desc, const pnp_yuv420_planes16* b_host_desc, int plane_mask,
                                 double* partials_dev, int frames, int h, int w, int crop_border, void* stream);
+int pnp_psnr_sse_yuvp16(const pnp_yuv420_planes16* a_host_desc, const pnp_yuv420_planes16* b_host_desc, unsigned long long* sse_dev,
+                        int frames, int h, int w, int crop_border, int chroma_format, void* stream);
+int pnp_ssim_partials_yuvp16(const pnp_yuv420_planes16* a_host_desc, const pnp_yuv420_planes16* b_host_desc, int plane_mask,
+                             double* partials_dev, int frames, int h, int w, int crop_border, int chroma_format, void* stream);
 
 /* Optional per-launch timing with HIP events recorded on the caller's stream around every
  * kernel of pnp_generator_forward (measurement aid for bench.py; replaces the reference's

@@ -53,7 +53,10 @@ FRAMES_F32_NCHW, FRAMES_U8_HWC = 0, 1        # PNP_FRAMES_*
 OUT_F32, OUT_U8, OUT_YUV420 = 1, 2, 4        # PNP_OUT_* (a mask; OUT_YUV420 on pnp_generator_forward_clips_yuv only)
 YUV_STANDARDS = {'bt601-limited': 0, 'bt601-full': 1, 'bt709-limited': 2, 'bt709-full': 3}      # PNP_YUV_*
 YUV_CHROMA = {'replicate': 0, 'center': 1, 'left': 2, 'topleft': 3}      # PNP_YUV_CHROMA_*: bits 8..11 of PNP_YUV_CODE(standard, chroma)
-COLOR_NONE, COLOR_Y = 0, 1                   # PNP_COLOR_* (the metrics' convert_to)
+# PNP_YUV_FORMAT_*: bits 12..13 of PNP_YUV_CODE3(standard, chroma, format); the chroma planes are (h / sy) x (w / sx)
+YUV_FORMAT = {'420': 0, '422': 1, '444': 2}
+YUV_FACTORS = {'420': (2, 2), '422': (2, 1), '444': (1, 1)}      # format -> (sx, sy)
+COLOR_NONE, COLOR_Y = 0, 1                  # PNP_COLOR_* (the metrics' convert_to)
 PLANE_Y, PLANE_CB, PLANE_CR = 1, 2, 4        # PNP_PLANE_* (a mask: the planes pnp_ssim_partials_yuv420 scores)
 
 # name -> (restype, argtypes); every symbol include/pnpvcve.h declares
@@ -101,6 +104,12 @@ SIGNATURES = {
     'pnp_psnr_sse_yuv420p16': (c_int, [POINTER(Yuv420Planes16), POINTER(Yuv420Planes16), c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'pnp_ssim_partials_yuv420p16': (c_int, [POINTER(Yuv420Planes16), POINTER(Yuv420Planes16), c_int, c_void_p, c_int, c_int, c_int, c_int,
                                             c_void_p]),
+    'pnp_psnr_sse_yuv': (c_int, [POINTER(Yuv420Planes), POINTER(Yuv420Planes), c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'pnp_ssim_blocks_yuv': (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    'pnp_ssim_partials_yuv': (c_int, [POINTER(Yuv420Planes), POINTER(Yuv420Planes), c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'pnp_psnr_sse_yuvp16': (c_int, [POINTER(Yuv420Planes16), POINTER(Yuv420Planes16), c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'pnp_ssim_partials_yuvp16': (c_int, [POINTER(Yuv420Planes16), POINTER(Yuv420Planes16), c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                         c_void_p]),
     'pnp_generator_set_precision': (c_int, [c_void_p, c_int]),
     'pnp_generator_get_precision': (c_int, [c_void_p]),
     'pnp_generator_set_option': (c_int, [c_void_p, c_int, c_int]),

@@ -19,10 +19,14 @@ def _to_device(data, device, byte_frames=False, byte_metrics=False):
     out = {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in data.items()}
     for k in ('lq', 'gt'):
         if k + '_yuv' in out:
-            from .ops import yuv420_views, yuv420p16_views
-            buf = out.pop(k + '_yuv')                                      # (n, T, 3h/2, w)
+            from .ops import YUV_FORMAT_LAYOUTS, _yuv_views_format, yuv420_views, yuv420p16_views
+            buf = out.pop(k + '_yuv')                                      # (n, T, 3h/2, w); 4:2:2: 2h rows, 4:4:4: 3h
             meta = data['meta'][0]
-            if meta.get('bit_depth', 8) != 8:
+            if meta.get('format', '420') != '420':                         # (the layout names the format and the plane order)
+                fmt, order = YUV_FORMAT_LAYOUTS[meta['layout']][:2]
+                tail = () if meta.get('bit_depth', 8) == 8 else (meta['bit_depth'], meta.get('msb_aligned', False))
+                out[k] = _yuv_views_format(buf, buf.shape[-2] // (2 if fmt == '422' else 3), buf.shape[-1], fmt, order, tail)
+            elif meta.get('bit_depth', 8) != 8:
                 out[k] = yuv420p16_views(buf, buf.shape[-2] * 2 // 3, buf.shape[-1], (meta['layout'], meta['bit_depth'], meta.get('msb_aligned', False)))
             else:
                 out[k] = yuv420_views(buf, buf.shape[-2] * 2 // 3, buf.shape[-1], meta['layout'])
@@ -199,12 +203,15 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
             raise ValueError('yuv_frames runs the generator on the GPU: a CUDA/HIP device and a model with a generator (not psnr_only)')
         if byte_frames:
             raise ValueError('yuv_frames and byte_frames / byte_metrics are two boundaries: pick one')
-        from .ops import YUV16_LAYOUTS
+        from .ops import YUV16_LAYOUTS, YUV_FORMAT_LAYOUTS, yuv_layout
         depth = getattr(dataset, 'bit_depth', 8)
-        if yuv_out_layout not in ('i420', 'nv12') and yuv_out_layout not in YUV16_LAYOUTS:
+        if yuv_out_layout not in ('i420', 'nv12') and yuv_out_layout not in YUV16_LAYOUTS and yuv_out_layout not in YUV_FORMAT_LAYOUTS:
             raise ValueError(f"yuv_out_layout must be 'i420' or 'nv12', or one of {sorted(YUV16_LAYOUTS)} for a 10 / 12-bit dataset, "
-                             f'got {yuv_out_layout!r}')
-        if YUV16_LAYOUTS.get(yuv_out_layout, (None, 8))[1] != depth:
+                             f'or one of {list(YUV_FORMAT_LAYOUTS)} for a 4:2:2 / 4:4:4 dataset, got {yuv_out_layout!r}')
+        if yuv_layout(yuv_out_layout)[0] != getattr(dataset, 'format', '420'):
+            raise ValueError(f'yuv_out_layout {yuv_out_layout!r} does not have the dataset\'s chroma format ({getattr(dataset, "format", "420")}): '
+                             f'the planes written have the input\'s format')
+        if yuv_layout(yuv_out_layout)[2] != depth:
             raise ValueError(f'yuv_out_layout {yuv_out_layout!r} does not have the dataset\'s bit depth ({depth}): the output is scored '
                              f'against the ground truth at one depth')
     yuv_standard = getattr(dataset, 'yuv_standard', 'bt601-limited')

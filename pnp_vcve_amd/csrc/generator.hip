@@ -1519,14 +1519,14 @@ int forward_clips_yuv(const pnp_generator* g, const float* flat, const float* pa
                       int h, int w, hipStream_t st) {
     YuvCoef k;
     if (!g || !yuv_coef(yuv_standard, 8, 0, &k) || out_mask < 1 || out_mask > (PNP_OUT_F32 | PNP_OUT_U8 | PNP_OUT_YUV420)) return PNP_ERR_BAD_ARG;
-    if (h < 2 || w < 2 || (h & 1) || (w & 1)) return PNP_ERR_BAD_ARG;
+    if (!yuv_frame_ok(k.format, 1, h, w)) return PNP_ERR_BAD_ARG;      // (the format's parity rules: sx divides w, sy divides h)
     const int os = g->cfg.vsr ? 4 : 1;
     for (const YuvClip& c : clips) {
-        if (!yuv_planes_ok(c.lq, w) || !c.mvs_dev || !c.par_dev) return PNP_ERR_BAD_ARG;
+        if (!yuv_planes_ok(c.lq, w, k.format) || !c.mvs_dev || !c.par_dev) return PNP_ERR_BAD_ARG;
         if ((out_mask & PNP_OUT_F32) && !c.out_f32_dev) return PNP_ERR_BAD_ARG;
         const uintptr_t amask = g->any_size ? 0 : 3;      // (the byte output's rule of pnp_generator_forward_clips)
         if ((out_mask & PNP_OUT_U8) && (!c.out_u8_dev || (reinterpret_cast<uintptr_t>(c.out_u8_dev) & amask))) return PNP_ERR_BAD_ARG;
-        if ((out_mask & PNP_OUT_YUV420) && !yuv_planes_ok(c.out, w * os)) return PNP_ERR_BAD_ARG;
+        if ((out_mask & PNP_OUT_YUV420) && !yuv_planes_ok(c.out, w * os, k.format)) return PNP_ERR_BAD_ARG;
     }
     return forward_batch(g, flat, packed, nullptr, (int)clips.size(), FRAMES_YUV420, out_mask, slices, qps, base_qps, workspace, workspace_bytes, t, h,
                          w, st, clips.data(), yuv_standard);

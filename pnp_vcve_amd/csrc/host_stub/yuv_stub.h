@@ -30,21 +30,21 @@ inline int pnp_stub_yuv_record(const PnpStubYuvLaunch& r) {
     return 0;
 }
 
-inline bool pnp_stub_yuv_args_ok(const YuvPlanes& p, int n, int H, int W) {      // yuv.hip's own checks
-    return n >= 1 && H >= 2 && W >= 2 && !(H & 1) && !(W & 1) && yuv_planes_ok(p, W);
+inline bool pnp_stub_yuv_args_ok(const YuvPlanes& p, const YuvCoef& k, int n, int H, int W) {      // yuv.hip's own checks
+    return yuv_frame_ok(k.format, n, H, W) && yuv_planes_ok(p, W, k.format);
 }
 
-inline int launch_pack_lr_yuv420(const YuvPlanes& in, const YuvCoef&, float* lr4, int T, int H, int W, bool force_general, hipStream_t stream) {
-    if (!lr4 || !pnp_stub_yuv_args_ok(in, T, H, W)) return PNP_ERR_BAD_ARG;
-    return pnp_stub_yuv_record(PnpStubYuvLaunch{PNP_STUB_YUV_PACK, stream, in, nullptr, lr4, T, H, W, !force_general && yuv_planes_fast(in, W)});
+inline int launch_pack_lr_yuv420(const YuvPlanes& in, const YuvCoef& k, float* lr4, int T, int H, int W, bool force_general, hipStream_t stream) {
+    if (!lr4 || !pnp_stub_yuv_args_ok(in, k, T, H, W)) return PNP_ERR_BAD_ARG;
+    return pnp_stub_yuv_record(PnpStubYuvLaunch{PNP_STUB_YUV_PACK, stream, in, nullptr, lr4, T, H, W, !force_general && yuv_planes_fast(in, W, k.format)});
 }
 
-inline int launch_frames_from_yuv420(const YuvPlanes& in, const YuvCoef&, float* out, int nframes, int H, int W, hipStream_t stream) {
-    if (!out || !pnp_stub_yuv_args_ok(in, nframes, H, W)) return PNP_ERR_BAD_ARG;
+inline int launch_frames_from_yuv420(const YuvPlanes& in, const YuvCoef& k, float* out, int nframes, int H, int W, hipStream_t stream) {
+    if (!out || !pnp_stub_yuv_args_ok(in, k, nframes, H, W)) return PNP_ERR_BAD_ARG;
     return pnp_stub_yuv_record(PnpStubYuvLaunch{PNP_STUB_YUV_FROM, stream, in, nullptr, out, nframes, H, W, false});
 }
 
-inline int launch_frames_to_yuv420(const float* in, const YuvPlanes& out, const YuvCoef&, int nframes, int H, int W, hipStream_t stream) {
-    if (!in || !pnp_stub_yuv_args_ok(out, nframes, H, W)) return PNP_ERR_BAD_ARG;
+inline int launch_frames_to_yuv420(const float* in, const YuvPlanes& out, const YuvCoef& k, int nframes, int H, int W, hipStream_t stream) {
+    if (!in || !pnp_stub_yuv_args_ok(out, k, nframes, H, W)) return PNP_ERR_BAD_ARG;
     return pnp_stub_yuv_record(PnpStubYuvLaunch{PNP_STUB_YUV_TO, stream, out, in, nullptr, nframes, H, W, false});
 }

@@ -3,9 +3,8 @@
 // frames, the optional luma step, 8-bit planes through plane_load.h, 16-bit words -- and what the entries refuse before they look at
 // their statistic.  Everything is internal to the unit that includes it (anonymous namespace); nothing here launches a kernel.
 #pragma once
-#include "plane_load.h"
+#include "plane_src.h"
 #include "prep.h"
-#include "yuv.h"
 #include <cmath>
 
 namespace {
@@ -130,31 +129,6 @@ inline bool io_args_ok(const void* a, int fa, const void* b, int fb, int color, 
     return c == 3 || planes_only;
 }
 
-// The chroma of one clip: paired (NV12 / NV21: one load gives both planes; c[0] is the pair at the lower address and cr_first says
-// which plane that is) or two planes of their own (I420; c[0] = Cb, c[1] = Cr).
-struct ChromaSrc {
-    PnpPlaneSrc c[2];
-    int paired, cr_first;
-};
-
-inline PnpPlaneSrc luma_src(const pnp_yuv420_planes& p, int h, int w) { return PnpPlaneSrc{p.y, p.y_pitch, p.y_frame, 1, h, w}; }
-
-inline ChromaSrc chroma_src(const pnp_yuv420_planes& p, int h, int w) {
-    ChromaSrc s;
-    const int rows = h / 2, cols = w / 2;
-    const uintptr_t cb = reinterpret_cast<uintptr_t>(p.cb), cr = reinterpret_cast<uintptr_t>(p.cr);
-    s.paired = p.c_step == 2 && (cb > cr ? cb - cr : cr - cb) == 1;
-    s.cr_first = cr < cb;
-    if (s.paired) {
-        s.c[0] = s.c[1] = PnpPlaneSrc{s.cr_first ? p.cr : p.cb, p.c_pitch, p.c_frame, 2, rows, 2 * cols};
-    } else {
-        const int rowbytes = p.c_step * (cols - 1) + 1;
-        s.c[0] = PnpPlaneSrc{p.cb, p.c_pitch, p.c_frame, p.c_step, rows, rowbytes};
-        s.c[1] = PnpPlaneSrc{p.cr, p.c_pitch, p.c_frame, p.c_step, rows, rowbytes};
-    }
-    return s;
-}
-
 // One plane of a 10 / 12-bit clip (pnp_yuv420_planes16): 2-byte loads, sample (row, col) of frame f is the word at
 // p + f * frame + row * pitch (bytes) + col * step (samples), read as (word >> shift) & mask.
 struct Plane16 {
@@ -173,17 +147,22 @@ inline Plane16 plane16(const pnp_yuv420_planes16& p, int plane) {      // plane:
     return Plane16{plane == 1 ? p.cb : p.cr, p.c_pitch, p.c_frame, p.c_step, shift, mask};
 }
 
-// what the plane entries refuse before they look at their statistic
-inline bool planes_args_ok(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, const void* out, int frames, int h, int w, int crop) {
-    if (!a || !b || !out || frames < 1 || h < 2 || w < 2 || (h & 1) || (w & 1)) return false;
-    if (crop < 0 || (crop & 1) || 2 * crop >= h || 2 * crop >= w) return false;
-    return yuv_planes_ok(*a, w) && yuv_planes_ok(*b, w);
+// the crop rule of a format: crop_border even where an axis is subsampled (4:2:0, 4:2:2), any value >= 0 at 4:4:4
+inline bool plane_crop_ok(int format, int h, int w, int crop) {
+    return crop >= 0 && !(yuv_sx(format) == 2 && (crop & 1)) && 2 * crop < h && 2 * crop < w;
 }
 
-inline bool planes16_args_ok(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, const void* out, int frames, int h, int w, int crop) {
-    if (!a || !b || !out || frames < 1 || h < 2 || w < 2 || (h & 1) || (w & 1)) return false;
-    if (crop < 0 || (crop & 1) || 2 * crop >= h || 2 * crop >= w) return false;
-    return yuv_planes_ok(*a, w) && yuv_planes_ok(*b, w) && a->bit_depth == b->bit_depth;
+// what the plane entries refuse before they look at their statistic
+inline bool planes_args_ok(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, const void* out, int frames, int h, int w, int crop,
+                           int format = PNP_YUV_FORMAT_420) {
+    if (!a || !b || !out || !yuv_frame_ok(format, frames, h, w) || !plane_crop_ok(format, h, w, crop)) return false;
+    return yuv_planes_ok(*a, w, format) && yuv_planes_ok(*b, w, format);
+}
+
+inline bool planes16_args_ok(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, const void* out, int frames, int h, int w, int crop,
+                             int format = PNP_YUV_FORMAT_420) {
+    if (!a || !b || !out || !yuv_frame_ok(format, frames, h, w) || !plane_crop_ok(format, h, w, crop)) return false;
+    return yuv_planes_ok(*a, w, format) && yuv_planes_ok(*b, w, format) && a->bit_depth == b->bit_depth;
 }
 
 inline void ssim_window(double* g) {                     // cv2.getGaussianKernel(11, 1.5)

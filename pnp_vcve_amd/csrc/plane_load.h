@@ -93,20 +93,24 @@ PNP_PLANE_HD int pnp_plane_load4(const PnpPlaneSrc& s, int64_t f, int row, int c
 
 // The samples of a plane inside its crop as `rows` runs of `roww` samples, each cut into `gpr` groups of four: group gx of run rr -> its
 // row, its first column and how many of the four exist.  (Runs and groups are walked as two indices: no division on the device.)
+// The crop is one per axis (crop: rows at the top and the bottom; cropx: columns left and right): the chroma planes of 4:2:2 are cropped
+// by crop_border down and crop_border / 2 across.
 struct PnpPlaneRuns {
-    int crop, rows, roww, gpr;
+    int crop, rows, roww, gpr, cropx;
 };
-PNP_PLANE_HD PnpPlaneRuns pnp_plane_runs(int prows, int pcols, int crop) {
+PNP_PLANE_HD PnpPlaneRuns pnp_plane_runs(int prows, int pcols, int cropy, int cropx) {
     PnpPlaneRuns r;
-    r.crop = crop;
-    r.rows = prows - 2 * crop;
-    r.roww = pcols - 2 * crop;
+    r.crop = cropy;
+    r.cropx = cropx;
+    r.rows = prows - 2 * cropy;
+    r.roww = pcols - 2 * cropx;
     r.gpr = (r.roww + 3) / 4;
     return r;
 }
+PNP_PLANE_HD PnpPlaneRuns pnp_plane_runs(int prows, int pcols, int crop) { return pnp_plane_runs(prows, pcols, crop, crop); }
 PNP_PLANE_HD void pnp_plane_group(const PnpPlaneRuns& r, int rr, int gx, int& row, int& col, int& npix) {
     const int left = r.roww - 4 * gx;
     npix = left < 4 ? left : 4;
     row = r.crop + rr;
-    col = r.crop + 4 * gx;
+    col = r.cropx + 4 * gx;
 }

@@ -1,4 +1,5 @@
-// Plane PSNR / SSIM of 8-bit 4:2:0 clips (include/pnpvcve.h, pnp_psnr_sse_yuv420 / pnp_ssim_partials_yuv420): the statistics of
+// Plane PSNR / SSIM of Y'CbCr clips (include/pnpvcve.h, pnp_psnr_sse_yuv / pnp_ssim_partials_yuv; the _yuv420 entries are those at
+// PNP_YUV_FORMAT_420; a format gives the chroma planes their true rows, columns and a crop per axis): the statistics of
 // metrics.hip read from the decoder's planes where they lie -- NV12 / NV21 / I420, any address and pitch, each of the two clips
 // described on its own -- 1.5 B per pixel and clip, no RGB and no fp32 copy in between.  What a codec-enhancement result is scored by:
 // Y, Cb and Cr on their own (and the 6:1:1 mean the host forms).  plane_load.h fetches; the statistics are metrics.hip's.
@@ -92,7 +93,7 @@ struct SsimPlane {
     PnpPlaneSrc a, b;
     Plane16 a16, b16;       // the 16-bit sample path's planes (ssim_yuv420_kernel<true>)
     int a_sel, b_sel;       // which word of the loader's pair the plane is (1: the second of an interleaved pair)
-    int H, W, crop, oh, ow, tiles_x, blocks, blk0;
+    int H, W, cropy, cropx, oh, ow, tiles_x, blocks, blk0;      // (a crop per axis: 4:2:2 chroma is cropped by c down, c / 2 across)
     long out0;              // first partial of this plane
 };
 struct SsimYuvArgs {
@@ -119,19 +120,19 @@ __global__ __launch_bounds__(256) void ssim_yuv420_kernel(const SsimYuvArgs s) {
     if (S16) {
         for (int i = t; i < 26 * 42; i += 256) {
             const int r = i / 42, cx = i - r * 42;
-            const int y = p.crop + ty0 + r, x = p.crop + tx0 + cx;
-            const bool in = y < p.H - p.crop && x < p.W - p.crop;       // absent samples are 0 in both tiles
+            const int y = p.cropy + ty0 + r, x = p.cropx + tx0 + cx;
+            const bool in = y < p.H - p.cropy && x < p.W - p.cropx;       // absent samples are 0 in both tiles
             ta[i] = in ? (float)load16(p.a16, frame, y, x) : 0.f;
             tb[i] = in ? (float)load16(p.b16, frame, y, x) : 0.f;
         }
     }
     for (int i = t; !S16 && i < 26 * 11; i += 256) {                              // a row of the tile = 10 groups of four and one of two
         const int r = i / 11, gc = i - r * 11;
-        const int y = p.crop + ty0 + r, x = p.crop + tx0 + 4 * gc;
+        const int y = p.cropy + ty0 + r, x = p.cropx + tx0 + 4 * gc;
         int npix = 42 - 4 * gc < 4 ? 42 - 4 * gc : 4;
-        if (p.W - p.crop - x < npix) npix = p.W - p.crop - x;
+        if (p.W - p.cropx - x < npix) npix = p.W - p.cropx - x;
         unsigned wa[2] = {0, 0}, wb[2] = {0, 0};
-        if (y < p.H - p.crop && npix > 0) {
+        if (y < p.H - p.cropy && npix > 0) {
             pnp_plane_load4(p.a, frame, y, x, npix, wa);
             pnp_plane_load4(p.b, frame, y, x, npix, wb);
         }
@@ -189,14 +190,14 @@ __global__ __launch_bounds__(256) void ssim_yuv420_kernel(const SsimYuvArgs s) {
 // plane's rows, then the chroma planes') with one 2-byte load per sample.  A squared difference reaches 2^24: 64-bit sums throughout.
 struct Psnr16Args {
     Plane16 a[3], b[3];
-    int crop, ry, wy, rc, wc;       // crop of the Y plane (the chroma planes': crop / 2); rows and columns of the cropped planes
+    int crop, ccy, ccx, ry, wy, rc, wc;     // crop of the Y plane; of the chroma planes down and across; rows and columns of the cropped planes
     unsigned long long* sse;        // (frames, 3), zeroed by the launcher
 };
 __global__ __launch_bounds__(256) void psnr_yuv420p16_kernel(const Psnr16Args s) {
     const long frame = blockIdx.y;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     unsigned long long acc[3] = {0, 0, 0};
-    const int total = s.ry + s.rc, cc = s.crop >> 1;
+    const int total = s.ry + s.rc;
     for (int r = blockIdx.x * 4 + ty; r < total; r += gridDim.x * 4) {
         if (r < s.ry) {
             for (int x = tx; x < s.wy; x += 64) {
@@ -204,10 +205,10 @@ __global__ __launch_bounds__(256) void psnr_yuv420p16_kernel(const Psnr16Args s)
                 acc[0] += (unsigned long long)(d * d);
             }
         } else {
-            const int row = cc + r - s.ry;
+            const int row = s.ccy + r - s.ry;
             for (int x = tx; x < s.wc; x += 64) {
-                const long db = (long)load16(s.a[1], frame, row, cc + x) - (long)load16(s.b[1], frame, row, cc + x);
-                const long dr = (long)load16(s.a[2], frame, row, cc + x) - (long)load16(s.b[2], frame, row, cc + x);
+                const long db = (long)load16(s.a[1], frame, row, s.ccx + x) - (long)load16(s.b[1], frame, row, s.ccx + x);
+                const long dr = (long)load16(s.a[2], frame, row, s.ccx + x) - (long)load16(s.b[2], frame, row, s.ccx + x);
                 acc[1] += (unsigned long long)(db * db);
                 acc[2] += (unsigned long long)(dr * dr);
             }
@@ -229,19 +230,52 @@ __global__ __launch_bounds__(256) void psnr_yuv420p16_kernel(const Psnr16Args s)
 
 }  // namespace
 
-extern "C" int pnp_psnr_sse_yuv420(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, unsigned long long* sse, int frames, int h,
-                                   int w, int crop_border, void* stream) {
-    if (!planes_args_ok(a, b, sse, frames, h, w, crop_border)) return PNP_ERR_BAD_ARG;
+namespace {
+
+// the planes of the mask, in the order Y, Cb, Cr, laid out in one grid and one partials array; false: a cropped plane below 11x11
+template <class Fill>
+bool ssim_planes(SsimYuvArgs& s, int plane_mask, int frames, int h, int w, int crop, int format, int& blk0, Fill fill) {
+    s.nplanes = 0;
+    blk0 = 0;
+    long out0 = 0;
+    for (int k = 0; k < 3; ++k) {
+        const int bit = 1 << k;
+        if (!(plane_mask & bit)) continue;
+        const int nb = pnp_ssim_blocks_yuv(h, w, crop, bit, format);
+        if (nb < 1) return false;
+        SsimPlane& p = s.pl[s.nplanes++];
+        fill(p, k);
+        const PlaneGeom g = plane_geom(h, w, crop, bit, format);
+        p.H = g.H, p.W = g.W, p.cropy = g.cropy, p.cropx = g.cropx;
+        p.oh = p.H - 2 * p.cropy - 10;
+        p.ow = p.W - 2 * p.cropx - 10;
+        p.tiles_x = (p.ow + 31) / 32;
+        p.blocks = nb;
+        p.blk0 = blk0;
+        p.out0 = out0;
+        blk0 += nb;
+        out0 += (long)frames * nb;
+    }
+    for (int k = s.nplanes; k < 3; ++k) s.pl[k] = s.pl[0];
+    return true;
+}
+
+}  // namespace
+
+extern "C" int pnp_psnr_sse_yuv(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, unsigned long long* sse, int frames, int h, int w,
+                                int crop_border, int chroma_format, void* stream) {
+    if (!yuv_format_ok(chroma_format) || !planes_args_ok(a, b, sse, frames, h, w, crop_border, chroma_format)) return PNP_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int ze = launch_zero_words(sse, 2L * 3 * frames, st);      // a kernel, not a memset node (prep.h)
     if (ze != PNP_OK) return ze;
     PsnrYuvArgs s;
     s.ay = luma_src(*a, h, w);
     s.by = luma_src(*b, h, w);
-    s.ac = chroma_src(*a, h, w);
-    s.bc = chroma_src(*b, h, w);
+    s.ac = chroma_src(*a, h, w, chroma_format);
+    s.bc = chroma_src(*b, h, w, chroma_format);
     s.ry = pnp_plane_runs(h, w, crop_border);
-    s.rc = pnp_plane_runs(h / 2, w / 2, crop_border / 2);
+    const PlaneGeom g = plane_geom(h, w, crop_border, PNP_PLANE_CB, chroma_format);
+    s.rc = pnp_plane_runs(g.H, g.W, g.cropy, g.cropx);
     s.sse = sse;
     int bx = (s.ry.rows + s.rc.rows + 3) / 4;                        // a row a wave, up to 4096 rows in flight per frame
     bx = bx > 1024 ? 1024 : bx;
@@ -249,69 +283,68 @@ extern "C" int pnp_psnr_sse_yuv420(const pnp_yuv420_planes* a, const pnp_yuv420_
     return (int)hipGetLastError();
 }
 
-extern "C" int pnp_ssim_blocks_yuv420(int h, int w, int crop_border, int plane) {
-    if (h < 2 || w < 2 || (h & 1) || (w & 1) || crop_border < 0 || (crop_border & 1)) return 0;
-    if (plane == PNP_PLANE_Y) return pnp_ssim_blocks(h, w, crop_border);
-    if (plane == PNP_PLANE_CB || plane == PNP_PLANE_CR) return pnp_ssim_blocks(h / 2, w / 2, crop_border / 2);
-    return 0;
+extern "C" int pnp_psnr_sse_yuv420(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, unsigned long long* sse, int frames, int h,
+                                   int w, int crop_border, void* stream) {
+    return pnp_psnr_sse_yuv(a, b, sse, frames, h, w, crop_border, PNP_YUV_FORMAT_420, stream);
 }
 
-extern "C" int pnp_ssim_partials_yuv420(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, int plane_mask, double* partials,
-                                        int frames, int h, int w, int crop_border, void* stream) {
-    if (!planes_args_ok(a, b, partials, frames, h, w, crop_border) || plane_mask < 1 || plane_mask > 7) return PNP_ERR_BAD_ARG;
+extern "C" int pnp_ssim_blocks_yuv(int h, int w, int crop_border, int plane, int chroma_format) {
+    if (!yuv_frame_ok(chroma_format, 1, h, w) || crop_border < 0 || (yuv_sx(chroma_format) == 2 && (crop_border & 1))) return 0;
+    if (plane != PNP_PLANE_Y && plane != PNP_PLANE_CB && plane != PNP_PLANE_CR) return 0;
+    const PlaneGeom g = plane_geom(h, w, crop_border, plane, chroma_format);
+    return pnp_ssim_blocks(g.H - 2 * g.cropy, g.W - 2 * g.cropx, 0);      // (pnp_ssim_blocks(rows, cols, crop) where the crops are equal)
+}
+
+extern "C" int pnp_ssim_blocks_yuv420(int h, int w, int crop_border, int plane) {
+    return pnp_ssim_blocks_yuv(h, w, crop_border, plane, PNP_YUV_FORMAT_420);
+}
+
+extern "C" int pnp_ssim_partials_yuv(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, int plane_mask, double* partials, int frames,
+                                     int h, int w, int crop_border, int chroma_format, void* stream) {
+    if (!yuv_format_ok(chroma_format) || !planes_args_ok(a, b, partials, frames, h, w, crop_border, chroma_format) || plane_mask < 1 || plane_mask > 7)
+        return PNP_ERR_BAD_ARG;
     SsimYuvArgs s;
-    s.nplanes = 0;
     s.partial = partials;
-    const ChromaSrc ac = chroma_src(*a, h, w), bc = chroma_src(*b, h, w);
+    const ChromaSrc ac = chroma_src(*a, h, w, chroma_format), bc = chroma_src(*b, h, w, chroma_format);
     int blk0 = 0;
-    long out0 = 0;
-    for (int k = 0; k < 3; ++k) {
-        const int bit = 1 << k;
-        if (!(plane_mask & bit)) continue;
-        const int nb = pnp_ssim_blocks_yuv420(h, w, crop_border, bit);
-        if (nb < 1) return PNP_ERR_BAD_ARG;                          // a cropped plane of the mask below 11x11
-        SsimPlane& p = s.pl[s.nplanes++];
+    const bool ok = ssim_planes(s, plane_mask, frames, h, w, crop_border, chroma_format, blk0, [&](SsimPlane& p, int k) {
         p.a16 = p.b16 = Plane16{};
-        if (bit == PNP_PLANE_Y) {
+        if (k == 0) {
             p.a = luma_src(*a, h, w);
             p.b = luma_src(*b, h, w);
             p.a_sel = p.b_sel = 0;
-            p.H = h, p.W = w, p.crop = crop_border;
         } else {
-            const int cr = bit == PNP_PLANE_CR;
+            const int cr = k == 2;
             p.a = ac.c[cr];
             p.b = bc.c[cr];
             p.a_sel = ac.paired && cr != ac.cr_first;                // the plane one byte behind the pair's first
             p.b_sel = bc.paired && cr != bc.cr_first;
-            p.H = h / 2, p.W = w / 2, p.crop = crop_border / 2;
         }
-        p.oh = p.H - 2 * p.crop - 10;
-        p.ow = p.W - 2 * p.crop - 10;
-        p.tiles_x = (p.ow + 31) / 32;
-        p.blocks = nb;
-        p.blk0 = blk0;
-        p.out0 = out0;
-        blk0 += nb;
-        out0 += (long)frames * nb;
-    }
-    for (int k = s.nplanes; k < 3; ++k) s.pl[k] = s.pl[0];
+    });
+    if (!ok) return PNP_ERR_BAD_ARG;                                 // a cropped plane of the mask below 11x11
     ssim_window(s.g);
     s.L = 255.0;
     hipLaunchKernelGGL(ssim_yuv420_kernel<false>, dim3(blk0, frames), dim3(256), 0, (hipStream_t)stream, s);
     return (int)hipGetLastError();
 }
 
-extern "C" int pnp_psnr_sse_yuv420p16(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, unsigned long long* sse, int frames, int h,
-                                      int w, int crop_border, void* stream) {
-    if (!planes16_args_ok(a, b, sse, frames, h, w, crop_border)) return PNP_ERR_BAD_ARG;
+extern "C" int pnp_ssim_partials_yuv420(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, int plane_mask, double* partials,
+                                        int frames, int h, int w, int crop_border, void* stream) {
+    return pnp_ssim_partials_yuv(a, b, plane_mask, partials, frames, h, w, crop_border, PNP_YUV_FORMAT_420, stream);
+}
+
+extern "C" int pnp_psnr_sse_yuvp16(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, unsigned long long* sse, int frames, int h,
+                                   int w, int crop_border, int chroma_format, void* stream) {
+    if (!yuv_format_ok(chroma_format) || !planes16_args_ok(a, b, sse, frames, h, w, crop_border, chroma_format)) return PNP_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int ze = launch_zero_words(sse, 2L * 3 * frames, st);      // a kernel, not a memset node (prep.h)
     if (ze != PNP_OK) return ze;
     Psnr16Args s;
     for (int k = 0; k < 3; ++k) s.a[k] = plane16(*a, k), s.b[k] = plane16(*b, k);
-    s.crop = crop_border;
+    const PlaneGeom g = plane_geom(h, w, crop_border, PNP_PLANE_CB, chroma_format);
+    s.crop = crop_border, s.ccy = g.cropy, s.ccx = g.cropx;
     s.ry = h - 2 * crop_border, s.wy = w - 2 * crop_border;
-    s.rc = h / 2 - crop_border, s.wc = w / 2 - crop_border;
+    s.rc = g.H - 2 * g.cropy, s.wc = g.W - 2 * g.cropx;
     s.sse = sse;
     int bx = (s.ry + s.rc + 3) / 4;
     bx = bx > 1024 ? 1024 : bx;
@@ -319,38 +352,32 @@ extern "C" int pnp_psnr_sse_yuv420p16(const pnp_yuv420_planes16* a, const pnp_yu
     return (int)hipGetLastError();
 }
 
-extern "C" int pnp_ssim_partials_yuv420p16(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, int plane_mask, double* partials,
-                                           int frames, int h, int w, int crop_border, void* stream) {
-    if (!planes16_args_ok(a, b, partials, frames, h, w, crop_border) || plane_mask < 1 || plane_mask > 7) return PNP_ERR_BAD_ARG;
+extern "C" int pnp_psnr_sse_yuv420p16(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, unsigned long long* sse, int frames, int h,
+                                      int w, int crop_border, void* stream) {
+    return pnp_psnr_sse_yuvp16(a, b, sse, frames, h, w, crop_border, PNP_YUV_FORMAT_420, stream);
+}
+
+extern "C" int pnp_ssim_partials_yuvp16(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, int plane_mask, double* partials,
+                                        int frames, int h, int w, int crop_border, int chroma_format, void* stream) {
+    if (!yuv_format_ok(chroma_format) || !planes16_args_ok(a, b, partials, frames, h, w, crop_border, chroma_format) || plane_mask < 1 || plane_mask > 7)
+        return PNP_ERR_BAD_ARG;
     SsimYuvArgs s;
-    s.nplanes = 0;
     s.partial = partials;
     s.L = (double)((1 << a->bit_depth) - 1);
     int blk0 = 0;
-    long out0 = 0;
-    for (int k = 0; k < 3; ++k) {
-        const int bit = 1 << k;
-        if (!(plane_mask & bit)) continue;
-        const int nb = pnp_ssim_blocks_yuv420(h, w, crop_border, bit);
-        if (nb < 1) return PNP_ERR_BAD_ARG;                          // a cropped plane of the mask below 11x11
-        SsimPlane& p = s.pl[s.nplanes++];
+    const bool ok = ssim_planes(s, plane_mask, frames, h, w, crop_border, chroma_format, blk0, [&](SsimPlane& p, int k) {
         p.a = p.b = PnpPlaneSrc{};
         p.a_sel = p.b_sel = 0;
         p.a16 = plane16(*a, k);
         p.b16 = plane16(*b, k);
-        if (bit == PNP_PLANE_Y) p.H = h, p.W = w, p.crop = crop_border;
-        else p.H = h / 2, p.W = w / 2, p.crop = crop_border / 2;
-        p.oh = p.H - 2 * p.crop - 10;
-        p.ow = p.W - 2 * p.crop - 10;
-        p.tiles_x = (p.ow + 31) / 32;
-        p.blocks = nb;
-        p.blk0 = blk0;
-        p.out0 = out0;
-        blk0 += nb;
-        out0 += (long)frames * nb;
-    }
-    for (int k = s.nplanes; k < 3; ++k) s.pl[k] = s.pl[0];
+    });
+    if (!ok) return PNP_ERR_BAD_ARG;                                 // a cropped plane of the mask below 11x11
     ssim_window(s.g);
     hipLaunchKernelGGL(ssim_yuv420_kernel<true>, dim3(blk0, frames), dim3(256), 0, (hipStream_t)stream, s);
     return (int)hipGetLastError();
+}
+
+extern "C" int pnp_ssim_partials_yuv420p16(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, int plane_mask, double* partials,
+                                           int frames, int h, int w, int crop_border, void* stream) {
+    return pnp_ssim_partials_yuvp16(a, b, plane_mask, partials, frames, h, w, crop_border, PNP_YUV_FORMAT_420, stream);
 }

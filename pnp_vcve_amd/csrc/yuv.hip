@@ -1,4 +1,5 @@
-// Y'CbCr 4:2:0 boundary: the decoder's planes straight into the conv source, and fp32 RGB planes out as planes an encoder or a display
+// Y'CbCr boundary (the 4:2:0 kernels first; the 4:2:2 and 4:4:4 ones, which own pixels of one row, behind them).
+// 4:2:0: the decoder's planes straight into the conv source, and fp32 RGB planes out as planes an encoder or a display
 // takes -- NV12 / NV21 / I420 bytes, or the 16-bit words a Main10 / VVC decoder writes (P010 / P012: the value in the high bits;
 // yuv420p10le / yuv420p12le: in the low bits).  The arithmetic is the one include/pnpvcve.h states (pnp_frames_from_yuv420 /
 // pnp_frames_to_yuv420, pnp_yuv420_planes16): constants of the depth rounded to fp32 once on the host (yuv.h), every product and sum
@@ -382,9 +383,233 @@ __global__ __launch_bounds__(256) void frames_to_yuv420_sited_kernel(const float
     at<S>(p.cr, co)[cx] = sample_of<S>(k, (float)k.cmid + k.sc * mr);
 }
 
+// ---- 4:2:2 and 4:4:4 (include/pnpvcve.h, "Chroma formats"): chroma rows are luma rows (sy = 1), so a thread owns pixels of ONE row and
+// no kernel has a vertical tap.  SX is the horizontal factor: 2 (4:2:2) | 1 (4:4:4).  XM is what the x axis does with the mode:
+//   XM_PLAIN   replication on the way in, (p0 + p1) * 0.5 on the way out -- and everything at SX = 1, where every mode is the pixel's
+//              own sample both ways (the sited sum is 16 (C - mid), and float(16 n) * 0.0625f = float(n) exactly)
+//   XM_MIDWAY  planes -> RGB with the midway taps (CENTER); its way out is XM_PLAIN's
+//   XM_COSITED the co-sited taps both ways (LEFT and TOPLEFT: the same function with no vertical axis to tell them apart)
+// The y axis weighs 4 in the sums of 16.
+enum { XM_PLAIN = 0, XM_MIDWAY = 1, XM_COSITED = 2 };
+
+// the chroma terms of the SX pixels of chroma sample bx from the samples (bm, rm) left of it, its own (bc, rc) and (bp, rp) right of it
+template <int SX, int XM>
+__device__ __forceinline__ void row_terms(const YuvCoef& k, int bm, int bc, int bp, int rm, int rc, int rp, ChromaTerms (&c)[SX]) {
+    if constexpr (XM == XM_PLAIN) {
+        c[0] = chroma_terms(k, (unsigned)bc, (unsigned)rc);
+        if constexpr (SX == 2) c[1] = c[0];
+    } else {
+        constexpr bool XCO = XM == XM_COSITED;
+        c[0] = chroma_terms16(k, 4 * tap_even<XCO>(bm, bc), 4 * tap_even<XCO>(rm, rc));
+        c[1] = chroma_terms16(k, 4 * tap_odd<XCO>(bc, bp), 4 * tap_odd<XCO>(rc, rp));
+    }
+}
+
+// General form, planes -> RGB0 (PLANAR false: the (T,H,W,4) conv source) or -> (n,3,H,W) fp32 planes (PLANAR true): one thread = one
+// chroma sample = SX pixels of a row, single-sample loads at any address, pitch and c_step.  i over T * H * (W / SX).
+template <class S, int SX, int XM, bool PLANAR>
+__global__ __launch_bounds__(256) void yuv_rows_in_kernel(const YuvPlanes p, const YuvCoef k, float* __restrict__ out, int H, int W, long total) {
+    static_assert(SX == 2 || XM == XM_PLAIN, "4:4:4 has one form");
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int bw = W / SX;
+    const int bx = (int)(i % bw);
+    const long r = i / bw;
+    const int y = (int)(r % H);
+    const long f = r / H;
+    const S* yr = at<S>(p.y, f * p.y_frame + (long)y * p.y_pitch) + SX * bx;
+    const long co = f * p.c_frame + (long)y * p.c_pitch;
+    const S *b = at<S>(p.cb, co), *q = at<S>(p.cr, co);
+    const long xc = (long)bx * p.c_step;
+    const int bc = (int)val<S>(k, b[xc]), rc = (int)val<S>(k, q[xc]);
+    int bm = bc, rm = rc, bp = bc, rp = rc;
+    if constexpr (XM != XM_PLAIN) {
+        const long xp = (long)min(bx + 1, bw - 1) * p.c_step;
+        bp = (int)val<S>(k, b[xp]), rp = (int)val<S>(k, q[xp]);
+        if constexpr (XM == XM_MIDWAY) {
+            const long xm = (long)max(bx - 1, 0) * p.c_step;
+            bm = (int)val<S>(k, b[xm]), rm = (int)val<S>(k, q[xm]);
+        }
+    }
+    ChromaTerms c[SX];
+    row_terms<SX, XM>(k, bm, bc, bp, rm, rc, rp, c);
+    const long hw = (long)H * W;
+#pragma unroll
+    for (int j = 0; j < SX; ++j) {
+        const f32x4 v = rgb0_of(k, val<S>(k, yr[j]), c[j]);
+        if constexpr (PLANAR) {
+            float* d = out + f * 3 * hw + (long)y * W + SX * bx + j;
+            d[0] = v[0];
+            d[hw] = v[1];
+            d[2 * hw] = v[2];
+        } else {
+            reinterpret_cast<f32x4*>(out)[(f * H + y) * W + SX * bx + j] = v;
+        }
+    }
+}
+
+// Aligned fast form (yuv_planes_fast with the format): one thread = four pixels of a row = one four-sample load of Y and four 16-byte
+// stores, 64 contiguous bytes.  Chroma of its columns: 4:2:2 one four-sample load of the interleaved pair (STEP 2: a0 b0 a1 b1;
+// cr_first says which plane starts) or a two-sample load of each plane (STEP 1), with the clamped columns beside them as single
+// samples where the mode has taps; 4:4:4 two four-sample loads of the pair or one of each plane.  W is a multiple of 4.  The same
+// integers as the general form, so the same values.  i over T * H * (W / 4).
+template <class S, int SX, int STEP, int XM>
+__global__ __launch_bounds__(256) void pack_lr_rows_fast_kernel(const YuvPlanes p, const YuvCoef k, float* __restrict__ lr4, int H, int W, int cr_first,
+                                                                long total) {
+    static_assert(SX == 2 || XM == XM_PLAIN, "4:4:4 has one form");
+    using L = Load<S>;
+    using Four = typename L::Four;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int gw = W >> 2;
+    const int gx = (int)(i % gw);
+    const long r = i / gw;
+    const int y = (int)(r % H);
+    const long f = r / H;
+    const Four ya = *at<Four>(p.y, f * p.y_frame + (long)y * p.y_pitch + (long)sizeof(S) * (4 * gx));
+    const long co = f * p.c_frame + (long)y * p.c_pitch;
+    constexpr int NC = 4 / SX;          // chroma samples of the thread's four pixels
+    unsigned cb[NC], cr[NC];
+    if constexpr (SX == 2) {
+        if (STEP == 2) {
+            const Four q = *at<Four>(cr_first ? p.cr : p.cb, co + (long)sizeof(S) * (4 * gx));
+            const unsigned a0 = L::get(q, 0), b0 = L::get(q, 1), a1 = L::get(q, 2), b1 = L::get(q, 3);
+            cb[0] = cr_first ? b0 : a0, cr[0] = cr_first ? a0 : b0;
+            cb[1] = cr_first ? b1 : a1, cr[1] = cr_first ? a1 : b1;
+        } else {
+            const long cx = co + (long)sizeof(S) * (2 * gx);
+            const unsigned qb = *at<typename L::Two>(p.cb, cx), qr = *at<typename L::Two>(p.cr, cx);
+            cb[0] = L::get2(qb, 0), cb[1] = L::get2(qb, 1), cr[0] = L::get2(qr, 0), cr[1] = L::get2(qr, 1);
+        }
+    } else {
+        if (STEP == 2) {
+            const long cx = co + (long)sizeof(S) * (8 * gx);
+            const Four q0 = *at<Four>(cr_first ? p.cr : p.cb, cx), q1 = *at<Four>(cr_first ? p.cr : p.cb, cx + 4 * (long)sizeof(S));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const unsigned a = L::get(j < 2 ? q0 : q1, 2 * (j & 1)), b = L::get(j < 2 ? q0 : q1, 2 * (j & 1) + 1);
+                cb[j] = cr_first ? b : a, cr[j] = cr_first ? a : b;
+            }
+        } else {
+            const long cx = co + (long)sizeof(S) * (4 * gx);
+            const Four qb = *at<Four>(p.cb, cx), qr = *at<Four>(p.cr, cx);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) cb[j] = L::get(qb, j), cr[j] = L::get(qr, j);
+        }
+    }
+    f32x4 t[4];
+    if constexpr (SX == 2) {
+        const int bw = W >> 1;
+        const int bA = (int)val<S>(k, cb[0]), bB = (int)val<S>(k, cb[1]), rA = (int)val<S>(k, cr[0]), rB = (int)val<S>(k, cr[1]);
+        int bL = bA, rL = rA, bR = bB, rR = rB;
+        if constexpr (XM != XM_PLAIN) {
+            const S *b = at<S>(p.cb, co), *q = at<S>(p.cr, co);
+            const long xr = (long)min(2 * gx + 2, bw - 1) * STEP;
+            bR = (int)val<S>(k, b[xr]), rR = (int)val<S>(k, q[xr]);
+            if constexpr (XM == XM_MIDWAY) {
+                const long xl = (long)max(2 * gx - 1, 0) * STEP;
+                bL = (int)val<S>(k, b[xl]), rL = (int)val<S>(k, q[xl]);
+            }
+        }
+        ChromaTerms c0[2], c1[2];
+        row_terms<2, XM>(k, bL, bA, bB, rL, rA, rB, c0);
+        row_terms<2, XM>(k, bA, bB, bR, rA, rB, rR, c1);
+        t[0] = rgb0_of(k, val<S>(k, L::get(ya, 0)), c0[0]);
+        t[1] = rgb0_of(k, val<S>(k, L::get(ya, 1)), c0[1]);
+        t[2] = rgb0_of(k, val<S>(k, L::get(ya, 2)), c1[0]);
+        t[3] = rgb0_of(k, val<S>(k, L::get(ya, 3)), c1[1]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) t[j] = rgb0_of(k, val<S>(k, L::get(ya, j)), chroma_terms(k, val<S>(k, cb[j]), val<S>(k, cr[j])));
+    }
+    f32x4* d = reinterpret_cast<f32x4*>(lr4) + (f * H + y) * W + 4 * gx;
+    d[0] = t[0];
+    d[1] = t[1];
+    d[2] = t[2];
+    d[3] = t[3];
+}
+
+// (n,3,H,W) fp32 planes -> planes: one thread = one chroma sample = SX pixels of a row, single-sample stores; nothing beyond a row's
+// width is written.  XM_PLAIN: the pixel's own pb, pr (SX 1) or (p0 + p1) * 0.5 (SX 2); XM_COSITED (SX 2): the taps max(2 bx - 1, 0),
+// 2 bx, 2 bx + 1 as ((pL + pR) + (pC + pC)) * 0.25 -- one left neighbour, evaluated once more (the same fp32 operations: the same
+// values), nothing outside the frame read.  i over n * H * (W / SX).
+template <class S, int SX, int XM>
+__global__ __launch_bounds__(256) void yuv_rows_out_kernel(const float* __restrict__ in, const YuvPlanes p, const YuvCoef k, int H, int W, long total) {
+#pragma clang fp contract(off)
+    static_assert(XM == XM_PLAIN || (SX == 2 && XM == XM_COSITED), "the forms of the way out");
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int bw = W / SX;
+    const int bx = (int)(i % bw);
+    const long r = i / bw;
+    const int y = (int)(r % H);
+    const long f = r / H;
+    const long hw = (long)H * W;
+    const float* s = in + f * 3 * hw + (long)y * W;
+    S* yo = at<S>(p.y, f * p.y_frame + (long)y * p.y_pitch);
+    constexpr int N = XM == XM_COSITED ? 3 : SX;
+    const int x0 = XM == XM_COSITED ? 2 * bx - 1 : SX * bx;     // the first tap before it is clamped
+    float pb[N], pr[N];
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        const int x = max(x0 + c, 0);
+        const float* q = s + x;
+        const float rr = fminf(fmaxf(q[0], 0.f), 1.f), gg = fminf(fmaxf(q[hw], 0.f), 1.f), bb = fminf(fmaxf(q[2 * hw], 0.f), 1.f);
+        const float yl = (k.kr * rr + k.kg * gg) + k.kb * bb;
+        if (XM != XM_COSITED || c >= 1) yo[x] = sample_of<S>(k, (float)k.yoff + k.sy * yl);
+        pb[c] = (bb - yl) * k.ipb;
+        pr[c] = (rr - yl) * k.ipr;
+    }
+    float mb, mr;
+    if constexpr (XM == XM_COSITED) mb = ((pb[0] + pb[2]) + (pb[1] + pb[1])) * 0.25f, mr = ((pr[0] + pr[2]) + (pr[1] + pr[1])) * 0.25f;
+    else if constexpr (SX == 2) mb = (pb[0] + pb[1]) * 0.5f, mr = (pr[0] + pr[1]) * 0.5f;
+    else mb = pb[0], mr = pr[0];
+    const long co = f * p.c_frame + (long)y * p.c_pitch;
+    const long cx = (long)bx * p.c_step;
+    at<S>(p.cb, co)[cx] = sample_of<S>(k, (float)k.cmid + k.sc * mb);
+    at<S>(p.cr, co)[cx] = sample_of<S>(k, (float)k.cmid + k.sc * mr);
+}
+
 unsigned blocks_of(long total) { return (unsigned)((total + 255) / 256); }
 
-bool frame_ok(int n, int H, int W) { return n >= 1 && H >= 2 && W >= 2 && !(H & 1) && !(W & 1); }
+// the x-axis form of a mode on the way in, for a format other than 4:2:0
+int xm_in(const YuvCoef& k) {
+    if (k.format == PNP_YUV_FORMAT_444 || k.chroma == PNP_YUV_CHROMA_REPLICATE) return XM_PLAIN;
+    return k.chroma == PNP_YUV_CHROMA_CENTER ? XM_MIDWAY : XM_COSITED;
+}
+
+// f<S, SX, XM>(args...) for the sample size, the format (4:2:2 | 4:4:4) and the x-axis form
+#define YUV_ROWS_S(f, S, fmt, xm, ...)                                                                  \
+    ((fmt) == PNP_YUV_FORMAT_444 ? f<S, 1, XM_PLAIN>(__VA_ARGS__)                                      \
+     : (xm) == XM_PLAIN          ? f<S, 2, XM_PLAIN>(__VA_ARGS__)                                      \
+     : (xm) == XM_MIDWAY         ? f<S, 2, XM_MIDWAY>(__VA_ARGS__)                                     \
+                                 : f<S, 2, XM_COSITED>(__VA_ARGS__))
+#define YUV_ROWS(f, bytes, fmt, xm, ...) \
+    ((bytes) == 1 ? YUV_ROWS_S(f, unsigned char, fmt, xm, __VA_ARGS__) : YUV_ROWS_S(f, unsigned short, fmt, xm, __VA_ARGS__))
+
+template <class S, int SX, int XM>
+int rows_in(const YuvPlanes& in, const YuvCoef& k, float* out, int n, int H, int W, bool planar, bool fast, hipStream_t stream) {
+    if (fast) {         // (the pack alone)
+        const long total = (long)n * H * (W / 4);
+        const int cr_first = in.cr < in.cb ? 1 : 0;
+        if (in.c_step == 2) hipLaunchKernelGGL((pack_lr_rows_fast_kernel<S, SX, 2, XM>), dim3(blocks_of(total)), dim3(256), 0, stream, in, k, out, H, W, cr_first, total);
+        else hipLaunchKernelGGL((pack_lr_rows_fast_kernel<S, SX, 1, XM>), dim3(blocks_of(total)), dim3(256), 0, stream, in, k, out, H, W, cr_first, total);
+        return (int)hipGetLastError();
+    }
+    const long total = (long)n * H * (W / SX);
+    if (planar) hipLaunchKernelGGL((yuv_rows_in_kernel<S, SX, XM, true>), dim3(blocks_of(total)), dim3(256), 0, stream, in, k, out, H, W, total);
+    else hipLaunchKernelGGL((yuv_rows_in_kernel<S, SX, XM, false>), dim3(blocks_of(total)), dim3(256), 0, stream, in, k, out, H, W, total);
+    return (int)hipGetLastError();
+}
+template <class S, int SX, int XM>
+int rows_out(const float* in, const YuvPlanes& out, const YuvCoef& k, int n, int H, int W, hipStream_t stream) {
+    const long total = (long)n * H * (W / SX);
+    if constexpr (XM == XM_MIDWAY) return rows_out<S, SX, XM_PLAIN>(in, out, k, n, H, W, stream);
+    else {
+        hipLaunchKernelGGL((yuv_rows_out_kernel<S, SX, XM>), dim3(blocks_of(total)), dim3(256), 0, stream, in, out, k, H, W, total);
+        return (int)hipGetLastError();
+    }
+}
 
 template <class S>
 int pack_lr(const YuvPlanes& in, const YuvCoef& k, float* lr4, int T, int H, int W, bool fast, hipStream_t stream) {
@@ -439,14 +664,16 @@ int frames_to_sited(const float* in, const YuvPlanes& out, const YuvCoef& k, int
 }  // namespace
 
 int launch_pack_lr_yuv420(const YuvPlanes& in, const YuvCoef& k, float* lr4, int T, int H, int W, bool force_general, hipStream_t stream) {
-    if (!frame_ok(T, H, W) || !lr4 || !yuv_planes_ok(in, W)) return PNP_ERR_BAD_ARG;
-    const bool fast = !force_general && yuv_planes_fast(in, W);
+    if (!yuv_frame_ok(k.format, T, H, W) || !lr4 || !yuv_planes_ok(in, W, k.format)) return PNP_ERR_BAD_ARG;
+    const bool fast = !force_general && yuv_planes_fast(in, W, k.format);
+    if (k.format != PNP_YUV_FORMAT_420) return YUV_ROWS(rows_in, in.sample_bytes, k.format, xm_in(k), in, k, lr4, T, H, W, false, fast, stream);
     if (k.chroma != PNP_YUV_CHROMA_REPLICATE) return YUV_SITED(pack_lr_sited, in.sample_bytes, k.chroma, in, k, lr4, T, H, W, fast, stream);
     return in.sample_bytes == 1 ? pack_lr<unsigned char>(in, k, lr4, T, H, W, fast, stream) : pack_lr<unsigned short>(in, k, lr4, T, H, W, fast, stream);
 }
 
 int launch_frames_from_yuv420(const YuvPlanes& in, const YuvCoef& k, float* out, int nframes, int H, int W, hipStream_t stream) {
-    if (!frame_ok(nframes, H, W) || !out || !yuv_planes_ok(in, W)) return PNP_ERR_BAD_ARG;
+    if (!yuv_frame_ok(k.format, nframes, H, W) || !out || !yuv_planes_ok(in, W, k.format)) return PNP_ERR_BAD_ARG;
+    if (k.format != PNP_YUV_FORMAT_420) return YUV_ROWS(rows_in, in.sample_bytes, k.format, xm_in(k), in, k, out, nframes, H, W, true, false, stream);
     const long total = (long)nframes * (H / 2) * (W / 2);
     if (k.chroma != PNP_YUV_CHROMA_REPLICATE) return YUV_SITED(frames_from_sited, in.sample_bytes, k.chroma, in, k, out, H, W, total, stream);
     if (in.sample_bytes == 1) hipLaunchKernelGGL(frames_from_yuv420_kernel<unsigned char>, dim3(blocks_of(total)), dim3(256), 0, stream, in, k, out, H, W, total);
@@ -455,7 +682,9 @@ int launch_frames_from_yuv420(const YuvPlanes& in, const YuvCoef& k, float* out,
 }
 
 int launch_frames_to_yuv420(const float* in, const YuvPlanes& out, const YuvCoef& k, int nframes, int H, int W, hipStream_t stream) {
-    if (!frame_ok(nframes, H, W) || !in || !yuv_planes_ok(out, W)) return PNP_ERR_BAD_ARG;
+    if (!yuv_frame_ok(k.format, nframes, H, W) || !in || !yuv_planes_ok(out, W, k.format)) return PNP_ERR_BAD_ARG;
+    if (k.format != PNP_YUV_FORMAT_420)         // (CENTER writes what REPLICATE writes, as at 4:2:0)
+        return YUV_ROWS(rows_out, out.sample_bytes, k.format, xm_in(k), in, out, k, nframes, H, W, stream);
     const long total = (long)nframes * (H / 2) * (W / 2);
     if (k.chroma == PNP_YUV_CHROMA_LEFT || k.chroma == PNP_YUV_CHROMA_TOPLEFT) {        // (CENTER writes the box mean, as REPLICATE)
         const bool yco = k.chroma == PNP_YUV_CHROMA_TOPLEFT;
@@ -473,17 +702,17 @@ namespace {
 template <class P>
 int frames_from(const P* in, int yuv_standard, float* out_planes, int n, int h, int w, void* stream) {
     YuvCoef k;
-    if (!in || !out_planes || !frame_ok(n, h, w)) return PNP_ERR_BAD_ARG;
+    if (!in || !out_planes) return PNP_ERR_BAD_ARG;
     const YuvPlanes p = yuv_planes(*in);
-    if (!yuv_coef(yuv_standard, p, &k) || !yuv_planes_ok(p, w)) return PNP_ERR_BAD_ARG;
+    if (!yuv_coef(yuv_standard, p, &k) || !yuv_frame_ok(k.format, n, h, w) || !yuv_planes_ok(p, w, k.format)) return PNP_ERR_BAD_ARG;
     return launch_frames_from_yuv420(p, k, out_planes, n, h, w, (hipStream_t)stream);
 }
 template <class P>
 int frames_to(const float* planes, const P* out, int yuv_standard, int n, int h, int w, void* stream) {
     YuvCoef k;
-    if (!out || !planes || !frame_ok(n, h, w)) return PNP_ERR_BAD_ARG;
+    if (!out || !planes) return PNP_ERR_BAD_ARG;
     const YuvPlanes p = yuv_planes(*out);
-    if (!yuv_coef(yuv_standard, p, &k) || !yuv_planes_ok(p, w)) return PNP_ERR_BAD_ARG;
+    if (!yuv_coef(yuv_standard, p, &k) || !yuv_frame_ok(k.format, n, h, w) || !yuv_planes_ok(p, w, k.format)) return PNP_ERR_BAD_ARG;
     return launch_frames_to_yuv420(planes, p, k, n, h, w, (hipStream_t)stream);
 }
 template <class P>

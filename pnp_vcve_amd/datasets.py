@@ -189,7 +189,11 @@ class Yuv420ClipFolderDataset(_EvalMixin, torch.utils.data.Dataset):
     'left' (H.264 / HEVC / VVC streams) | 'topleft' (BT.2020 / UHD), the chroma modes of include/pnpvcve.h.
     bit_depth 10 | 12: the files hold 16-bit little-endian samples (`-pix_fmt yuv420p10le` / `yuv420p12le`, VTM / HM output; with
     msb_aligned the value sits in the word's high bits, as in P010 / P012 with layout 'nv12'), a frame is 3 h w bytes, the buffers are
-    int16 (T, 3h/2, w) -- the words as they are, uploaded as they are -- and meta carries `bit_depth` and `msb_aligned`."""
+    int16 (T, 3h/2, w) -- the words as they are, uploaded as they are -- and meta carries `bit_depth` and `msb_aligned`.
+    4:2:2 and 4:4:4 clips (HEVC RExt / VVC streams, what HM and VTM write for those profiles): layout 'yuv422p' | 'nv16' | 'yuv444p' |
+    'nv24' names the plane order AND implies the chroma format (meta `format`: '420' | '422' | '444'); a frame is 2hw or 3hw samples,
+    the buffers (T, 2h, w) or (T, 3h, w); with bit_depth 10 | 12 the same order applies in words ('yuv422p' reads yuv422p10le, 'nv16'
+    with msb_aligned P210, ...).  4:2:2 needs an even width only, 4:4:4 no parity."""
 
     def __init__(self, lq_folder, gt_folder, height, width, layout='i420', yuv_standard='bt601-limited', mv_folder=None,
                  num_input_frames=100, scale=1, repeat=1, qp_slice_file=None, replace_qp_withIPB=False, pipeline=None, test_mode=True,
@@ -198,8 +202,10 @@ class Yuv420ClipFolderDataset(_EvalMixin, torch.utils.data.Dataset):
         import os
         if not isinstance(repeat, int):
             raise TypeError(f'"repeat" must be an integer, but got {type(repeat)}.')
-        if layout not in ('i420', 'nv12', 'nv21'):
-            raise ValueError(f"layout must be 'i420', 'nv12' or 'nv21', got {layout!r}")
+        formats = {'yuv422p': '422', 'nv16': '422', 'yuv444p': '444', 'nv24': '444'}      # the layout implies the chroma format
+        if layout not in ('i420', 'nv12', 'nv21') and layout not in formats:
+            raise ValueError(f"layout must be 'i420', 'nv12' or 'nv21', or {tuple(formats)} for 4:2:2 / 4:4:4 clips, got {layout!r}")
+        self.format = formats.get(layout, '420')
         if yuv_standard not in ('bt601-limited', 'bt601-full', 'bt709-limited', 'bt709-full'):
             raise ValueError(f'unknown yuv_standard {yuv_standard!r}')
         if chroma not in ('replicate', 'center', 'left', 'topleft'):
@@ -211,8 +217,14 @@ class Yuv420ClipFolderDataset(_EvalMixin, torch.utils.data.Dataset):
             raise ValueError('msb_aligned describes 16-bit containers: bit_depth 10 or 12')
         self.bit_depth, self.msb_aligned = int(bit_depth), bool(msb_aligned)
         self.h, self.w, self.scale = int(height), int(width), int(scale)
-        if self.h < 2 or self.w < 2 or self.h % 2 or self.w % 2 or self.scale < 1:
+        if self.format == '420' and (self.h < 2 or self.w < 2 or self.h % 2 or self.w % 2 or self.scale < 1):
             raise ValueError(f'4:2:0 frames need an even height and width (and scale >= 1), got {height} x {width}, scale {scale}')
+        if self.h < 1 or self.w < 1:
+            raise ValueError(f'4:{self.format[1]}:{self.format[2]} frames need a height and a width of at least 1, got {height} x {width}')
+        if self.scale < 1:
+            raise ValueError(f'scale must be at least 1, got {scale}')
+        if self.format == '422' and self.w % 2:
+            raise ValueError(f'4:2:2 frames need an even width, got {height} x {width}')
         self.lq_folder, self.gt_folder = str(lq_folder), str(gt_folder)
         self.layout, self.yuv_standard, self.num_input_frames = layout, yuv_standard, int(num_input_frames)
         if mv_folder is None:
@@ -235,29 +247,30 @@ class Yuv420ClipFolderDataset(_EvalMixin, torch.utils.data.Dataset):
         return len(self.keys)
 
     @staticmethod
-    def _read_yuv(path, h, w, max_frames, bit_depth=8):
-        """-> the first min(frames in the file, max_frames) frames as (T, 3h/2, w) uint8, or int16 words (little-endian in the file) for
-        bit_depth 10 | 12"""
+    def _read_yuv(path, h, w, max_frames, bit_depth=8, fmt='420'):
+        """-> the first min(frames in the file, max_frames) frames as (T, 3h/2, w) uint8 (4:2:2: 2h rows, a frame is 2hw samples; 4:4:4:
+        3h rows, 3hw samples), or int16 words (little-endian in the file) for bit_depth 10 | 12"""
         import os
         import numpy as np
         wide = bit_depth != 8
-        per = h * w * 3 // 2 * (2 if wide else 1)
+        rows = {'420': h * 3 // 2, '422': 2 * h, '444': 3 * h}[fmt]
+        per = rows * w * (2 if wide else 1)
         size = os.path.getsize(path)
         if size < per or size % per:
-            raise ValueError(f'{path}: {size} bytes is not a whole number (>= 1) of {h} x {w} {bit_depth}-bit 4:2:0 frames of {per} bytes')
+            raise ValueError(f'{path}: {size} bytes is not a whole number (>= 1) of {h} x {w} {bit_depth}-bit 4:{fmt[1]}:{fmt[2]} frames of {per} bytes')
         t = min(size // per, max_frames)
         if wide:
-            return np.fromfile(path, dtype='<i2', count=t * per // 2).astype(np.int16, copy=False).reshape(t, h * 3 // 2, w)
-        return np.fromfile(path, dtype=np.uint8, count=t * per).reshape(t, h * 3 // 2, w)
+            return np.fromfile(path, dtype='<i2', count=t * per // 2).astype(np.int16, copy=False).reshape(t, rows, w)
+        return np.fromfile(path, dtype=np.uint8, count=t * per).reshape(t, rows, w)
 
     def __getitem__(self, idx):
         import os
         import numpy as np
         key = self.keys[idx]
         lq_path, gt_path = os.path.join(self.lq_folder, key + '.yuv'), os.path.join(self.gt_folder, key + '.yuv')
-        lq = self._read_yuv(lq_path, self.h, self.w, self.num_input_frames, self.bit_depth)
+        lq = self._read_yuv(lq_path, self.h, self.w, self.num_input_frames, self.bit_depth, self.format)
         T = lq.shape[0]
-        gt = self._read_yuv(gt_path, self.h * self.scale, self.w * self.scale, T, self.bit_depth)
+        gt = self._read_yuv(gt_path, self.h * self.scale, self.w * self.scale, T, self.bit_depth, self.format)
         if gt.shape[0] != T:
             raise ValueError(f'{gt_path}: {gt.shape[0]} frames for the {T} of {lq_path}')
         parts = self.lq_folder.rstrip('/').split('/')
@@ -283,7 +296,7 @@ class Yuv420ClipFolderDataset(_EvalMixin, torch.utils.data.Dataset):
                     base_QPs=torch.full((T, 1, 1, 1), base_qp / 255.0, dtype=torch.float32),
                     mv_records=torch.from_numpy(np.concatenate(recs)), rec_frame=torch.from_numpy(np.concatenate(rec_frame)),
                     meta=dict(key=f'{key}/{0:08d}', lq_path=lq_path, gt_path=gt_path, layout=self.layout, yuv_standard=self.yuv_standard,
-                              bit_depth=self.bit_depth, msb_aligned=self.msb_aligned, chroma=self.chroma))
+                              bit_depth=self.bit_depth, msb_aligned=self.msb_aligned, chroma=self.chroma, format=self.format))
 
 
 def collate(batch):

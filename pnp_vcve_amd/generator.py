@@ -617,14 +617,14 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
                 kinds.append('f32')
             elif d == torch.uint8:
                 kinds.append('u8')
-            elif isinstance(d, str) and (d in ('nv12', 'i420') or d in ops.YUV16_LAYOUTS):
+            elif isinstance(d, str) and (d in ('nv12', 'i420') or d in ops.YUV16_LAYOUTS or d in ops.YUV_FORMAT_LAYOUTS):
                 if layout is not None:
-                    raise ValueError('one 4:2:0 output layout per call')
+                    raise ValueError('one 4:2:0 / 4:2:2 / 4:4:4 planes layout per call')
                 layout = d
                 kinds.append('yuv')
             else:
-                raise ValueError(f"out_dtype must be None, torch.float32, torch.uint8, 'nv12', 'i420', one of {sorted(ops.YUV16_LAYOUTS)} "
-                                 f"or a tuple of them, got {d!r}")
+                raise ValueError(f"out_dtype must be None, torch.float32, torch.uint8, 'nv12', 'i420', one of {sorted(ops.YUV16_LAYOUTS)}, "
+                                 f"one of {list(ops.YUV_FORMAT_LAYOUTS)} (4:2:2 / 4:4:4 planes in) or a tuple of them, got {d!r}")
         if not kinds or len(set(kinds)) != len(kinds):
             raise ValueError(f'out_dtype names no output or one twice: {out_dtype!r}')
         bits = {'f32': _native.OUT_F32, 'u8': _native.OUT_U8, 'yuv': _native.OUT_YUV420}
@@ -634,12 +634,19 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
     def _yuv_out_route(lrs, kinds, layout):
         """What the planes output of a call needs beside the library's own: (None, out_dtype) where the library writes it, or -- 8-bit
         planes of a 10 / 12-bit clip, which the library's entry for such clips does not write -- (layout, the out_dtype tuple to run
-        instead: the other outputs and the fp32 one the planes are then made of).  16-bit planes of an 8-bit clip are refused."""
-        sixteen = isinstance(lrs, ops.Yuv420Frames16)
-        if layout in ops.YUV16_LAYOUTS and not sixteen:
+        instead: the other outputs and the fp32 one the planes are then made of).  16-bit planes of an 8-bit clip are refused, and so is
+        a layout of another chroma format than the input's (one code serves both directions: there is no format conversion)."""
+        sixteen = isinstance(lrs, ops._YUV16_CLASSES)
+        if layout is None:
+            return None, None
+        fmt, _, depth, _ = ops.yuv_layout(layout)
+        if fmt != ops.yuv_format(lrs):
+            raise ValueError(f'out_dtype {layout!r} is a 4:{fmt[1]}:{fmt[2]} layout and the input planes are {type(lrs).__name__}: the planes '
+                             f'written have the input\'s chroma format')
+        if depth != 8 and not sixteen:
             raise ValueError(f'out_dtype {layout!r}: 10 / 12-bit planes out of 8-bit planes in are not offered (the input holds no such '
                              f'precision); pass ops.Yuv420Frames16 frames or ask for \'nv12\' / \'i420\'')
-        if not sixteen or layout not in ('nv12', 'i420'):
+        if not sixteen or depth != 8:
             return None, None
         run = [torch.float32 if k == 'f32' else torch.uint8 for k in kinds if k != 'yuv']
         return layout, tuple(run if 'f32' in kinds else run + [torch.float32])
@@ -650,8 +657,8 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         output; std: the code of ops._yuv_code"""
         ran = [k for k in kinds if k != 'yuv'] + ([] if 'f32' in kinds else ['f32'])
         got = dict(zip(ran, res))
-        standard, chroma = ops._yuv_code_split(std)
-        got['yuv'] = ops.frames_to_yuv420(got['f32'], standard, layout, chroma=chroma)[0]
+        standard, chroma, _ = ops._yuv_code_split3(std)      # (the layout names the format)
+        got['yuv'] = ops.frames_to_yuv(got['f32'], standard, layout, chroma=chroma)[0]
         return tuple(got[k] for k in kinds)
 
     def _yuv_side(self, t, QPs, slices, base_QPs):
@@ -667,7 +674,7 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
                             base_QPs.reshape(t).float() if base_QPs is not None else zero])
 
     def _forward_yuv(self, frames, QPs, slices, mvs, base_QPs, par_map, out_dtype, yuv_standard, chroma='replicate'):
-        std = ops._yuv_code(yuv_standard, chroma)      # (what the library takes as yuv_standard; part of a graph's key)
+        std = ops._yuv_code(yuv_standard, chroma, ops.yuv_format(frames))      # (what the library takes as yuv_standard; part of a graph's key)
         kinds, mask, layout, many = self._yuv_outs(out_dtype)
         clips, lead = ops._yuv_clips(frames, 'lrs')
         if not lead:
@@ -718,10 +725,7 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
             x = torch.empty((n, t, h * s, w * s, 3), device=dev, dtype=torch.uint8)
             outs['u8'] = (x, list(x))
         if mask & _native.OUT_YUV420:
-            if layout in ops.YUV16_LAYOUTS:
-                buf, views = ops.empty_yuv420p16((n, t), h * s, w * s, layout, dev, word_dtype)
-            else:
-                buf, views = ops.empty_yuv420((n, t), h * s, w * s, layout, dev)
+            buf, views = ops.empty_yuv((n, t), h * s, w * s, layout, dev, word_dtype)
             outs['yuv'] = (buf, ops._yuv_clips(views, 'out')[0])
         return outs
 
@@ -729,7 +733,7 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         """One pnp_generator_forward_clips_yuv call (Yuv420Frames16 clips: pnp_generator_forward_clips_yuv16) on torch's current stream:
         per-clip plane views, nothing copied or concatenated."""
         n = len(clips)
-        sixteen = isinstance(clips[0], ops.Yuv420Frames16)
+        sixteen = isinstance(clips[0], ops._YUV16_CLASSES)
         Clip, Planes = (_native.ClipYuv16, _native.Yuv420Planes16) if sixteen else (_native.ClipYuv, _native.Yuv420Planes)
         entry = 'pnp_generator_forward_clips_yuv16' if sixteen else 'pnp_generator_forward_clips_yuv'
         arr = (Clip * n)()
@@ -763,7 +767,8 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         fill = lambda e: [dst.copy_(src) for b in range(n) for dst, src in zip(e['clips'][b][:3], clips[b][:3])]      # noqa: E731
         if ent is None:
             mk = lambda hh, ww: torch.empty((n, t, hh, ww), device=dev, dtype=c0.y.dtype)      # noqa: E731
-            static = type(c0)(mk(h, w), mk(h // 2, w // 2), mk(h // 2, w // 2), *c0[3:])
+            sx, sy = _native.YUV_FACTORS[ops.yuv_format(c0)]
+            static = type(c0)(mk(h, w), mk(h // sy, w // sx), mk(h // sy, w // sx), *c0[3:])
             ent = dict(clips=ops._yuv_clips(static, 'lrs')[0], mvs=torch.empty_like(mvs_c), par=torch.empty_like(par_c), side=side.clone(),
                        ws=torch.empty(self._workspace_bytes(t, h, w, 'yuv', mask) * self._contexts(n, h, w), device=dev, dtype=torch.uint8),
                        outs=self._alloc_yuv_outs(n, t, h, w, mask, layout, dev, c0.y.dtype))
@@ -793,7 +798,9 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         return {k: (v[0].clone(), None) for k, v in ent['outs'].items()}
 
     def _forward_clips_yuv(self, clips, out_dtype, yuv_standard, chroma='replicate'):
-        std = ops._yuv_code(yuv_standard, chroma)
+        if not ops.is_yuv(clips[0][0]):
+            raise TypeError('the clips of one forward_clips call must all be planes')
+        std = ops._yuv_code(yuv_standard, chroma, ops.yuv_format(clips[0][0]))
         kinds, mask, layout, many = self._yuv_outs(out_dtype)
         if self.sparse_val and not self.training and len(clips) != 1:
             raise NotImplementedError('sparse_val=True evaluates one clip at a time: the reference reads feature[0] '
@@ -809,7 +816,7 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
             if len(one) != 1:
                 raise ValueError('a clip of forward_clips is one sample: Yuv420Frames of (t,...) or (1,t,...) views')
             _, t, h, w = ops._yuv_clip_desc(one[0], 'lrs')
-            sig = (t, h, w, lrs.y.device) + ((type(lrs), lrs.y.dtype) + tuple(lrs[3:]) if isinstance(lrs0, ops.Yuv420Frames16) else ())
+            sig = (t, h, w, lrs.y.device, type(lrs)) + ((lrs.y.dtype,) + tuple(lrs[3:]) if isinstance(lrs0, ops._YUV16_CLASSES) else ())
             if first is None:
                 first = sig
             elif sig != first:
@@ -833,13 +840,12 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
                 if self.get_option(_native.OPT_SPARSE_EVAL) != sparse_now:
                     self.set_option(_native.OPT_SPARSE_EVAL, sparse_now)
             side = torch.stack(sides, dim=1).cpu().contiguous()
-            if isinstance(lrs0, ops.Yuv420Frames16):
-                names = sorted(ops.YUV16_LAYOUTS)
+            if isinstance(lrs0, ops._YUV16_CLASSES):
                 flat = torch.ops.pnpvcve.generator_forward_clips_yuv16(self._op_handle, ys, cbs, crs, int(lrs0.bit_depth), bool(lrs0.msb_aligned),
-                                                                       mv_l, par_l, side, std, mask, names.index(layout) if layout else -1)
+                                                                       mv_l, par_l, side, std, mask, ops._yuv_layout_index(layout))
             else:
                 flat = torch.ops.pnpvcve.generator_forward_clips_yuv(self._op_handle, ys, cbs, crs, mv_l, par_l, side, std, mask,
-                                                                     ops.YUV_LAYOUTS.index(layout) if layout else -1)
+                                                                     ops._yuv_layout_index(layout))
         n = len(ys)
         order = [k for k in ('f32', 'u8', 'yuv') if k in kinds]
         per = {k: flat[j * n:(j + 1) * n] for j, k in enumerate(order)}
@@ -850,10 +856,11 @@ class IconVSR_restore_wo_refill_mv_ipb_fast_domain_dynamic_with_par(nn.Module):
         """Body of torch.ops.pnpvcve.generator_forward_clips_yuv: per-clip plane views -> the fp32 outputs (mask & 1), then the uint8
         ones (mask & 2), then the packed 4:2:0 buffers (mask & 4), one freshly allocated tensor per clip."""
         n = len(ys)
+        cls8, cls16 = ops._YUV_CLASSES[ops._yuv_code_split3(std)[2]]      # (the `standard` integer carries the chroma format)
         if bit_depth == 8:
-            clips = [ops.Yuv420Frames(ys[b], cbs[b], crs[b]) for b in range(n)]
+            clips = [cls8(ys[b], cbs[b], crs[b]) for b in range(n)]
         else:      # (torch.ops.pnpvcve.generator_forward_clips_yuv16)
-            clips = [ops.Yuv420Frames16(ys[b], cbs[b], crs[b], bit_depth, msb_aligned) for b in range(n)]
+            clips = [cls16(ys[b], cbs[b], crs[b], bit_depth, msb_aligned) for b in range(n)]
         t, h, w = ys[0].shape
         dev = ys[0].device
         with torch.cuda.device(dev):

@@ -776,15 +776,87 @@ class Yuv420Frames16(_Yuv420Base16):
     __slots__ = ()
 
 
+# 4:2:2 and 4:4:4 frames (include/pnpvcve.h, "Chroma formats"): siblings of the 4:2:0 classes, not subclasses -- the *_yuv420*
+# functions keep refusing them -- with chroma planes (n,t,h,w/2) and (n,t,h,w).  The format-generic functions (yuv_views, empty_yuv,
+# frames_from_yuv, frames_to_yuv, pack_lr_yuv, psnr_yuv, ssim_yuv) and generator.forward take every class.
+class Yuv422Frames(collections.namedtuple('Yuv422Frames', ['y', 'cb', 'cr'])):
+    """8-bit 4:2:2 frames: Yuv420Frames' rules with cb and cr (n,t,h,w/2) (yuv422p: last stride 1; NV16: 2, one byte apart)"""
+    __slots__ = ()
+
+
+class Yuv444Frames(collections.namedtuple('Yuv444Frames', ['y', 'cb', 'cr'])):
+    """8-bit 4:4:4 frames: Yuv420Frames' rules with cb and cr (n,t,h,w) (yuv444p: last stride 1; NV24: 2, one byte apart)"""
+    __slots__ = ()
+
+
+class Yuv422Frames16(collections.namedtuple('Yuv422Frames16', ['y', 'cb', 'cr', 'bit_depth', 'msb_aligned'], defaults=(10, False))):
+    """10 / 12-bit 4:2:2 frames: Yuv420Frames16's rules with cb and cr (n,t,h,w/2) (yuv422p10le / yuv422p12le, P210 / P212)"""
+    __slots__ = ()
+
+
+class Yuv444Frames16(collections.namedtuple('Yuv444Frames16', ['y', 'cb', 'cr', 'bit_depth', 'msb_aligned'], defaults=(10, False))):
+    """10 / 12-bit 4:4:4 frames: Yuv420Frames16's rules with cb and cr (n,t,h,w) (yuv444p10le / yuv444p12le, P410 / P412)"""
+    __slots__ = ()
+
+
 YUV_LAYOUTS = ('nv12', 'nv21', 'i420')
 # name -> (the 8-bit layout with the same plane order, bit depth, msb_aligned)
 YUV16_LAYOUTS = {'p010': ('nv12', 10, True), 'p012': ('nv12', 12, True), 'yuv420p10le': ('i420', 10, False), 'yuv420p12le': ('i420', 12, False)}
 _WORD_DTYPES = tuple(d for d in (torch.int16, getattr(torch, 'uint16', None)) if d is not None)
+YUV_FORMATS = tuple(sorted(_native.YUV_FORMAT, key=_native.YUV_FORMAT.get))      # '420', '422', '444': the chroma formats in the order of their codes
+_YUV_CLASSES = {'420': (Yuv420Frames, Yuv420Frames16), '422': (Yuv422Frames, Yuv422Frames16), '444': (Yuv444Frames, Yuv444Frames16)}
+_YUV8_CLASSES = tuple(c[0] for c in _YUV_CLASSES.values())
+_YUV16_CLASSES = tuple(c[1] for c in _YUV_CLASSES.values())
+# The layouts of the 4:2:2 and 4:4:4 formats by ffmpeg's names: name -> (format, the 4:2:0 layout with the same plane order, bit depth,
+# msb_aligned).  Their order here is the index a custom op's `layout` integer carries, offset by _FORMAT_LAYOUT0.
+YUV_FORMAT_LAYOUTS = {
+    'yuv422p': ('422', 'i420', 8, False), 'nv16': ('422', 'nv12', 8, False), 'yuv444p': ('444', 'i420', 8, False), 'nv24': ('444', 'nv12', 8, False),
+    'yuv422p10le': ('422', 'i420', 10, False), 'yuv422p12le': ('422', 'i420', 12, False), 'yuv444p10le': ('444', 'i420', 10, False),
+    'yuv444p12le': ('444', 'i420', 12, False), 'p210': ('422', 'nv12', 10, True), 'p212': ('422', 'nv12', 12, True),
+    'p410': ('444', 'nv12', 10, True), 'p412': ('444', 'nv12', 12, True)}
+_FORMAT_LAYOUT0 = 16
 
 
 def is_yuv(frames):
-    """frames are 4:2:0 planes of either sample size"""
-    return isinstance(frames, (Yuv420Frames, Yuv420Frames16))
+    """frames are Y'CbCr planes of any chroma format and either sample size"""
+    return isinstance(frames, _YUV8_CLASSES + _YUV16_CLASSES)
+
+
+def yuv_format(frames):
+    """the chroma format of Y'CbCr frames: '420' | '422' | '444'"""
+    for fmt, classes in _YUV_CLASSES.items():
+        if isinstance(frames, classes):
+            return fmt
+    raise TypeError(f'not Y\'CbCr frames: {type(frames).__name__}')
+
+
+def yuv_layout(layout):
+    """a layout name of any format -> (format, the 4:2:0 layout with the same plane order, bit depth, msb_aligned)"""
+    if isinstance(layout, str):
+        if layout in YUV_FORMAT_LAYOUTS:
+            return YUV_FORMAT_LAYOUTS[layout]
+        if layout in YUV_LAYOUTS:
+            return '420', layout, 8, False
+        if layout in YUV16_LAYOUTS:
+            return ('420',) + tuple(YUV16_LAYOUTS[layout])
+    raise ValueError(f'layout must be one of {YUV_LAYOUTS + tuple(sorted(YUV16_LAYOUTS)) + tuple(YUV_FORMAT_LAYOUTS)}, got {layout!r}')
+
+
+def _yuv_layout_index(layout):
+    """the integer a custom op's `layout` argument carries (-1: none): the 4:2:0 layouts keep the index of their own list"""
+    if layout is None:
+        return -1
+    if layout in YUV_FORMAT_LAYOUTS:
+        return _FORMAT_LAYOUT0 + list(YUV_FORMAT_LAYOUTS).index(layout)
+    return YUV_LAYOUTS.index(layout) if layout in YUV_LAYOUTS else sorted(YUV16_LAYOUTS).index(layout)
+
+
+def _yuv_layout_of_index(i, sixteen):
+    if i < 0:
+        return None
+    if i >= _FORMAT_LAYOUT0:
+        return list(YUV_FORMAT_LAYOUTS)[i - _FORMAT_LAYOUT0]
+    return sorted(YUV16_LAYOUTS)[i] if sixteen else YUV_LAYOUTS[i]
 
 
 def _yuv_standard(standard):
@@ -800,12 +872,15 @@ def _yuv_standard(standard):
 YUV_CHROMA = tuple(sorted(_native.YUV_CHROMA, key=_native.YUV_CHROMA.get))      # the chroma modes by name, in the order of their codes
 
 
-def _yuv_code(standard, chroma='replicate'):
-    """PNP_YUV_CODE(standard, chroma), what every 4:2:0 entry of the library takes as yuv_standard: the standard (a name or 0..3) in
-    bits 0..7, the chroma mode (a name of YUV_CHROMA) in bits 8..11; 'replicate' leaves the bare standard"""
+def _yuv_code(standard, chroma='replicate', format='420'):
+    """PNP_YUV_CODE3(standard, chroma, format), what every Y'CbCr entry of the library takes as yuv_standard: the standard (a name or
+    0..3) in bits 0..7, the chroma mode (a name of YUV_CHROMA) in bits 8..11, the chroma format (a name of YUV_FORMATS) in bits
+    12..13; 'replicate' and '420' leave the bare standard"""
     if not isinstance(chroma, str) or chroma not in _native.YUV_CHROMA:
         raise ValueError(f'chroma must be one of {YUV_CHROMA}, got {chroma!r}')
-    return _yuv_standard(standard) | _native.YUV_CHROMA[chroma] << 8
+    if not isinstance(format, str) or format not in _native.YUV_FORMAT:
+        raise ValueError(f'format must be one of {YUV_FORMATS}, got {format!r}')
+    return _yuv_standard(standard) | _native.YUV_CHROMA[chroma] << 8 | _native.YUV_FORMAT[format] << 12
 
 
 def _yuv_code_split(code):
@@ -814,6 +889,14 @@ def _yuv_code_split(code):
     if code < 0 or code >> 8 >= len(YUV_CHROMA):
         raise ValueError(f'not a code of a yuv_standard and a chroma mode: {code!r}')
     return _yuv_standard(code & 255), YUV_CHROMA[code >> 8]
+
+
+def _yuv_code_split3(code):
+    """a code of _yuv_code with its format -> (standard 0..3, chroma name, format name)"""
+    code = int(code)
+    if code < 0 or code >> 12 >= len(YUV_FORMATS):
+        raise ValueError(f'not a code of a yuv_standard, a chroma mode and a chroma format: {code!r}')
+    return _yuv_code_split(code & 0xfff) + (YUV_FORMATS[code >> 12],)
 
 
 def _yuv16_layout(layout):
@@ -836,6 +919,12 @@ def _bit_depth(d):
 def _yuv_expect(frames, what, cls=None):
     """TypeError unless frames are `cls` (Yuv420Frames | Yuv420Frames16; None: either, anything else is told what 8-bit frames are)
     -> frames are 16-bit"""
+    if cls is None and is_yuv(frames):          # (frames of any chroma format: the format-generic callers)
+        return isinstance(frames, _YUV16_CLASSES)
+    if cls is not None and cls not in (Yuv420Frames, Yuv420Frames16):      # a class of another format, asked for by name
+        if not isinstance(frames, cls):
+            raise TypeError(f'{what} must be ops.{cls.__name__}({", ".join(cls._fields)})')
+        return cls in _YUV16_CLASSES
     if cls is Yuv420Frames16 or (cls is None and isinstance(frames, Yuv420Frames16)):
         if not isinstance(frames, Yuv420Frames16):
             raise TypeError(f'{what} must be ops.Yuv420Frames16(y, cb, cr, bit_depth, msb_aligned)')
@@ -847,7 +936,7 @@ def _yuv_expect(frames, what, cls=None):
 
 def _yuv_entry(name, frames):
     """the C entry `name` for the frames' sample size"""
-    return name + ('p16' if isinstance(frames, Yuv420Frames16) else '')
+    return name + ('p16' if isinstance(frames, _YUV16_CLASSES) else '')
 
 
 def _yuv_views(buf, h, w, order, tail=()):
@@ -897,6 +986,25 @@ def yuv420p16_views(buf, h, w, layout='yuv420p10le'):
     return _yuv_views(buf, h, w, order, (depth, msb))
 
 
+def _yuv_size_check(fmt, h, w):
+    """ValueError unless h x w frames exist in the format: sx divides w and sy divides h"""
+    if fmt == '420':
+        if h < 2 or w < 2 or h % 2 or w % 2:
+            raise ValueError(f'4:2:0 frames need an even height and width, got {h} x {w}')
+    elif h < 1 or w < 1 or (fmt == '422' and w % 2):
+        raise ValueError(f'4:2:2 frames need an even width, got {h} x {w}' if fmt == '422' else f'frames need a height and a width, got {h} x {w}')
+
+
+def _yuv_shape_check(fmt, y_shape, cb_shape, cr_shape):
+    """ValueError unless (t,h,w) frames exist in the format and the chroma planes have the format's shape, (t, h / sy, w / sx)"""
+    t, h, w = y_shape
+    sx, sy = _native.YUV_FACTORS[fmt]
+    _yuv_size_check(fmt, h, w)
+    if tuple(cb_shape) != (t, h // sy, w // sx) or tuple(cr_shape) != (t, h // sy, w // sx):
+        named_c = {'420': '(t,h/2,w/2)', '422': '(t,h,w/2)', '444': '(t,h,w)'}[fmt]
+        raise ValueError(f'cb and cr must be {named_c} = {(t, h // sy, w // sx)}, got {tuple(cb_shape)} and {tuple(cr_shape)}')
+
+
 def _yuv_clip_desc(frames, what='frames', cls=None):
     """Yuv420Frames / Yuv420Frames16 of (t,h,w) / (t,h/2,w/2) views -> (_native.Yuv420Planes / Yuv420Planes16, t, h, w): pointers,
     pitches and frame strides in BYTES, the chroma step in samples; every refusal a ValueError / TypeError raised before any GPU
@@ -915,10 +1023,9 @@ def _yuv_clip_desc(frames, what='frames', cls=None):
         if x.dim() != 3:
             raise ValueError(f'{what}.{name} must be (t,rows,cols) per clip, got {tuple(x.shape)}')
     t, h, w = y.shape
-    if h < 2 or w < 2 or h % 2 or w % 2:
-        raise ValueError(f'4:2:0 frames need an even height and width, got {h} x {w}')
-    if tuple(cb.shape) != (t, h // 2, w // 2) or tuple(cr.shape) != (t, h // 2, w // 2):
-        raise ValueError(f'cb and cr must be (t,h/2,w/2) = {(t, h // 2, w // 2)}, got {tuple(cb.shape)} and {tuple(cr.shape)}')
+    fmt = yuv_format(frames)
+    sx = _native.YUV_FACTORS[fmt][0]
+    _yuv_shape_check(fmt, y.shape, cb.shape, cr.shape)
     if y.stride(2) != 1:
         raise ValueError(f'{what}.y must have a unit last stride, got {y.stride(2)}')
     if cb.stride() != cr.stride() or cb.stride(2) not in (1, 2):
@@ -926,14 +1033,14 @@ def _yuv_clip_desc(frames, what='frames', cls=None):
     step, size = cb.stride(2), y.element_size()
     if step == 2 and abs(cb.data_ptr() - cr.data_ptr()) != size:
         raise ValueError(f'chroma with a step of 2 must be interleaved: cb and cr one {apart}')
-    if y.stride(1) < w or cb.stride(1) < step * (w // 2) or (t > 1 and (y.stride(0) < 0 or cb.stride(0) < 0)):
+    if y.stride(1) < w or cb.stride(1) < step * (w // sx) or (t > 1 and (y.stride(0) < 0 or cb.stride(0) < 0)):
         raise ValueError(f'{what}: a pitch below the row\'s {unit} (strides {y.stride()}, {cb.stride()})')
     if size == 2 and (y.data_ptr() | cb.data_ptr() | cr.data_ptr()) & 1:
         raise ValueError(f'{what}: 16-bit planes must lie at even addresses')
     args = (y.data_ptr(), cb.data_ptr(), cr.data_ptr(), size * y.stride(1), size * cb.stride(1), size * y.stride(0) if t > 1 else 0,
             size * cb.stride(0) if t > 1 else 0, step)
     d = _native.Yuv420Planes16(*args, depth, int(bool(frames.msb_aligned))) if sixteen else _native.Yuv420Planes(*args)
-    return d, t, h, w
+    return d, t, h, w      # (the descriptors serve every format: the format rides in the code, yuv_format(frames))
 
 
 def _yuv_clips(frames, what='frames', cls=None):
@@ -951,7 +1058,7 @@ def _yuv_clips(frames, what='frames', cls=None):
     n = frames.y.shape[0]
     if frames.cb.shape[0] != n or frames.cr.shape[0] != n:
         raise ValueError(f'{what}: y, cb and cr disagree in the batch size')
-    kind = Yuv420Frames16 if isinstance(frames, Yuv420Frames16) else Yuv420Frames
+    kind = type(frames)
     return [kind(frames.y[b], frames.cb[b], frames.cr[b], *frames[3:]) for b in range(n)], (n,)
 
 
@@ -959,6 +1066,7 @@ def _frames_from_yuv(frames, standard, cls=None, chroma='replicate'):
     """frames_from_yuv420 / frames_from_yuv420p16 (cls: as _yuv_expect; None: by the frames' type)"""
     std = _yuv_code(standard, chroma)
     clips, lead = _yuv_clips(frames, 'frames', cls)
+    std |= _native.YUV_FORMAT[yuv_format(frames)] << 12
     descs = [_yuv_clip_desc(c) for c in clips]
     _, t, h, w = descs[0]
     if any(d[1:] != (t, h, w) for d in descs):
@@ -973,15 +1081,15 @@ def _frames_from_yuv(frames, standard, cls=None, chroma='replicate'):
     return out if lead else out[0]
 
 
-def _frames_to_yuv(planes, standard, out, cls, empty, chroma='replicate'):
-    """frames_to_yuv420 / frames_to_yuv420p16; empty(lead, h, w, device) -> (a fresh packed buffer, its views) where out is None"""
-    std = _yuv_code(standard, chroma)
+def _frames_to_yuv(planes, standard, out, cls, empty, chroma='replicate', fmt='420'):
+    """frames_to_yuv420 / frames_to_yuv420p16 / frames_to_yuv; empty(lead, h, w, device) -> (a fresh packed buffer, its views) where out
+    is None; fmt: the chroma format of the planes written"""
+    std = _yuv_code(standard, chroma, fmt)
     planes = _chk(planes, 'planes')
     if planes.dim() not in (4, 5) or planes.shape[-3] != 3:
         raise ValueError(f'planes must be (n,t,3,h,w) or (t,3,h,w), got {tuple(planes.shape)}')
     h, w = planes.shape[-2:]
-    if h < 2 or w < 2 or h % 2 or w % 2:
-        raise ValueError(f'4:2:0 frames need an even height and width, got {h} x {w}')
+    _yuv_size_check(fmt, h, w)
     lead = tuple(planes.shape[:-3])
     with torch.cuda.device(planes.device):
         buf = None
@@ -1005,6 +1113,7 @@ def _pack_lr_yuv(frames, standard, general, cls, chroma='replicate'):
     """pack_lr_yuv420 / pack_lr_yuv420p16"""
     std = _yuv_code(standard, chroma)
     d, t, h, w = _yuv_clip_desc(frames, 'frames', cls)
+    std |= _native.YUV_FORMAT[yuv_format(frames)] << 12
     entry = _yuv_entry('pnp_debug_pack_lr_yuv420', frames)
     with torch.cuda.device(frames.y.device):
         out = torch.empty((t, h, w, 4), device=frames.y.device, dtype=torch.float32)
@@ -1067,6 +1176,95 @@ def pack_lr_yuv420p16(frames, standard='bt601-limited', general=False, chroma='r
     return _pack_lr_yuv(frames, standard, general, Yuv420Frames16, chroma)
 
 
+# ---------------------------------------------------------------- every chroma format (include/pnpvcve.h, "Chroma formats")
+def _yuv_views_format(buf, h, w, fmt, order, tail=()):
+    """yuv_views for 4:2:2 | 4:4:4: a packed buffer (..., 2h | 3h, pitch) -> views of the format's class; order 'nv12' | 'nv21' |
+    'i420' (the plane order, as in _yuv_views); tail () or (bit_depth, msb_aligned)"""
+    cls = _YUV_CLASSES[fmt][1 if tail else 0]
+    sx = _native.YUV_FACTORS[fmt][0]
+    _yuv_size_check(fmt, h, w)
+    if tail and (not isinstance(buf, torch.Tensor) or buf.dtype not in _WORD_DTYPES):
+        raise TypeError(f'buf must be a tensor of 16-bit words (torch.int16 / torch.uint16), got {getattr(buf, "dtype", type(buf))}')
+    if not tail and buf.dtype != torch.uint8:
+        raise TypeError(f'buf must be uint8, got {buf.dtype}')
+    rows = h + 2 * h // sx          # Y, then two chroma planes of h rows, w / sx samples each
+    if buf.dim() >= 2 and buf.shape[-2] == rows and buf.shape[-1] >= w and buf.stride(-1) == 1:
+        pitch = buf.shape[-1]
+        y = buf[..., :h, :w]
+        if order != 'i420':         # h rows of chroma pairs: w samples of a row at 4:2:2, 2w samples of two buffer rows at 4:4:4
+            if sx == 2:
+                c = buf[..., h:, :w]
+            elif buf.stride(-2) != pitch:
+                raise ValueError('an interleaved 4:4:4 buffer needs whole rows: a row of chroma pairs is two buffer rows long')
+            else:
+                c = buf[..., h:, :].flatten(-2).unflatten(-1, (h, 2 * pitch))[..., :2 * w]
+            a, b = c[..., 0::2], c[..., 1::2]
+            return cls(y, a, b, *tail) if order == 'nv12' else cls(y, b, a, *tail)
+        if sx == 1:
+            return cls(y, buf[..., h:2 * h, :w], buf[..., 2 * h:, :w], *tail)
+        if pitch % 2 or buf.stride(-2) != pitch:
+            raise ValueError('a planar 4:2:2 buffer needs an even pitch and whole rows: its chroma rows are half a luma row long')
+        flat = buf.flatten(-2)
+        n = h * (pitch // 2)
+        cb = flat[..., h * pitch:h * pitch + n].unflatten(-1, (h, pitch // 2))[..., :w // 2]
+        cr = flat[..., h * pitch + n:h * pitch + 2 * n].unflatten(-1, (h, pitch // 2))[..., :w // 2]
+        return cls(y, cb, cr, *tail)
+    if order == 'i420' and buf.dim() >= 1 and buf.shape[-1] == rows * w and buf.stride(-1) == 1:
+        return _yuv_views_format(buf.unflatten(-1, (rows, w)), h, w, fmt, order, tail)
+    raise ValueError(f'buf must be (..., {rows}, pitch >= {w}) with a unit last stride, got {tuple(buf.shape)}')
+
+
+def yuv_views(buf, h, w, layout):
+    """A packed buffer in any layout of any chroma format -> views of the format's frame class (no copy).  4:2:0 layouts: yuv420_views /
+    yuv420p16_views.  4:2:2 ('yuv422p', 'nv16', 'yuv422p10le', 'yuv422p12le', 'p210', 'p212'): (..., 2h, pitch); 4:4:4 ('yuv444p',
+    'nv24', 'yuv444p10le', 'yuv444p12le', 'p410', 'p412'): (..., 3h, pitch) -- h rows of Y, then the Cb and the Cr plane (planar) or h
+    rows of Cb Cr pairs (interleaved), by yuv420_views' plane-order rules; planar layouts also as a flat (..., samples) buffer."""
+    fmt, order, depth, msb = yuv_layout(layout)
+    if fmt == '420':
+        return yuv420_views(buf, h, w, layout) if depth == 8 else yuv420p16_views(buf, h, w, layout)
+    return _yuv_views_format(buf, h, w, fmt, order, () if depth == 8 else (depth, msb))
+
+
+def empty_yuv(lead, h, w, layout, device, dtype=torch.int16):
+    """-> (a fresh packed buffer lead + (rows, w) in `layout`, its views); dtype: the dtype of 16-bit words"""
+    fmt, order, depth, msb = yuv_layout(layout)
+    if fmt == '420':
+        return empty_yuv420(lead, h, w, layout, device) if depth == 8 else empty_yuv420p16(lead, h, w, layout, device, dtype)
+    _yuv_size_check(fmt, h, w)
+    buf = torch.empty(tuple(lead) + (h + 2 * h // _native.YUV_FACTORS[fmt][0], w), device=device, dtype=torch.uint8 if depth == 8 else dtype)
+    return buf, yuv_views(buf, h, w, layout)
+
+
+def frames_from_yuv(frames, standard='bt601-limited', chroma='replicate'):
+    """Frames of any class (n,t,...) or (t,...) -> (n,t,3,h,w) / (t,3,h,w) fp32 RGB planes clamped to [0,1]: the arithmetic of
+    include/pnpvcve.h for the frames' chroma format, bit-equal to tests/yuv_formats_ref.py.  In 4:2:2 'left' and 'topleft' are one
+    function, in 4:4:4 all four chroma modes are."""
+    if not is_yuv(frames):
+        raise TypeError('frames must be ops.Yuv420Frames / Yuv422Frames / Yuv444Frames or their 16-bit siblings')
+    return _frames_from_yuv(frames, standard, None, chroma)
+
+
+def frames_to_yuv(planes, standard='bt601-limited', layout='nv16', out=None, chroma='replicate', dtype=torch.int16):
+    """(n,t,3,h,w) or (t,3,h,w) fp32 CUDA planes -> (a packed buffer in `layout`, its views), any layout of any format
+    (include/pnpvcve.h).  out: views of any frame class to write instead (returns (None, out)); the format, depth and container are
+    then out's."""
+    if out is not None:
+        if not is_yuv(out):
+            raise TypeError('out must be ops.Yuv420Frames / Yuv422Frames / Yuv444Frames or their 16-bit siblings')
+        fmt = yuv_format(out)
+    else:
+        fmt = yuv_layout(layout)[0]
+    return _frames_to_yuv(planes, standard, out, None, lambda lead, h, w, dev: empty_yuv(lead, h, w, layout, dev, dtype), chroma, fmt)
+
+
+def pack_lr_yuv(frames, standard='bt601-limited', general=False, chroma='replicate'):
+    """(include/pnpvcve_debug.h) one clip's frames of any class (t,...) -> the (t,h,w,4) fp32 RGB0 conv source the forward unpacks them
+    into; general: the single-sample-load form whatever the alignment"""
+    if not is_yuv(frames):
+        raise TypeError('frames must be ops.Yuv420Frames / Yuv422Frames / Yuv444Frames or their 16-bit siblings')
+    return _pack_lr_yuv(frames, standard, general, None, chroma)
+
+
 # ---------------------------------------------------------------- plane metrics of 4:2:0 clips (include/pnpvcve.h states the arithmetic)
 _PLANE_BITS = {'y': _native.PLANE_Y, 'u': _native.PLANE_CB, 'v': _native.PLANE_CR}
 
@@ -1078,13 +1276,21 @@ def _metric_planes(planes):
     return planes.lower()
 
 
-def _yuv_metric_pair(a, b, crop_border):
+def _yuv_metric_pair(a, b, crop_border, any_format=False):
     """two Yuv420Frames that show the same frames, (n,t,...) or (t,...), each in a layout of its own -> (per-clip descriptor pairs,
     lead shape, t, h, w, crop); every refusal a ValueError / TypeError raised before any GPU work.  Two Yuv420Frames16 of one bit
-    depth (each in a container of its own) are scored at that depth; an 8-bit clip against a 16-bit one is refused."""
-    if isinstance(a, Yuv420Frames16) != isinstance(b, Yuv420Frames16):
+    depth (each in a container of its own) are scored at that depth; an 8-bit clip against a 16-bit one is refused.  any_format: frames
+    of the other chroma formats are taken too (both clips of one format; crop_border even unless the format is 4:4:4); otherwise they
+    are a TypeError."""
+    for name, x in (('a', a), ('b', b)):
+        if is_yuv(x) and yuv_format(x) != '420' and not any_format:
+            raise TypeError(f'{name} must be ops.Yuv420Frames or ops.Yuv420Frames16: the metric is defined on 4:2:0 clips, got a 4:{yuv_format(x)[1:2]}:'
+                            f'{yuv_format(x)[2:]} clip ({type(x).__name__})')
+    if is_yuv(a) and is_yuv(b) and yuv_format(a) != yuv_format(b):
+        raise ValueError(f'the two clips differ in chroma format: {yuv_format(a)} and {yuv_format(b)}')
+    if isinstance(a, _YUV16_CLASSES) != isinstance(b, _YUV16_CLASSES):
         raise ValueError('a and b must both be 8-bit (Yuv420Frames) or both 16-bit (Yuv420Frames16) clips')
-    if isinstance(a, Yuv420Frames16) and _bit_depth(a.bit_depth) != _bit_depth(b.bit_depth):
+    if isinstance(a, _YUV16_CLASSES) and _bit_depth(a.bit_depth) != _bit_depth(b.bit_depth):
         raise ValueError(f'the two clips differ in bit depth: {a.bit_depth} and {b.bit_depth}')
     clips_a, lead_a = _yuv_clips(a, 'a')
     clips_b, lead_b = _yuv_clips(b, 'b')
@@ -1098,7 +1304,7 @@ def _yuv_metric_pair(a, b, crop_border):
     if isinstance(crop_border, bool) or int(crop_border) != crop_border:
         raise TypeError(f'crop_border must be an integer, got {crop_border!r}')
     crop = int(crop_border)
-    if crop < 0 or crop % 2:
+    if crop < 0 or (crop % 2 and yuv_format(a) != '444'):
         raise ValueError(f'crop_border must be even and >= 0 (the chroma planes are cropped by half of it), got {crop}')
     if 2 * crop >= h or 2 * crop >= w:
         raise ValueError(f'a crop of {crop} leaves nothing of {h} x {w} frames')
@@ -1164,6 +1370,75 @@ def ssim_yuv420(a, b, crop_border=0, planes='y'):
             for p in order:
                 rows, cols, c = (h, w, crop) if p == 'y' else (h // 2, w // 2, crop // 2)
                 n = (rows - 2 * c - 10) * (cols - 2 * c - 10)
+                res[i, :, planes.index(p)] = (part[off:off + t * nb[p]].reshape(t, nb[p]).sum(dim=1) / n).cpu()
+                off += t * nb[p]
+    return res.reshape(lead + (len(planes),))
+
+
+def _plane_geometry(fmt, h, w, crop):
+    """-> {'y' | 'u' | 'v': (rows, cols, crop down, crop across)} of a format (include/pnpvcve.h, the crop rule)"""
+    sx, sy = _native.YUV_FACTORS[fmt]
+    c = (h // sy, w // sx, crop // sy, crop // sx)
+    return {'y': (h, w, crop, crop), 'u': c, 'v': c}
+
+
+def psnr_sse_yuv(a, b, crop_border=0):
+    """psnr_sse_yuv420 for clips of any chroma format (pnp_psnr_sse_yuv / pnp_psnr_sse_yuvp16): the exact SSE of the cropped Y, Cb and Cr
+    planes of every frame, an int64 CPU tensor lead + (3,).  The chroma planes are cropped by crop_border / sx across and / sy down;
+    crop_border is even for 4:2:0 and 4:2:2, any value >= 0 for 4:4:4."""
+    pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border, any_format=True)
+    entry = 'pnp_psnr_sse_yuvp16' if isinstance(a, _YUV16_CLASSES) else 'pnp_psnr_sse_yuv'
+    fmt = _native.YUV_FORMAT[yuv_format(a)]
+    dev = a.y.device
+    with torch.cuda.device(dev):
+        sse = torch.empty((len(pairs), t, 3), dtype=torch.int64, device=dev)
+        for i, (da, db) in enumerate(pairs):
+            if t:
+                _native.check(getattr(_native.lib(), entry)(ctypes.byref(da), ctypes.byref(db), _ptr(sse[i]), t, h, w, crop, fmt, _stream()), entry)
+    return sse.cpu().reshape(lead + (3,))
+
+
+def psnr_yuv(a, b, crop_border=0):
+    """psnr_yuv420 for clips of any chroma format: a float64 CPU tensor lead + (3,) = Y, U, V, PSNR_p = 10 log10(peak^2 N_p / SSE_p) with
+    N_p the samples of the cropped plane (N_C = (h/sy - 2c/sy)(w/sx - 2c/sx)), inf where the planes are equal."""
+    import numpy as np
+    sse = psnr_sse_yuv(a, b, crop_border).numpy().astype(np.float64)
+    h, w = a.y.shape[-2:]
+    geo = _plane_geometry(yuv_format(a), h, w, int(crop_border))
+    n = [(r - 2 * cy) * (c - 2 * cx) for r, c, cy, cx in (geo[p] for p in 'yuv')]
+    with np.errstate(divide='ignore'):
+        peak = float((1 << a.bit_depth) - 1) if isinstance(a, _YUV16_CLASSES) else 255.0
+        out = 10.0 * np.log10(peak ** 2 * np.array(n, np.float64) / sse)
+    out[sse == 0] = np.inf
+    return torch.from_numpy(out)
+
+
+def ssim_yuv(a, b, crop_border=0, planes='y'):
+    """ssim_yuv420 for clips of any chroma format (pnp_ssim_partials_yuv / pnp_ssim_partials_yuvp16): per-frame plane SSIM, a float64
+    CPU tensor lead + (len(planes),) in the order of `planes`.  Crop as psnr_sse_yuv."""
+    planes = _metric_planes(planes)
+    pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border, any_format=True)
+    L = _native.lib()
+    fmt = _native.YUV_FORMAT[yuv_format(a)]
+    geo = _plane_geometry(yuv_format(a), h, w, crop)
+    mask = sum(_PLANE_BITS[p] for p in planes)
+    order = [p for p in 'yuv' if p in planes]                      # the order the library writes
+    nb = {p: int(L.pnp_ssim_blocks_yuv(h, w, crop, _PLANE_BITS[p], fmt)) for p in order}
+    if any(v < 1 for v in nb.values()):
+        raise ValueError('a cropped plane is smaller than the 11x11 SSIM window')
+    dev = a.y.device
+    res = torch.empty((len(pairs), t, len(planes)), dtype=torch.float64)
+    entry = 'pnp_ssim_partials_yuvp16' if isinstance(a, _YUV16_CLASSES) else 'pnp_ssim_partials_yuv'
+    with torch.cuda.device(dev):
+        for i, (da, db) in enumerate(pairs):
+            if not t:
+                continue
+            part = torch.empty(t * sum(nb.values()), dtype=torch.float64, device=dev)
+            _native.check(getattr(L, entry)(ctypes.byref(da), ctypes.byref(db), mask, _ptr(part), t, h, w, crop, fmt, _stream()), entry)
+            off = 0
+            for p in order:
+                rows, cols, cy, cx = geo[p]
+                n = (rows - 2 * cy - 10) * (cols - 2 * cx - 10)
                 res[i, :, planes.index(p)] = (part[off:off + t * nb[p]].reshape(t, nb[p]).sum(dim=1) / n).cpu()
                 off += t * nb[p]
     return res.reshape(lead + (len(planes),))

@@ -118,13 +118,13 @@ class BasicVSR(nn.Module):
         crops the Y plane, half of it the chroma planes.  test_cfg.convert_to may be None or 'y' and both mean the same here: the decoder's
         Y' plane IS the luma -- it is NOT the BT.601 Y that convert_to='y' derives from RGB bytes, so the two modes' numbers differ.
         Two ops.Yuv420Frames16 of one bit depth d are scored the same way on their sample values, with the peak 2^d - 1."""
-        from .ops import Yuv420Frames, Yuv420Frames16, is_yuv
+        from .ops import is_yuv
         if is_yuv(output) or is_yuv(gt):
-            if not ((isinstance(output, Yuv420Frames) and isinstance(gt, Yuv420Frames)) or
-                    (isinstance(output, Yuv420Frames16) and isinstance(gt, Yuv420Frames16))):
-                raise ValueError('plane metrics compare two 4:2:0 clips: output and gt must both be ops.Yuv420Frames '
-                                 "(ask the generator for out_dtype='i420' / 'nv12', or convert with ops.frames_to_yuv420), or both "
-                                 'ops.Yuv420Frames16 of one bit depth')
+            if not (is_yuv(output) and type(output) is type(gt)):      # (one chroma format and one sample size: one frame class)
+                raise ValueError('plane metrics compare two clips of one chroma format and sample size: output and gt must both be '
+                                 "ops.Yuv420Frames (ask the generator for out_dtype='i420' / 'nv12', or convert with ops.frames_to_yuv420), "
+                                 'both ops.Yuv420Frames16 of one bit depth, or both the same 4:2:2 / 4:4:4 class (ops.Yuv422Frames, '
+                                 f'Yuv444Frames, their 16 forms; ops.frames_to_yuv): got {type(output).__name__} and {type(gt).__name__}')
             return self._evaluate_yuv(output, gt)
         crop_border = self.test_cfg['crop_border']
         convert_to = self.test_cfg.get('convert_to', None)
@@ -177,13 +177,21 @@ class BasicVSR(nn.Module):
                 eval_result[metric] = self.allowed_metrics[metric](tensor2img(output), tensor2img(gt), crop_border, **kw)
         return eval_result
 
-    YUV_OUT_LAYOUTS = ('nv12', 'i420', 'p010', 'p012', 'yuv420p10le', 'yuv420p12le')      # the packed 4:2:0 layouts generator.forward writes
+    # the packed layouts generator.forward writes: 4:2:0, then 4:2:2 and 4:4:4 (ops.YUV_FORMAT_LAYOUTS)
+    YUV_OUT_LAYOUTS = ('nv12', 'i420', 'p010', 'p012', 'yuv420p10le', 'yuv420p12le', 'yuv422p', 'nv16', 'yuv444p', 'nv24', 'yuv422p10le',
+                       'yuv422p12le', 'yuv444p10le', 'yuv444p12le', 'p210', 'p212', 'p410', 'p412')
+    YUV_FORMAT_METRICS = ('PSNR', 'SSIM', 'PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V', 'PSNR_YUV')      # what 4:2:2 and 4:4:4 clips are scored by
     YUV_METRICS = ('PSNR', 'SSIM', 'PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V', 'PSNR_YUV', 'MS-SSIM', 'MS-SSIM_U', 'MS-SSIM_V', 'XPSNR', 'XPSNR_U',
                    'XPSNR_V', 'PSNR-B', 'PSNR-B_U', 'PSNR-B_V')
 
     def _evaluate_yuv(self, output, gt):
-        """evaluate() of two ops.Yuv420Frames (or two ops.Yuv420Frames16) clips: plane PSNR / SSIM on the device, means over the clip's frames"""
-        from .ops import msssim_yuv420, psnr_yuv420, psnrb_yuv420, ssim_yuv420, xpsnr_yuv420
+        """evaluate() of two ops.Yuv420Frames (or two ops.Yuv420Frames16) clips: plane PSNR / SSIM on the device, means over the clip's frames.
+        Two clips of one 4:2:2 or 4:4:4 class are scored by YUV_FORMAT_METRICS through ops.psnr_yuv / ops.ssim_yuv; MS-SSIM, XPSNR and
+        PSNR-B are defined on 4:2:0 clips only and raise a ValueError that names the format."""
+        from .ops import msssim_yuv420, psnr_yuv, psnrb_yuv420, ssim_yuv, xpsnr_yuv420, yuv_format
+        # PSNR and SSIM go through the format-generic functions for every clip (at 4:2:0 they are the _yuv420 entries called with format
+        # 0: the same numbers); the other three metrics are defined on 4:2:0 clips only and refused for the other formats below
+        fmt = yuv_format(output)
         crop_border = self.test_cfg['crop_border']
         convert_to = self.test_cfg.get('convert_to', None)
         if not (convert_to is None or (isinstance(convert_to, str) and convert_to.lower() == 'y')):
@@ -191,7 +199,9 @@ class BasicVSR(nn.Module):
         metrics = list(self.test_cfg['metrics'])
         for metric in metrics:
             if metric not in self.YUV_METRICS:
-                raise ValueError(f'4:2:0 clips are scored by {self.YUV_METRICS}, got {metric!r}')
+                raise ValueError(f'clips of planes are scored by {self.YUV_METRICS} (4:2:0; 4:2:2 and 4:4:4: {self.YUV_FORMAT_METRICS}), got {metric!r}')
+            if fmt != '420' and metric not in self.YUV_FORMAT_METRICS:
+                raise ValueError(f'{metric!r} is defined on 4:2:0 clips only: 4:{fmt[1]}:{fmt[2]} clips are scored by {self.YUV_FORMAT_METRICS}')
 
         def one_clip(x, name):
             if x.y.dim() == 4:
@@ -203,10 +213,10 @@ class BasicVSR(nn.Module):
         output, gt = one_clip(output, 'output'), one_clip(gt, 'gt')
         gt = type(gt)(*[p.to(output.y.device) for p in gt[:3]], *gt[3:])
         eval_result = dict()
-        psnr = psnr_yuv420(output, gt, crop_border) if any(m in ('PSNR', 'PSNR_U', 'PSNR_V', 'PSNR_YUV') for m in metrics) else None      # (t, 3)
+        psnr = psnr_yuv(output, gt, crop_border) if any(m in ('PSNR', 'PSNR_U', 'PSNR_V', 'PSNR_YUV') for m in metrics) else None      # (t, 3)
         col = {'SSIM': 'y', 'SSIM_U': 'u', 'SSIM_V': 'v'}
         planes = ''.join(dict.fromkeys(col[m] for m in metrics if m in col))
-        ssim = ssim_yuv420(output, gt, crop_border, planes) if planes else None                                    # (t, len(planes))
+        ssim = ssim_yuv(output, gt, crop_border, planes) if planes else None                                       # (t, len(planes))
         ms_col = {'MS-SSIM': 'y', 'MS-SSIM_U': 'u', 'MS-SSIM_V': 'v'}
         ms_planes = ''.join(dict.fromkeys(ms_col[m] for m in metrics if m in ms_col))
         msssim = msssim_yuv420(output, gt, crop_border, ms_planes) if ms_planes else None                          # (t, len(ms_planes))
@@ -349,11 +359,14 @@ class BasicVSR(nn.Module):
                 buf = self.generator(lq, QPs, slices, mvs, base_QPs, par_map, out_dtype=layout, yuv_standard=yuv_standard, **kw)
                 torch.cuda.synchronize()
                 self.last_forward_seconds = time.time() - begin
-        wide = layout in ops.YUV16_LAYOUTS
-        if not isinstance(buf, torch.Tensor) or (buf.dtype == torch.uint8) == wide or buf.dim() != 4 or buf.shape[-2] % 3:
-            raise ValueError('the 4:2:0 output is the packed (n,t,3H/2,W) buffer the generator returns: uint8, or 16-bit words for a 10 / 12-bit layout')
-        H, W = buf.shape[-2] * 2 // 3, buf.shape[-1]
-        output = ops.yuv420p16_views(buf, H, W, layout) if wide else ops.yuv420_views(buf, H, W, layout)
+        fmt, _, depth, _ = ops.yuv_layout(layout)
+        wide = depth != 8
+        rows2 = {'420': 3, '422': 4, '444': 6}[fmt]        # twice the buffer's rows per luma row
+        if not isinstance(buf, torch.Tensor) or (buf.dtype == torch.uint8) == wide or buf.dim() != 4 or 2 * buf.shape[-2] % rows2:
+            raise ValueError('the 4:2:0 output is the packed (n,t,3H/2,W) buffer the generator returns (4:2:2: 2H rows, 4:4:4: 3H): uint8, or '
+                             '16-bit words for a 10 / 12-bit layout')
+        H, W = buf.shape[-2] * 2 // rows2, buf.shape[-1]
+        output = ops.yuv_views(buf, H, W, layout)
         if self.test_cfg is not None and self.test_cfg.get('metrics', None):
             assert gt is not None, 'evaluation with metrics must have gt images.'
             results = dict(eval_result=self.evaluate(output, gt))

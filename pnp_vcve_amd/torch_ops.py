@@ -133,6 +133,9 @@ def _(handle, lrs, mvs, par, side, out_mask):
     return outs
 
 
+_YUV_ROWS2 = (3, 4, 6)      # twice the rows of a packed buffer per luma row, by the chroma format in bits 12..13 of `standard`
+
+
 @torch.library.custom_op('pnpvcve::frames_from_yuv420', mutates_args=())
 def frames_from_yuv420(y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, standard: int) -> torch.Tensor:
     """uint8 views y (...,h,w), cb / cr (...,h/2,w/2) with 3 or 4 dimensions -> (...,3,h,w) fp32 RGB; standard = PNP_YUV_*, or
@@ -155,7 +158,7 @@ def generator_forward_clips_yuv(handle: int, y: list[torch.Tensor], cb: list[tor
     if m is None:
         raise RuntimeError(f'pnpvcve::generator_forward_clips_yuv: unknown generator handle {handle}')
     return m._forward_clips_yuv_native(list(y), list(cb), list(cr), list(mvs), list(par), side, int(standard), int(out_mask),
-                                       ops.YUV_LAYOUTS[layout] if layout >= 0 else None)
+                                       ops._yuv_layout_of_index(layout, False))
 
 
 @generator_forward_clips_yuv.register_fake
@@ -168,7 +171,7 @@ def _(handle, y, cb, cr, mvs, par, side, standard, out_mask, layout):
             if not out_mask & bit:
                 continue
             t, h, w = x.shape
-            shape = {1: (t, 3, h * s, w * s), 2: (t, h * s, w * s, 3), 4: (t, h * s * 3 // 2, w * s)}[bit]
+            shape = {1: (t, 3, h * s, w * s), 2: (t, h * s, w * s, 3), 4: (t, h * s * _YUV_ROWS2[(standard >> 12) & 3] // 2, w * s)}[bit]
             outs.append(x.new_empty(shape, dtype=torch.float32 if bit == 1 else torch.uint8))
     return outs
 
@@ -230,7 +233,7 @@ def generator_forward_clips_yuv16(handle: int, y: list[torch.Tensor], cb: list[t
     if m is None:
         raise RuntimeError(f'pnpvcve::generator_forward_clips_yuv16: unknown generator handle {handle}')
     return m._forward_clips_yuv_native(list(y), list(cb), list(cr), list(mvs), list(par), side, int(standard), int(out_mask),
-                                       sorted(ops.YUV16_LAYOUTS)[layout] if layout >= 0 else None, int(bit_depth), bool(msb_aligned))
+                                       ops._yuv_layout_of_index(layout, True), int(bit_depth), bool(msb_aligned))
 
 
 @generator_forward_clips_yuv16.register_fake
@@ -243,6 +246,6 @@ def _(handle, y, cb, cr, bit_depth, msb_aligned, mvs, par, side, standard, out_m
             if not out_mask & bit:
                 continue
             t, h, w = x.shape
-            shape = {1: (t, 3, h * s, w * s), 2: (t, h * s, w * s, 3), 4: (t, h * s * 3 // 2, w * s)}[bit]
+            shape = {1: (t, 3, h * s, w * s), 2: (t, h * s, w * s, 3), 4: (t, h * s * _YUV_ROWS2[(standard >> 12) & 3] // 2, w * s)}[bit]
             outs.append(x.new_empty(shape, dtype={1: torch.float32, 2: torch.uint8, 4: x.dtype}[bit]))
     return outs

@@ -61,9 +61,11 @@ def parse_args():
                         'may be listed in test_cfg.metrics too) and --save-path gets one <clip>.yuv '
                         'per clip; a dataset with bit_depth=10 | 12 (16-bit little-endian .yuv files) goes the same way at its depth; '
                         'default off')
-    p.add_argument('--yuv-out-layout', choices=['i420', 'nv12', 'p010', 'p012', 'yuv420p10le', 'yuv420p12le'], default='i420',
-                   help='with --yuv-frames: the layout of the packed 4:2:0 output (and of the written .yuv files); default i420 (yuv420p); '
-                        'the 10 / 12-bit layouts for a dataset of that bit depth')
+    p.add_argument('--yuv-out-layout', choices=['i420', 'nv12', 'p010', 'p012', 'yuv420p10le', 'yuv420p12le', 'yuv422p', 'nv16', 'yuv444p', 'nv24', 'yuv422p10le',
+                                                'yuv422p12le', 'yuv444p10le', 'yuv444p12le', 'p210', 'p212', 'p410', 'p412'], default='i420',
+                   help='with --yuv-frames: the layout of the packed planes output (and of the written .yuv files); default i420 (yuv420p); '
+                        'the 10 / 12-bit layouts for a dataset of that bit depth, the 4:2:2 / 4:4:4 layouts (yuv422p, nv16, yuv444p, nv24, '
+                        'p210, ...) for a dataset of that chroma format: the output has the input\'s format')
     p.add_argument('--yuv-chroma', choices=['replicate', 'center', 'left', 'topleft'], default=None,
                    help='with --yuv-frames: where the clips\' chroma samples lie (sets data.test.chroma; include/pnpvcve.h states the modes): '
                         'replicate -- replicated in, box mean out, the default; center -- the same position, bilinear in; left -- H.264 / '
