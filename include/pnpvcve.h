@@ -787,6 +787,66 @@ int pnp_psnrb_sums_yuv420(const pnp_yuv420_planes* a_host_desc, const pnp_yuv420
 int pnp_psnrb_sums_yuv420p16(const pnp_yuv420_planes16* a_host_desc, const pnp_yuv420_planes16* b_host_desc, int plane_mask,
                              unsigned long long* sums_dev, int frames, int h, int w, int crop_border, int block, void* stream);
 
+/* Enhancement gain (gain.hip): what the enhancement gained over the compressed input -- the dPSNR / dSSIM of the compression-artifact-
+ * reduction literature, per frame, per cell of the picture and per partition class.  Nothing here is pinned to an external tool; this
+ * is the ONE statement of the definition, pinned by two independent numpy restatements (pnp_vcve_amd/metrics.py::gain_sums, which
+ * reshapes, and tests/gain_ref.py, which loops over cells and pixels).
+ * Three clips of one size, one chroma format and one bit depth: a, the test clip (the generator's output); l, the compressed input the
+ * generator was given; g, the original.
+ *   Region: what PSNR scores.  Frames of pixels and the Y plane are cropped by c = crop_border on every side, a chroma plane by c / sy
+ *   down and c / sx across (crop_border even where an axis is subsampled).
+ *   Cells: a gain block B is 16, 32, 64 or 128 luma samples (64: the CTU of HEVC, every caller's default; 128: VVC's).  The grid is
+ *   anchored at the UNCROPPED frame's origin, as PSNR-B's is, and has ceil(h / B) rows and ceil(w / B) columns for every plane of every
+ *   format.  A chroma cell is B / sy x B / sx samples, so cell (i, j) covers the same picture area in every plane: sample (y, x) of a
+ *   plane lies in cell (floor(y / (B / sy)), floor(x / (B / sx))).  A cell's sums run over its samples inside the region; a cell wholly
+ *   inside the crop holds zeros.
+ *   Sums, two per frame, plane and cell: E_a = sum (a - g)^2 and E_l = sum (l - g)^2.  On planes they are exact integers over the
+ *   samples pnp_psnr_sse_yuv / _yuvp16 compare.  On frames with PNP_COLOR_NONE they are exact integers over the very samples
+ *   pnp_psnr_stat_io compares -- to_u8 of an fp32 channel or the byte of a U8_HWC frame, each of the three inputs in its own format
+ *   -- the three channels of a pixel added.  With PNP_COLOR_Y they are fp64 sums of (double)d * d, d the one fp32 subtraction of two
+ *   Y of pnp_luma_from_frames, as pnp_psnr_stat_io forms it.  A cell is owned by one thread block, reduced in a fixed order and stored
+ *   once: no atomic, integer or floating-point, touches the grid, and every run gives the same bits.
+ *   Partition classes (only with a partition map par (frames, 3, h, w) fp32, as the generator takes it): the class of a pixel is the
+ *   3-bit mask (par0 != 0) | (par1 != 0) << 1 | (par2 != 0) << 2; class 0 is "no block painted", overlapping planes give the mixed
+ *   classes.  Per frame and class three numbers N (pixels of the class in the region), E_a and E_l, kept on the Y plane of planes clips
+ *   and on the pixels of frames (a pixel's error: the sum over its channels), never on chroma planes.
+ *   Values (host, fp64, one function for the device path and the numpy path), with peak P = 255 or 2^d - 1 and N the samples of the
+ *   region (frames with PNP_COLOR_NONE: 3 per pixel):
+ *     PSNR_t(x) = 10 log10(P^2 N / E_x,t), +inf for E = 0;   dPSNR_t = 10 log10(E_l,t / E_a,t): 0 for 0 / 0, +inf for E_a = 0 < E_l,
+ *     -inf for E_l = 0 < E_a.  A clip's dPSNR is the mean over frames; PSNR_SD is the population standard deviation (ddof 0) of
+ *     PSNR_t over the frames; dPSNR_YUV_t = (6 dY + dU + dV) / 8.  The SSIM halves are the existing SSIM entries called twice.
+ * pnp_gain_grid: rows, cols of the grid of h x w frames.  pnp_gain_cell_count: the samples of cell (row, col) of `plane` (PNP_PLANE_*;
+ * PNP_PLANE_Y with any format for frames of pixels, where it counts pixels) inside the region, in closed form.  pnp_gain_luma_tiles:
+ * the thread blocks per frame that PNP_COLOR_Y leaves class partials of, 0 when nothing can be scored.  All three host only
+ * (gain_plan.h, the one copy of the geometry the launcher and the kernel use too).
+ * pnp_gain_sums_io: frames as pnp_psnr_stat_io takes them, c == 3, each of a, l, g in its own format.  grid_dev
+ * [frames][rows][cols][2] = E_a, E_l: uint64 with PNP_COLOR_NONE, doubles with PNP_COLOR_Y.  class_dev, with par_dev: PNP_COLOR_NONE
+ * [frames][8][3] uint64 = N, E_a, E_l (integer atomics, one per thread block, class and sum, into a buffer the entry zeroes);
+ * PNP_COLOR_Y [frames][pnp_gain_luma_tiles(h, w, crop_border, block)][8][3] doubles, a thread block's own partials, which the host adds
+ * in index order.
+ * pnp_gain_sums_yuv / _yuvp16: the planes as pnp_psnr_sse_yuv / _yuvp16 take them, each of the three clips described on its own (any
+ * address, any pitch that holds a row, interleaved or planar chroma, low- or high-aligned words; no byte outside [plane, plane + rows *
+ * pitch) is read).  grid_dev [frames][3][rows][cols][2] uint64 in the order Y, Cb, Cr; plane_mask (PNP_PLANE_*) selects the planes:
+ * only they are read, the others' cells are written as 0.  class_dev [frames][8][3] uint64 with par_dev, classes of the Y plane.
+ * The grid and the integer class sums are zeroed by the entry (a kernel, not a memset node), the class partials of PNP_COLOR_Y are written
+ * whole by their tiles, and ONE kernel launch follows per call.
+ * PNP_ERR_BAD_ARG, decided on the host before any HIP call: whatever pnp_psnr_stat_io / pnp_psnr_sse_yuv / _yuvp16 refuse for (a, g)
+ * or (l, g), c != 3, a NULL input or grid, a block outside the four values, a crop that leaves nothing, a mask outside 1..7, class_dev
+ * without par_dev or par_dev without class_dev, par_dev with a mask that lacks PNP_PLANE_Y. */
+int pnp_gain_grid(int h, int w, int block, int* rows, int* cols);
+int pnp_gain_cell_count(int h, int w, int crop_border, int block, int plane, int chroma_format, int row, int col, int64_t* count);
+int pnp_gain_luma_tiles(int h, int w, int crop_border, int block);
+int pnp_gain_sums_io(const void* a_dev, int a_format, const void* l_dev, int l_format, const void* g_dev, int g_format, int color,
+                     const float* par_dev, void* grid_dev, void* class_dev, int frames, int c, int h, int w, int crop_border, int block,
+                     void* stream);
+int pnp_gain_sums_yuv(const pnp_yuv420_planes* a_host_desc, const pnp_yuv420_planes* l_host_desc, const pnp_yuv420_planes* g_host_desc,
+                      int plane_mask, const float* par_dev, unsigned long long* grid_dev, unsigned long long* class_dev, int frames, int h,
+                      int w, int crop_border, int block, int chroma_format, void* stream);
+int pnp_gain_sums_yuvp16(const pnp_yuv420_planes16* a_host_desc, const pnp_yuv420_planes16* l_host_desc,
+                         const pnp_yuv420_planes16* g_host_desc, int plane_mask, const float* par_dev, unsigned long long* grid_dev,
+                         unsigned long long* class_dev, int frames, int h, int w, int crop_border, int block, int chroma_format,
+                         void* stream);
+
 /* Modulated deformable 3x3 conv, 64 -> 64 channels, deform_groups 16 (mmcv.ops.modulated_deform_conv2d as
  * called at mmedit/models/backbones/sr_backbones/iconvsr_mv.py:38-41,81-84; semantics restated, mmcv is not
  * vendored).  x_dev (h,w,64) pixel-major; om_dev (h,w,448): conv_offset[2] output (pre-sigmoid masks) in the

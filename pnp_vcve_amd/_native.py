@@ -170,6 +170,15 @@ SIGNATURES = {
                                       c_void_p]),
     'pnp_psnrb_sums_yuv420p16': (c_int, [POINTER(Yuv420Planes16), POINTER(Yuv420Planes16), c_int, c_void_p, c_int, c_int, c_int, c_int,
                                          c_int, c_void_p]),
+    'pnp_gain_grid': (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    'pnp_gain_cell_count': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int64)]),
+    'pnp_gain_luma_tiles': (c_int, [c_int, c_int, c_int, c_int]),
+    'pnp_gain_sums_io': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                 c_int, c_int, c_int, c_void_p]),
+    'pnp_gain_sums_yuv': (c_int, [POINTER(Yuv420Planes), POINTER(Yuv420Planes), POINTER(Yuv420Planes), c_int, c_void_p, c_void_p, c_void_p,
+                                  c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'pnp_gain_sums_yuvp16': (c_int, [POINTER(Yuv420Planes16), POINTER(Yuv420Planes16), POINTER(Yuv420Planes16), c_int, c_void_p, c_void_p,
+                                     c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'pnp_conv3x3_f32': (c_int, [c_int, POINTER(c_void_p), POINTER(c_int), POINTER(c_void_p), c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     'pnp_bae_block_f32': (c_int, [c_void_p] * 10 + [c_int, c_int, c_void_p]),

@@ -176,6 +176,11 @@ def multi_gpu_test(model, dataset, save_image=False, save_path=None, device='cud
     also takes 'p010' | 'p012' | 'yuv420p10le' | 'yuv420p12le', the ground truth and the output must agree in depth, and the file is
     ops.frames_to_yuv420p16's words, little-endian.
 
+    The enhancement-gain names (metrics.GAIN_METRICS: 'dPSNR', 'dSSIM', 'PSNR_LQ', 'SSIM_LQ', 'PSNR_SD', 'PSNR_SD_LQ'; with yuv_frames
+    also metrics.GAIN_PLANE_METRICS) travel as ordinary columns of the gathered table under every switch above: forward_test hands
+    the clip's `lq` and partition map to BasicVSR.evaluate, and with test_cfg.gain_report = DIR each rank writes DIR/<clip>.json for
+    the clips it scored.
+
     A model built with ensemble=dict(type='SpatialTemporalEnsemble', ...) runs clip by clip whatever clips_in_flight says (the same
     metrics); byte_frames / byte_metrics work as above, yuv_frames raises ValueError."""
     import time

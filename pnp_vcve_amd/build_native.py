@@ -13,7 +13,7 @@ from . import isa_hazards
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'lib', 'libpnpvcve_hip.so')
-SOURCES = ['conv_mfma.hip', 'conv_persist.hip', 'conv_wino.hip', 'conv_wino_ms.hip', 'conv_f16.hip', 'conv_f16x3.hip', 'conv_last.hip', 'warp.hip', 'prep.hip', 'yuv.hip', 'metrics.hip', 'plane_metrics.hip', 'msssim.hip', 'xpsnr.hip', 'psnrb.hip', 'raster.hip', 'ensemble.hip', 'dcn.hip', 'generator.hip', 'ops_abi.hip']
+SOURCES = ['conv_mfma.hip', 'conv_persist.hip', 'conv_wino.hip', 'conv_wino_ms.hip', 'conv_f16.hip', 'conv_f16x3.hip', 'conv_last.hip', 'warp.hip', 'prep.hip', 'yuv.hip', 'metrics.hip', 'plane_metrics.hip', 'msssim.hip', 'xpsnr.hip', 'psnrb.hip', 'gain.hip', 'raster.hip', 'ensemble.hip', 'dcn.hip', 'generator.hip', 'ops_abi.hip']
 # units of host code only (the stand-alone op wrappers): no kernel, so no code object in the library
 HOST_ONLY = ['ops_abi.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall']

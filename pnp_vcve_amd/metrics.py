@@ -441,3 +441,206 @@ def xpsnr(o, r, d, fps=30, crop_border=0):
     sums = xpsnr_sums(o, r, fps)
     wsse, frames, clip = xpsnr_values(sums, d, fps, h, w)
     return dict(sums=sums, wsse=wsse, frames=frames, clip=clip)
+
+
+# ---------------------------------------------------------------- enhancement gain (include/pnpvcve.h, pnp_gain_*: the one statement of the definition)
+# What the test clip a gained over the compressed input l, both against the original g.  The host path: the two squared-error sums of
+# every gain cell by reshaping (gain_sums), a cell's sample count in closed form (gain_cell_counts), and the fp64 part (gain_values,
+# gain_sd, gain_yuv, gain_report), which ops.gain_* and BasicVSR.evaluate call on the device's sums too: that part exists once.
+GAIN_BLOCKS = (16, 32, 64, 128)
+GAIN_METRICS = ('PSNR_LQ', 'SSIM_LQ', 'dPSNR', 'dSSIM', 'PSNR_SD', 'PSNR_SD_LQ')                   # served on every boundary
+GAIN_PLANE_METRICS = ('dPSNR_U', 'dPSNR_V', 'PSNR_LQ_U', 'PSNR_LQ_V', 'dSSIM_U', 'dSSIM_V', 'SSIM_LQ_U', 'SSIM_LQ_V', 'dPSNR_YUV')      # clips of planes only
+GAIN_FACTORS = {'420': (2, 2), '422': (2, 1), '444': (1, 1)}      # chroma format -> (sx, sy)
+
+
+def gain_block(block):
+    """the gain block: one of GAIN_BLOCKS luma samples (64: the CTU of HEVC; 128: VVC's)"""
+    if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or int(block) not in GAIN_BLOCKS:
+        raise ValueError(f'block must be one of {GAIN_BLOCKS}, got {block!r}')
+    return int(block)
+
+
+def gain_grid(h, w, block=64):
+    """(rows, cols) of the cell grid of h x w frames: anchored at the uncropped frame's origin, the same for every plane"""
+    b = gain_block(block)
+    if h < 1 or w < 1:
+        raise ValueError(f'frames of {h} x {w}')
+    return -(-int(h) // b), -(-int(w) // b)
+
+
+def _gain_plane(h, w, crop, block, sx, sy):
+    """-> (rows, cols, crop down, crop across, cell rows, cell columns) of the plane of h x w frames that (sx, sy) subsample"""
+    b = gain_block(block)
+    if isinstance(crop, bool) or int(crop) != crop or crop < 0 or 2 * crop >= h or 2 * crop >= w:
+        raise ValueError(f'a crop of {crop!r} leaves nothing of {h} x {w} frames (or is no integer >= 0)')
+    if h % sy or w % sx:
+        raise ValueError(f'{h} x {w} frames cannot be subsampled by {sx} across and {sy} down')
+    return h // sy, w // sx, int(crop) // sy, int(crop) // sx, b // sy, b // sx
+
+
+def gain_cell_counts(h, w, crop_border=0, block=64, sx=1, sy=1):
+    """(rows, cols) int64: the samples of every cell inside the region, in closed form -- the overlap of [i bh, (i + 1) bh) with
+    [cy, rows - cy) times the overlap of [j bw, (j + 1) bw) with [cx, cols - cx); a cell inside the crop has 0"""
+    rows, cols, cy, cx, bh, bw = _gain_plane(h, w, crop_border, block, sx, sy)
+    gr, gc = gain_grid(h, w, block)
+
+    def overlap(count, b, lo, hi):
+        k = np.arange(count, dtype=np.int64)
+        return np.maximum(np.minimum((k + 1) * b, hi) - np.maximum(k * b, lo), 0)
+
+    return overlap(gr, bh, cy, rows - cy)[:, None] * overlap(gc, bw, cx, cols - cx)[None, :]
+
+
+def _gain_cells(e, cy, cx, bh, bw, gr, gc):
+    """(T, rows, cols) per-sample errors -> (T, gr, gc): zeros outside the region, the plane padded to whole cells, one reshape"""
+    t, rows, cols = e.shape
+    pad = np.zeros((t, gr * bh, gc * bw), e.dtype)
+    pad[:, cy:rows - cy, cx:cols - cx] = e[:, cy:rows - cy, cx:cols - cx]
+    return pad.reshape(t, gr, bh, gc, bw).sum(axis=(2, 4))
+
+
+def _gain_errors(x, g):
+    """per-sample squared error of two (T, rows, cols[, C]) arrays, a pixel's channels added: integers exactly (int64); float32 samples
+    (the Y of convert_to='y') as one float32 subtraction squared in float64"""
+    x, g = np.asarray(x), np.asarray(g)
+    if x.shape != g.shape or x.ndim not in (3, 4):
+        raise ValueError(f'clips of different shapes: {x.shape} and {g.shape}')
+    if x.dtype == np.float32 and g.dtype == np.float32:
+        d = (x - g).astype(np.float64)
+    elif np.issubdtype(x.dtype, np.integer) and np.issubdtype(g.dtype, np.integer):
+        d = x.astype(np.int64) - g.astype(np.int64)
+    else:
+        raise TypeError(f'samples must be integers, or float32 luma on both sides: got {x.dtype} and {g.dtype}')
+    e = d * d
+    return e.sum(axis=-1) if e.ndim == 4 else e
+
+
+def gain_classes(par):
+    """(T, 3, h, w) partition map -> (T, h, w) int64 classes: (par0 != 0) | (par1 != 0) << 1 | (par2 != 0) << 2"""
+    par = np.asarray(par)
+    if par.ndim != 4 or par.shape[1] != 3:
+        raise ValueError(f'par must be (frames, 3, h, w), got {par.shape}')
+    nz = (par != 0).astype(np.int64)
+    return nz[:, 0] | (nz[:, 1] << 1) | (nz[:, 2] << 2)
+
+
+def gain_sums(a, l, g, crop_border=0, block=64, fmt=None, par=None):
+    """The sums of the enhancement gain on the host (include/pnpvcve.h).  a (the test clip), l (the compressed input), g (the original):
+    three (y, u, v) triples of (T, rows, cols) integer arrays of a clip of planes in the chroma format fmt ('420' | '422' | '444'); or
+    three (T, h, w, C) integer arrays of pixels (the channels of a pixel are added); or three (T, h, w) float32 luma arrays.  ->
+    (grid (T, planes, rows, cols, 2) = E_a, E_l of every cell, int64 -- float64 for float32 samples --, classes (T, 8, 3) = N, E_a, E_l
+    of every partition class on the Y plane / the pixels, or None without par (T, 3, h, w))."""
+    if isinstance(a, (tuple, list)):
+        if fmt not in GAIN_FACTORS:
+            raise ValueError(f'a clip of planes needs its chroma format, one of {sorted(GAIN_FACTORS)}: got {fmt!r}')
+        planes = [(a[k], l[k], g[k], (1, 1) if k == 0 else GAIN_FACTORS[fmt]) for k in range(3)]
+    else:
+        planes = [(a, l, g, (1, 1))]
+    t, h, w = np.asarray(planes[0][0]).shape[:3]
+    gr, gc = gain_grid(h, w, block)
+    grid, classes = None, None
+    for k, (pa, pl, pg, (sx, sy)) in enumerate(planes):
+        rows, cols, cy, cx, bh, bw = _gain_plane(h, w, crop_border, block, sx, sy)
+        ea, el = _gain_errors(pa, pg), _gain_errors(pl, pg)
+        if ea.shape != (t, rows, cols) or el.shape != (t, rows, cols):
+            raise ValueError(f'plane {k} must be {(t, rows, cols)}, got {ea.shape} and {el.shape}')
+        if grid is None:
+            grid = np.zeros((t, len(planes), gr, gc, 2), ea.dtype)
+        grid[:, k, :, :, 0] = _gain_cells(ea, cy, cx, bh, bw, gr, gc)
+        grid[:, k, :, :, 1] = _gain_cells(el, cy, cx, bh, bw, gr, gc)
+        if k == 0 and par is not None:
+            cls = gain_classes(par)
+            if cls.shape != (t, h, w):
+                raise ValueError(f'par must be {(t, 3, h, w)}, got {np.asarray(par).shape}')
+            region = (slice(None), slice(cy, rows - cy), slice(cx, cols - cx))
+            classes = np.zeros((t, 8, 3), ea.dtype)
+            for c in range(8):
+                m = cls[region] == c
+                classes[:, c, 0] = m.sum(axis=(1, 2))
+                classes[:, c, 1] = (ea[region] * m).sum(axis=(1, 2))
+                classes[:, c, 2] = (el[region] * m).sum(axis=(1, 2))
+    return grid, classes
+
+
+def gain_frame_sums(grid):
+    """grid (..., rows, cols, 2) -> (..., 2): a frame's E_a, E_l, its cells added in index order (row by row) -- ONE order for every
+    caller, so the fp64 sums of convert_to='y' give the same bits wherever they are formed; integers are exact in any order"""
+    g = np.asarray(grid)
+    return g.reshape(g.shape[:-3] + (-1, 2)).cumsum(axis=-2)[..., -1, :]
+
+
+def gain_values(e_a, e_l, n, peak=255.0):
+    """The fp64 part.  e_a, e_l: arrays (...) of squared-error sums over n samples each (n: a number or an array that broadcasts), peak
+    P -> (PSNR of a, PSNR of l, dPSNR), float64 arrays (...): PSNR(x) = 10 log10(P^2 n / E_x), +inf for E = 0; dPSNR = 10 log10(E_l /
+    E_a), 0 for 0 / 0, +inf for E_a = 0 < E_l, -inf for E_l = 0 < E_a."""
+    ea, el = np.asarray(e_a, np.float64), np.asarray(e_l, np.float64)
+    n = np.asarray(n, np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        pa = np.where(ea > 0, 10.0 * np.log10(float(peak) ** 2 * n / ea), np.inf)
+        pl = np.where(el > 0, 10.0 * np.log10(float(peak) ** 2 * n / el), np.inf)
+        d = np.where(ea > 0, np.where(el > 0, 10.0 * np.log10(el / ea), -np.inf), np.where(el > 0, np.inf, 0.0))
+    return pa, pl, d
+
+
+def gain_sd(per_frame):
+    """the quality fluctuation of a clip: the population standard deviation (ddof 0) of the frames' values, fp64"""
+    x = np.asarray(per_frame, np.float64).reshape(-1)
+    return float(np.sqrt(np.mean((x - np.mean(x)) ** 2)))
+
+
+def gain_yuv(dy, du, dv):
+    """(6 dY + dU + dV) / 8 per frame, the weights of PSNR_YUV"""
+    return (6.0 * np.asarray(dy, np.float64) + np.asarray(du, np.float64) + np.asarray(dv, np.float64)) / 8.0
+
+
+def _gain_json(x):
+    x = float(x)
+    return x if np.isfinite(x) else ('inf' if x > 0 else ('-inf' if x < 0 else 'nan'))
+
+
+def gain_report(grid, counts, peak=255.0, slices=None, qps=None, base_qps=None, classes=None, class_samples=1, ssim=None, ssim_lq=None, block=64):
+    """One clip's gain as a JSON-ready dict.  grid (T, rows, cols, 2): the cells' E_a, E_l of the Y plane / the pixels; counts (rows,
+    cols): the cells' samples (gain_cell_counts, times 3 for RGB sums); slices (T) letters or their codes ord('I' | 'P' | 'B'), qps and
+    base_qps (T) numbers or None; classes (T, 8, 3) or None, class_samples the samples a pixel stands for (3 for RGB sums); ssim,
+    ssim_lq (T) the SSIM of a and of l per frame or None.  ->
+      frames:   per frame index, slice, qp, base_qp, PSNR, PSNR_LQ, dPSNR (and SSIM, SSIM_LQ, dSSIM);
+      by_slice / by_qp: the means of those values over the frames of a slice type / a QP, with the number of frames;
+      classes:  per partition class, summed over the clip: N, PSNR, PSNR_LQ, dPSNR (None without a partition map);
+      grid:     dPSNR of every cell, frames summed, as nested lists (0 for a cell inside the crop);
+      dPSNR:    the clip's value, the mean over frames.
+    Infinite values are written as the strings 'inf' / '-inf' (JSON has no infinity)."""
+    grid = np.asarray(grid)
+    t = grid.shape[0]
+    n = float(np.asarray(counts, np.float64).sum())
+    e = gain_frame_sums(grid)
+    pa, pl, dp = gain_values(e[:, 0], e[:, 1], n, peak)
+
+    def letter(s):
+        return s if isinstance(s, str) else chr(int(round(float(s))))
+
+    sl = [None] * t if slices is None else [letter(s) for s in np.asarray(slices).reshape(-1)[:t].tolist()]
+    qp = [None] * t if qps is None else [float(q) for q in np.asarray(qps, np.float64).reshape(-1)[:t]]
+    bq = [None] * t if base_qps is None else [float(q) for q in np.asarray(base_qps, np.float64).reshape(-1)[:t]]
+    cols = dict(PSNR=pa, PSNR_LQ=pl, dPSNR=dp)
+    if ssim is not None and ssim_lq is not None:
+        sa, sq = np.asarray(ssim, np.float64).reshape(-1), np.asarray(ssim_lq, np.float64).reshape(-1)
+        cols.update(SSIM=sa, SSIM_LQ=sq, dSSIM=sa - sq)
+    frames = [dict(index=i, slice=sl[i], qp=qp[i], base_qp=bq[i], **{k: _gain_json(v[i]) for k, v in cols.items()}) for i in range(t)]
+
+    def groups(keys):
+        out = {}
+        for key in dict.fromkeys(k for k in keys if k is not None):
+            idx = [i for i in range(t) if keys[i] == key]
+            with np.errstate(invalid='ignore'):
+                out[str(key) if isinstance(key, str) else repr(key)] = dict(frames=len(idx), **{k: _gain_json(np.mean(v[idx])) for k, v in cols.items()})
+        return out
+
+    table = None
+    if classes is not None:
+        c = np.asarray(classes).sum(axis=0)
+        ca, cl, cd = gain_values(c[:, 1], c[:, 2], c[:, 0].astype(np.float64) * class_samples, peak)
+        table = [dict(**{'class': k}, N=int(c[k, 0]), PSNR=_gain_json(ca[k]), PSNR_LQ=_gain_json(cl[k]), dPSNR=_gain_json(cd[k])) for k in range(8)]
+    cells = gain_values(grid[..., 0].sum(axis=0), grid[..., 1].sum(axis=0), 1.0, peak)[2]
+    with np.errstate(invalid='ignore'):
+        return dict(block=int(block), frames=frames, by_slice=groups(sl), by_qp=groups(qp), classes=table,
+                    grid=[[_gain_json(v) for v in row] for row in cells], dPSNR=_gain_json(np.mean(dp)))

@@ -1664,6 +1664,129 @@ def bef_yuv420(a, crop_border=0, planes='y', block=8):
     return _psnrb_yuv420(a, None, crop_border, planes, block)[1]
 
 
+# ---------------------------------------------------------------- enhancement gain (include/pnpvcve.h, pnp_gain_*)
+def _gain_par(par, lead, h, w, device):
+    """the partition map of a gain call: None, or fp32 lead + (3, h, w) on the clips' device -> contiguous"""
+    if par is None:
+        return None
+    if not isinstance(par, torch.Tensor) or not par.is_cuda or par.device != device:
+        raise RuntimeError("par must be a CUDA/HIP tensor on the clips' device: the PnP-VCVE hot path has no CPU fallback")
+    if par.dtype != torch.float32 or tuple(par.shape) != tuple(lead) + (3, h, w):
+        raise ValueError(f'par must be float32 {tuple(lead) + (3, h, w)}, as the generator takes it: got {par.dtype} {tuple(par.shape)}')
+    return par.contiguous()
+
+
+def _gain_crop(crop_border, h, w):
+    if isinstance(crop_border, bool) or int(crop_border) != crop_border or crop_border < 0 or 2 * crop_border >= h or 2 * crop_border >= w:
+        raise ValueError(f'a crop of {crop_border!r} leaves nothing of {h} x {w} frames (or is no integer >= 0)')
+    return int(crop_border)
+
+
+@_on_device_of_first_tensor
+def gain_sums_frames(a, l, g, crop_border=0, convert_to=None, block=64, par=None):
+    """The sums behind gain_frames (pnp_gain_sums_io; include/pnpvcve.h states the definition): a the test clip, l the compressed input,
+    g the original, each on its own fp32 (...,3,h,w) planes or uint8 (...,h,w,3) RGB frames of one leading shape.  ONE launch reads the
+    three clips once.  -> (grid, classes): grid lead + (1, rows, cols, 2) = E_a, E_l of every block x block cell (16, 32, 64 or 128;
+    anchored at the uncropped frame's origin), an int64 CPU tensor -- the three channels of a pixel added, exact, the same bits every
+    run --, float64 with convert_to 'y'; classes lead + (8, 3) = N, E_a, E_l of every partition class of par (fp32 lead + (3, h, w)),
+    or None without par.  Every refusal is raised before any GPU work."""
+    from . import metrics
+    a, fa, g, fg, color, lead, frames, c, h, w = _metric_pair(a, g, convert_to)
+    l, fl, lead_l, cl, hl, wl = _metric_frames(l, 'l')
+    if (lead_l, cl, hl, wl) != (lead, c, h, w):
+        raise ValueError(f'the three clips differ in shape: a and g show {lead + (c, h, w)}, l {lead_l + (cl, hl, wl)}')
+    if l.device != a.device:
+        raise RuntimeError('a, l and g must be on the same device')
+    if c != 3:
+        raise ValueError(f'the gain is kept on RGB frames (3 channels), got {c}')
+    block, crop = metrics.gain_block(block), _gain_crop(crop_border, h, w)
+    par = _gain_par(par, lead, h, w, a.device)
+    rows, cols = metrics.gain_grid(h, w, block)
+    L = _native.lib()
+    y = color == _native.COLOR_Y
+    grid = torch.empty((frames, 1, rows, cols, 2), dtype=torch.float64 if y else torch.int64, device=a.device)
+    cls = None
+    if par is not None:
+        tiles = int(L.pnp_gain_luma_tiles(h, w, crop, block))
+        cls = torch.empty((frames, tiles, 8, 3) if y else (frames, 8, 3), dtype=grid.dtype, device=a.device)
+    if frames:
+        _native.check(L.pnp_gain_sums_io(_ptr(a), fa, _ptr(l), fl, _ptr(g), fg, color, None if par is None else _ptr(par), _ptr(grid),
+                                         None if cls is None else _ptr(cls), frames, c, h, w, crop, block, _stream()), 'pnp_gain_sums_io')
+    grid = grid.cpu().reshape(lead + (1, rows, cols, 2))
+    if cls is None:
+        return grid, None
+    if y:
+        import numpy as np
+        part = cls.cpu().numpy()
+        cls = torch.from_numpy(part.cumsum(axis=1)[:, -1].copy() if frames else np.zeros((0, 8, 3), np.float64))      # a frame's tiles in index order
+    return grid, cls.cpu().reshape(lead + (8, 3))
+
+
+def gain_sums_yuv(a, l, g, crop_border=0, planes='y', block=64, par=None):
+    """The sums behind gain_yuv (pnp_gain_sums_yuv / _yuvp16): three clips of ONE frame class (any of the six: 4:2:0, 4:2:2, 4:4:4, 8-bit
+    or 16-bit words of one depth), (n,t,...) or (t,...), each in a layout of its own.  -> (grid, classes): grid an int64 CPU tensor lead +
+    (len(planes), rows, cols, 2) = E_a, E_l of every cell of the planes named, in that order (a chroma cell is block / sy x block / sx
+    samples: cell (i, j) is the same picture area in every plane); classes lead + (8, 3) = N, E_a, E_l of every partition class on the Y
+    plane (par: fp32 lead + (3, h, w); it needs 'y' among the planes), or None.  The crop as psnr_yuv."""
+    from . import metrics
+    planes = _metric_planes(planes)
+    if type(a) is not type(l) or type(a) is not type(g):
+        raise ValueError(f'the three clips must be of one frame class, got {type(a).__name__}, {type(l).__name__} and {type(g).__name__}')
+    pairs, lead, t, h, w, crop = _yuv_metric_pair(a, g, crop_border, any_format=True)
+    pairs_l = _yuv_metric_pair(l, g, crop_border, any_format=True)[0]
+    block = metrics.gain_block(block)
+    if par is not None and 'y' not in planes:
+        raise ValueError(f"partition classes are kept on the Y plane: planes must name 'y' with par, got {planes!r}")
+    dev = a.y.device
+    par = _gain_par(par, lead, h, w, dev)
+    rows, cols = metrics.gain_grid(h, w, block)
+    mask = sum(_PLANE_BITS[p] for p in planes)
+    entry = 'pnp_gain_sums_yuvp16' if isinstance(a, _YUV16_CLASSES) else 'pnp_gain_sums_yuv'
+    fmt = _native.YUV_FORMAT[yuv_format(a)]
+    with torch.cuda.device(dev):
+        grid = torch.empty((len(pairs), t, 3, rows, cols, 2), dtype=torch.int64, device=dev)
+        cls = None if par is None else torch.empty((len(pairs), t, 8, 3), dtype=torch.int64, device=dev)
+        par_clips = None if par is None else par.reshape((len(pairs), t, 3, h, w))
+        for i, ((da, dg), (dl, _)) in enumerate(zip(pairs, pairs_l)):
+            if t:
+                _native.check(getattr(_native.lib(), entry)(ctypes.byref(da), ctypes.byref(dl), ctypes.byref(dg), mask,
+                                                            None if par is None else _ptr(par_clips[i]), _ptr(grid[i]),
+                                                            None if cls is None else _ptr(cls[i]), t, h, w, crop, block, fmt, _stream()), entry)
+    idx = ['yuv'.index(p) for p in planes]
+    grid = grid.cpu()[:, :, idx].reshape(lead + (len(planes), rows, cols, 2))
+    return grid, (None if cls is None else cls.cpu().reshape(lead + (8, 3)))
+
+
+def _gain_frame_values(grid, n, peak):
+    """grid (..., planes, rows, cols, 2), n (planes,) samples of a frame's region -> three float64 tensors (..., planes)"""
+    import numpy as np
+    from . import metrics
+    e = metrics.gain_frame_sums(grid.numpy())
+    return tuple(torch.from_numpy(np.ascontiguousarray(v)) for v in metrics.gain_values(e[..., 0], e[..., 1], np.asarray(n, np.float64), peak))
+
+
+def gain_frames(a, l, g, crop_border=0, convert_to=None, block=64):
+    """Per-frame gain of the test clip a over the compressed input l against the original g on the GPU (include/pnpvcve.h): -> (PSNR_t(a),
+    PSNR_t(l), dPSNR_t), three float64 CPU tensors of the leading shape; a, l, g, crop_border and convert_to as psnr_frames.  The sums are
+    the device's (gain_sums_frames, one launch for both halves); the fp64 part is metrics.gain_values."""
+    grid = gain_sums_frames(a, l, g, crop_border, convert_to, block)[0]
+    h, w = (a.shape[-3:-1] if a.dtype == torch.uint8 else a.shape[-2:])
+    n = (int(h) - 2 * int(crop_border)) * (int(w) - 2 * int(crop_border)) * (1 if _metric_color(convert_to) == _native.COLOR_Y else 3)
+    return tuple(v[..., 0] for v in _gain_frame_values(grid, [n], 255.0))
+
+
+def gain_yuv(a, l, g, crop_border=0, planes='y', block=64):
+    """Per-frame plane gain of three clips of one frame class (gain_sums_yuv): -> (PSNR_t(a), PSNR_t(l), dPSNR_t), three float64 CPU
+    tensors lead + (len(planes),) in the order of `planes`; the peak is 255 or 2^d - 1."""
+    planes = _metric_planes(planes)
+    grid = gain_sums_yuv(a, l, g, crop_border, planes, block)[0]
+    h, w = (int(x) for x in a.y.shape[-2:])
+    geo = _plane_geometry(yuv_format(a), h, w, int(crop_border))
+    n = [(r - 2 * cy) * (c - 2 * cx) for r, c, cy, cx in (geo[p] for p in planes)]
+    peak = float((1 << a.bit_depth) - 1) if isinstance(a, _YUV16_CLASSES) else 255.0
+    return _gain_frame_values(grid, n, peak)
+
+
 # ---------------------------------------------------------------- self-ensemble (include/pnpvcve.h, "Self-ensemble")
 #: variant ids: bit 0 flips the width axis, bit 1 the height axis, bit 2 transposes, bit 3 reverses time
 ENSEMBLE_SPATIAL = tuple(range(8))

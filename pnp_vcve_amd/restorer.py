@@ -13,7 +13,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .metrics import ALLOWED_METRICS, tensor2img
+from .metrics import ALLOWED_METRICS, GAIN_METRICS, GAIN_PLANE_METRICS, tensor2img
 from .registry import LOSSES, MODELS, build_backbone, build_loss
 
 
@@ -103,8 +103,16 @@ class BasicVSR(nn.Module):
             return self.forward_test(lq, gt, QPs, slices, mvs, base_QPs, partitions, **kwargs)
         raise NotImplementedError('training is out of scope of the MI355X hot-path build')
 
-    def evaluate(self, output, gt):
+    def evaluate(self, output, gt, lq=None, par_map=None):
         """basicvsr.py:119-153.
+        Enhancement gain (not in the reference; include/pnpvcve.h, pnp_gain_*): with `lq`, the compressed input the generator was given,
+        the names of metrics.GAIN_METRICS -- 'PSNR_LQ', 'SSIM_LQ' (lq against gt), 'dPSNR', 'dSSIM' (the mean over frames of the output's
+        value minus lq's), 'PSNR_SD', 'PSNR_SD_LQ' (the population standard deviation of the frames' PSNR) -- are served on every kind
+        of clip, and on clips of planes also their `_U` / `_V` forms and 'dPSNR_YUV' (6:1:1; KeyError on RGB clips, as 'PSNR_YUV').
+        test_cfg.get('gain_block', 64) is the cell size; `par_map` (the generator's partition map) adds the per-class sums to
+        self.last_gain, which test_cfg.gain_report writes out (forward_test).  A gain name without lq, with a vsr generator (lq is a
+        quarter of the size) or with an lq of another frame class, size or bit depth raises ValueError before any GPU work.  Every
+        other result is what it was.
         4:2:0 clips (not in the reference): when `output` and `gt` are both ops.Yuv420Frames -- one clip, (t,...) or (1,t,...) views,
         each in a layout of its own -- the metrics are PLANE metrics read from the 8-bit planes on the device (ops.psnr_yuv420 /
         ssim_yuv420 / msssim_yuv420): 'PSNR' / 'SSIM' / 'MS-SSIM' score the Y plane, and in this mode only 'PSNR_U', 'PSNR_V', 'SSIM_U',
@@ -125,7 +133,9 @@ class BasicVSR(nn.Module):
                                  "ops.Yuv420Frames (ask the generator for out_dtype='i420' / 'nv12', or convert with ops.frames_to_yuv420), "
                                  'both ops.Yuv420Frames16 of one bit depth, or both the same 4:2:2 / 4:4:4 class (ops.Yuv422Frames, '
                                  f'Yuv444Frames, their 16 forms; ops.frames_to_yuv): got {type(output).__name__} and {type(gt).__name__}')
-            return self._evaluate_yuv(output, gt)
+            self._gain_check(output, lq)
+            return self._evaluate_yuv(output, gt, lq, par_map)
+        self._gain_check(output, lq)
         crop_border = self.test_cfg['crop_border']
         convert_to = self.test_cfg.get('convert_to', None)
         eval_result = dict()
@@ -144,6 +154,13 @@ class BasicVSR(nn.Module):
             return x if x.dtype == torch.uint8 else x.float()
 
         for metric in self.test_cfg['metrics']:
+            if metric in GAIN_PLANE_METRICS:
+                raise KeyError(metric)                  # a plane metric, as 'PSNR_YUV': clips of planes only
+        gain = self._gain_frames(output, gt, lq, par_map, crop_border, convert_to, on_device, frames_of) if self._gain_wanted() else {}
+        for metric in self.test_cfg['metrics']:
+            if metric in GAIN_METRICS:
+                eval_result[metric] = gain[metric]
+                continue
             if metric == 'PSNR' and on_device:
                 # on-device statistic (pnp_psnr_stat_io): 8 bytes per frame (or per block, for Y) cross PCIe instead of the frames
                 from .ops import psnr_frames
@@ -177,14 +194,165 @@ class BasicVSR(nn.Module):
                 eval_result[metric] = self.allowed_metrics[metric](tensor2img(output), tensor2img(gt), crop_border, **kw)
         return eval_result
 
+    # ---- enhancement gain (include/pnpvcve.h, pnp_gain_*): the output against the compressed input, both scored against gt
+    def _gain_names(self):
+        return [m for m in ((self.test_cfg or {}).get('metrics', None) or ()) if m in GAIN_METRICS or m in GAIN_PLANE_METRICS]
+
+    def _gain_wanted(self):
+        return bool(self._gain_names()) or bool((self.test_cfg or {}).get('gain_report', None))
+
+    def _gain_check(self, output, lq):
+        """what the gain refuses, before any GPU work: no lq, a vsr generator, an lq of another frame class, bit depth or size"""
+        from .metrics import gain_block
+        from .ops import _YUV16_CLASSES, is_yuv, yuv_format
+        self.last_gain = None
+        if not self._gain_wanted():
+            return
+        names = self._gain_names() or ['test_cfg.gain_report']
+        if lq is None:
+            raise ValueError(f'{names} compare the output with the compressed input: evaluate() needs lq, the frames the generator was given '
+                             '(forward_test passes them on)')
+        if getattr(self.generator, 'vsr', False):
+            raise ValueError(f'{names} with a vsr generator: lq is a quarter of the output size, so the gain over it is not defined')
+        gain_block(self.test_cfg.get('gain_block', 64))
+        if is_yuv(output) != is_yuv(lq):
+            raise ValueError(f'{names}: lq and the output must be of one frame class, got {type(lq).__name__} and {type(output).__name__}')
+        if is_yuv(output):
+            depth = lambda x: int(x.bit_depth) if isinstance(x, _YUV16_CLASSES) else 8
+            if depth(lq) != depth(output):
+                raise ValueError(f'{names}: lq has {depth(lq)}-bit samples and the output {depth(output)}-bit: the gain compares clips of one bit depth')
+            if yuv_format(lq) != yuv_format(output):
+                raise ValueError(f'{names}: lq is a {yuv_format(lq)} clip and the output a {yuv_format(output)} clip')
+            if tuple(lq.y.shape[-3:]) != tuple(output.y.shape[-3:]):
+                raise ValueError(f'{names}: lq shows {tuple(lq.y.shape[-3:])} and the output {tuple(output.y.shape[-3:])} (frames, rows, columns)')
+            return
+        if output.ndim != 5 or lq.ndim != 5:
+            raise ValueError(f'{names} are a clip\'s: the centre-frame output has no frame of lq to be compared with')
+        size = lambda x: (x.shape[1],) + (tuple(x.shape[2:4]) if x.dtype == torch.uint8 else tuple(x.shape[3:5]))
+        if size(lq) != size(output) or lq.size(0) != output.size(0):
+            raise ValueError(f'{names}: lq shows {size(lq)} and the output {size(output)} (frames, rows, columns)')
+
+    @staticmethod
+    def _gain_results(names, pa, pl, dp, ssim_a=None, ssim_l=None, suffix=''):
+        """the clip's values of the names that end in `suffix` from the frames' values (float64 numpy arrays)"""
+        from .metrics import gain_sd
+        out = {}
+        for m in names:
+            base = m[:-len(suffix)] if suffix and m.endswith(suffix) else (m if not suffix else None)
+            if base == 'PSNR_LQ':
+                out[m] = float(np.mean(pl))
+            elif base == 'dPSNR':
+                out[m] = float(np.mean(dp))
+            elif base == 'PSNR_SD' and not suffix:
+                out[m] = gain_sd(pa)
+            elif base == 'PSNR_SD_LQ' and not suffix:
+                out[m] = gain_sd(pl)
+            elif base == 'SSIM_LQ':
+                out[m] = float(np.mean(ssim_l))
+            elif base == 'dSSIM':
+                out[m] = float(np.mean(ssim_a - ssim_l))
+        return out
+
+    def _gain_frames(self, output, gt, lq, par_map, crop_border, convert_to, on_device, frames_of):
+        """the gain names of an RGB / Y clip (1,t,...): the device's sums (ops.gain_sums_frames, one launch for both halves) or, for host
+        tensors, the numpy path's (metrics.gain_sums); the values are metrics.gain_values' either way.  Leaves self.last_gain."""
+        from . import metrics
+        names = self._gain_names()
+        block = metrics.gain_block(self.test_cfg.get('gain_block', 64))
+        is_y = isinstance(convert_to, str) and convert_to.lower() == 'y'
+        want_ssim = any(m in ('SSIM_LQ', 'dSSIM') for m in names)
+        ssim_a = ssim_l = None
+        if on_device:
+            from .ops import gain_sums_frames, ssim_frames
+            a, l, g = frames_of(output), frames_of(lq), frames_of(gt)
+            par = None if par_map is None else par_map.to(output.device).float().reshape((-1,) + tuple(par_map.shape[-3:]))
+            grid, classes = gain_sums_frames(a, l, g, crop_border, convert_to, block, par)
+            grid, classes = grid.numpy()[:, 0], (None if classes is None else classes.numpy())
+            if want_ssim:       # the existing SSIM entry, called twice
+                ssim_a, ssim_l = (ssim_frames(x, g, crop_border, convert_to).numpy() for x in (a, l))
+            h, w = (a.shape[-3:-1] if a.dtype == torch.uint8 else a.shape[-2:])
+        else:
+            if convert_to is not None and not is_y:
+                raise ValueError('Wrong color model. Supported values are "Y" and None.')
+            t = output.size(1)
+            imgs = [np.stack([tensor2img(x[:, i]) for i in range(t)]) for x in (output, lq, gt)]          # (t,h,w,3) BGR bytes
+            if want_ssim:
+                ssim_a, ssim_l = (np.array([self.allowed_metrics['SSIM'](x[i], imgs[2][i], crop_border, convert_to=convert_to) for i in range(t)])
+                                  for x in imgs[:2])
+            if is_y:
+                imgs = [np.stack([metrics.bgr2y(f.astype(np.float32) / 255.) * 255. for f in x]) for x in imgs]
+            par = None if par_map is None else par_map.detach().cpu().float().numpy().reshape((-1,) + tuple(par_map.shape[-3:]))
+            grid, classes = metrics.gain_sums(imgs[0], imgs[1], imgs[2], crop_border, block, par=par)
+            grid = grid[:, 0]
+            h, w = imgs[0].shape[1:3]
+        ch = 1 if is_y else 3
+        counts = metrics.gain_cell_counts(int(h), int(w), crop_border, block) * ch
+        e = metrics.gain_frame_sums(grid)
+        pa, pl, dp = metrics.gain_values(e[:, 0], e[:, 1], float(counts.sum()), 255.0)
+        self.last_gain = dict(grid=grid, counts=counts, peak=255.0, classes=classes, class_samples=ch, ssim=ssim_a, ssim_lq=ssim_l, block=block)
+        return self._gain_results(names, pa, pl, dp, ssim_a, ssim_l)
+
+    def _gain_yuv(self, output, gt, lq, par_map, crop_border):
+        """the gain names of a clip of planes: ops.gain_sums_yuv on the planes the names ask for (Y always: the report is the Y plane's)"""
+        from . import metrics
+        from .ops import _YUV16_CLASSES, _plane_geometry, gain_sums_yuv, ssim_yuv, yuv_format
+        names = self._gain_names()
+        block = metrics.gain_block(self.test_cfg.get('gain_block', 64))
+        need = lambda s: any(m.endswith(s) for m in names) or 'dPSNR_YUV' in names
+        planes = 'y' + ('u' if need('_U') else '') + ('v' if need('_V') else '')
+        par = None if par_map is None else par_map.to(output.y.device).float().reshape((-1,) + tuple(par_map.shape[-3:]))
+        grid, classes = gain_sums_yuv(output, lq, gt, crop_border, planes, block, par)
+        grid = grid.numpy()
+        h, w = (int(x) for x in output.y.shape[-2:])
+        fmt = yuv_format(output)
+        sx, sy = metrics.GAIN_FACTORS[fmt]
+        peak = float((1 << output.bit_depth) - 1) if isinstance(output, _YUV16_CLASSES) else 255.0
+        scol = {'y': ('SSIM_LQ', 'dSSIM'), 'u': ('SSIM_LQ_U', 'dSSIM_U'), 'v': ('SSIM_LQ_V', 'dSSIM_V')}
+        splanes = ''.join(p for p in planes if any(m in names for m in scol[p]))
+        ssim_a = ssim_l = None
+        if splanes:             # the existing SSIM entries, called twice
+            ssim_a, ssim_l = (ssim_yuv(x, gt, crop_border, splanes).numpy() for x in (output, lq))
+        out, d = {}, {}
+        for k, p in enumerate(planes):
+            counts = metrics.gain_cell_counts(h, w, crop_border, block, *((1, 1) if p == 'y' else (sx, sy)))
+            e = metrics.gain_frame_sums(grid[:, k])
+            pa, pl, d[p] = metrics.gain_values(e[:, 0], e[:, 1], float(counts.sum()), peak)
+            sa, sl = (None, None) if p not in splanes else (ssim_a[:, splanes.index(p)], ssim_l[:, splanes.index(p)])
+            out.update(self._gain_results([m for m in names if m != 'dPSNR_YUV'], pa, pl, d[p], sa, sl, suffix={'y': '', 'u': '_U', 'v': '_V'}[p]))
+            if p == 'y':
+                self.last_gain = dict(grid=grid[:, 0], counts=counts, peak=peak, classes=None if classes is None else classes.numpy(),
+                                      class_samples=1, ssim=sa, ssim_lq=sl, block=block)
+        if 'dPSNR_YUV' in names:
+            out['dPSNR_YUV'] = float(np.mean(metrics.gain_yuv(d['y'], d['u'], d['v'])))
+        return out
+
+    def _gain_report(self, meta, slices, QPs, base_QPs):
+        """test_cfg.gain_report = DIR: one <clip>.json per clip scored (metrics.gain_report of the sums evaluate() left), as save_path
+        gets one file per clip; the QPs are written as the codec's numbers (the tensors carry qp / 255)"""
+        import json
+        import os
+        from .metrics import gain_report
+        folder = (self.test_cfg or {}).get('gain_report', None)
+        if not folder or self.last_gain is None:
+            return
+        qp = lambda x: None if x is None else np.round(x.detach().cpu().double().reshape(-1).numpy() * 255.0, 3)
+        sl = None if slices is None else slices.detach().cpu().reshape(-1).numpy()
+        doc = gain_report(slices=sl, qps=qp(QPs), base_qps=qp(base_QPs), **self.last_gain)
+        clip = meta[0]['key'].split('/')[0] if meta else 'clip'
+        doc['clip'] = clip
+        os.makedirs(folder, exist_ok=True)
+        with open(osp.join(folder, f'{clip}.json'), 'w') as f:
+            json.dump(doc, f, indent=1)
+
     # the packed layouts generator.forward writes: 4:2:0, then 4:2:2 and 4:4:4 (ops.YUV_FORMAT_LAYOUTS)
     YUV_OUT_LAYOUTS = ('nv12', 'i420', 'p010', 'p012', 'yuv420p10le', 'yuv420p12le', 'yuv422p', 'nv16', 'yuv444p', 'nv24', 'yuv422p10le',
                        'yuv422p12le', 'yuv444p10le', 'yuv444p12le', 'p210', 'p212', 'p410', 'p412')
-    YUV_FORMAT_METRICS = ('PSNR', 'SSIM', 'PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V', 'PSNR_YUV')      # what 4:2:2 and 4:4:4 clips are scored by
+    # what 4:2:2 and 4:4:4 clips are scored by (the gain names are served wherever PSNR and SSIM are)
+    YUV_FORMAT_METRICS = ('PSNR', 'SSIM', 'PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V', 'PSNR_YUV') + GAIN_METRICS + GAIN_PLANE_METRICS
     YUV_METRICS = ('PSNR', 'SSIM', 'PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V', 'PSNR_YUV', 'MS-SSIM', 'MS-SSIM_U', 'MS-SSIM_V', 'XPSNR', 'XPSNR_U',
-                   'XPSNR_V', 'PSNR-B', 'PSNR-B_U', 'PSNR-B_V')
+                   'XPSNR_V', 'PSNR-B', 'PSNR-B_U', 'PSNR-B_V') + GAIN_METRICS + GAIN_PLANE_METRICS
 
-    def _evaluate_yuv(self, output, gt):
+    def _evaluate_yuv(self, output, gt, lq=None, par_map=None):
         """evaluate() of two ops.Yuv420Frames (or two ops.Yuv420Frames16) clips: plane PSNR / SSIM on the device, means over the clip's frames.
         Two clips of one 4:2:2 or 4:4:4 class are scored by YUV_FORMAT_METRICS through ops.psnr_yuv / ops.ssim_yuv; MS-SSIM, XPSNR and
         PSNR-B are defined on 4:2:0 clips only and raise a ValueError that names the format."""
@@ -213,6 +381,10 @@ class BasicVSR(nn.Module):
         output, gt = one_clip(output, 'output'), one_clip(gt, 'gt')
         gt = type(gt)(*[p.to(output.y.device) for p in gt[:3]], *gt[3:])
         eval_result = dict()
+        gain = {}
+        if self._gain_wanted():         # (refused before this point without lq or with an lq of another kind: _gain_check)
+            lq = one_clip(lq, 'lq')
+            gain = self._gain_yuv(output, gt, type(lq)(*[p.to(output.y.device) for p in lq[:3]], *lq[3:]), par_map, crop_border)
         psnr = psnr_yuv(output, gt, crop_border) if any(m in ('PSNR', 'PSNR_U', 'PSNR_V', 'PSNR_YUV') for m in metrics) else None      # (t, 3)
         col = {'SSIM': 'y', 'SSIM_U': 'u', 'SSIM_V': 'v'}
         planes = ''.join(dict.fromkeys(col[m] for m in metrics if m in col))
@@ -229,7 +401,9 @@ class BasicVSR(nn.Module):
         # the output is the test clip, whose block edges are measured: (t, len(pb_planes))
         psnrb = psnrb_yuv420(output, gt, crop_border, pb_planes, self.test_cfg.get('psnrb_block', 8)) if pb_planes else None
         for metric in metrics:
-            if metric in col:
+            if metric in gain:
+                eval_result[metric] = gain[metric]
+            elif metric in col:
                 eval_result[metric] = float(ssim[:, planes.index(col[metric])].mean())
             elif metric in pb_col:
                 eval_result[metric] = float(psnrb[:, pb_planes.index(pb_col[metric])].mean())
@@ -305,7 +479,9 @@ class BasicVSR(nn.Module):
                 output = output[:, t // 2]
         if self.test_cfg is not None and self.test_cfg.get('metrics', None):
             assert gt is not None, 'evaluation with metrics must have gt images.'
-            results = dict(eval_result=self.evaluate(output, gt))
+            gain_kw = dict(lq=lq, par_map=par_map) if self._gain_wanted() else {}
+            results = dict(eval_result=self.evaluate(output, gt, **gain_kw))
+            self._gain_report(meta, slices, QPs, base_QPs)
         else:
             lq_planes = lq
             if yuv_in:
@@ -369,7 +545,9 @@ class BasicVSR(nn.Module):
         output = ops.yuv_views(buf, H, W, layout)
         if self.test_cfg is not None and self.test_cfg.get('metrics', None):
             assert gt is not None, 'evaluation with metrics must have gt images.'
-            results = dict(eval_result=self.evaluate(output, gt))
+            gain_kw = dict(lq=lq, par_map=par_map) if self._gain_wanted() else {}
+            results = dict(eval_result=self.evaluate(output, gt, **gain_kw))
+            self._gain_report(meta, slices, QPs, base_QPs)
         else:
             from_planes = ops._frames_from_yuv
             results = dict(lq=from_planes(lq, yuv_standard, chroma=chroma).cpu(), output=buf.cpu())

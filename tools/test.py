@@ -80,6 +80,13 @@ def parse_args():
                         'of the outputs over the 8 flips / transposes of every clip, with spatial-temporal also over their 8 time '
                         'reversals, the motion vectors and partition maps transformed with the frames; 8 or 16 generator runs per '
                         'clip, clips run one at a time; not with --yuv-frames.  Default off')
+    p.add_argument('--gain-report', default=None, type=str, metavar='DIR',
+                   help='sets test_cfg.gain_report: every rank writes DIR/<clip>.json for each clip it scored -- per frame the slice type, QP, '
+                        'PSNR of the output and of the compressed input and their difference dPSNR (SSIM likewise when dSSIM or SSIM_LQ is '
+                        'listed), the same grouped by slice type and by QP, the table of partition classes and the grid of '
+                        'test_cfg.gain_block (64) cells (include/pnpvcve.h, "Enhancement gain").  The gain names PSNR_LQ, SSIM_LQ, dPSNR, '
+                        'dSSIM, PSNR_SD, PSNR_SD_LQ (and on --yuv-frames their _U / _V forms and dPSNR_YUV) may be listed in '
+                        'test_cfg.metrics with or without it')
     p.add_argument('--local_rank', type=int, default=0)
     a = p.parse_args()
     if 'LOCAL_RANK' not in os.environ:
@@ -119,6 +126,8 @@ def main():
     if args.ensemble is not None:
         cfg.merge_from_dict({'model.ensemble': dict(_delete_=True, type='SpatialTemporalEnsemble',
                                                     is_temporal_ensemble=args.ensemble == 'spatial-temporal')})
+    if args.gain_report is not None:
+        cfg.merge_from_dict({'test_cfg.gain_report': args.gain_report})
     dataset = build_dataset(cfg.data.test)
     model = build_model(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)
     if args.checkpoint.lower() != 'none':
@@ -158,6 +167,8 @@ def main():
             line += '/{:.4f}'.format(float(stats.get('XPSNR', float('nan'))))
         if 'PSNR-B' in (cfg.test_cfg.get('metrics', None) or ()):       # and a PSNR-B field only when the config lists it
             line += '/{:.4f}'.format(float(stats.get('PSNR-B', float('nan'))))
+        if 'dPSNR' in (cfg.test_cfg.get('metrics', None) or ()):        # and a dPSNR field only when the config lists it
+            line += '/{:.4f}'.format(float(stats.get('dPSNR', float('nan'))))
         print(line)
         fps = [o['frames_per_s'] for o in outputs]
         import torch.distributed as dist
