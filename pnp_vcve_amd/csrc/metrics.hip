@@ -6,8 +6,7 @@
 // Here: one pass over the two frames in HBM, rounding exactly as numpy does (half to even), the
 // squared differences summed as 64-bit INTEGERS (exact, order-independent, deterministic), so the
 // host only sees 8 bytes per frame instead of 2 x 3*H*W*4.  HBM-bound: 8 B per element.
-#include "metric_src.h"
-#include <cmath>
+#include "ssim_tile.h"
 
 namespace {
 
@@ -46,77 +45,57 @@ __global__ __launch_bounds__(256) void psnr_sse_kernel(const float* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
-// SSIM (mmedit/core/evaluation/metrics.py:266-355): per channel, 11x11 Gaussian (sigma 1.5) 'valid' window
-// over the uint8-rounded frames, in fp64 like the reference.  The reference filters with cv2.filter2D
-// (absent here -> parity unpinned; checked against the numpy restatement in pnp_vcve_amd/metrics.py).
-// One block = a 16x32 tile of the valid map of one (frame, channel): the two u8 tiles (26x42) go to LDS,
-// a horizontal pass leaves the five windowed moments of 26x32 positions in LDS, the vertical pass finishes
-// them and forms the SSIM ratio; each block writes ONE partial sum (deterministic; the host adds them).
+// SSIM (mmedit/core/evaluation/metrics.py:266-355): per channel, 11x11 Gaussian (sigma 1.5) 'valid' window over the uint8-rounded
+// frames, in fp64 like the reference.  The reference filters with cv2.filter2D (absent here -> parity unpinned; checked against the
+// numpy restatement in pnp_vcve_amd/metrics.py).  One block = a 16x32 tile of the valid map of one plane; the tile body -- LDS tiles,
+// both passes, the block's sum -- is ssim_tile.h's, which every SSIM and MS-SSIM kernel runs, so a byte frame, a luma plane or a
+// decoder's plane gives the partials of its fp32 planes bit for bit.  Each block writes ONE partial sum.
 struct SsimArgs {
     double g[11];
-    const float* a;
-    const float* b;
-    double* partial;       // [frames*C][blocks_per_plane]
+    FrameSrc a, b;         // ssim_kernel: fp32 planes at a.p / b.p
+    double* partial;       // [planes][blocks_per_plane]
     int H, W, crop, oh, ow, tiles_x, blocks_per_plane;
 };
 
+// what follows a kernel's tile fill: both passes, SSIM's closing expression at the 8-bit peak, the block's partial
+__device__ __forceinline__ void ssim_tile_partial(const SsimArgs& s, const float* ta, const float* tb, double (*hm)[SSIM_HM], double (*red)[1],
+                                                  int ty0, int tx0) {
+    __syncthreads();
+    ssim_rows_pass(ta, tb, hm, s.g);
+    __syncthreads();
+    const SsimConsts k(255.0);
+    double acc[1] = {0};
+    ssim_cols_pass(hm, s.g, ty0, tx0, s.oh, s.ow,
+                   [&](double mu1, double mu2, double sg1, double sg2, double sg12) { acc[0] += ssim_index(k, mu1, mu2, sg1, sg2, sg12); });
+    ssim_block_sums(acc, red, s.partial + (long)blockIdx.y * s.blocks_per_plane + blockIdx.x);
+}
+
+// (frames, C, H, W) fp32 planes, rounded by to_u8: a plane per y of the grid
 __global__ __launch_bounds__(256) void ssim_kernel(const SsimArgs s) {
-    __shared__ float ta[26 * 42], tb[26 * 42];
-    __shared__ double hm[5][26 * 32];
-    __shared__ double red[4];
-    const int plane = blockIdx.y, blk = blockIdx.x, t = threadIdx.x;
-    const int ty0 = (blk / s.tiles_x) * 16, tx0 = (blk % s.tiles_x) * 32;        // in valid-map coordinates
-    const float* pa = s.a + (long)plane * s.H * s.W;
-    const float* pb = s.b + (long)plane * s.H * s.W;
-    for (int i = t; i < 26 * 42; i += 256) {
-        const int r = i / 42, c = i - r * 42;
-        const int y = s.crop + ty0 + r, x = s.crop + tx0 + c;
-        float va = 0.f, vb = 0.f;
-        if (y < s.H - s.crop && x < s.W - s.crop) {
-            va = (float)to_u8(pa[(long)y * s.W + x]);
-            vb = (float)to_u8(pb[(long)y * s.W + x]);
-        }
-        ta[i] = va;
-        tb[i] = vb;
-    }
-    __syncthreads();
-    for (int i = t; i < 26 * 32; i += 256) {
-        const int r = i >> 5, c = i & 31;
-        double m1 = 0, m2 = 0, s11 = 0, s22 = 0, s12 = 0;
-#pragma unroll
-        for (int k = 0; k < 11; ++k) {
-            const double x = ta[r * 42 + c + k], y = tb[r * 42 + c + k], gk = s.g[k];
-            m1 += gk * x;
-            m2 += gk * y;
-            s11 += gk * x * x;
-            s22 += gk * y * y;
-            s12 += gk * x * y;
-        }
-        hm[0][i] = m1;
-        hm[1][i] = m2;
-        hm[2][i] = s11;
-        hm[3][i] = s22;
-        hm[4][i] = s12;
-    }
-    __syncthreads();
-    const double C1 = (0.01 * 255) * (0.01 * 255), C2 = (0.03 * 255) * (0.03 * 255);
-    double acc = 0;
-    for (int i = t; i < 16 * 32; i += 256) {
-        const int r = i >> 5, c = i & 31;
-        if (ty0 + r >= s.oh || tx0 + c >= s.ow) continue;
-        double v[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < 11; ++k)
-#pragma unroll
-            for (int q = 0; q < 5; ++q) v[q] += s.g[k] * hm[q][(r + k) * 32 + c];
-        const double mu1 = v[0], mu2 = v[1];
-        const double sg1 = v[2] - mu1 * mu1, sg2 = v[3] - mu2 * mu2, sg12 = v[4] - mu1 * mu2;
-        acc += ((2 * mu1 * mu2 + C1) * (2 * sg12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (sg1 + sg2 + C2));
-    }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((t & 63) == 0) red[t >> 6] = acc;
-    __syncthreads();
-    if (t == 0) s.partial[(long)plane * s.blocks_per_plane + blk] = red[0] + red[1] + red[2] + red[3];
+    __shared__ float ta[SSIM_TILE], tb[SSIM_TILE];
+    __shared__ double hm[5][SSIM_HM];
+    __shared__ double red[4][1];
+    const int plane = blockIdx.y, blk = blockIdx.x;
+    const int ty0 = (blk / s.tiles_x) * SSIM_OUT_R, tx0 = (blk % s.tiles_x) * SSIM_OUT_C;        // in valid-map coordinates
+    ssim_fill_f32(ta, tb, static_cast<const float*>(s.a.p) + (long)plane * s.H * s.W, static_cast<const float*>(s.b.p) + (long)plane * s.H * s.W,
+                  s.H, s.W, s.crop, ty0, tx0);
+    ssim_tile_partial(s, ta, tb, hm, red, ty0, tx0);
+}
+
+SsimArgs ssim_args(const void* a, int a_format, const void* b, int b_format, double* partials, int frames, int h, int w, int crop, int nb) {
+    SsimArgs s;
+    ssim_window(s.g);
+    s.a = frame_src(a, a_format, frames, h, w);
+    s.b = frame_src(b, b_format, frames, h, w);
+    s.partial = partials;
+    s.H = h;
+    s.W = w;
+    s.crop = crop;
+    s.oh = h - 2 * crop - 10;
+    s.ow = w - 2 * crop - 10;
+    s.tiles_x = (s.ow + 31) / 32;
+    s.blocks_per_plane = nb;
+    return s;
 }
 
 }  // namespace
@@ -131,23 +110,7 @@ extern "C" int pnp_ssim_partials_f32(const float* a, const float* b, double* par
                                      int crop_border, void* stream) {
     const int nb = pnp_ssim_blocks(h, w, crop_border);
     if (frames < 1 || c < 1 || nb < 1 || crop_border < 0) return PNP_ERR_BAD_ARG;
-    SsimArgs s;
-    double sum = 0;
-    for (int i = 0; i < 11; ++i) {                       // cv2.getGaussianKernel(11, 1.5)
-        s.g[i] = exp(-((i - 5.0) * (i - 5.0)) / (2 * 1.5 * 1.5));
-        sum += s.g[i];
-    }
-    for (int i = 0; i < 11; ++i) s.g[i] /= sum;
-    s.a = a;
-    s.b = b;
-    s.partial = partials;
-    s.H = h;
-    s.W = w;
-    s.crop = crop_border;
-    s.oh = h - 2 * crop_border - 10;
-    s.ow = w - 2 * crop_border - 10;
-    s.tiles_x = (s.ow + 31) / 32;
-    s.blocks_per_plane = nb;
+    const SsimArgs s = ssim_args(a, PNP_FRAMES_F32_NCHW, b, PNP_FRAMES_F32_NCHW, partials, frames, h, w, crop_border, nb);
     hipLaunchKernelGGL(ssim_kernel, dim3(nb, frames * c), dim3(256), 0, (hipStream_t)stream, s);
     return (int)hipGetLastError();
 }
@@ -324,87 +287,18 @@ __global__ __launch_bounds__(256) void luma_kernel(const FrameSrc src, float* __
 }
 
 // ssim_kernel with a loader in front: the value of (plane, y, x) comes from either format and, with Y, through the luma step (one
-// plane per frame, the window runs over the fp32 Y).  Tiling, LDS layout and both passes are ssim_kernel's, statement for statement,
-// so a byte frame gives the partials of its fp32 planes bit for bit.
-struct SsimIoArgs {
-    double g[11];
-    FrameSrc a, b;
-    double* partial;       // [planes][blocks_per_plane]
-    int H, W, crop, oh, ow, tiles_x, blocks_per_plane;
-};
-
+// plane per frame, the window runs over the fp32 Y).
 template <bool Y>
-__device__ __forceinline__ float ssim_value(const FrameSrc& s, long frame, int ch, long hw, long pix, const double* lt) {
-    if (s.fmt == PNP_FRAMES_U8_HWC) {
-        const unsigned char* q = static_cast<const unsigned char*>(s.p) + (frame * hw + pix) * 3;
-        if (!Y) return (float)q[ch];
-        return luma_of(lt, (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16));
-    }
-    const float* f = static_cast<const float*>(s.p) + frame * 3 * hw + pix;
-    if (!Y) return (float)to_u8(f[ch * hw]);
-    return luma_of(lt, px_of_f32(f[0], f[hw], f[2 * hw]));
-}
-
-template <bool Y>
-__global__ __launch_bounds__(256) void ssim_io_kernel(const SsimIoArgs s) {
-    __shared__ float ta[26 * 42], tb[26 * 42];
-    __shared__ double hm[5][26 * 32];
-    __shared__ double red[4];
+__global__ __launch_bounds__(256) void ssim_io_kernel(const SsimArgs s) {
+    __shared__ float ta[SSIM_TILE], tb[SSIM_TILE];
+    __shared__ double hm[5][SSIM_HM];
+    __shared__ double red[4][1];
     __shared__ double lt[Y ? 768 : 1];
     if (Y) stage_luma_table(lt);
-    const int plane = blockIdx.y, blk = blockIdx.x, t = threadIdx.x;
-    const int ty0 = (blk / s.tiles_x) * 16, tx0 = (blk % s.tiles_x) * 32;        // in valid-map coordinates
-    const long frame = Y ? plane : plane / 3, hw = (long)s.H * s.W;
-    const int ch = Y ? 0 : plane % 3;
-    for (int i = t; i < 26 * 42; i += 256) {
-        const int r = i / 42, c = i - r * 42;
-        const int y = s.crop + ty0 + r, x = s.crop + tx0 + c;
-        float va = 0.f, vb = 0.f;
-        if (y < s.H - s.crop && x < s.W - s.crop) {
-            va = ssim_value<Y>(s.a, frame, ch, hw, (long)y * s.W + x, lt);
-            vb = ssim_value<Y>(s.b, frame, ch, hw, (long)y * s.W + x, lt);
-        }
-        ta[i] = va;
-        tb[i] = vb;
-    }
-    __syncthreads();
-    for (int i = t; i < 26 * 32; i += 256) {
-        const int r = i >> 5, c = i & 31;
-        double m1 = 0, m2 = 0, s11 = 0, s22 = 0, s12 = 0;
-#pragma unroll
-        for (int k = 0; k < 11; ++k) {
-            const double x = ta[r * 42 + c + k], y = tb[r * 42 + c + k], gk = s.g[k];
-            m1 += gk * x;
-            m2 += gk * y;
-            s11 += gk * x * x;
-            s22 += gk * y * y;
-            s12 += gk * x * y;
-        }
-        hm[0][i] = m1;
-        hm[1][i] = m2;
-        hm[2][i] = s11;
-        hm[3][i] = s22;
-        hm[4][i] = s12;
-    }
-    __syncthreads();
-    const double C1 = (0.01 * 255) * (0.01 * 255), C2 = (0.03 * 255) * (0.03 * 255);
-    double acc = 0;
-    for (int i = t; i < 16 * 32; i += 256) {
-        const int r = i >> 5, c = i & 31;
-        if (ty0 + r >= s.oh || tx0 + c >= s.ow) continue;
-        double v[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < 11; ++k)
-#pragma unroll
-            for (int q = 0; q < 5; ++q) v[q] += s.g[k] * hm[q][(r + k) * 32 + c];
-        const double mu1 = v[0], mu2 = v[1];
-        const double sg1 = v[2] - mu1 * mu1, sg2 = v[3] - mu2 * mu2, sg12 = v[4] - mu1 * mu2;
-        acc += ((2 * mu1 * mu2 + C1) * (2 * sg12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (sg1 + sg2 + C2));
-    }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((t & 63) == 0) red[t >> 6] = acc;
-    __syncthreads();
-    if (t == 0) s.partial[(long)plane * s.blocks_per_plane + blk] = red[0] + red[1] + red[2] + red[3];
+    const int plane = blockIdx.y, blk = blockIdx.x;
+    const int ty0 = (blk / s.tiles_x) * SSIM_OUT_R, tx0 = (blk % s.tiles_x) * SSIM_OUT_C;        // in valid-map coordinates
+    ssim_fill_frames<Y>(ta, tb, s.a, s.b, Y ? plane : plane / 3, Y ? 0 : plane % 3, s.H, s.W, s.crop, ty0, tx0, lt);
+    ssim_tile_partial(s, ta, tb, hm, red, ty0, tx0);
 }
 
 // blocks per frame of the pixel-group kernels: about four groups (16 pixels) a thread, so that staging the table is paid seldom
@@ -448,23 +342,7 @@ extern "C" int pnp_ssim_partials_io(const void* a, int a_format, const void* b, 
     if (nb < 1) return PNP_ERR_BAD_ARG;
     if (a_format == PNP_FRAMES_F32_NCHW && b_format == PNP_FRAMES_F32_NCHW && color == PNP_COLOR_NONE)
         return pnp_ssim_partials_f32(static_cast<const float*>(a), static_cast<const float*>(b), partials, frames, c, h, w, crop_border, stream);
-    SsimIoArgs s;
-    double sum = 0;
-    for (int i = 0; i < 11; ++i) {                       // cv2.getGaussianKernel(11, 1.5)
-        s.g[i] = exp(-((i - 5.0) * (i - 5.0)) / (2 * 1.5 * 1.5));
-        sum += s.g[i];
-    }
-    for (int i = 0; i < 11; ++i) s.g[i] /= sum;
-    s.a = frame_src(a, a_format, frames, h, w);
-    s.b = frame_src(b, b_format, frames, h, w);
-    s.partial = partials;
-    s.H = h;
-    s.W = w;
-    s.crop = crop_border;
-    s.oh = h - 2 * crop_border - 10;
-    s.ow = w - 2 * crop_border - 10;
-    s.tiles_x = (s.ow + 31) / 32;
-    s.blocks_per_plane = nb;
+    const SsimArgs s = ssim_args(a, a_format, b, b_format, partials, frames, h, w, crop_border, nb);
     if (color == PNP_COLOR_Y)
         hipLaunchKernelGGL((ssim_io_kernel<true>), dim3(nb, frames), dim3(256), 0, (hipStream_t)stream, s);
     else

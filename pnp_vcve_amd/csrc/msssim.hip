@@ -6,14 +6,14 @@
 // Two kernels.  msssim_down_kernel makes level s + 1 of BOTH clips from level s: at s = 0 it reads through the boundary's loaders
 // (metric_src.h, plane_load.h), from s = 1 on it reads the fp32 pyramid; a thread makes two neighbouring output samples of one row
 // from a group of four input samples on two rows, whole samples only, so nothing is divided or accumulated across threads.
-// msssim_level_kernel is ssim_kernel (metrics.hip) -- a 16 x 32 tile of the valid map per block, two 26 x 42 input tiles in LDS, a
-// horizontal pass that leaves five windowed moments of 26 x 32 positions in LDS, a vertical pass -- whose closing pass forms
-// cs = (2 s_ab + C2) / (s_a^2 + s_b^2 + C2) and l * cs and writes the block's TWO partial sums.  ONE launch covers every level of
+// msssim_level_kernel runs the SSIM tile body of ssim_tile.h, as ssim_kernel (metrics.hip) does -- a 16 x 32 tile of the valid map per
+// block, two 26 x 42 input tiles in LDS, a horizontal pass that leaves five windowed moments of 26 x 32 positions in LDS, a vertical
+// pass -- and closes it with cs = (2 s_ab + C2) / (s_a^2 + s_b^2 + C2) and l * cs, the block's TWO partial sums.  ONE launch covers every level of
 // every plane: a plane's blocks are the concatenation of its levels' blocks (msssim_plan.h), the planes of a mask follow each
 // other along the grid's x, so the 1 x 1 valid map of level 4 costs one block and no empty tile is launched.  Four launches of
 // the first kernel and one of the second per call; the host adds a level's partials in index order (deterministic).
 // The library owns no device memory: the pyramid (levels 1..4 of both clips, fp32) lives in the caller's workspace.
-#include "metric_src.h"
+#include "ssim_tile.h"
 #include "msssim_plan.h"
 
 namespace {
@@ -47,21 +47,6 @@ struct MsArgs {
     double* partial;        // [class][unit][level][block][2]
     double L;               // the peak
 };
-
-// sample `pix` (= y * W + x) of unit `unit` of a clip of frames: the byte SSIM reads, or (Y) the fp32 luma of the pixel
-template <bool Y>
-__device__ __forceinline__ float frame_value(const FrameSrc& s, long unit, long hw, long pix, const double* lt) {
-    if (s.fmt == PNP_FRAMES_U8_HWC) {                                              // three channels
-        const long frame = Y ? unit : unit / 3;
-        const unsigned char* q = static_cast<const unsigned char*>(s.p) + (frame * hw + pix) * 3;
-        if (!Y) return (float)q[unit - frame * 3];
-        return luma_of(lt, (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16));
-    }
-    const float* f = static_cast<const float*>(s.p);
-    if (!Y) return (float)to_u8(f[unit * hw + pix]);
-    f += unit * 3 * hw + pix;
-    return luma_of(lt, px_of_f32(f[0], f[hw], f[2 * hw]));
-}
 
 // v[i][j]: sample crop + 4 gx + j (j < npix = 2 | 4) of row crop + 2 r + i of the unit's level-0 plane
 template <int KIND>
@@ -155,13 +140,13 @@ __global__ __launch_bounds__(256) void msssim_down_kernel(const MsArgs s, const 
     }
 }
 
-// ssim_kernel's scheme on one 16 x 32 tile of the valid map of one level of one unit; the block's place along x names the class, the
-// level and the tile.  Level 0 is filled through the loaders of the instance's kind, levels 1..4 from the fp32 pyramid; both passes
-// are one body for all of them.
+// The SSIM tile body (ssim_tile.h) on one 16 x 32 tile of the valid map of one level of one unit; the block's place along x names the
+// class, the level and the tile.  Level 0 is filled through the loaders of the instance's kind, levels 1..4 from the fp32 pyramid;
+// the closing expression is MS-SSIM's own: cs and l by a division each, TWO sums a block.
 template <int KIND>
 __global__ __launch_bounds__(256) void msssim_level_kernel(const MsArgs s) {
-    __shared__ float ta[26 * 42], tb[26 * 42];
-    __shared__ double hm[5][26 * 32];
+    __shared__ float ta[SSIM_TILE], tb[SSIM_TILE];
+    __shared__ double hm[5][SSIM_HM];
     __shared__ double red[4][2];
     __shared__ double lt[KIND == K_Y ? 768 : 1];
     if (KIND == K_Y) stage_luma_table(lt);
@@ -169,7 +154,7 @@ __global__ __launch_bounds__(256) void msssim_level_kernel(const MsArgs s) {
     if (s.nclass > 1 && (int)blockIdx.x >= s.cl[1].blk0) ci = 1;
     if (s.nclass > 2 && (int)blockIdx.x >= s.cl[2].blk0) ci = 2;
     const MsClass& c = s.cl[ci];                                        // (read where it lies, in the kernel's argument segment)
-    const int blk = blockIdx.x - c.blk0, t = threadIdx.x;
+    const int blk = blockIdx.x - c.blk0;
     const long unit = blockIdx.y;
     int level = 0;
 #pragma unroll
@@ -177,103 +162,29 @@ __global__ __launch_bounds__(256) void msssim_level_kernel(const MsArgs s) {
         if (blk >= c.plan.lv[k].blk0) level = k;
     const PnpMsLevel& lv = c.plan.lv[level];
     const int b = blk - lv.blk0;
-    const int ty0 = (b / lv.tiles_x) * 16, tx0 = (b % lv.tiles_x) * 32;            // in valid-map coordinates
+    const int ty0 = (b / lv.tiles_x) * SSIM_OUT_R, tx0 = (b % lv.tiles_x) * SSIM_OUT_C;            // in valid-map coordinates
     if (level > 0) {
-        const float* pa = c.wa + unit * s.slot + lv.ws_off;
-        const float* pb = c.wb + unit * s.slot + lv.ws_off;
-        for (int i = t; i < 26 * 42; i += 256) {
-            const int r = i / 42, cx = i - r * 42;
-            const int y = ty0 + r, x = tx0 + cx;
-            const bool in = y < lv.rows && x < lv.cols;                             // absent samples are 0 in both tiles
-            ta[i] = in ? pa[(long)y * lv.cols + x] : 0.f;
-            tb[i] = in ? pb[(long)y * lv.cols + x] : 0.f;
-        }
+        ssim_fill_level(ta, tb, c.wa + unit * s.slot + lv.ws_off, c.wb + unit * s.slot + lv.ws_off, lv.rows, lv.cols, ty0, tx0);
     } else if (KIND == K_P8) {
-        for (int i = t; i < 26 * 11; i += 256) {                                   // a row of the tile = 10 groups of four and one of two
-            const int r = i / 11, gc = i - r * 11;
-            const int y = c.crop + ty0 + r, x = c.crop + tx0 + 4 * gc;
-            int npix = 42 - 4 * gc < 4 ? 42 - 4 * gc : 4;
-            if (c.W - c.crop - x < npix) npix = c.W - c.crop - x;
-            unsigned wa[2] = {0, 0}, wb[2] = {0, 0};
-            if (y < c.H - c.crop && npix > 0) {
-                pnp_plane_load4(c.a.p8, unit, y, x, npix, wa);
-                pnp_plane_load4(c.b.p8, unit, y, x, npix, wb);
-            }
-            const unsigned va = c.a.sel ? wa[1] : wa[0], vb = c.b.sel ? wb[1] : wb[0];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (4 * gc + j < 42) {
-                    ta[r * 42 + 4 * gc + j] = (float)((va >> (8 * j)) & 255u);
-                    tb[r * 42 + 4 * gc + j] = (float)((vb >> (8 * j)) & 255u);
-                }
-            }
-        }
-    } else {
-        const long hw = (long)c.H * c.W;
-        for (int i = t; i < 26 * 42; i += 256) {
-            const int r = i / 42, cx = i - r * 42;
-            const int y = c.crop + ty0 + r, x = c.crop + tx0 + cx;
-            float va = 0.f, vb = 0.f;
-            if (y < c.H - c.crop && x < c.W - c.crop) {
-                if (KIND == K_P16) {
-                    va = (float)load16(c.a.p16, unit, y, x);
-                    vb = (float)load16(c.b.p16, unit, y, x);
-                } else {
-                    va = frame_value<KIND == K_Y>(c.a.fs, unit, hw, (long)y * c.W + x, lt);
-                    vb = frame_value<KIND == K_Y>(c.b.fs, unit, hw, (long)y * c.W + x, lt);
-                }
-            }
-            ta[i] = va;
-            tb[i] = vb;
-        }
+        ssim_fill_plane8(ta, tb, c.a.p8, c.b.p8, c.a.sel, c.b.sel, unit, c.H, c.W, c.crop, c.crop, ty0, tx0);
+    } else if (KIND == K_P16) {
+        ssim_fill_plane16(ta, tb, c.a.p16, c.b.p16, unit, c.H, c.W, c.crop, c.crop, ty0, tx0);
+    } else {                                                            // a unit of K_RGB is frame * 3 + channel
+        const long frame = KIND == K_Y ? unit : unit / 3;
+        ssim_fill_frames<KIND == K_Y>(ta, tb, c.a.fs, c.b.fs, frame, (int)(unit - frame * 3), c.H, c.W, c.crop, ty0, tx0, lt);
     }
     __syncthreads();
-    for (int i = t; i < 26 * 32; i += 256) {
-        const int r = i >> 5, cx = i & 31;
-        double m1 = 0, m2 = 0, s11 = 0, s22 = 0, s12 = 0;
-#pragma unroll
-        for (int k = 0; k < 11; ++k) {
-            const double x = ta[r * 42 + cx + k], y = tb[r * 42 + cx + k], gk = s.g[k];
-            m1 += gk * x;
-            m2 += gk * y;
-            s11 += gk * x * x;
-            s22 += gk * y * y;
-            s12 += gk * x * y;
-        }
-        hm[0][i] = m1;
-        hm[1][i] = m2;
-        hm[2][i] = s11;
-        hm[3][i] = s22;
-        hm[4][i] = s12;
-    }
+    ssim_rows_pass(ta, tb, hm, s.g);
     __syncthreads();
-    const double C1 = (0.01 * s.L) * (0.01 * s.L), C2 = (0.03 * s.L) * (0.03 * s.L);
-    double acc_cs = 0, acc_s = 0;
-    for (int i = t; i < 16 * 32; i += 256) {
-        const int r = i >> 5, cx = i & 31;
-        if (ty0 + r >= lv.oh || tx0 + cx >= lv.ow) continue;
-        double v[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < 11; ++k)
-#pragma unroll
-            for (int q = 0; q < 5; ++q) v[q] += s.g[k] * hm[q][(r + k) * 32 + cx];
-        const double mu1 = v[0], mu2 = v[1];
-        const double sg1 = v[2] - mu1 * mu1, sg2 = v[3] - mu2 * mu2, sg12 = v[4] - mu1 * mu2;
-        const double cs = (2 * sg12 + C2) / (sg1 + sg2 + C2);
-        const double l = (2 * mu1 * mu2 + C1) / (mu1 * mu1 + mu2 * mu2 + C1);
-        acc_cs += cs;
-        acc_s += l * cs;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        acc_cs += __shfl_down(acc_cs, off, 64);
-        acc_s += __shfl_down(acc_s, off, 64);
-    }
-    if ((t & 63) == 0) {
-        red[t >> 6][0] = acc_cs;
-        red[t >> 6][1] = acc_s;
-    }
-    __syncthreads();
-    if (t < 2) s.partial[c.part0 + (unit * c.plan.blocks + blk) * 2 + t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
+    const SsimConsts k(s.L);
+    double acc[2] = {0, 0};                                             // cs, l * cs
+    ssim_cols_pass(hm, s.g, ty0, tx0, lv.oh, lv.ow, [&](double mu1, double mu2, double sg1, double sg2, double sg12) {
+        const double cs = (2 * sg12 + k.C2) / (sg1 + sg2 + k.C2);
+        const double l = (2 * mu1 * mu2 + k.C1) / (mu1 * mu1 + mu2 * mu2 + k.C1);
+        acc[0] += cs;
+        acc[1] += l * cs;
+    });
+    ssim_block_sums(acc, red, s.partial + c.part0 + (unit * c.plan.blocks + blk) * 2);
 }
 
 // the five launches of one call: level 1 from the source, levels 2..4 from the pyramid, then every level's statistics

@@ -3,7 +3,7 @@
 // metrics.hip read from the decoder's planes where they lie -- NV12 / NV21 / I420, any address and pitch, each of the two clips
 // described on its own -- 1.5 B per pixel and clip, no RGB and no fp32 copy in between.  What a codec-enhancement result is scored by:
 // Y, Cb and Cr on their own (and the 6:1:1 mean the host forms).  plane_load.h fetches; the statistics are metrics.hip's.
-#include "metric_src.h"
+#include "ssim_tile.h"
 
 namespace {
 
@@ -86,9 +86,9 @@ __global__ __launch_bounds__(256) void psnr_yuv420_kernel(const PsnrYuvArgs s) {
     }
 }
 
-// ssim_kernel (metrics.hip) with the plane loader in front: tiling, LDS layout and both passes are ssim_kernel's, statement for
-// statement, so a plane gives the partials of its (frames,1,rows,cols) fp32 plane byte / 255.0f bit for bit (to_u8 of that value is
-// the byte).  One launch serves every plane of the mask: blocks [blk0, blk0 + blocks) of the grid's x are plane k's.
+// ssim_kernel (metrics.hip) with the plane loader in front: the tile body is ssim_tile.h's, as it is ssim_kernel's, so a plane gives the
+// partials of its (frames,1,rows,cols) fp32 plane byte / 255.0f bit for bit (to_u8 of that value is the byte).  One launch serves
+// every plane of the mask: blocks [blk0, blk0 + blocks) of the grid's x are plane k's.
 struct SsimPlane {
     PnpPlaneSrc a, b;
     Plane16 a16, b16;       // the 16-bit sample path's planes (ssim_yuv420_kernel<true>)
@@ -105,85 +105,28 @@ struct SsimYuvArgs {
 };
 
 // S16: the samples are the values of 16-bit words (Plane16), fetched one by one; otherwise bytes through the plane loader.  Only the
-// tile fill and the peak differ: both passes are one body.
+// tile fill and the peak differ.
 template <bool S16>
 __global__ __launch_bounds__(256) void ssim_yuv420_kernel(const SsimYuvArgs s) {
-    __shared__ float ta[26 * 42], tb[26 * 42];
-    __shared__ double hm[5][26 * 32];
-    __shared__ double red[4];
+    __shared__ float ta[SSIM_TILE], tb[SSIM_TILE];
+    __shared__ double hm[5][SSIM_HM];
+    __shared__ double red[4][1];
     SsimPlane p = s.pl[0];
     if (s.nplanes > 1 && (int)blockIdx.x >= s.pl[1].blk0) p = s.pl[1];
     if (s.nplanes > 2 && (int)blockIdx.x >= s.pl[2].blk0) p = s.pl[2];
-    const int blk = blockIdx.x - p.blk0, t = threadIdx.x;
+    const int blk = blockIdx.x - p.blk0;
     const long frame = blockIdx.y;
-    const int ty0 = (blk / p.tiles_x) * 16, tx0 = (blk % p.tiles_x) * 32;        // in valid-map coordinates
-    if (S16) {
-        for (int i = t; i < 26 * 42; i += 256) {
-            const int r = i / 42, cx = i - r * 42;
-            const int y = p.cropy + ty0 + r, x = p.cropx + tx0 + cx;
-            const bool in = y < p.H - p.cropy && x < p.W - p.cropx;       // absent samples are 0 in both tiles
-            ta[i] = in ? (float)load16(p.a16, frame, y, x) : 0.f;
-            tb[i] = in ? (float)load16(p.b16, frame, y, x) : 0.f;
-        }
-    }
-    for (int i = t; !S16 && i < 26 * 11; i += 256) {                              // a row of the tile = 10 groups of four and one of two
-        const int r = i / 11, gc = i - r * 11;
-        const int y = p.cropy + ty0 + r, x = p.cropx + tx0 + 4 * gc;
-        int npix = 42 - 4 * gc < 4 ? 42 - 4 * gc : 4;
-        if (p.W - p.cropx - x < npix) npix = p.W - p.cropx - x;
-        unsigned wa[2] = {0, 0}, wb[2] = {0, 0};
-        if (y < p.H - p.cropy && npix > 0) {
-            pnp_plane_load4(p.a, frame, y, x, npix, wa);
-            pnp_plane_load4(p.b, frame, y, x, npix, wb);
-        }
-        const unsigned va = p.a_sel ? wa[1] : wa[0], vb = p.b_sel ? wb[1] : wb[0];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (4 * gc + j < 42) {
-                ta[r * 42 + 4 * gc + j] = (float)((va >> (8 * j)) & 255u);
-                tb[r * 42 + 4 * gc + j] = (float)((vb >> (8 * j)) & 255u);
-            }
-        }
-    }
+    const int ty0 = (blk / p.tiles_x) * SSIM_OUT_R, tx0 = (blk % p.tiles_x) * SSIM_OUT_C;        // in valid-map coordinates
+    if (S16) ssim_fill_plane16(ta, tb, p.a16, p.b16, frame, p.H, p.W, p.cropy, p.cropx, ty0, tx0);
+    else ssim_fill_plane8(ta, tb, p.a, p.b, p.a_sel, p.b_sel, frame, p.H, p.W, p.cropy, p.cropx, ty0, tx0);
     __syncthreads();
-    for (int i = t; i < 26 * 32; i += 256) {
-        const int r = i >> 5, c = i & 31;
-        double m1 = 0, m2 = 0, s11 = 0, s22 = 0, s12 = 0;
-#pragma unroll
-        for (int k = 0; k < 11; ++k) {
-            const double x = ta[r * 42 + c + k], y = tb[r * 42 + c + k], gk = s.g[k];
-            m1 += gk * x;
-            m2 += gk * y;
-            s11 += gk * x * x;
-            s22 += gk * y * y;
-            s12 += gk * x * y;
-        }
-        hm[0][i] = m1;
-        hm[1][i] = m2;
-        hm[2][i] = s11;
-        hm[3][i] = s22;
-        hm[4][i] = s12;
-    }
+    ssim_rows_pass(ta, tb, hm, s.g);
     __syncthreads();
-    const double L = S16 ? s.L : 255.0;
-    const double C1 = (0.01 * L) * (0.01 * L), C2 = (0.03 * L) * (0.03 * L);
-    double acc = 0;
-    for (int i = t; i < 16 * 32; i += 256) {
-        const int r = i >> 5, c = i & 31;
-        if (ty0 + r >= p.oh || tx0 + c >= p.ow) continue;
-        double v[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < 11; ++k)
-#pragma unroll
-            for (int q = 0; q < 5; ++q) v[q] += s.g[k] * hm[q][(r + k) * 32 + c];
-        const double mu1 = v[0], mu2 = v[1];
-        const double sg1 = v[2] - mu1 * mu1, sg2 = v[3] - mu2 * mu2, sg12 = v[4] - mu1 * mu2;
-        acc += ((2 * mu1 * mu2 + C1) * (2 * sg12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (sg1 + sg2 + C2));
-    }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((t & 63) == 0) red[t >> 6] = acc;
-    __syncthreads();
-    if (t == 0) s.partial[p.out0 + frame * p.blocks + blk] = red[0] + red[1] + red[2] + red[3];
+    const SsimConsts k(S16 ? s.L : 255.0);
+    double acc[1] = {0};
+    ssim_cols_pass(hm, s.g, ty0, tx0, p.oh, p.ow,
+                   [&](double mu1, double mu2, double sg1, double sg2, double sg12) { acc[0] += ssim_index(k, mu1, mu2, sg1, sg2, sg12); });
+    ssim_block_sums(acc, red, s.partial + p.out0 + frame * p.blocks + blk);
 }
 
 // The exact integer SSE of the three planes of two 16-bit clips in one launch: psnr_yuv420_kernel's walk (a wave a row, first the Y

@@ -1311,70 +1311,6 @@ def _yuv_metric_pair(a, b, crop_border, any_format=False):
     return [(x[0], y[0]) for x, y in zip(da, db)], lead_a + (t,), t, h, w, crop
 
 
-def psnr_sse_yuv420(a, b, crop_border=0):
-    """The statistic behind psnr_yuv420: the exact sum of squared byte differences of the cropped Y, Cb and Cr planes of every frame, an
-    int64 CPU tensor lead + (3,) (pnp_psnr_sse_yuv420: integer, the same bits every run).  Two Yuv420Frames16: the sample values'
-    differences (pnp_psnr_sse_yuv420p16)."""
-    pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border)
-    entry = 'pnp_psnr_sse_yuv420p16' if isinstance(a, Yuv420Frames16) else 'pnp_psnr_sse_yuv420'
-    dev = a.y.device
-    with torch.cuda.device(dev):
-        sse = torch.empty((len(pairs), t, 3), dtype=torch.int64, device=dev)
-        for i, (da, db) in enumerate(pairs):
-            if t:
-                _native.check(getattr(_native.lib(), entry)(ctypes.byref(da), ctypes.byref(db), _ptr(sse[i]), t, h, w, crop, _stream()), entry)
-    return sse.cpu().reshape(lead + (3,))
-
-
-def psnr_yuv420(a, b, crop_border=0):
-    """Per-frame plane PSNR of two 8-bit 4:2:0 clips, read from the planes where they lie (1.5 B per pixel and clip).
-    a, b: Yuv420Frames (n,t,...) or (t,...) of one shape, each in its own layout (NV12 output against an I420 ground truth); the Y
-    plane is cropped by crop_border (even), the chroma planes by crop_border / 2.  Returns a float64 CPU tensor lead + (3,) = Y, U, V:
-    PSNR_p = 10 log10(255^2 N_p / SSE_p) with N_p the samples of the cropped plane, inf where the planes are equal.  Two
-    Yuv420Frames16 of one bit depth d are scored on their sample values with the peak 2^d - 1 in place of 255."""
-    import numpy as np
-    sse = psnr_sse_yuv420(a, b, crop_border).numpy().astype(np.float64)
-    h, w = a.y.shape[-2:]
-    crop = int(crop_border)
-    n_y, n_c = (h - 2 * crop) * (w - 2 * crop), (h // 2 - crop) * (w // 2 - crop)
-    with np.errstate(divide='ignore'):
-        peak = float((1 << a.bit_depth) - 1) if isinstance(a, Yuv420Frames16) else 255.0
-        out = 10.0 * np.log10(peak ** 2 * np.array([n_y, n_c, n_c], np.float64) / sse)
-    out[sse == 0] = np.inf
-    return torch.from_numpy(out)
-
-
-def ssim_yuv420(a, b, crop_border=0, planes='y'):
-    """Per-frame plane SSIM of two 8-bit 4:2:0 clips (pnp_ssim_partials_yuv420: ssim_frames' window and fp64 arithmetic on the bytes of a
-    plane).  planes: any of 'y', 'u', 'v' in any order ('yuv', 'u', 'vy', ...); returns a float64 CPU tensor lead + (len(planes),) in
-    that order.  Crop as psnr_yuv420.  Two Yuv420Frames16 of one bit depth d: the same on the sample values, L = 2^d - 1
-    (pnp_ssim_partials_yuv420p16)."""
-    planes = _metric_planes(planes)
-    pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border)
-    L = _native.lib()
-    mask = sum(_PLANE_BITS[p] for p in planes)
-    order = [p for p in 'yuv' if p in planes]                      # the order the library writes
-    nb = {p: int(L.pnp_ssim_blocks_yuv420(h, w, crop, _PLANE_BITS[p])) for p in order}
-    if any(v < 1 for v in nb.values()):
-        raise ValueError('a cropped plane is smaller than the 11x11 SSIM window')
-    dev = a.y.device
-    res = torch.empty((len(pairs), t, len(planes)), dtype=torch.float64)
-    with torch.cuda.device(dev):
-        for i, (da, db) in enumerate(pairs):
-            if not t:
-                continue
-            part = torch.empty(t * sum(nb.values()), dtype=torch.float64, device=dev)
-            entry = 'pnp_ssim_partials_yuv420p16' if isinstance(a, Yuv420Frames16) else 'pnp_ssim_partials_yuv420'
-            _native.check(getattr(L, entry)(ctypes.byref(da), ctypes.byref(db), mask, _ptr(part), t, h, w, crop, _stream()), entry)
-            off = 0
-            for p in order:
-                rows, cols, c = (h, w, crop) if p == 'y' else (h // 2, w // 2, crop // 2)
-                n = (rows - 2 * c - 10) * (cols - 2 * c - 10)
-                res[i, :, planes.index(p)] = (part[off:off + t * nb[p]].reshape(t, nb[p]).sum(dim=1) / n).cpu()
-                off += t * nb[p]
-    return res.reshape(lead + (len(planes),))
-
-
 def _plane_geometry(fmt, h, w, crop):
     """-> {'y' | 'u' | 'v': (rows, cols, crop down, crop across)} of a format (include/pnpvcve.h, the crop rule)"""
     sx, sy = _native.YUV_FACTORS[fmt]
@@ -1382,11 +1318,8 @@ def _plane_geometry(fmt, h, w, crop):
     return {'y': (h, w, crop, crop), 'u': c, 'v': c}
 
 
-def psnr_sse_yuv(a, b, crop_border=0):
-    """psnr_sse_yuv420 for clips of any chroma format (pnp_psnr_sse_yuv / pnp_psnr_sse_yuvp16): the exact SSE of the cropped Y, Cb and Cr
-    planes of every frame, an int64 CPU tensor lead + (3,).  The chroma planes are cropped by crop_border / sx across and / sy down;
-    crop_border is even for 4:2:0 and 4:2:2, any value >= 0 for 4:4:4."""
-    pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border, any_format=True)
+def _psnr_sse_yuv(a, b, crop_border, any_format):
+    pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border, any_format=any_format)
     entry = 'pnp_psnr_sse_yuvp16' if isinstance(a, _YUV16_CLASSES) else 'pnp_psnr_sse_yuv'
     fmt = _native.YUV_FORMAT[yuv_format(a)]
     dev = a.y.device
@@ -1398,11 +1331,9 @@ def psnr_sse_yuv(a, b, crop_border=0):
     return sse.cpu().reshape(lead + (3,))
 
 
-def psnr_yuv(a, b, crop_border=0):
-    """psnr_yuv420 for clips of any chroma format: a float64 CPU tensor lead + (3,) = Y, U, V, PSNR_p = 10 log10(peak^2 N_p / SSE_p) with
-    N_p the samples of the cropped plane (N_C = (h/sy - 2c/sy)(w/sx - 2c/sx)), inf where the planes are equal."""
+def _psnr_yuv(a, b, crop_border, any_format):
     import numpy as np
-    sse = psnr_sse_yuv(a, b, crop_border).numpy().astype(np.float64)
+    sse = _psnr_sse_yuv(a, b, crop_border, any_format).numpy().astype(np.float64)
     h, w = a.y.shape[-2:]
     geo = _plane_geometry(yuv_format(a), h, w, int(crop_border))
     n = [(r - 2 * cy) * (c - 2 * cx) for r, c, cy, cx in (geo[p] for p in 'yuv')]
@@ -1413,11 +1344,9 @@ def psnr_yuv(a, b, crop_border=0):
     return torch.from_numpy(out)
 
 
-def ssim_yuv(a, b, crop_border=0, planes='y'):
-    """ssim_yuv420 for clips of any chroma format (pnp_ssim_partials_yuv / pnp_ssim_partials_yuvp16): per-frame plane SSIM, a float64
-    CPU tensor lead + (len(planes),) in the order of `planes`.  Crop as psnr_sse_yuv."""
+def _ssim_yuv(a, b, crop_border, planes, any_format):
     planes = _metric_planes(planes)
-    pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border, any_format=True)
+    pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border, any_format=any_format)
     L = _native.lib()
     fmt = _native.YUV_FORMAT[yuv_format(a)]
     geo = _plane_geometry(yuv_format(a), h, w, crop)
@@ -1442,6 +1371,49 @@ def ssim_yuv(a, b, crop_border=0, planes='y'):
                 res[i, :, planes.index(p)] = (part[off:off + t * nb[p]].reshape(t, nb[p]).sum(dim=1) / n).cpu()
                 off += t * nb[p]
     return res.reshape(lead + (len(planes),))
+
+
+def psnr_sse_yuv420(a, b, crop_border=0):
+    """The statistic behind psnr_yuv420: the exact sum of squared byte differences of the cropped Y, Cb and Cr planes of every frame, an
+    int64 CPU tensor lead + (3,) (pnp_psnr_sse_yuv420: integer, the same bits every run).  Two Yuv420Frames16: the sample values'
+    differences (pnp_psnr_sse_yuv420p16)."""
+    return _psnr_sse_yuv(a, b, crop_border, False)
+
+
+def psnr_yuv420(a, b, crop_border=0):
+    """Per-frame plane PSNR of two 8-bit 4:2:0 clips, read from the planes where they lie (1.5 B per pixel and clip).
+    a, b: Yuv420Frames (n,t,...) or (t,...) of one shape, each in its own layout (NV12 output against an I420 ground truth); the Y
+    plane is cropped by crop_border (even), the chroma planes by crop_border / 2.  Returns a float64 CPU tensor lead + (3,) = Y, U, V:
+    PSNR_p = 10 log10(255^2 N_p / SSE_p) with N_p the samples of the cropped plane, inf where the planes are equal.  Two
+    Yuv420Frames16 of one bit depth d are scored on their sample values with the peak 2^d - 1 in place of 255."""
+    return _psnr_yuv(a, b, crop_border, False)
+
+
+def ssim_yuv420(a, b, crop_border=0, planes='y'):
+    """Per-frame plane SSIM of two 8-bit 4:2:0 clips (pnp_ssim_partials_yuv420: ssim_frames' window and fp64 arithmetic on the bytes of a
+    plane).  planes: any of 'y', 'u', 'v' in any order ('yuv', 'u', 'vy', ...); returns a float64 CPU tensor lead + (len(planes),) in
+    that order.  Crop as psnr_yuv420.  Two Yuv420Frames16 of one bit depth d: the same on the sample values, L = 2^d - 1
+    (pnp_ssim_partials_yuv420p16)."""
+    return _ssim_yuv(a, b, crop_border, planes, False)
+
+
+def psnr_sse_yuv(a, b, crop_border=0):
+    """psnr_sse_yuv420 for clips of any chroma format (pnp_psnr_sse_yuv / pnp_psnr_sse_yuvp16): the exact SSE of the cropped Y, Cb and Cr
+    planes of every frame, an int64 CPU tensor lead + (3,).  The chroma planes are cropped by crop_border / sx across and / sy down;
+    crop_border is even for 4:2:0 and 4:2:2, any value >= 0 for 4:4:4."""
+    return _psnr_sse_yuv(a, b, crop_border, True)
+
+
+def psnr_yuv(a, b, crop_border=0):
+    """psnr_yuv420 for clips of any chroma format: a float64 CPU tensor lead + (3,) = Y, U, V, PSNR_p = 10 log10(peak^2 N_p / SSE_p) with
+    N_p the samples of the cropped plane (N_C = (h/sy - 2c/sy)(w/sx - 2c/sx)), inf where the planes are equal."""
+    return _psnr_yuv(a, b, crop_border, True)
+
+
+def ssim_yuv(a, b, crop_border=0, planes='y'):
+    """ssim_yuv420 for clips of any chroma format (pnp_ssim_partials_yuv / pnp_ssim_partials_yuvp16): per-frame plane SSIM, a float64
+    CPU tensor lead + (len(planes),) in the order of `planes`.  Crop as psnr_sse_yuv."""
+    return _ssim_yuv(a, b, crop_border, planes, True)
 
 
 def msssim_yuv420(a, b, crop_border=0, planes='y', scales=False):
