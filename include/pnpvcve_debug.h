@@ -121,6 +121,44 @@ int pnp_mv_warp_nhwc_f16out(const float* feat_dev, const float* flow_x_dev, cons
 int pnp_mv_warp_nhwc_f16out_mode(const float* feat_dev, const float* flow_x_dev, const float* flow_y_dev, void* out16_dev, int h,
                                  int w, int c, int mode, void* stream);
 
+/* ---- The reconstruction head's two conv forms alone (iconvsr_ipb_par.py:135-146), each with an explicit kernel route, so that a test
+ * knows which kernel it ran.  Arguments only, no process-wide state; the launch is the one the clip scheduler makes for the head.  A
+ * route that the project's own eligibility rule does not select for exactly these arguments is PNP_ERR_UNSUPPORTED: nothing is rerouted.
+ * NULL pointers, act outside 0..2, h or w below 1 and unknown routes / modes / forms are PNP_ERR_BAD_ARG, a map beyond 32-bit byte
+ * offsets is PNP_ERR_UNSUPPORTED, all before any launch. */
+#define PNP_HEAD_AUTO 0    /* what the clip scheduler launches at the given precision */
+#define PNP_HEAD_F32 1     /* the fp32 matrix-core tile kernel (pixel shuffle: 4x16 or 8x16 tiles by frame size; conv_last: the RGB configuration) */
+#define PNP_HEAD_F16 2     /* the fp16-operand kernel (pixel shuffle: any mix of fp32 / fp16 maps; conv_last: its RGB body) */
+#define PNP_HEAD_F16X3 3   /* pixel shuffle only: the split-fp16 kernel, four launches */
+#define PNP_HEAD_VALU 4    /* conv_last only: the vector-ALU kernel, with or without a byte / RGB0 boundary */
+
+/* PixelShufflePack (common/upsample.py:40-51): x_dev (h,w,64) fp32, or fp16 when x_f16 -> out_dev (2h,2w,64) fp32, or fp16 when
+ * out_f16.  packed_dev: the image of pnp_pack_pixel_shuffle_f32.  twin_dev / twin_kind: that image's first 36 chunks as
+ * pnp_f16_image_from_f32 makes them (kind 1) or as pnp_f16x3_image_from_f32 does (kind 2), or NULL / 0; the kind is the precision
+ * PNP_HEAD_AUTO routes for.
+ * tile_queue_dev (kind 2 only): NULL or the 16 ints of pnp_conv3x3_f16x3_ex. */
+int pnp_debug_pixel_shuffle_conv(const void* x_dev, int x_f16, const float* packed_dev, const void* twin_dev, int twin_kind, int act,
+                                 void* out_dev, int out_f16, int h, int w, int route, int* tile_queue_dev, void* stream);
+
+/* conv_last's weights as pnp_generator_pack lays them out, from conv_last.weight (3,64,3,3) and conv_last.bias (3): the matrix-core
+ * image (9 chunks of one 32-channel N tile, 3 channels valid), the bias padded to 32 floats, the [9][64][4] vector-ALU layout and the
+ * fp16 twin of the image, in that order; the second function is the size of dst_dev in floats. */
+int pnp_debug_pack_conv_last(const float* w_dev, const float* b_dev, float* dst_dev, void* stream);
+int64_t pnp_debug_conv_last_packed_floats(void);
+
+#define PNP_HEAD_FRAME_PLANES 0   /* the frame to add as 3 fp32 planes */
+#define PNP_HEAD_FRAME_U8 1       /* as (h,w,3) bytes, read through the table of pnp_frames_from_rgb8 */
+#define PNP_HEAD_FRAME_RGB0 2     /* as (h,w,4) fp32 RGB0, what a 4:2:0 clip is unpacked into */
+
+/* out = act(conv_last(src)) + frame (out_mode 2; the frame is H x W) or + bilinear x4 of the frame (out_mode 3; the frame is
+ * H/4 x W/4, H and W multiples of 4).  src_dev (H,W,64) fp32, or fp16 when src_f16.  packed_dev: pnp_debug_pack_conv_last's buffer.
+ * prec: the PNP_PREC_* that PNP_HEAD_AUTO routes for (ignored by the explicit routes).  out_dev: 3 fp32 planes (H,W) and / or
+ * out_u8_dev: (H,W,3) bytes, round-half-even of clamp(x, 0, 1) * 255 of the fp32 sum x; either may be NULL, not both.  Byte output
+ * and the two frame forms other than planes exist on the vector-ALU kernel only. */
+int pnp_debug_conv_last(const void* src_dev, int src_f16, const float* packed_dev, int prec, int act, int out_mode,
+                        const void* frame_dev, int frame_form, float* out_dev, unsigned char* out_u8_dev, int H, int W, int route,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -235,6 +235,14 @@ DEBUG_SIGNATURES['pnp_conv3x3_f16_maps'] = (c_int, [c_int, POINTER(c_void_p), PO
                                                     c_int, c_int, c_int, c_void_p, c_void_p])
 DEBUG_SIGNATURES['pnp_mv_warp_nhwc_f16out'] = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p])
 DEBUG_SIGNATURES['pnp_mv_warp_nhwc_f16out_mode'] = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
+DEBUG_SIGNATURES['pnp_debug_pixel_shuffle_conv'] = (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                                            c_int, c_void_p, c_void_p])
+DEBUG_SIGNATURES['pnp_debug_pack_conv_last'] = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p])
+DEBUG_SIGNATURES['pnp_debug_conv_last_packed_floats'] = (c_int64, [])
+DEBUG_SIGNATURES['pnp_debug_conv_last'] = (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                                   c_int, c_int, c_void_p])
+HEAD_ROUTES = {'auto': 0, 'f32': 1, 'f16': 2, 'f16x3': 3, 'valu': 4}      # PNP_HEAD_* (include/pnpvcve_debug.h)
+HEAD_FRAME_PLANES, HEAD_FRAME_U8, HEAD_FRAME_RGB0 = range(3)              # PNP_HEAD_FRAME_*
 
 # pnp_generator_set_option ids (include/pnpvcve.h)
 (OPT_F16_MAPS, OPT_PAR_SKIP, OPT_CONV_LAST_VALU, OPT_PERSIST, OPT_SMALL_F16, OPT_SPARSE_EVAL, OPT_F16_MIRRORS, OPT_F16_CHAIN_MIRRORS,

@@ -375,6 +375,108 @@ int pnp_pixel_shuffle_conv_f32(const float* x, const float* packed, int act, flo
     return launch_conv3x3(a, conv_pick_cfg(h, w), 4, (hipStream_t)st);
 }
 
+// pnpvcve_debug.h: the reconstruction head's two conv forms alone (generator.hip head()), ConvArgs filled as Clip::conv_args fills
+// them for those calls, handed to the launch_* functions Clip::conv hands them to.  An explicit route runs iff the project's own
+// predicate selects it for exactly these arguments; nothing is rerouted.
+
+// the pixel-shuffle conv: ConvCall(h, w, cfg).source(x, 64, up_img).bias(up_bias, 64).act(act).mode(1, 4, IMG_WIDE).to(out).f16_map(..)
+int pnp_debug_pixel_shuffle_conv(const void* x, int x_f16, const float* packed, const void* twin, int twin_kind, int act, void* out,
+                                 int out_f16, int h, int w, int route, int* tile_queue, void* st) {
+    if (!x || !packed || !out || h < 1 || w < 1 || act < 0 || act > 2) return PNP_ERR_BAD_ARG;
+    if (twin_kind < 0 || twin_kind > 2 || (twin_kind != 0) != (twin != nullptr)) return PNP_ERR_BAD_ARG;
+    if (route != PNP_HEAD_AUTO && route != PNP_HEAD_F32 && route != PNP_HEAD_F16 && route != PNP_HEAD_F16X3) return PNP_ERR_BAD_ARG;
+    if ((int64_t)h * w * 4 * 256 >= (int64_t)1 << 32) return PNP_ERR_UNSUPPORTED;      // 32-bit byte offsets into the (2h, 2w, 64) map
+    const int channels = 64, cfg = conv_pick_cfg(h, w);
+    const float* src = reinterpret_cast<const float*>(x);
+    ConvArgs a = op_conv_args(1, &src, &channels, packed + 4 * IMG_WIDE, nullptr, nullptr, nullptr, nullptr, act, reinterpret_cast<float*>(out), h, w,
+                              nullptr);
+    a.wsrc[0] = packed;
+    a.wsrc_h[0] = twin;
+    a.w_ystride = IMG_WIDE;
+    a.bias_ystride = 64;
+    a.out_mode = 1;
+    a.out_cstride = 448;
+    a.src_f16 = x_f16 ? 1 : 0;
+    a.out_f16 = out_f16 ? 1 : 0;
+    a.tile_queue = twin_kind == 2 ? tile_queue : nullptr;
+    a.prec = route == PNP_HEAD_F32 ? 0 : twin_kind;      // (the generator's precision is the kind of twin its packed buffer carries)
+    if (a.tile_queue) {      // as pnp_conv3x3_f16x3_ex: a queue that is not all zero would end the blocks' walk early
+        const int rc = launch_fill(reinterpret_cast<float*>(a.tile_queue), 0.0f, 16, (hipStream_t)st);
+        if (rc) return rc;
+    }
+    switch (route) {
+        case PNP_HEAD_AUTO: return launch_conv3x3(a, cfg, 4, (hipStream_t)st);
+        case PNP_HEAD_F32:       // (launch_conv3x3's order: no other fp32 kernel may claim the launch in front of the tile kernel)
+            if (a.src_f16 || a.out_f16 || conv_wino_eligible(a, cfg, 4) || conv_wino_ms_eligible(a, cfg, 4) || conv_last_valu_eligible(a, cfg, 4) ||
+                conv_persist_eligible(a, cfg, 4))
+                return PNP_ERR_UNSUPPORTED;
+            return launch_conv3x3(a, cfg, 4, (hipStream_t)st);
+        case PNP_HEAD_F16:
+            if (twin_kind != 1 || !conv_f16_eligible(a, cfg, 4)) return PNP_ERR_UNSUPPORTED;
+            return launch_conv3x3_f16(a, 4, (hipStream_t)st);
+        default:
+            if (twin_kind != 2 || !conv_f16x3_eligible(a, cfg, 4)) return PNP_ERR_UNSUPPORTED;
+            return launch_conv3x3_f16x3(a, cfg, (hipStream_t)st);
+    }
+}
+
+// conv_last's weights as pnp_generator_pack lays them out: [IMG_RGB image | 32-float bias | [9][64][4] vector-ALU layout | fp16 twin]
+static constexpr int64_t LAST_BIAS = IMG_RGB, LAST_VALU = LAST_BIAS + 32, LAST_TWIN = LAST_VALU + 9 * 64 * 4;
+int64_t pnp_debug_conv_last_packed_floats(void) { return LAST_TWIN + IMG_RGB / 2; }
+
+int pnp_debug_pack_conv_last(const float* w, const float* b, float* dst, void* st_) {
+    hipStream_t st = (hipStream_t)st_;
+    if (!w || !b || !dst) return PNP_ERR_BAD_ARG;
+    int rc = pack_weight_image(WeightImage{0, 0, 64, 9, PACK_WIDE, 0, 1, 3}, w, dst, nullptr, st);     // ONE 32-channel N tile per k-step, 3 valid
+    if (!rc) rc = launch_small_copy(b, dst + LAST_BIAS, 3, 32, PNP_COPY_PAD, st);
+    if (!rc) rc = launch_pack_last_valu(w, dst + LAST_VALU, st);
+    if (!rc) rc = launch_f16_image(dst, dst + LAST_TWIN, 9, 1, st);
+    return rc;
+}
+
+// conv_last: ConvCall(H, W, CONV_CFG_RGB).source(src, 64, last_img).bias(last_bias).mode(2 | 3).rgb(lr, plane, last_valu)
+//                .rgb8(lr8, out8).rgb0(lr0).to(out).f16_map(..)
+int pnp_debug_conv_last(const void* src, int src_f16, const float* packed, int prec, int act, int out_mode, const void* frame,
+                        int frame_form, float* out, unsigned char* out_u8, int H, int W, int route, void* st) {
+    if (!src || !packed || !frame || (!out && !out_u8) || H < 1 || W < 1 || act < 0 || act > 2) return PNP_ERR_BAD_ARG;
+    if ((out_mode != 2 && out_mode != 3) || prec < 0 || prec > 2) return PNP_ERR_BAD_ARG;
+    if (out_mode == 3 && ((H | W) & 3)) return PNP_ERR_BAD_ARG;      // the x4 heads: the frame is (H / 4, W / 4)
+    if (frame_form != PNP_HEAD_FRAME_PLANES && frame_form != PNP_HEAD_FRAME_U8 && frame_form != PNP_HEAD_FRAME_RGB0) return PNP_ERR_BAD_ARG;
+    if (route != PNP_HEAD_AUTO && route != PNP_HEAD_F32 && route != PNP_HEAD_F16 && route != PNP_HEAD_VALU) return PNP_ERR_BAD_ARG;
+    if (!op_map_fits(H, W)) return PNP_ERR_UNSUPPORTED;      // 32-bit byte offsets into the source map
+    const int channels = 64;
+    const float* s = reinterpret_cast<const float*>(src);
+    ConvArgs a = op_conv_args(1, &s, &channels, packed + LAST_BIAS, nullptr, nullptr, nullptr, nullptr, act, out, H, W, nullptr);
+    a.wsrc[0] = packed;
+    a.out_mode = out_mode;
+    a.out_cstride = 448;
+    a.src_f16 = src_f16 ? 1 : 0;
+    a.lr_plane = out_mode == 3 ? (long)(H >> 2) * (W >> 2) : (long)H * W;
+    if (frame_form == PNP_HEAD_FRAME_PLANES) a.lr = reinterpret_cast<const float*>(frame);
+    if (frame_form == PNP_HEAD_FRAME_U8) a.lr_u8 = reinterpret_cast<const unsigned char*>(frame);
+    if (frame_form == PNP_HEAD_FRAME_RGB0) a.lr_rgb0 = reinterpret_cast<const float*>(frame);
+    a.out_u8 = out_u8;
+    const bool io = a.lr_u8 || a.out_u8 || a.lr_rgb0;      // Clip::conv: the byte boundary goes to launch_conv_last_io
+    a.prec = route == PNP_HEAD_AUTO ? prec : (route == PNP_HEAD_F16 ? 1 : 0);
+    a.wsrc_h[0] = a.prec == 1 ? (const void*)(packed + LAST_TWIN) : nullptr;
+    a.wvalu = route == PNP_HEAD_F32 ? nullptr : packed + LAST_VALU;
+    switch (route) {
+        case PNP_HEAD_AUTO:
+            if (io && prec == 1) return PNP_ERR_UNSUPPORTED;      // io_staged: the fp16 path keeps conv_last's fp32 interface
+            return io ? launch_conv_last_io(a, (hipStream_t)st) : launch_conv3x3(a, CONV_CFG_RGB, 1, (hipStream_t)st);
+        case PNP_HEAD_VALU:
+            if (io) return launch_conv_last_io(a, (hipStream_t)st);      // (refuses by conv_last_valu_shape itself)
+            if (!conv_last_valu_eligible(a, CONV_CFG_RGB, 1)) return PNP_ERR_UNSUPPORTED;
+            return launch_conv_last_valu(a, (hipStream_t)st);
+        case PNP_HEAD_F32:       // the fp32 MFMA RGB configuration: fp32 planes in and out only
+            if (io || a.src_f16) return PNP_ERR_UNSUPPORTED;
+            return launch_conv3x3(a, CONV_CFG_RGB, 1, (hipStream_t)st);
+        default:
+            if (io || !conv_f16_eligible(a, CONV_CFG_RGB, 1)) return PNP_ERR_UNSUPPORTED;
+            return launch_conv3x3_f16(a, 1, (hipStream_t)st);
+    }
+}
+
 int pnp_par_tile_flags_f32(const float* par, int* flags, int h, int w, void* st) {
     if (!par || !flags || h < 1 || w < 1) return PNP_ERR_BAD_ARG;
     return launch_par_tile_flags(par, (long)h * w, flags, 1, h, w, (hipStream_t)st);

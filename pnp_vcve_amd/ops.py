@@ -752,6 +752,85 @@ def pixel_shuffle_conv(x, packed, act=0):
     return out
 
 
+def _head_map(t, name, shape=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous():
+        raise RuntimeError(f'{name} must be a contiguous CUDA/HIP tensor: the PnP-VCVE hot path has no CPU fallback')
+    if t.dtype not in (torch.float32, torch.float16):
+        raise TypeError(f'{name}: float32 or float16, got {t.dtype}')
+    if t.dim() != 3 or t.shape[2] != 64 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f'{name}: a pixel-major (h,w,64) map' + (f' of shape {tuple(shape)}' if shape is not None else ''))
+    return int(t.dtype == torch.float16)
+
+
+@_on_device_of_first_tensor
+def head_pixel_shuffle_conv(x, packed, act=0, route='auto', twin=None, out=None, out_f16=False, tile_queue=None):
+    """The head's pixel-shuffle conv with an explicit kernel route (include/pnpvcve_debug.h, pnp_debug_pixel_shuffle_conv).
+    x (h,w,64) float32 or float16; packed = pack_pixel_shuffle(); twin = f16_image(packed[:4 * 36864]) or f16x3_image of the same
+    (told apart by size), or None; route 'auto' | 'f32' | 'f16' | 'f16x3'.  out: a (2h,2w,64) float32 / float16 tensor to write
+    into, or None: a new one (float16 when out_f16).  A route the arguments are not eligible for raises (pnp error 1002)."""
+    x16 = _head_map(x, 'x')
+    packed = _chk(packed, 'packed')
+    h, w, _ = x.shape
+    kind = 0
+    if twin is not None:
+        if not twin.is_cuda or twin.dtype != torch.float16 or not twin.is_contiguous() or twin.numel() not in (4 * 36864, 8 * 36864):
+            raise TypeError('twin: ops.f16_image or ops.f16x3_image of the four sub-pixel images')
+        kind = 1 if twin.numel() == 4 * 36864 else 2
+    if out is None:
+        out = torch.empty((2 * h, 2 * w, 64), device=x.device, dtype=torch.float16 if out_f16 else torch.float32)
+    o16 = _head_map(out, 'out', (2 * h, 2 * w, 64))
+    if tile_queue is not None and (tile_queue.dtype != torch.int32 or tile_queue.numel() < 16 or not tile_queue.is_cuda):
+        raise TypeError('tile_queue: 16 int32 on the device')
+    _native.check(_native.lib().pnp_debug_pixel_shuffle_conv(_ptr(x), x16, _ptr(packed), _ptr(twin), kind, int(act), _ptr(out), o16, h, w,
+                                                             _native.HEAD_ROUTES[route], _ptr(tile_queue), _stream()),
+                  'pnp_debug_pixel_shuffle_conv')
+    return out
+
+
+@_on_device_of_first_tensor
+def pack_conv_last(weight, bias):
+    """conv_last.weight (3,64,3,3) + bias (3,) -> the buffer head_conv_last reads: every layout pnp_generator_pack makes of them."""
+    weight, bias = _chk(weight, 'weight'), _chk(bias, 'bias')
+    if tuple(weight.shape) != (3, 64, 3, 3) or tuple(bias.shape) != (3,):
+        raise ValueError('conv_last: weight (3,64,3,3), bias (3,)')
+    L = _native.lib()
+    dst = torch.empty(int(L.pnp_debug_conv_last_packed_floats()), device=weight.device, dtype=torch.float32)
+    _native.check(L.pnp_debug_pack_conv_last(_ptr(weight), _ptr(bias), _ptr(dst), _stream()), 'pnp_debug_pack_conv_last')
+    return dst
+
+
+@_on_device_of_first_tensor
+def head_conv_last(src, packed, frame, out_mode=2, act=0, route='auto', precision=0, frame_form=None, out=True, out_u8=False):
+    """conv_last + the frame with an explicit kernel route (include/pnpvcve_debug.h, pnp_debug_conv_last) -> (out, out_u8).
+    src (H,W,64) float32 or float16; packed = pack_conv_last(); out_mode 2: the frame is H x W, 3: H/4 x W/4 (bilinear x4).
+    frame_form 'planes' (3,h,w) float32 | 'u8' (h,w,3) uint8 | 'rgb0' (h,w,4) float32; None: by dtype, planes or u8.
+    route 'auto' (at `precision` 0 fp32 / 1 fp16 / 2 split fp16) | 'valu' | 'f32' | 'f16'.  out / out_u8: True (a new tensor), a
+    tensor to write into ((3,H,W) float32 / (H,W,3) uint8), or False (not written; None is returned in its place)."""
+    s16 = _head_map(src, 'src')
+    packed = _chk(packed, 'packed')
+    H, W, _ = src.shape
+    if frame_form is None:
+        frame_form = 'u8' if frame.dtype == torch.uint8 else 'planes'
+    fh, fw = (H // 4, W // 4) if out_mode == 3 else (H, W)
+    want = {'planes': ((3, fh, fw), torch.float32), 'u8': ((fh, fw, 3), torch.uint8), 'rgb0': ((fh, fw, 4), torch.float32)}[frame_form]
+    if not frame.is_cuda or not frame.is_contiguous() or tuple(frame.shape) != want[0] or frame.dtype != want[1]:
+        raise ValueError(f'frame ({frame_form}): a contiguous CUDA {want[1]} tensor of shape {want[0]}, got {tuple(frame.shape)} {frame.dtype}')
+    form = {'planes': _native.HEAD_FRAME_PLANES, 'u8': _native.HEAD_FRAME_U8, 'rgb0': _native.HEAD_FRAME_RGB0}[frame_form]
+    if out is True:
+        out = torch.empty((3, H, W), device=src.device, dtype=torch.float32)
+    if out_u8 is True:
+        out_u8 = torch.empty((H, W, 3), device=src.device, dtype=torch.uint8)
+    out = None if out is False else out
+    out_u8 = None if out_u8 is False else out_u8
+    for t, shp, dt, nm in ((out, (3, H, W), torch.float32, 'out'), (out_u8, (H, W, 3), torch.uint8, 'out_u8')):
+        if t is not None and (not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shp or t.dtype != dt):
+            raise ValueError(f'{nm}: a contiguous CUDA {dt} tensor of shape {shp}')
+    _native.check(_native.lib().pnp_debug_conv_last(_ptr(src), s16, _ptr(packed), int(precision), int(act), int(out_mode), _ptr(frame), form,
+                                                    _ptr(out), _ptr(out_u8), H, W, _native.HEAD_ROUTES[route], _stream()),
+                  'pnp_debug_conv_last')
+    return out, out_u8
+
+
 # ---------------------------------------------------------------- Y'CbCr 4:2:0 frames (include/pnpvcve.h states the arithmetic)
 # 8-bit planes (Yuv420Frames: bytes) and 10 / 12-bit planes (Yuv420Frames16: 16-bit words) share every helper below; the sample's size
 # is the tensors' element_size(), and a function named for one sample size refuses frames of the other.

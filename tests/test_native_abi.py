@@ -207,6 +207,50 @@ def test_warp_entries_refuse_bad_sizes_before_touching_memory(lib):
             assert call(8, 8, 64, 2) == 1001 and call(8, 8, 8, -1) == 1001, name
 
 
+def test_head_debug_entries_refuse_bad_arguments_and_ineligible_routes_before_touching_memory(lib):
+    """pnp_debug_pixel_shuffle_conv / pnp_debug_conv_last / pnp_debug_pack_conv_last (include/pnpvcve_debug.h): NULL pointers, an act
+    outside 0..2, h or w below 1, an out_mode other than 2 / 3 and unknown routes are PNP_ERR_BAD_ARG (1001); a map beyond 32-bit
+    byte offsets and a route the project's eligibility rules do not select for the arguments are PNP_ERR_UNSUPPORTED (1002): all
+    decided on the host before any launch (runs without a GPU; the pointers are fakes)."""
+    fake = 0x1000
+    AUTO, F32, F16, F16X3, VALU = (_native.HEAD_ROUTES[k] for k in ('auto', 'f32', 'f16', 'f16x3', 'valu'))
+
+    def shuffle(x=fake, x16=0, packed=fake, twin=None, kind=0, act=2, out=fake, o16=0, h=8, w=8, route=F32, queue=None):
+        return lib.pnp_debug_pixel_shuffle_conv(x, x16, packed, twin, kind, act, out, o16, h, w, route, queue, None)
+
+    for kw in (dict(x=None), dict(packed=None), dict(out=None), dict(act=-1), dict(act=3), dict(h=0), dict(w=0), dict(h=-4), dict(route=VALU),
+               dict(route=7), dict(route=-1), dict(kind=3, twin=fake), dict(kind=1), dict(kind=0, twin=fake), dict(kind=2, twin=None)):
+        assert shuffle(**kw) == 1001, kw
+    # the (2h, 2w, 64) fp32 map of a 2048 x 2048 input is exactly 4 GiB
+    assert shuffle(h=2048, w=2048) == 1002 and shuffle(h=2048, w=2048, route=AUTO) == 1002
+    for kw in (dict(route=F16), dict(route=F16X3),                                   # no twin to read
+               dict(route=F16, twin=fake, kind=2), dict(route=F16X3, twin=fake, kind=1),     # the other kernel's twin
+               dict(route=F32, x16=1), dict(route=F32, o16=1),                       # fp16 maps exist on the fp16 kernel only
+               dict(route=F16X3, twin=fake, kind=2, x16=1), dict(route=F16X3, twin=fake, kind=2, o16=1),
+               dict(route=AUTO, x16=1), dict(route=AUTO, twin=fake, kind=2, o16=1)):
+        assert shuffle(**kw) == 1002, kw
+
+    def last(src=fake, s16=0, packed=fake, prec=0, act=0, mode=2, frame=fake, form=0, out=fake, out8=None, H=8, W=16, route=VALU):
+        return lib.pnp_debug_conv_last(src, s16, packed, prec, act, mode, frame, form, out, out8, H, W, route, None)
+
+    for kw in (dict(src=None), dict(packed=None), dict(frame=None), dict(out=None), dict(act=-1), dict(act=3), dict(H=0), dict(W=0), dict(W=-16),
+               dict(mode=0), dict(mode=1), dict(mode=4), dict(form=3), dict(form=-1), dict(route=F16X3), dict(route=9), dict(prec=3),
+               dict(mode=3, H=10), dict(mode=3, W=18)):
+        assert last(**kw) == 1001, kw
+    assert last(H=4096, W=4096) == 1002 and last(H=4096, W=4096, route=AUTO) == 1002      # the NHWC64 fp32 source map is exactly 4 GiB
+    for kw in (dict(route=VALU, s16=1), dict(route=VALU, s16=1, form=1), dict(route=VALU, s16=1, out8=fake),      # conv_last_valu_shape
+               dict(route=F32, form=1), dict(route=F32, form=2), dict(route=F32, out8=fake), dict(route=F32, s16=1),
+               dict(route=F16, form=1), dict(route=F16, form=2), dict(route=F16, out8=fake),
+               dict(route=AUTO, prec=1, form=1), dict(route=AUTO, prec=1, out8=fake),     # the fp16 path stages bytes around its fp32 interface
+               dict(route=AUTO, prec=0, s16=1), dict(route=AUTO, prec=2, s16=1), dict(route=AUTO, prec=0, s16=1, form=2)):
+        assert last(**kw) == 1002, kw
+    assert lib.pnp_debug_pack_conv_last(None, fake, fake, None) == 1001
+    assert lib.pnp_debug_pack_conv_last(fake, None, fake, None) == 1001
+    assert lib.pnp_debug_pack_conv_last(fake, fake, None, None) == 1001
+    # image (9 chunks of 2048) + bias (32) + vector-ALU layout (9 * 64 * 4) + the image's fp16 twin (half the floats)
+    assert lib.pnp_debug_conv_last_packed_floats() == 9 * 2048 + 32 + 2304 + 9 * 1024
+
+
 def test_graft_entry_build_runs_and_agrees_with_the_header_on_the_abi_version():
     """__graft_entry__.build() is the driver's "does it build" check: it must pass on a CPU box (hipcc cross-compiles) and its ABI
     assertion must follow include/pnpvcve.h (r04: the header went to 4 while build() still asserted 3)."""
