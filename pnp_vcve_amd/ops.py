@@ -1018,33 +1018,45 @@ def _yuv_entry(name, frames):
     return name + ('p16' if isinstance(frames, _YUV16_CLASSES) else '')
 
 
-def _yuv_views(buf, h, w, order, tail=()):
-    """yuv420_views / yuv420p16_views: tail () -> Yuv420Frames of a uint8 buffer, (bit_depth, msb_aligned) -> Yuv420Frames16 of 16-bit
-    words; order 'nv12' | 'nv21' | 'i420'"""
-    cls, words, planar = (Yuv420Frames16, '16-bit words', 'a planar') if tail else (Yuv420Frames, 'uint8', 'an I420')
-    if h < 2 or w < 2 or h % 2 or w % 2:
-        raise ValueError(f'4:2:0 frames need an even height and width, got {h} x {w}')
+def _yuv_views_format(buf, h, w, fmt, order, tail=()):
+    """yuv420_views / yuv420p16_views / yuv_views: a packed buffer (..., h + 2 (h / sy) / sx, pitch) -> views of the format's frame
+    class; order 'nv12' | 'nv21' | 'i420' (the plane order); tail () -> the class of a uint8 buffer, (bit_depth, msb_aligned) -> the
+    class of 16-bit words.  The format is its factors (sx, sy): the chroma planes are (h / sy) x (w / sx)"""
+    cls = _YUV_CLASSES[fmt][1 if tail else 0]
+    sx, sy = _native.YUV_FACTORS[fmt]
+    _yuv_size_check(fmt, h, w)
     if tail and (not isinstance(buf, torch.Tensor) or buf.dtype not in _WORD_DTYPES):
         raise TypeError(f'buf must be a tensor of 16-bit words (torch.int16 / torch.uint16), got {getattr(buf, "dtype", type(buf))}')
     if not tail and buf.dtype != torch.uint8:
         raise TypeError(f'buf must be uint8, got {buf.dtype}')
-    if buf.dim() >= 2 and buf.shape[-2] == h * 3 // 2 and buf.shape[-1] >= w and buf.stride(-1) == 1:
+    ch = h // sy
+    rows = h + 2 * ch // sx         # Y, then two chroma planes of h / sy rows, w / sx samples each
+    if buf.dim() >= 2 and buf.shape[-2] == rows and buf.shape[-1] >= w and buf.stride(-1) == 1:
         pitch = buf.shape[-1]
         y = buf[..., :h, :w]
-        if order != 'i420':
-            c = buf[..., h:, :w]
+        if order != 'i420':         # h / sy rows of chroma pairs: w samples of a row at sx = 2, 2w samples of two buffer rows at 4:4:4
+            if sx == 2:
+                c = buf[..., h:, :w]
+            elif buf.stride(-2) != pitch:
+                raise ValueError('an interleaved 4:4:4 buffer needs whole rows: a row of chroma pairs is two buffer rows long')
+            else:
+                c = buf[..., h:, :].flatten(-2).unflatten(-1, (h, 2 * pitch))[..., :2 * w]
             a, b = c[..., 0::2], c[..., 1::2]
             return cls(y, a, b, *tail) if order == 'nv12' else cls(y, b, a, *tail)
+        if sx == 1:
+            return cls(y, buf[..., h:2 * h, :w], buf[..., 2 * h:, :w], *tail)
         if pitch % 2 or buf.stride(-2) != pitch:
+            planar = 'a planar 4:2:2' if fmt == '422' else 'a planar' if tail else 'an I420'
             raise ValueError(f'{planar} buffer needs an even pitch and whole rows: its chroma rows are half a luma row long')
         flat = buf.flatten(-2)          # (a view: the two last dimensions are contiguous)
-        n = (h // 2) * (pitch // 2)
-        cb = flat[..., h * pitch:h * pitch + n].unflatten(-1, (h // 2, pitch // 2))[..., :w // 2]
-        cr = flat[..., h * pitch + n:h * pitch + 2 * n].unflatten(-1, (h // 2, pitch // 2))[..., :w // 2]
+        n = ch * (pitch // 2)
+        cb = flat[..., h * pitch:h * pitch + n].unflatten(-1, (ch, pitch // 2))[..., :w // 2]
+        cr = flat[..., h * pitch + n:h * pitch + 2 * n].unflatten(-1, (ch, pitch // 2))[..., :w // 2]
         return cls(y, cb, cr, *tail)
-    if order == 'i420' and buf.dim() >= 1 and buf.shape[-1] == h * w * 3 // 2 and buf.stride(-1) == 1:
-        return _yuv_views(buf.unflatten(-1, (h * 3 // 2, w)), h, w, order, tail)
-    raise ValueError(f'buf must be (..., {h * 3 // 2}, pitch >= {w}) {words} with a unit last stride, got {tuple(buf.shape)}')
+    if order == 'i420' and buf.dim() >= 1 and buf.shape[-1] == rows * w and buf.stride(-1) == 1:
+        return _yuv_views_format(buf.unflatten(-1, (rows, w)), h, w, fmt, order, tail)
+    words = '' if fmt != '420' else ' 16-bit words' if tail else ' uint8'
+    raise ValueError(f'buf must be (..., {rows}, pitch >= {w}){words} with a unit last stride, got {tuple(buf.shape)}')
 
 
 def yuv420_views(buf, h, w, layout='nv12'):
@@ -1053,7 +1065,7 @@ def yuv420_views(buf, h, w, layout='nv12'):
     bytes apart.  I420: the Y plane, then the Cb plane and the Cr plane with rows pitch/2 apart (pitch even)."""
     if layout not in YUV_LAYOUTS:
         raise ValueError(f'layout must be one of {YUV_LAYOUTS}, got {layout!r}')
-    return _yuv_views(buf, h, w, layout)
+    return _yuv_views_format(buf, h, w, '420', layout)
 
 
 def yuv420p16_views(buf, h, w, layout='yuv420p10le'):
@@ -1062,7 +1074,7 @@ def yuv420p16_views(buf, h, w, layout='yuv420p10le'):
     high bits) | 'yuv420p10le' | 'yuv420p12le' (Y, Cb, Cr planes, value in the low bits), or ('nv12' | 'nv21' | 'i420', bit_depth,
     msb_aligned)."""
     order, depth, msb = _yuv16_layout(layout)
-    return _yuv_views(buf, h, w, order, (depth, msb))
+    return _yuv_views_format(buf, h, w, '420', order, (depth, msb))
 
 
 def _yuv_size_check(fmt, h, w):
@@ -1256,43 +1268,6 @@ def pack_lr_yuv420p16(frames, standard='bt601-limited', general=False, chroma='r
 
 
 # ---------------------------------------------------------------- every chroma format (include/pnpvcve.h, "Chroma formats")
-def _yuv_views_format(buf, h, w, fmt, order, tail=()):
-    """yuv_views for 4:2:2 | 4:4:4: a packed buffer (..., 2h | 3h, pitch) -> views of the format's class; order 'nv12' | 'nv21' |
-    'i420' (the plane order, as in _yuv_views); tail () or (bit_depth, msb_aligned)"""
-    cls = _YUV_CLASSES[fmt][1 if tail else 0]
-    sx = _native.YUV_FACTORS[fmt][0]
-    _yuv_size_check(fmt, h, w)
-    if tail and (not isinstance(buf, torch.Tensor) or buf.dtype not in _WORD_DTYPES):
-        raise TypeError(f'buf must be a tensor of 16-bit words (torch.int16 / torch.uint16), got {getattr(buf, "dtype", type(buf))}')
-    if not tail and buf.dtype != torch.uint8:
-        raise TypeError(f'buf must be uint8, got {buf.dtype}')
-    rows = h + 2 * h // sx          # Y, then two chroma planes of h rows, w / sx samples each
-    if buf.dim() >= 2 and buf.shape[-2] == rows and buf.shape[-1] >= w and buf.stride(-1) == 1:
-        pitch = buf.shape[-1]
-        y = buf[..., :h, :w]
-        if order != 'i420':         # h rows of chroma pairs: w samples of a row at 4:2:2, 2w samples of two buffer rows at 4:4:4
-            if sx == 2:
-                c = buf[..., h:, :w]
-            elif buf.stride(-2) != pitch:
-                raise ValueError('an interleaved 4:4:4 buffer needs whole rows: a row of chroma pairs is two buffer rows long')
-            else:
-                c = buf[..., h:, :].flatten(-2).unflatten(-1, (h, 2 * pitch))[..., :2 * w]
-            a, b = c[..., 0::2], c[..., 1::2]
-            return cls(y, a, b, *tail) if order == 'nv12' else cls(y, b, a, *tail)
-        if sx == 1:
-            return cls(y, buf[..., h:2 * h, :w], buf[..., 2 * h:, :w], *tail)
-        if pitch % 2 or buf.stride(-2) != pitch:
-            raise ValueError('a planar 4:2:2 buffer needs an even pitch and whole rows: its chroma rows are half a luma row long')
-        flat = buf.flatten(-2)
-        n = h * (pitch // 2)
-        cb = flat[..., h * pitch:h * pitch + n].unflatten(-1, (h, pitch // 2))[..., :w // 2]
-        cr = flat[..., h * pitch + n:h * pitch + 2 * n].unflatten(-1, (h, pitch // 2))[..., :w // 2]
-        return cls(y, cb, cr, *tail)
-    if order == 'i420' and buf.dim() >= 1 and buf.shape[-1] == rows * w and buf.stride(-1) == 1:
-        return _yuv_views_format(buf.unflatten(-1, (rows, w)), h, w, fmt, order, tail)
-    raise ValueError(f'buf must be (..., {rows}, pitch >= {w}) with a unit last stride, got {tuple(buf.shape)}')
-
-
 def yuv_views(buf, h, w, layout):
     """A packed buffer in any layout of any chroma format -> views of the format's frame class (no copy).  4:2:0 layouts: yuv420_views /
     yuv420p16_views.  4:2:2 ('yuv422p', 'nv16', 'yuv422p10le', 'yuv422p12le', 'p210', 'p212'): (..., 2h, pitch); 4:4:4 ('yuv444p',

@@ -3,8 +3,9 @@
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/yuv_probe.py --reps 4
 
 runs `--reps` forwards at the fp32 boundary, at the byte boundary (uint8 HWC in and out) and at the 4:2:0 boundary (NV12 in and out),
-so that pack_lr_kernel / pack_lr_u8_kernel / pack_lr_yuv420_kernel<unsigned char>, the three forms of conv_last and the per-frame converters appear
-in one trace.  Prints wall-clock frames/s per boundary (HIP events; a record, not a benchmark: bench.py measures the headline)."""
+so that pack_lr_kernel / pack_lr_u8_kernel / pack_lr_yuv420_fast_kernel<unsigned char, 2, 0> (the aligned NV12 pack), the three forms
+of conv_last and the per-frame converters appear in one trace.  Prints wall-clock frames/s per boundary (HIP events; a record, not a benchmark: bench.py measures the
+headline)."""
 import argparse
 import json
 import os
