@@ -17,16 +17,8 @@ namespace {
 
 enum { GN_RGB, GN_Y, GN_P8, GN_P16 };
 
-// one clip on any of the sample paths
-struct GnSrc {
-    FrameSrc fs;            // GN_RGB, GN_Y: frames of either format
-    PnpPlaneSrc p8[3];      // GN_P8: Y, Cb, Cr
-    int sel[3];             //        the plane is the second of an interleaved pair
-    Plane16 p16[3];         // GN_P16
-};
-
 struct GnArgs {
-    GnSrc a, l, g;
+    ClipSrc a, l, g;        // GN_RGB, GN_Y: fs; GN_P8 / GN_P16: pl
     PnpGainPlane geo[3];    // GN_P8 / GN_P16: the planes (ok = 0: not in the mask); else geo[0] is the frame of pixels
     int W;                  // GN_RGB / GN_Y: the frame's width, hw = h * w
     long hw;
@@ -74,9 +66,10 @@ __device__ __forceinline__ typename GnTraits<MODE>::Acc gn_err(typename GnTraits
     }
 }
 
-// v[j] = sample (row, col + j) of frame f for j < n, the value of an all-zero sample for n <= j < 4; 1 <= n <= 4
+// v[j] = sample (row, col + j) of frame f for j < n, the value of an all-zero sample for n <= j < 4 -- on the luma path the luma of a
+// black pixel, the same in all three clips, so an absent sample adds 0 to both sums; 1 <= n <= 4
 template <int MODE>
-__device__ __forceinline__ void gn_load4(const GnSrc& s, const GnArgs& g, const double* lt, long f, int plane, int row, int col, int n,
+__device__ __forceinline__ void gn_load4(const ClipSrc& s, const GnArgs& g, const double* lt, long f, int plane, int row, int col, int n,
                                          typename GnTraits<MODE>::T v[4]) {
     if constexpr (MODE == GN_RGB || MODE == GN_Y) {
         unsigned px[4];
@@ -86,37 +79,18 @@ __device__ __forceinline__ void gn_load4(const GnSrc& s, const GnArgs& g, const 
             if constexpr (MODE == GN_Y) v[j] = luma_of(lt, px[j]);
             else v[j] = px[j];
         }
-    } else if constexpr (MODE == GN_P8) {
-        unsigned w[2];
-        pnp_plane_load4(s.p8[plane], f, row, col, n, w);            // bytes >= n are 0
-        const unsigned x = s.sel[plane] ? w[1] : w[0];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = (x >> (8 * j)) & 255u;
     } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = j < n ? load16(s.p16[plane], f, row, col + j) : 0u;
+        plane_load4<MODE == GN_P16>(s.pl[plane], f, row, col, n, v);
     }
 }
 
 // k[j] = the 3-bit class of pixel (row, col + j) for j < n: (par0 != 0) | (par1 != 0) << 1 | (par2 != 0) << 2
 __device__ __forceinline__ void gn_class4(const float* par, long f, long hw, int W, int row, int col, int n, int k[4]) {
+    float v[3][4];                                                  // (the three loads first: 2 - 6 VGPRs fewer than a load and an OR per channel)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) k[j] = 0;
+    for (int c = 0; c < 3; ++c) f32_load4(par + (f * 3 + c) * hw + (long)row * W + col, n, v[c]);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float* p = par + (f * 3 + c) * hw + (long)row * W + col;
-        float v[4];
-        if (n == 4 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = t[j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = j < n ? p[j] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) k[j] |= (v[j] != 0.f ? 1 : 0) << c;
-    }
+    for (int j = 0; j < 4; ++j) k[j] = (v[0][j] != 0.f ? 1 : 0) | (v[1][j] != 0.f ? 2 : 0) | (v[2][j] != 0.f ? 4 : 0);
 }
 
 // grid = (tiles of the largest plane, frames, planes); a block past its plane's tiles, or of a plane outside the mask, has nothing to do
@@ -140,9 +114,9 @@ __global__ __launch_bounds__(256) void gain_kernel(const GnArgs s) {
     pnp_gain_lane_cols(g, tx, lane, col, n, cell);
     const bool classes = CLS && plane == 0;                         // kept on the Y plane / the pixels only
     Acc ea = 0, el = 0;
-    Acc cn[CLS ? 8 : 1], ca[CLS ? 8 : 1], cl[CLS ? 8 : 1];
+    Acc cs[CLS ? 24 : 1];                                           // [class][N, E_a, E_l]
 #pragma unroll
-    for (int c = 0; c < (CLS ? 8 : 1); ++c) cn[c] = ca[c] = cl[c] = 0;
+    for (int c = 0; c < (CLS ? 24 : 1); ++c) cs[c] = 0;
     if (n > 0) {
         for (int row = r0 + wave; row < r1; row += 4) {
             T va[4], vl[4], vg[4];
@@ -161,9 +135,9 @@ __global__ __launch_bounds__(256) void gain_kernel(const GnArgs s) {
 #pragma unroll
                     for (int c = 0; c < 8; ++c) {
                         const bool m = in && k[j] == c;
-                        cn[c] += m ? (Acc)1 : (Acc)0;
-                        ca[c] += m ? xa : (Acc)0;
-                        cl[c] += m ? xl : (Acc)0;
+                        cs[3 * c] += m ? (Acc)1 : (Acc)0;
+                        cs[3 * c + 1] += m ? xa : (Acc)0;
+                        cs[3 * c + 2] += m ? xl : (Acc)0;
                     }
                 }
             }
@@ -183,17 +157,7 @@ __global__ __launch_bounds__(256) void gain_kernel(const GnArgs s) {
         red[wave][cell][0] = wa;
         red[wave][cell][1] = wl;
     }
-    if (CLS && classes) {
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            Wide v[3] = {(Wide)cn[c], (Wide)ca[c], (Wide)cl[c]};
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_down(v[q], off, 64);
-                if (lane == 0) redc[wave][c * 3 + q] = v[q];
-            }
-        }
-    }
+    if (CLS && classes) wave_sums(cs, redc);                        // (block_sums' two halves around the one barrier of both reductions)
     __syncthreads();
     const int t = threadIdx.x;
     if (t < 2 * ncell) {                                            // the only writer of this cell's two sums
@@ -203,7 +167,7 @@ __global__ __launch_bounds__(256) void gain_kernel(const GnArgs s) {
         out[((((frame * s.slots + plane) * g.grows + ti) * g.gcols) + j0 + ce) * 2 + q] = v;
     }
     if (CLS && classes && t < 24) {
-        const Wide v = ((redc[0][t] + redc[1][t]) + redc[2][t]) + redc[3][t];
+        const Wide v = waves_sum(redc, t);
         if constexpr (MODE == GN_Y) {
             static_cast<double*>(s.cls)[(frame * ntiles + blockIdx.x) * 24 + t] = v;
         } else if (v != 0) {
@@ -227,7 +191,7 @@ int launch(GnArgs& s, int frames, int planes, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-// the planes of a clip of a format that the mask names
+// the planes of a clip of a format that the mask names (psnrb.hip has a loop of the same shape; why the two are not shared is said there)
 bool plan_planes(GnArgs& s, int mask, int h, int w, int crop, int block, int format) {
     for (int k = 0; k < 3; ++k) {
         s.geo[k] = pnp_gain_plane(0, 0, 0, 0, 1, 1);
@@ -236,6 +200,16 @@ bool plan_planes(GnArgs& s, int mask, int h, int w, int crop, int block, int for
         if (!s.geo[k].ok) return false;
     }
     return true;
+}
+
+// the launch of the two plane entries, their sources filled
+template <int MODE>
+int launch_planes(GnArgs& s, const float* par, void* grid, void* cls, int frames, void* stream) {
+    s.slots = 3;
+    s.par = par;
+    s.grid = grid;
+    s.cls = cls;
+    return launch<MODE>(s, frames, 3, (hipStream_t)stream);
 }
 
 // par and the class sums come together, and classes are kept on Y
@@ -291,45 +265,28 @@ extern "C" int pnp_gain_sums_yuv(const pnp_yuv420_planes* a, const pnp_yuv420_pl
                                  const float* par, unsigned long long* grid, unsigned long long* cls, int frames, int h, int w,
                                  int crop_border, int block, int chroma_format, void* stream) {
     if (!yuv_format_ok(chroma_format) || !planes_args_ok(a, g, grid, frames, h, w, crop_border, chroma_format) ||
-        !planes_args_ok(l, g, grid, frames, h, w, crop_border, chroma_format) || plane_mask < 1 || plane_mask > 7 || !pnp_gain_block_ok(block) ||
+        !planes_args_ok(l, g, grid, frames, h, w, crop_border, chroma_format) || !plane_mask_ok(plane_mask) || !pnp_gain_block_ok(block) ||
         !class_args_ok(par, cls, plane_mask))
         return PNP_ERR_BAD_ARG;
     GnArgs s = {};
     if (!plan_planes(s, plane_mask, h, w, crop_border, block, chroma_format)) return PNP_ERR_BAD_ARG;
-    for (int side = 0; side < 3; ++side) {
-        const pnp_yuv420_planes& p = side == 0 ? *a : (side == 1 ? *l : *g);
-        GnSrc& d = side == 0 ? s.a : (side == 1 ? s.l : s.g);
-        const ChromaSrc cs = chroma_src(p, h, w, chroma_format);
-        d.p8[0] = luma_src(p, h, w);
-        for (int cr = 0; cr < 2; ++cr) {
-            d.p8[1 + cr] = cs.c[cr];
-            d.sel[1 + cr] = cs.paired && cr != cs.cr_first;         // the plane one byte behind the pair's first
-        }
-    }
-    s.slots = 3;
-    s.par = par;
-    s.grid = grid;
-    s.cls = cls;
-    return launch<GN_P8>(s, frames, 3, (hipStream_t)stream);
+    clip_planes(*a, h, w, chroma_format, s.a.pl);
+    clip_planes(*l, h, w, chroma_format, s.l.pl);
+    clip_planes(*g, h, w, chroma_format, s.g.pl);
+    return launch_planes<GN_P8>(s, par, grid, cls, frames, stream);
 }
 
 extern "C" int pnp_gain_sums_yuvp16(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* l, const pnp_yuv420_planes16* g, int plane_mask,
                                     const float* par, unsigned long long* grid, unsigned long long* cls, int frames, int h, int w,
                                     int crop_border, int block, int chroma_format, void* stream) {
     if (!yuv_format_ok(chroma_format) || !planes16_args_ok(a, g, grid, frames, h, w, crop_border, chroma_format) ||
-        !planes16_args_ok(l, g, grid, frames, h, w, crop_border, chroma_format) || plane_mask < 1 || plane_mask > 7 || !pnp_gain_block_ok(block) ||
+        !planes16_args_ok(l, g, grid, frames, h, w, crop_border, chroma_format) || !plane_mask_ok(plane_mask) || !pnp_gain_block_ok(block) ||
         !class_args_ok(par, cls, plane_mask))
         return PNP_ERR_BAD_ARG;
     GnArgs s = {};
     if (!plan_planes(s, plane_mask, h, w, crop_border, block, chroma_format)) return PNP_ERR_BAD_ARG;
-    for (int k = 0; k < 3; ++k) {
-        s.a.p16[k] = plane16(*a, k);
-        s.l.p16[k] = plane16(*l, k);
-        s.g.p16[k] = plane16(*g, k);
-    }
-    s.slots = 3;
-    s.par = par;
-    s.grid = grid;
-    s.cls = cls;
-    return launch<GN_P16>(s, frames, 3, (hipStream_t)stream);
+    clip_planes(*a, s.a.pl);
+    clip_planes(*l, s.l.pl);
+    clip_planes(*g, s.g.pl);
+    return launch_planes<GN_P16>(s, par, grid, cls, frames, stream);
 }

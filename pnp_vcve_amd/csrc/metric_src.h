@@ -1,7 +1,16 @@
-// The front ends of the device metrics, shared by metrics.hip (PSNR / SSIM of frames), plane_metrics.hip (PSNR / SSIM of 4:2:0
-// planes) and msssim.hip (MS-SSIM on every boundary): how a sample of a clip is fetched -- fp32 planes rounded to the byte, uint8 RGB
-// frames, the optional luma step, 8-bit planes through plane_load.h, 16-bit words -- and what the entries refuse before they look at
-// their statistic.  Everything is internal to the unit that includes it (anonymous namespace); nothing here launches a kernel.
+// The front ends of the device metrics: how a clip is named and how its samples are fetched.  Included by all six metric units --
+// metrics.hip (PSNR / SSIM of frames), plane_metrics.hip (PSNR / SSIM of Y'CbCr planes), msssim.hip, xpsnr.hip, psnrb.hip and gain.hip
+// (the SSIM ones through ssim_tile.h).  What lives here:
+//   - the byte of an fp32 sample (to_u8), the luma step (luma_of and its table), the pixel-group loader of frames (FrameSrc, load_px4);
+//   - one clip on any sample path (ClipSrc; its planes are plane_src.h's PlaneSamp, filled by clip_planes) and the two group loaders
+//     the kernels read through: plane_load4<S16> (8-bit planes through plane_load.h, 16-bit words through load16) and f32_load4.
+//     ONE exception: psnrb_kernel's plane arms keep a private struct and loader (psnrb.hip::PbSrc, pb_load4 -- the shared ones cost
+//     that kernel 5 % / 3 % of a call; profiles/metric_src_refactor.txt), filled on the host from clip_planes all the same;
+//   - the block reduction every deterministic sum leaves through (block_sums);
+//   - what the entries refuse before they look at their statistic, and SSIM's window.
+// The loaders return integers or raw floats, 0 where a group ends: luma_of, to_u8, the channels of a pixel and what an ABSENT sample is
+// worth are the calling kernel's.  Everything is internal to the unit that includes it (anonymous namespace); nothing here launches
+// a kernel.
 #pragma once
 #include "plane_src.h"
 #include "prep.h"
@@ -52,6 +61,18 @@ __device__ __forceinline__ unsigned px_of_f32(float r, float g, float b) {
     return (unsigned)to_u8(r) | ((unsigned)to_u8(g) << 8) | ((unsigned)to_u8(b) << 16);
 }
 
+// v[j] = p[j] for j < n, 0.f for n <= j < 4: ONE aligned 16-byte load where n == 4 and the address allows it, one by one elsewhere
+__device__ __forceinline__ void f32_load4(const float* p, int n, float v[4]) {
+    if (n == 4 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = t[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = j < n ? p[j] : 0.f;
+    }
+}
+
 // One input of a metric: the clip's first frame and, for a byte clip, the bytes [lo, hi) that may be read.
 struct FrameSrc {
     const void* p;
@@ -95,17 +116,7 @@ __device__ __forceinline__ void load_px4(const FrameSrc& s, long frame, long hw,
     const float* f = static_cast<const float*>(s.p) + frame * 3 * hw + p0;
     float v[3][4];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float* fc = f + c * hw;
-        if (npix == 4 && (reinterpret_cast<uintptr_t>(fc) & 15) == 0) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(fc);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[c][j] = t[j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[c][j] = j < npix ? fc[j] : 0.f;
-        }
-    }
+    for (int c = 0; c < 3; ++c) f32_load4(f + c * hw, npix, v[c]);
 #pragma unroll
     for (int j = 0; j < 4; ++j) px[j] = j < npix ? px_of_f32(v[0][j], v[1][j], v[2][j]) : 0u;
 }
@@ -129,22 +140,66 @@ inline bool io_args_ok(const void* a, int fa, const void* b, int fb, int color, 
     return c == 3 || planes_only;
 }
 
-// One plane of a 10 / 12-bit clip (pnp_yuv420_planes16): 2-byte loads, sample (row, col) of frame f is the word at
-// p + f * frame + row * pitch (bytes) + col * step (samples), read as (word >> shift) & mask.
-struct Plane16 {
-    const unsigned short* p;
-    long pitch, frame;
-    int step;
-    unsigned shift, mask;
-};
+// sample (row, col) of frame f of a plane of 16-bit words (plane_src.h)
 __device__ __forceinline__ unsigned load16(const Plane16& s, long f, int row, int col) {
     const unsigned short* q = reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(s.p) + f * s.frame + (long)row * s.pitch);
     return ((unsigned)q[(long)col * s.step] >> s.shift) & s.mask;
 }
-inline Plane16 plane16(const pnp_yuv420_planes16& p, int plane) {      // plane: 0 Y | 1 Cb | 2 Cr
-    const unsigned shift = p.msb_aligned ? 16u - (unsigned)p.bit_depth : 0u, mask = (1u << p.bit_depth) - 1u;
-    if (plane == 0) return Plane16{p.y, p.y_pitch, p.y_frame, 1, shift, mask};
-    return Plane16{plane == 1 ? p.cb : p.cr, p.c_pitch, p.c_frame, p.c_step, shift, mask};
+
+// One clip on any sample path; only the members of the kernel instance's kind are read.
+struct ClipSrc {
+    FrameSrc fs;            // frames of either format; or (frames, C, h, w) fp32 planes at fs.p
+    int C;
+    PlaneSamp pl[3];        // the Y, Cb and Cr planes of a plane clip (clip_planes)
+};
+
+// v[j] = sample (row, col + j) of frame f of the plane for j < n, 0 for n <= j < 4; 1 <= n <= 4.  S16: 16-bit words, one load each;
+// otherwise bytes, a group through the plane loader.  T: the integer (or float) type the caller computes in.
+template <bool S16, class T>
+__device__ __forceinline__ void plane_load4(const PlaneSamp& s, long f, int row, int col, int n, T v[4]) {
+    if (S16) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = j < n ? (T)load16(s.p16, f, row, col + j) : (T)0;
+    } else {
+        unsigned w[2];
+        pnp_plane_load4(s.p8, f, row, col, n, w);           // bytes >= n are 0
+        const unsigned x = s.sel ? w[1] : w[0];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = (T)((x >> (8 * j)) & 255u);
+    }
+}
+
+// The block reduction of every deterministic sum (blocks of 256 threads, red: Wide[4][N] of LDS).  wave_sums: sum n of a wave by
+// shuffles (32, 16, .. 1) into red[wave][n].  waves_sum, behind a barrier: the four waves added in wave order.  block_sums: both; the
+// block's sum n is returned to thread n < N, which stores it, keeps it as an fp64 partial or adds it with `if (v) atomicAdd`.
+// The chains of one or two sums (the SSIM / MS-SSIM kernels: one tile a block, so the tail's latency shows -- MS-SSIM on fp32 planes
+// took 2 % longer with its two chains one after the other) run side by side; more sums go one after the other, so that only one
+// widened sum is live at a time (PSNR-B has up to 15, the gain's classes 24).  Either way a sum's own chain and order are the same.
+template <int N, class Wide, class Acc>
+__device__ __forceinline__ void wave_sums(const Acc (&acc)[N], Wide (*red)[N]) {
+    constexpr int G = N <= 2 ? N : 1;
+#pragma unroll
+    for (int n0 = 0; n0 < N; n0 += G) {
+        Wide v[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) v[g] = acc[n0 + g];
+        for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+            for (int g = 0; g < G; ++g) v[g] += __shfl_down(v[g], off, 64);
+        if ((threadIdx.x & 63) == 0)
+#pragma unroll
+            for (int g = 0; g < G; ++g) red[threadIdx.x >> 6][n0 + g] = v[g];
+    }
+}
+template <int N, class Wide>
+__device__ __forceinline__ Wide waves_sum(Wide (*red)[N], int n) {
+    return ((red[0][n] + red[1][n]) + red[2][n]) + red[3][n];
+}
+template <int N, class Wide, class Acc>
+__device__ __forceinline__ Wide block_sums(const Acc (&acc)[N], Wide (*red)[N]) {
+    wave_sums(acc, red);
+    __syncthreads();
+    return (int)threadIdx.x < N ? waves_sum(red, (int)threadIdx.x) : Wide(0);
 }
 
 // the crop rule of a format: crop_border even where an axis is subsampled (4:2:0, 4:2:2), any value >= 0 at 4:4:4

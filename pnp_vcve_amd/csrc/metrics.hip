@@ -220,16 +220,16 @@ struct PsnrIoArgs {
 };
 
 // !Y: the exact integer SSE of the three channels, one integer atomic per wave like psnr_sse_kernel.  Y: d = Y_a - Y_b in fp32 as the
-// reference subtracts, (double)d * d (exact: 48 bits) summed in fp64 in a fixed order -- a thread's groups in index order, the wave
-// by shuffles, the block's four waves through four doubles of LDS -- and ONE partial per block, which the host adds in index order.
+// reference subtracts, (double)d * d (exact: 48 bits) summed in fp64 in a fixed order -- a thread's groups in index order, then
+// metric_src.h::block_sums -- and ONE partial per block, which the host adds in index order.
 template <bool Y>
 __global__ __launch_bounds__(256) void psnr_io_kernel(const PsnrIoArgs s) {
     __shared__ double lt[Y ? 768 : 1];
-    __shared__ double red[4];
+    __shared__ double red[4][1];
     if (Y) stage_luma_table(lt);
     const long frame = blockIdx.y;
     unsigned long long acc = 0;
-    double accd = 0;
+    double accd[1] = {0};
     for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < s.runs.groups; g += (long)gridDim.x * 256) {
         int npix;
         const long p0 = s.runs.first(g, npix);
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(256) void psnr_io_kernel(const PsnrIoArgs s) {
             if (j >= npix) continue;
             if (Y) {
                 const float d = luma_of(lt, pa[j]) - luma_of(lt, pb[j]);
-                accd += (double)d * (double)d;
+                accd[0] += (double)d * (double)d;
             } else {
                 unsigned e = 0;
 #pragma unroll
@@ -254,10 +254,8 @@ __global__ __launch_bounds__(256) void psnr_io_kernel(const PsnrIoArgs s) {
         }
     }
     if (Y) {
-        for (int off = 32; off > 0; off >>= 1) accd += __shfl_down(accd, off, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = accd;
-        __syncthreads();
-        if (threadIdx.x == 0) s.partial[frame * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+        const double v = block_sums(accd, red);
+        if (threadIdx.x == 0) s.partial[frame * gridDim.x + blockIdx.x] = v;
     } else {
         for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
         if ((threadIdx.x & 63) == 0 && acc) atomicAdd(&s.sse[frame], acc);

@@ -20,18 +20,10 @@ namespace {
 
 enum { K_RGB = 0, K_Y = 1, K_P8 = 2, K_P16 = 3, K_LEVEL = 4 };      // what a kernel instance reads at level 0 (K_LEVEL: the pyramid only)
 
-// One clip's source of one class of planes (only the member of the instance's kind is read)
-struct MsSrc {
-    FrameSrc fs;            // K_RGB, K_Y
-    PnpPlaneSrc p8;         // K_P8
-    Plane16 p16;            // K_P16
-    int sel;                // K_P8: the plane is the second of an interleaved pair
-};
-
 // Planes of one size and source: the channels of RGB frames, the Y of frames, or one plane of a 4:2:0 mask.  A `unit` (the grid's y)
 // is one plane of one frame: frame * planes + channel (K_RGB), the frame otherwise.
 struct MsClass {
-    MsSrc a, b;
+    int plane;              // K_P8 / K_P16: which of the clips' planes (MsArgs::a.pl, b.pl) the class is
     PnpMsPlan plan;
     int H, W, crop;         // the plane before its crop
     int blk0;               // first block of the class along the level kernel's x
@@ -41,6 +33,7 @@ struct MsClass {
 
 struct MsArgs {
     double g[11];
+    ClipSrc a, b;           // the two clips: fs (K_RGB, K_Y) or pl (K_P8, K_P16)
     MsClass cl[3];
     int nclass;
     long slot;              // floats between two units' pyramid slots
@@ -50,7 +43,7 @@ struct MsArgs {
 
 // v[i][j]: sample crop + 4 gx + j (j < npix = 2 | 4) of row crop + 2 r + i of the unit's level-0 plane
 template <int KIND>
-__device__ __forceinline__ void fetch_2x4(const MsSrc& s, const MsClass& c, long unit, int r, int gx, int npix, const double* lt,
+__device__ __forceinline__ void fetch_2x4(const ClipSrc& s, const MsClass& c, long unit, int r, int gx, int npix, const double* lt,
                                           float v[2][4]) {
     const int y0 = c.crop + 2 * r, x0 = c.crop + 4 * gx;
     const long hw = (long)c.H * c.W;
@@ -58,8 +51,7 @@ __device__ __forceinline__ void fetch_2x4(const MsSrc& s, const MsClass& c, long
     for (int i = 0; i < 2; ++i) {
         const long p0 = (long)(y0 + i) * c.W + x0;
         if (KIND == K_P16) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[i][j] = j < npix ? (float)load16(s.p16, unit, y0 + i, x0 + j) : 0.f;
+            plane_load4<true>(s.pl[c.plane], unit, y0 + i, x0, npix, v[i]);
         } else if (KIND == K_Y) {
             unsigned px[4];
             load_px4(s.fs, unit, hw, p0, npix, px);
@@ -73,15 +65,10 @@ __device__ __forceinline__ void fetch_2x4(const MsSrc& s, const MsClass& c, long
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[i][j] = (float)((px[j] >> sh) & 255u);
         } else {                                                                    // K_RGB, fp32 planes (any number of them a frame)
-            const float* f = static_cast<const float*>(s.fs.p) + unit * hw + p0;
-            if (npix == 4 && (reinterpret_cast<uintptr_t>(f) & 15) == 0) {
-                const f32x4 t = *reinterpret_cast<const f32x4*>(f);
+            float x[4];
+            f32_load4(static_cast<const float*>(s.fs.p) + unit * hw + p0, npix, x);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[i][j] = (float)to_u8(t[j]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[i][j] = j < npix ? (float)to_u8(f[j]) : 0.f;
-            }
+            for (int j = 0; j < 4; ++j) v[i][j] = j < npix ? (float)to_u8(x[j]) : 0.f;
         }
     }
 }
@@ -106,8 +93,8 @@ __global__ __launch_bounds__(256) void msssim_down_kernel(const MsArgs s, const 
         const int ncol = dst.cols - 2 * gx < 2 ? 1 : 2;
         float ra[2], rb[2];
         if constexpr (KIND == K_P8) {
-            pnp_ms_down_plane8(c.a.p8, c.a.sel, unit, c.crop, r, gx, ncol, ra);
-            pnp_ms_down_plane8(c.b.p8, c.b.sel, unit, c.crop, r, gx, ncol, rb);
+            pnp_ms_down_plane8(s.a.pl[c.plane].p8, s.a.pl[c.plane].sel, unit, c.crop, r, gx, ncol, ra);
+            pnp_ms_down_plane8(s.b.pl[c.plane].p8, s.b.pl[c.plane].sel, unit, c.crop, r, gx, ncol, rb);
         } else {
             float va[2][4], vb[2][4];
             if constexpr (KIND == K_LEVEL) {
@@ -121,8 +108,8 @@ __global__ __launch_bounds__(256) void msssim_down_kernel(const MsArgs s, const 
                         vb[i][j] = in ? ib[p0 + (long)i * src.cols + j] : 0.f;
                     }
             } else {
-                fetch_2x4<KIND>(c.a, c, unit, r, gx, 2 * ncol, lt, va);
-                fetch_2x4<KIND>(c.b, c, unit, r, gx, 2 * ncol, lt, vb);
+                fetch_2x4<KIND>(s.a, c, unit, r, gx, 2 * ncol, lt, va);
+                fetch_2x4<KIND>(s.b, c, unit, r, gx, 2 * ncol, lt, vb);
             }
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -166,12 +153,12 @@ __global__ __launch_bounds__(256) void msssim_level_kernel(const MsArgs s) {
     if (level > 0) {
         ssim_fill_level(ta, tb, c.wa + unit * s.slot + lv.ws_off, c.wb + unit * s.slot + lv.ws_off, lv.rows, lv.cols, ty0, tx0);
     } else if (KIND == K_P8) {
-        ssim_fill_plane8(ta, tb, c.a.p8, c.b.p8, c.a.sel, c.b.sel, unit, c.H, c.W, c.crop, c.crop, ty0, tx0);
+        ssim_fill_plane8(ta, tb, s.a.pl[c.plane], s.b.pl[c.plane], unit, c.H, c.W, c.crop, c.crop, ty0, tx0);
     } else if (KIND == K_P16) {
-        ssim_fill_plane16(ta, tb, c.a.p16, c.b.p16, unit, c.H, c.W, c.crop, c.crop, ty0, tx0);
+        ssim_fill_plane16(ta, tb, s.a.pl[c.plane], s.b.pl[c.plane], unit, c.H, c.W, c.crop, c.crop, ty0, tx0);
     } else {                                                            // a unit of K_RGB is frame * 3 + channel
         const long frame = KIND == K_Y ? unit : unit / 3;
-        ssim_fill_frames<KIND == K_Y>(ta, tb, c.a.fs, c.b.fs, frame, (int)(unit - frame * 3), c.H, c.W, c.crop, ty0, tx0, lt);
+        ssim_fill_frames<KIND == K_Y>(ta, tb, s.a.fs, s.b.fs, frame, (int)(unit - frame * 3), c.H, c.W, c.crop, ty0, tx0, lt);
     }
     __syncthreads();
     ssim_rows_pass(ta, tb, hm, s.g);
@@ -228,9 +215,26 @@ void place_classes(MsArgs& s, float* ws, long units_per_class) {
     for (int k = s.nclass; k < 3; ++k) s.cl[k] = s.cl[0];
 }
 
-// the plane of `plane` (PNP_PLANE_*) of h x w 4:2:0 frames cropped by `crop` on the Y plane
-PnpMsPlan plane_plan(int h, int w, int crop, int plane) {
-    return plane == PNP_PLANE_Y ? pnp_ms_plan(h, w, crop) : pnp_ms_plan(h / 2, w / 2, crop / 2);
+// The classes of a plane mask over h x w 4:2:0 frames cropped by `crop` on the Y plane (the clips' planes are in s.a.pl, s.b.pl), then
+// what both plane entries set and their launches
+template <int KIND>
+int launch_planes(MsArgs& s, int plane_mask, double* partials, void* workspace, int frames, int h, int w, int crop, double L, void* stream) {
+    s.nclass = 0;
+    for (int p = 0; p < 3; ++p) {
+        if (!(plane_mask & (1 << p))) continue;
+        MsClass& k = s.cl[s.nclass++];
+        k.plane = p;
+        if (p == 0) k.H = h, k.W = w, k.crop = crop;
+        else k.H = h / 2, k.W = w / 2, k.crop = crop / 2;
+        k.plan = pnp_ms_plan(k.H, k.W, k.crop);
+        if (!k.plan.ok) return PNP_ERR_BAD_ARG;                                     // a cropped plane of the mask below 176
+    }
+    s.slot = pnp_ms_plan(h, w, crop).ws_floats;
+    s.partial = partials;
+    s.L = L;
+    ssim_window(s.g);
+    place_classes(s, static_cast<float*>(workspace), frames);
+    return launch_all<KIND>(s, frames, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -264,9 +268,10 @@ extern "C" int pnp_msssim_partials_io(const void* a, int a_format, const void* b
     MsClass& k = s.cl[0];
     k.plan = pnp_ms_plan(h, w, crop_border);
     if (!k.plan.ok) return PNP_ERR_BAD_ARG;
-    k.a = k.b = MsSrc{};
-    k.a.fs = frame_src(a, a_format, frames, h, w);
-    k.b.fs = frame_src(b, b_format, frames, h, w);
+    s.a = s.b = ClipSrc{};
+    s.a.fs = frame_src(a, a_format, frames, h, w);
+    s.b.fs = frame_src(b, b_format, frames, h, w);
+    k.plane = 0;
     k.H = h, k.W = w, k.crop = crop_border;
     const int planes = color == PNP_COLOR_Y ? 1 : c;
     s.nclass = 1;
@@ -281,58 +286,20 @@ extern "C" int pnp_msssim_partials_io(const void* a, int a_format, const void* b
 
 extern "C" int pnp_msssim_partials_yuv420(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, int plane_mask, double* partials,
                                           void* workspace, int frames, int h, int w, int crop_border, void* stream) {
-    if (!planes_args_ok(a, b, partials, frames, h, w, crop_border) || !workspace || plane_mask < 1 || plane_mask > 7) return PNP_ERR_BAD_ARG;
+    if (!planes_args_ok(a, b, partials, frames, h, w, crop_border) || !workspace || !plane_mask_ok(plane_mask)) return PNP_ERR_BAD_ARG;
     MsArgs s;
-    s.nclass = 0;
-    const ChromaSrc ac = chroma_src(*a, h, w), bc = chroma_src(*b, h, w);
-    for (int bit = 1; bit < 8; bit <<= 1) {
-        if (!(plane_mask & bit)) continue;
-        MsClass& k = s.cl[s.nclass++];
-        k.plan = plane_plan(h, w, crop_border, bit);
-        if (!k.plan.ok) return PNP_ERR_BAD_ARG;                                     // a cropped plane of the mask below 176
-        k.a = k.b = MsSrc{};
-        if (bit == PNP_PLANE_Y) {
-            k.a.p8 = luma_src(*a, h, w);
-            k.b.p8 = luma_src(*b, h, w);
-            k.H = h, k.W = w, k.crop = crop_border;
-        } else {
-            const int cr = bit == PNP_PLANE_CR;
-            k.a.p8 = ac.c[cr];
-            k.b.p8 = bc.c[cr];
-            k.a.sel = ac.paired && cr != ac.cr_first;                                // the plane one byte behind the pair's first
-            k.b.sel = bc.paired && cr != bc.cr_first;
-            k.H = h / 2, k.W = w / 2, k.crop = crop_border / 2;
-        }
-    }
-    s.slot = pnp_ms_plan(h, w, crop_border).ws_floats;
-    s.partial = partials;
-    s.L = 255.0;
-    ssim_window(s.g);
-    place_classes(s, static_cast<float*>(workspace), frames);
-    return launch_all<K_P8>(s, frames, (hipStream_t)stream);
+    s.a = s.b = ClipSrc{};
+    clip_planes(*a, h, w, PNP_YUV_FORMAT_420, s.a.pl);
+    clip_planes(*b, h, w, PNP_YUV_FORMAT_420, s.b.pl);
+    return launch_planes<K_P8>(s, plane_mask, partials, workspace, frames, h, w, crop_border, 255.0, stream);
 }
 
 extern "C" int pnp_msssim_partials_yuv420p16(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, int plane_mask, double* partials,
                                              void* workspace, int frames, int h, int w, int crop_border, void* stream) {
-    if (!planes16_args_ok(a, b, partials, frames, h, w, crop_border) || !workspace || plane_mask < 1 || plane_mask > 7) return PNP_ERR_BAD_ARG;
+    if (!planes16_args_ok(a, b, partials, frames, h, w, crop_border) || !workspace || !plane_mask_ok(plane_mask)) return PNP_ERR_BAD_ARG;
     MsArgs s;
-    s.nclass = 0;
-    for (int p = 0; p < 3; ++p) {
-        const int bit = 1 << p;
-        if (!(plane_mask & bit)) continue;
-        MsClass& k = s.cl[s.nclass++];
-        k.plan = plane_plan(h, w, crop_border, bit);
-        if (!k.plan.ok) return PNP_ERR_BAD_ARG;                                     // a cropped plane of the mask below 176
-        k.a = k.b = MsSrc{};
-        k.a.p16 = plane16(*a, p);
-        k.b.p16 = plane16(*b, p);
-        if (p == 0) k.H = h, k.W = w, k.crop = crop_border;
-        else k.H = h / 2, k.W = w / 2, k.crop = crop_border / 2;
-    }
-    s.slot = pnp_ms_plan(h, w, crop_border).ws_floats;
-    s.partial = partials;
-    s.L = (double)((1 << a->bit_depth) - 1);
-    ssim_window(s.g);
-    place_classes(s, static_cast<float*>(workspace), frames);
-    return launch_all<K_P16>(s, frames, (hipStream_t)stream);
+    s.a = s.b = ClipSrc{};
+    clip_planes(*a, s.a.pl);
+    clip_planes(*b, s.b.pl);
+    return launch_planes<K_P16>(s, plane_mask, partials, workspace, frames, h, w, crop_border, (double)((1 << a->bit_depth) - 1), stream);
 }

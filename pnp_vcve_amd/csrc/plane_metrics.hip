@@ -71,28 +71,17 @@ __global__ __launch_bounds__(256) void psnr_yuv420_kernel(const PsnrYuvArgs s) {
             }
         }
     }
-    // wave reduction, the block's four waves through LDS, then one atomic per block and plane
+    // the block's three sums (metric_src.h::block_sums), then one atomic per block and plane
     __shared__ unsigned long long red[4][3];
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-        unsigned long long v = acc[p];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if (tx == 0) red[ty][p] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const unsigned long long v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        if (v) atomicAdd(&s.sse[frame * 3 + threadIdx.x], v);
-    }
+    const unsigned long long v = block_sums(acc, red);
+    if (threadIdx.x < 3 && v) atomicAdd(&s.sse[frame * 3 + threadIdx.x], v);
 }
 
 // ssim_kernel (metrics.hip) with the plane loader in front: the tile body is ssim_tile.h's, as it is ssim_kernel's, so a plane gives the
 // partials of its (frames,1,rows,cols) fp32 plane byte / 255.0f bit for bit (to_u8 of that value is the byte).  One launch serves
 // every plane of the mask: blocks [blk0, blk0 + blocks) of the grid's x are plane k's.
 struct SsimPlane {
-    PnpPlaneSrc a, b;
-    Plane16 a16, b16;       // the 16-bit sample path's planes (ssim_yuv420_kernel<true>)
-    int a_sel, b_sel;       // which word of the loader's pair the plane is (1: the second of an interleaved pair)
+    PlaneSamp a, b;         // the plane of the two clips (clip_planes)
     int H, W, cropy, cropx, oh, ow, tiles_x, blocks, blk0;      // (a crop per axis: 4:2:2 chroma is cropped by c down, c / 2 across)
     long out0;              // first partial of this plane
 };
@@ -117,8 +106,8 @@ __global__ __launch_bounds__(256) void ssim_yuv420_kernel(const SsimYuvArgs s) {
     const int blk = blockIdx.x - p.blk0;
     const long frame = blockIdx.y;
     const int ty0 = (blk / p.tiles_x) * SSIM_OUT_R, tx0 = (blk % p.tiles_x) * SSIM_OUT_C;        // in valid-map coordinates
-    if (S16) ssim_fill_plane16(ta, tb, p.a16, p.b16, frame, p.H, p.W, p.cropy, p.cropx, ty0, tx0);
-    else ssim_fill_plane8(ta, tb, p.a, p.b, p.a_sel, p.b_sel, frame, p.H, p.W, p.cropy, p.cropx, ty0, tx0);
+    if (S16) ssim_fill_plane16(ta, tb, p.a, p.b, frame, p.H, p.W, p.cropy, p.cropx, ty0, tx0);
+    else ssim_fill_plane8(ta, tb, p.a, p.b, frame, p.H, p.W, p.cropy, p.cropx, ty0, tx0);
     __syncthreads();
     ssim_rows_pass(ta, tb, hm, s.g);
     __syncthreads();
@@ -158,26 +147,18 @@ __global__ __launch_bounds__(256) void psnr_yuv420p16_kernel(const Psnr16Args s)
         }
     }
     __shared__ unsigned long long red[4][3];
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-        unsigned long long v = acc[p];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if (tx == 0) red[ty][p] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const unsigned long long v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        if (v) atomicAdd(&s.sse[frame * 3 + threadIdx.x], v);
-    }
+    const unsigned long long v = block_sums(acc, red);
+    if (threadIdx.x < 3 && v) atomicAdd(&s.sse[frame * 3 + threadIdx.x], v);
 }
 
 }  // namespace
 
 namespace {
 
-// the planes of the mask, in the order Y, Cb, Cr, laid out in one grid and one partials array; false: a cropped plane below 11x11
-template <class Fill>
-bool ssim_planes(SsimYuvArgs& s, int plane_mask, int frames, int h, int w, int crop, int format, int& blk0, Fill fill) {
+// the planes of the mask, in the order Y, Cb, Cr, laid out in one grid and one partials array, and the window; a, b: the two clips'
+// planes (clip_planes); false: a cropped plane below 11x11
+bool ssim_planes(SsimYuvArgs& s, const PlaneSamp (&a)[3], const PlaneSamp (&b)[3], int plane_mask, int frames, int h, int w, int crop, int format,
+                 int& blk0) {
     s.nplanes = 0;
     blk0 = 0;
     long out0 = 0;
@@ -187,7 +168,7 @@ bool ssim_planes(SsimYuvArgs& s, int plane_mask, int frames, int h, int w, int c
         const int nb = pnp_ssim_blocks_yuv(h, w, crop, bit, format);
         if (nb < 1) return false;
         SsimPlane& p = s.pl[s.nplanes++];
-        fill(p, k);
+        p.a = a[k], p.b = b[k];
         const PlaneGeom g = plane_geom(h, w, crop, bit, format);
         p.H = g.H, p.W = g.W, p.cropy = g.cropy, p.cropx = g.cropx;
         p.oh = p.H - 2 * p.cropy - 10;
@@ -200,6 +181,7 @@ bool ssim_planes(SsimYuvArgs& s, int plane_mask, int frames, int h, int w, int c
         out0 += (long)frames * nb;
     }
     for (int k = s.nplanes; k < 3; ++k) s.pl[k] = s.pl[0];
+    ssim_window(s.g);
     return true;
 }
 
@@ -244,29 +226,16 @@ extern "C" int pnp_ssim_blocks_yuv420(int h, int w, int crop_border, int plane) 
 
 extern "C" int pnp_ssim_partials_yuv(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, int plane_mask, double* partials, int frames,
                                      int h, int w, int crop_border, int chroma_format, void* stream) {
-    if (!yuv_format_ok(chroma_format) || !planes_args_ok(a, b, partials, frames, h, w, crop_border, chroma_format) || plane_mask < 1 || plane_mask > 7)
+    if (!yuv_format_ok(chroma_format) || !planes_args_ok(a, b, partials, frames, h, w, crop_border, chroma_format) || !plane_mask_ok(plane_mask))
         return PNP_ERR_BAD_ARG;
     SsimYuvArgs s;
     s.partial = partials;
-    const ChromaSrc ac = chroma_src(*a, h, w, chroma_format), bc = chroma_src(*b, h, w, chroma_format);
-    int blk0 = 0;
-    const bool ok = ssim_planes(s, plane_mask, frames, h, w, crop_border, chroma_format, blk0, [&](SsimPlane& p, int k) {
-        p.a16 = p.b16 = Plane16{};
-        if (k == 0) {
-            p.a = luma_src(*a, h, w);
-            p.b = luma_src(*b, h, w);
-            p.a_sel = p.b_sel = 0;
-        } else {
-            const int cr = k == 2;
-            p.a = ac.c[cr];
-            p.b = bc.c[cr];
-            p.a_sel = ac.paired && cr != ac.cr_first;                // the plane one byte behind the pair's first
-            p.b_sel = bc.paired && cr != bc.cr_first;
-        }
-    });
-    if (!ok) return PNP_ERR_BAD_ARG;                                 // a cropped plane of the mask below 11x11
-    ssim_window(s.g);
     s.L = 255.0;
+    PlaneSamp pa[3], pb[3];
+    clip_planes(*a, h, w, chroma_format, pa);
+    clip_planes(*b, h, w, chroma_format, pb);
+    int blk0 = 0;
+    if (!ssim_planes(s, pa, pb, plane_mask, frames, h, w, crop_border, chroma_format, blk0)) return PNP_ERR_BAD_ARG;      // a cropped plane of the mask below 11x11
     hipLaunchKernelGGL(ssim_yuv420_kernel<false>, dim3(blk0, frames), dim3(256), 0, (hipStream_t)stream, s);
     return (int)hipGetLastError();
 }
@@ -302,20 +271,16 @@ extern "C" int pnp_psnr_sse_yuv420p16(const pnp_yuv420_planes16* a, const pnp_yu
 
 extern "C" int pnp_ssim_partials_yuvp16(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, int plane_mask, double* partials,
                                         int frames, int h, int w, int crop_border, int chroma_format, void* stream) {
-    if (!yuv_format_ok(chroma_format) || !planes16_args_ok(a, b, partials, frames, h, w, crop_border, chroma_format) || plane_mask < 1 || plane_mask > 7)
+    if (!yuv_format_ok(chroma_format) || !planes16_args_ok(a, b, partials, frames, h, w, crop_border, chroma_format) || !plane_mask_ok(plane_mask))
         return PNP_ERR_BAD_ARG;
     SsimYuvArgs s;
     s.partial = partials;
     s.L = (double)((1 << a->bit_depth) - 1);
+    PlaneSamp pa[3], pb[3];
+    clip_planes(*a, pa);
+    clip_planes(*b, pb);
     int blk0 = 0;
-    const bool ok = ssim_planes(s, plane_mask, frames, h, w, crop_border, chroma_format, blk0, [&](SsimPlane& p, int k) {
-        p.a = p.b = PnpPlaneSrc{};
-        p.a_sel = p.b_sel = 0;
-        p.a16 = plane16(*a, k);
-        p.b16 = plane16(*b, k);
-    });
-    if (!ok) return PNP_ERR_BAD_ARG;                                 // a cropped plane of the mask below 11x11
-    ssim_window(s.g);
+    if (!ssim_planes(s, pa, pb, plane_mask, frames, h, w, crop_border, chroma_format, blk0)) return PNP_ERR_BAD_ARG;      // a cropped plane of the mask below 11x11
     hipLaunchKernelGGL(ssim_yuv420_kernel<true>, dim3(blk0, frames), dim3(256), 0, (hipStream_t)stream, s);
     return (int)hipGetLastError();
 }

@@ -1,7 +1,8 @@
 // The planes of a Y'CbCr clip as sources of the plane loader (plane_load.h): the Y plane, and the chroma planes with the rows and
-// columns their chroma format gives them (yuv.h: (h / sy) x (w / sx)), and the geometry and crop of a plane of a format.  Host code
-// only, shared by the plane-metric units through metric_src.h; tests/host/yuv_formats_desc.cpp walks these very sources through
-// pnp_plane_load4 over exactly-sized heap blocks under AddressSanitizer (-DPNP_HOST_STUB).
+// columns their chroma format gives them (yuv.h: (h / sy) x (w / sx)), the geometry and crop of a plane of a format, and -- what every
+// plane entry of the device metrics fills its kernel arguments with -- the three planes of a clip on either sample path (PlaneSamp,
+// clip_planes).  Host code only, shared by the metric units through metric_src.h; tests/host/yuv_formats_desc.cpp walks these very
+// sources through pnp_plane_load4 over exactly-sized heap blocks under AddressSanitizer (-DPNP_HOST_STUB).
 #pragma once
 #include "plane_load.h"
 #include "yuv.h"
@@ -40,3 +41,38 @@ static inline PlaneGeom plane_geom(int h, int w, int crop, int plane, int format
     const int sx = yuv_sx(format), sy = yuv_sy(format);
     return PlaneGeom{h / sy, w / sx, crop / sy, crop / sx};
 }
+
+// One plane of a 10 / 12-bit clip (pnp_yuv420_planes16): 2-byte loads, sample (row, col) of frame f is the word at
+// p + f * frame + row * pitch (bytes) + col * step (samples), read as (word >> shift) & mask (metric_src.h::load16).
+struct Plane16 {
+    const unsigned short* p;
+    long pitch, frame;
+    int step;
+    unsigned shift, mask;
+};
+static inline Plane16 plane16(const pnp_yuv420_planes16& p, int plane) {      // plane: 0 Y | 1 Cb | 2 Cr
+    const unsigned shift = p.msb_aligned ? 16u - (unsigned)p.bit_depth : 0u, mask = (1u << p.bit_depth) - 1u;
+    if (plane == 0) return Plane16{p.y, p.y_pitch, p.y_frame, 1, shift, mask};
+    return Plane16{plane == 1 ? p.cb : p.cr, p.c_pitch, p.c_frame, p.c_step, shift, mask};
+}
+
+// One plane of one clip on either sample path; only the members of the kernel instance's kind are read.
+struct PlaneSamp {
+    PnpPlaneSrc p8;         // 8-bit: the plane, or the interleaved pair it is one of, as pnp_plane_load4 reads it
+    int sel;                //        the plane is the second word of the loader's pair
+    Plane16 p16;            // 16-bit words
+};
+
+// out = the Y, Cb and Cr planes of a clip of h x w frames of a chroma format (PNP_YUV_FORMAT_*) / of a 16-bit clip
+static inline void clip_planes(const pnp_yuv420_planes& p, int h, int w, int format, PlaneSamp out[3]) {
+    const ChromaSrc cs = chroma_src(p, h, w, format);
+    out[0] = PlaneSamp{luma_src(p, h, w), 0, Plane16{}};
+    for (int cr = 0; cr < 2; ++cr)
+        out[1 + cr] = PlaneSamp{cs.c[cr], cs.paired && cr != cs.cr_first, Plane16{}};      // sel: the plane one byte behind the pair's first
+}
+static inline void clip_planes(const pnp_yuv420_planes16& p, PlaneSamp out[3]) {
+    for (int k = 0; k < 3; ++k) out[k] = PlaneSamp{PnpPlaneSrc{}, 0, plane16(p, k)};
+}
+
+// a plane mask names at least one of PNP_PLANE_Y | PNP_PLANE_CB | PNP_PLANE_CR and nothing else
+static inline bool plane_mask_ok(int mask) { return mask >= 1 && mask <= 7; }

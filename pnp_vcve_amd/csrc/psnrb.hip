@@ -17,7 +17,10 @@ namespace {
 
 enum { PB_RGB, PB_Y, PB_F32, PB_P8, PB_P16 };
 
-// one clip on any of the five sample paths
+// One clip on any of the five sample paths.  NOT metric_src.h's ClipSrc / plane_load4: with them psnrb_kernel<PB_P8> / <PB_P16> took
+// 28.3 / 36.1 us a call against 26.8 / 35.0 (tools/bench_psnrb.py, profiles/metric_src_refactor.txt), at the same registers and within
+// 12 instructions of the same listing; with this struct and the loader below the time is the parent's.  The host side fills it from
+// clip_planes like every other plane entry, and the sums leave through block_sums.
 struct PbSrc {
     FrameSrc fs;            // PB_RGB, PB_Y: frames of either format; PB_F32: (frames, C, h, w) fp32 planes
     int C;
@@ -55,7 +58,8 @@ struct PbTraits<PB_Y> {
 __device__ __forceinline__ unsigned pb_sq(int d) { return (unsigned)(d * d); }
 __device__ __forceinline__ double pb_sq(float d) { return (double)d * (double)d; }
 
-// v[c][j] = sample (row, col + j) of frame f for j < n, 0 for n <= j < 4; 1 <= n <= 4
+// v[c][j] = sample (row, col + j) of frame f for j < n, 0 for n <= j < 4 -- on the luma path too, where an absent sample is 0 and not
+// the luma of a black pixel: absent samples only ever meet absent samples; 1 <= n <= 4
 template <int MODE>
 __device__ __forceinline__ void pb_load4(const PbSrc& s, const PbArgs& g, const double* lt, long f, int plane, int row, int col, int n,
                                          typename PbTraits<MODE>::T v[][4]) {
@@ -72,15 +76,10 @@ __device__ __forceinline__ void pb_load4(const PbSrc& s, const PbArgs& g, const 
             }
         }
     } else if (MODE == PB_F32) {
-        const float* fc = static_cast<const float*>(s.fs.p) + (f * s.C + plane) * g.hw + (long)row * g.W + col;
-        if (n == 4 && (reinterpret_cast<uintptr_t>(fc) & 15) == 0) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(fc);
+        float x[4];
+        f32_load4(static_cast<const float*>(s.fs.p) + (f * s.C + plane) * g.hw + (long)row * g.W + col, n, x);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) v[0][j] = to_u8(t[j]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[0][j] = j < n ? to_u8(fc[j]) : 0;
-        }
+        for (int j = 0; j < 4; ++j) v[0][j] = to_u8(x[j]);         // (to_u8(0.f) = 0)
     } else if (MODE == PB_P8) {
         unsigned w[2];
         pnp_plane_load4(s.p8[plane], f, row, col, n, w);
@@ -102,6 +101,7 @@ __global__ __launch_bounds__(256) void psnrb_kernel(const PbArgs s) {
     constexpr int NCH = PbTraits<MODE>::NCH;
     __shared__ double lt[MODE == PB_Y ? 768 : 1];
     __shared__ Wide red[4][NCH * 5];
+    Acc acc[NCH * 5];                                               // [channel][sum]
     const int plane = blockIdx.z;
     const PnpPbPlane g = s.geo[(MODE == PB_P8 || MODE == PB_P16) ? plane : 0];
     const int ntiles = g.tiles_x * g.tiles_y;
@@ -115,12 +115,11 @@ __global__ __launch_bounds__(256) void psnrb_kernel(const PbArgs s) {
     pnp_pb_lane_cols(g, tx, lane, col, n);
     const bool right = n == 4 && col + 4 < g.x1;                    // the pair (col + 3, col + 4) exists
     const int rend = r1 > r0 && r1 < g.y1 ? r1 + 1 : r1;            // row r1 is read for the pairs (r1 - 1, r1) only
-    Acc acc[NCH][5];
     T prev[NCH][4];
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
 #pragma unroll
-        for (int q = 0; q < 5; ++q) acc[c][q] = 0;
+        for (int q = 0; q < 5; ++q) acc[c * 5 + q] = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) prev[c][j] = 0;
     }
@@ -147,7 +146,7 @@ __global__ __launch_bounds__(256) void psnrb_kernel(const PbArgs s) {
 #pragma unroll
                 for (int c = 0; c < NCH; ++c)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[c][0] += pb_sq(cur[c][j] - ref[c][j]);      // absent samples are 0 in both
+                    for (int j = 0; j < 4; ++j) acc[c * 5] += pb_sq(cur[c][j] - ref[c][j]);      // absent samples are 0 in both
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -157,8 +156,8 @@ __global__ __launch_bounds__(256) void psnrb_kernel(const PbArgs s) {
                 for (int c = 0; c < NCH; ++c) {
                     const T nb = j < 3 ? cur[c][(j + 1) & 3] : nxt[c];
                     const Acc e = exists ? (Acc)pb_sq(cur[c][j] - nb) : (Acc)0;
-                    acc[c][1] += bnd ? e : (Acc)0;
-                    acc[c][2] += bnd ? (Acc)0 : e;
+                    acc[c * 5 + 1] += bnd ? e : (Acc)0;
+                    acc[c * 5 + 2] += bnd ? (Acc)0 : e;
                 }
             }
         }
@@ -169,8 +168,8 @@ __global__ __launch_bounds__(256) void psnrb_kernel(const PbArgs s) {
                 Acc e = 0;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) e += pb_sq(prev[c][j] - cur[c][j]);                 // absent samples are 0 in both rows
-                if (q == 3) acc[c][3] += e;
-                else acc[c][4] += e;
+                if (q == 3) acc[c * 5 + 3] += e;
+                else acc[c * 5 + 4] += e;
             }
         }
 #pragma unroll
@@ -178,21 +177,11 @@ __global__ __launch_bounds__(256) void psnrb_kernel(const PbArgs s) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) prev[c][j] = cur[c][j];
     }
-    // registers -> the wave by shuffles -> the block's four waves through LDS -> one integer atomic per block and sum, or (Y) the block's
-    // own five partials, added in a fixed order
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-#pragma unroll
-        for (int q = 0; q < 5; ++q) {
-            Wide v = acc[c][q];
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-            if (lane == 0) red[wave][c * 5 + q] = v;
-        }
-    }
-    __syncthreads();
+    // registers -> the block's sums (metric_src.h::block_sums) -> one integer atomic per block and sum, or (Y) the block's own five
+    // partials, added in a fixed order
+    const Wide v = block_sums(acc, red);
     const int t = threadIdx.x;
     if (t < NCH * 5) {
-        const Wide v = red[0][t] + red[1][t] + red[2][t] + red[3][t];
         if (MODE == PB_Y) {
             s.partial[(frame * ntiles + blockIdx.x) * 5 + t] = (double)v;
         } else if (v != 0) {
@@ -216,15 +205,30 @@ int launch(PbArgs& s, int frames, int planes, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-// the planes of a 4:2:0 clip that the mask names: Y with `block`, Cb / Cr with half of it and half the crop
+// the planes of a 4:2:0 clip that the mask names: Y with `block`, Cb / Cr with half of it and half the crop.  (gain.hip has a loop of
+// the same shape; the two are not shared: the plans are different structs made from different arguments, and a template over both
+// would need a functor per unit that is as long as the loop.)
 bool plan_planes(PbArgs& s, int mask, int h, int w, int crop, int block) {
     for (int k = 0; k < 3; ++k) {
         s.geo[k] = pnp_pb_plane(0, 0, 0, 0);
-        if (!(mask & (k == 0 ? PNP_PLANE_Y : (k == 1 ? PNP_PLANE_CB : PNP_PLANE_CR)))) continue;
+        if (!(mask & (1 << k))) continue;
         s.geo[k] = k == 0 ? pnp_pb_plane(h, w, crop, block) : pnp_pb_plane(h / 2, w / 2, crop / 2, block / 2);
         if (!s.geo[k].ok) return false;
     }
     return true;
+}
+
+// the launch of the two plane entries: pa, pb = the planes of the two clips (clip_planes; pb: nullptr without a reference)
+template <int MODE>
+int launch_planes(PbArgs& s, const PlaneSamp* pa, const PlaneSamp* pb, unsigned long long* sums, int frames, void* stream) {
+    for (int k = 0; k < 3; ++k) {
+        s.a.p8[k] = pa[k].p8, s.a.sel[k] = pa[k].sel, s.a.p16[k] = pa[k].p16;
+        if (pb) s.b.p8[k] = pb[k].p8, s.b.sel[k] = pb[k].sel, s.b.p16[k] = pb[k].p16;
+    }
+    s.has_b = pb != nullptr;
+    s.slots = 3;
+    s.sums = sums;
+    return launch<MODE>(s, frames, 3, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -268,38 +272,22 @@ extern "C" int pnp_psnrb_sums_io(const void* a, int a_format, const void* b, int
 
 extern "C" int pnp_psnrb_sums_yuv420(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, int plane_mask, unsigned long long* sums,
                                      int frames, int h, int w, int crop_border, int block, void* stream) {
-    if (!planes_args_ok(a, b ? b : a, sums, frames, h, w, crop_border) || plane_mask < 1 || plane_mask > 7 || !block_ok(block))
-        return PNP_ERR_BAD_ARG;
+    if (!planes_args_ok(a, b ? b : a, sums, frames, h, w, crop_border) || !plane_mask_ok(plane_mask) || !block_ok(block)) return PNP_ERR_BAD_ARG;
     PbArgs s = {};
     if (!plan_planes(s, plane_mask, h, w, crop_border, block)) return PNP_ERR_BAD_ARG;
-    for (int side = 0; side < (b ? 2 : 1); ++side) {
-        const pnp_yuv420_planes& p = side ? *b : *a;
-        PbSrc& d = side ? s.b : s.a;
-        const ChromaSrc cs = chroma_src(p, h, w);
-        d.p8[0] = luma_src(p, h, w);
-        for (int cr = 0; cr < 2; ++cr) {
-            d.p8[1 + cr] = cs.c[cr];
-            d.sel[1 + cr] = cs.paired && cr != cs.cr_first;         // the plane one byte behind the pair's first
-        }
-    }
-    s.has_b = b != nullptr;
-    s.slots = 3;
-    s.sums = sums;
-    return launch<PB_P8>(s, frames, 3, (hipStream_t)stream);
+    PlaneSamp pa[3], pb[3];
+    clip_planes(*a, h, w, PNP_YUV_FORMAT_420, pa);
+    if (b) clip_planes(*b, h, w, PNP_YUV_FORMAT_420, pb);
+    return launch_planes<PB_P8>(s, pa, b ? pb : nullptr, sums, frames, stream);
 }
 
 extern "C" int pnp_psnrb_sums_yuv420p16(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, int plane_mask, unsigned long long* sums,
                                         int frames, int h, int w, int crop_border, int block, void* stream) {
-    if (!planes16_args_ok(a, b ? b : a, sums, frames, h, w, crop_border) || plane_mask < 1 || plane_mask > 7 || !block_ok(block))
-        return PNP_ERR_BAD_ARG;
+    if (!planes16_args_ok(a, b ? b : a, sums, frames, h, w, crop_border) || !plane_mask_ok(plane_mask) || !block_ok(block)) return PNP_ERR_BAD_ARG;
     PbArgs s = {};
     if (!plan_planes(s, plane_mask, h, w, crop_border, block)) return PNP_ERR_BAD_ARG;
-    for (int k = 0; k < 3; ++k) {
-        s.a.p16[k] = plane16(*a, k);
-        if (b) s.b.p16[k] = plane16(*b, k);
-    }
-    s.has_b = b != nullptr;
-    s.slots = 3;
-    s.sums = sums;
-    return launch<PB_P16>(s, frames, 3, (hipStream_t)stream);
+    PlaneSamp pa[3], pb[3];
+    clip_planes(*a, pa);
+    if (b) clip_planes(*b, pb);
+    return launch_planes<PB_P16>(s, pa, b ? pb : nullptr, sums, frames, stream);
 }

@@ -3,7 +3,7 @@
 // reference.  One block of 256 threads = a 16 x 32 tile of the valid map of one plane: the two 26 x 42 input tiles go to LDS as fp32
 // (a fill below), the horizontal pass leaves the five windowed moments of 26 x 32 positions in LDS, the vertical pass finishes them
 // and hands mu1, mu2, sg1, sg2, sg12 to the caller's closing expression; the block's sums go through wave shuffles and four doubles
-// of LDS per sum to ONE partial each (deterministic; the host adds them).  Every kernel that uses the body declares
+// of LDS per sum (metric_src.h::block_sums) to ONE partial each (deterministic; the host adds them).  Every kernel that uses the body declares
 //     __shared__ float ta[SSIM_TILE], tb[SSIM_TILE];  __shared__ double hm[5][SSIM_HM];  __shared__ double red[4][N];
 // The kernels agree to the bit because they run these statements; nothing here is a kernel or launches one.
 #pragma once
@@ -68,11 +68,11 @@ __device__ __forceinline__ void ssim_fill_frames(float* ta, float* tb, const Fra
 }
 
 // 16-bit words, fetched one by one
-__device__ __forceinline__ void ssim_fill_plane16(float* ta, float* tb, const Plane16& a, const Plane16& b, long frame, int H, int W, int cropy,
+__device__ __forceinline__ void ssim_fill_plane16(float* ta, float* tb, const PlaneSamp& a, const PlaneSamp& b, long frame, int H, int W, int cropy,
                                                   int cropx, int ty0, int tx0) {
     ssim_fill(ta, tb, H, W, cropy, cropx, ty0, tx0, [&](int y, int x, float& va, float& vb) {
-        va = (float)load16(a, frame, y, x);
-        vb = (float)load16(b, frame, y, x);
+        va = (float)load16(a.p16, frame, y, x);
+        vb = (float)load16(b.p16, frame, y, x);
     });
 }
 
@@ -84,26 +84,24 @@ __device__ __forceinline__ void ssim_fill_level(float* ta, float* tb, const floa
     });
 }
 
-// 8-bit planes through the plane loader, a group of four bytes a thread and step; sel: the plane is the second word of the loader's
-// pair (the later plane of an interleaved pair)
-__device__ __forceinline__ void ssim_fill_plane8(float* ta, float* tb, const PnpPlaneSrc& a, const PnpPlaneSrc& b, int a_sel, int b_sel, long frame,
-                                                 int H, int W, int cropy, int cropx, int ty0, int tx0) {
+// 8-bit planes through the plane loader (metric_src.h::plane_load4), a group of four bytes a thread and step
+__device__ __forceinline__ void ssim_fill_plane8(float* ta, float* tb, const PlaneSamp& a, const PlaneSamp& b, long frame, int H, int W, int cropy,
+                                                 int cropx, int ty0, int tx0) {
     for (int i = threadIdx.x; i < SSIM_IN_R * SSIM_GROUPS; i += 256) {
         const int r = i / SSIM_GROUPS, gc = i - r * SSIM_GROUPS;
         const int y = cropy + ty0 + r, x = cropx + tx0 + 4 * gc;
         int npix = SSIM_IN_C - 4 * gc < 4 ? SSIM_IN_C - 4 * gc : 4;
         if (W - cropx - x < npix) npix = W - cropx - x;
-        unsigned wa[2] = {0, 0}, wb[2] = {0, 0};
+        float va[4] = {0.f, 0.f, 0.f, 0.f}, vb[4] = {0.f, 0.f, 0.f, 0.f};
         if (y < H - cropy && npix > 0) {
-            pnp_plane_load4(a, frame, y, x, npix, wa);
-            pnp_plane_load4(b, frame, y, x, npix, wb);
+            plane_load4<false>(a, frame, y, x, npix, va);
+            plane_load4<false>(b, frame, y, x, npix, vb);
         }
-        const unsigned va = a_sel ? wa[1] : wa[0], vb = b_sel ? wb[1] : wb[0];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (4 * gc + j < SSIM_IN_C) {
-                ta[r * SSIM_IN_C + 4 * gc + j] = (float)((va >> (8 * j)) & 255u);
-                tb[r * SSIM_IN_C + 4 * gc + j] = (float)((vb >> (8 * j)) & 255u);
+                ta[r * SSIM_IN_C + 4 * gc + j] = va[j];
+                tb[r * SSIM_IN_C + 4 * gc + j] = vb[j];
             }
         }
     }
@@ -160,18 +158,11 @@ __device__ __forceinline__ double ssim_index(const SsimConsts& k, double mu1, do
     return ((2 * mu1 * mu2 + k.C1) * (2 * sg12 + k.C2)) / ((mu1 * mu1 + mu2 * mu2 + k.C1) * (sg1 + sg2 + k.C2));
 }
 
-// out[n] = the block's sum of acc[n], n < N: the wave by shuffles, the block's four waves through red, added in wave order
+// out[n] = the block's sum of acc[n], n < N (metric_src.h::block_sums)
 template <int N>
-__device__ __forceinline__ void ssim_block_sums(double (&acc)[N], double (*red)[N], double* out) {
-    const int t = threadIdx.x;
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int n = 0; n < N; ++n) acc[n] += __shfl_down(acc[n], off, 64);
-    if ((t & 63) == 0)
-#pragma unroll
-        for (int n = 0; n < N; ++n) red[t >> 6][n] = acc[n];
-    __syncthreads();
-    if (t < N) out[t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
+__device__ __forceinline__ void ssim_block_sums(const double (&acc)[N], double (*red)[N], double* out) {
+    const double v = block_sums(acc, red);
+    if ((int)threadIdx.x < N) out[threadIdx.x] = v;
 }
 
 }  // namespace

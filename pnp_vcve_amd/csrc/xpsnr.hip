@@ -8,34 +8,12 @@
 
 namespace {
 
-// one plane of one clip on either sample path
-struct XpSrc {
-    PnpPlaneSrc p8;
-    int sel;                // 8-bit: the plane is the second of an interleaved pair
-    Plane16 p16;
-};
-
-// v[j] = sample (row, col + j) of frame f for j < n, 0 for n <= j < 4; 1 <= n <= 4
+// metric_src.h::plane_load4 (samples (row, col ..) of frame f, 0 beyond n) for 1 <= n <= 8
 template <bool S16>
-__device__ __forceinline__ void xp_load4(const XpSrc& s, long f, int row, int col, int n, int v[4]) {
-    if (S16) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = j < n ? (int)load16(s.p16, f, row, col + j) : 0;
-    } else {
-        unsigned w[2];
-        pnp_plane_load4(s.p8, f, row, col, n, w);
-        const unsigned x = s.sel ? w[1] : w[0];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = (int)((x >> (8 * j)) & 255u);
-    }
-}
-
-// the same for 1 <= n <= 8
-template <bool S16>
-__device__ __forceinline__ void xp_load8(const XpSrc& s, long f, int row, int col, int n, int v[8]) {
-    xp_load4<S16>(s, f, row, col, n < 4 ? n : 4, v);
+__device__ __forceinline__ void xp_load8(const PlaneSamp& s, long f, int row, int col, int n, int v[8]) {
+    plane_load4<S16>(s, f, row, col, n < 4 ? n : 4, v);
     if (n > 4) {
-        xp_load4<S16>(s, f, row, col + 4, n - 4, v + 4);
+        plane_load4<S16>(s, f, row, col + 4, n - 4, v + 4);
     } else {
 #pragma unroll
         for (int j = 4; j < 8; ++j) v[j] = 0;
@@ -43,7 +21,7 @@ __device__ __forceinline__ void xp_load8(const XpSrc& s, long f, int row, int co
 }
 
 struct XpArgs {
-    XpSrc a[3], b[3];               // the test clip and the original: Y, Cb, Cr
+    PlaneSamp a[3], b[3];           // the test clip and the original: Y, Cb, Cr (clip_planes)
     PnpXpPlan plan;
     int mask, fps;
     int lanes, lanes_log2;          // pnp_xp_lanes(N): the lanes that share one block
@@ -52,15 +30,15 @@ struct XpArgs {
 
 // the squared error of two planes over rect k (coordinates of the cropped plane), a group of four samples of a row per lane and step
 template <bool S16>
-__device__ __forceinline__ unsigned long long xp_sse(const XpSrc& a, const XpSrc& b, long f, const PnpXpRect& k, int crop, int lane, int lanes) {
+__device__ __forceinline__ unsigned long long xp_sse(const PlaneSamp& a, const PlaneSamp& b, long f, const PnpXpRect& k, int crop, int lane, int lanes) {
     const int g = (k.x1 - k.x0 + 3) / 4, items = (k.y1 - k.y0) * g;
     unsigned long long acc = 0;
     for (int i = lane; i < items; i += lanes) {
         const int r = i / g, x = k.x0 + 4 * (i - r * g);
         const int n = k.x1 - x < 4 ? k.x1 - x : 4;
         int va[4], vb[4];
-        xp_load4<S16>(a, f, crop + k.y0 + r, crop + x, n, va);
-        xp_load4<S16>(b, f, crop + k.y0 + r, crop + x, n, vb);
+        plane_load4<S16>(a, f, crop + k.y0 + r, crop + x, n, va);
+        plane_load4<S16>(b, f, crop + k.y0 + r, crop + x, n, vb);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {                       // absent samples are 0 in both
             const int d = va[j] - vb[j];
@@ -73,7 +51,7 @@ __device__ __forceinline__ unsigned long long xp_sse(const XpSrc& a, const XpSrc
 // b = 1: every sample of region R is a position; the 3 x 3 filter 12 / -2 / -1; s_t is the sample.  A lane takes four positions of a
 // row: the six samples around them from three rows, and the four of the one or two frames before.
 template <bool S16>
-__device__ __forceinline__ void xp_activity1(const XpSrc& o, long f, const PnpXpRect& R, int crop, int order, int lane, int lanes,
+__device__ __forceinline__ void xp_activity1(const PlaneSamp& o, long f, const PnpXpRect& R, int crop, int order, int lane, int lanes,
                                              unsigned long long& sa, unsigned long long& ta) {
     const int g = (R.x1 - R.x0 + 3) / 4, items = (R.y1 - R.y0) * g;
     for (int i = lane; i < items; i += lanes) {
@@ -83,8 +61,8 @@ __device__ __forceinline__ void xp_activity1(const XpSrc& o, long f, const PnpXp
 #pragma unroll
         for (int q = 0; q < 3; ++q) xp_load8<S16>(o, f, crop + y - 1 + q, crop + x - 1, np + 2, v[q]);
         int p1[4] = {0, 0, 0, 0}, p2[4] = {0, 0, 0, 0};
-        if (order >= 1) xp_load4<S16>(o, f - 1, crop + y, crop + x, np, p1);
-        if (order == 2) xp_load4<S16>(o, f - 2, crop + y, crop + x, np, p2);
+        if (order >= 1) plane_load4<S16>(o, f - 1, crop + y, crop + x, np, p1);
+        if (order == 2) plane_load4<S16>(o, f - 2, crop + y, crop + x, np, p2);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (j < np) {
@@ -101,7 +79,7 @@ __device__ __forceinline__ void xp_activity1(const XpSrc& o, long f, const PnpXp
 // b = 2: every second row and column of region R, from its first, is a position; the 6 x 6 zero-sum filter over rows and columns
 // -2 .. +3; s_t is the sum of the 2 x 2 samples at the position.  A lane takes two neighbouring positions: eight samples of six rows.
 template <bool S16>
-__device__ __forceinline__ void xp_activity2(const XpSrc& o, long f, const PnpXpRect& R, int crop, int order, int lane, int lanes,
+__device__ __forceinline__ void xp_activity2(const PlaneSamp& o, long f, const PnpXpRect& R, int crop, int order, int lane, int lanes,
                                              unsigned long long& sa, unsigned long long& ta) {
     constexpr int K6[6][6] = {{0, -1, -1, -1, -1, 0}, {-1, -2, -3, -3, -2, -1}, {-1, -3, 12, 12, -3, -1},
                               {-1, -3, 12, 12, -3, -1}, {-1, -2, -3, -3, -2, -1}, {0, -1, -1, -1, -1, 0}};
@@ -117,8 +95,8 @@ __device__ __forceinline__ void xp_activity2(const XpSrc& o, long f, const PnpXp
         int p1[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, p2[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            if (order >= 1) xp_load4<S16>(o, f - 1, crop + y + q, crop + x, 2 * np, p1[q]);
-            if (order == 2) xp_load4<S16>(o, f - 2, crop + y + q, crop + x, 2 * np, p2[q]);
+            if (order >= 1) plane_load4<S16>(o, f - 1, crop + y + q, crop + x, 2 * np, p1[q]);
+            if (order == 2) plane_load4<S16>(o, f - 2, crop + y + q, crop + x, 2 * np, p2[q]);
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -140,8 +118,8 @@ __device__ __forceinline__ void xp_activity2(const XpSrc& o, long f, const PnpXp
 }
 
 // A thread block of 256 owns 256 / lanes whole XPSNR blocks, `lanes` consecutive threads each (64 blocks when N = 4, 16 when N = 8,
-// one from N = 20 on), so a wave is busy whatever N.  Sums go registers -> shuffles within the block's lanes -> (a block shared by
-// four waves) LDS -> plain stores of the five totals.  No atomics: every slot has one writer and every slot is written, the planes
+// one from N = 20 on), so a wave is busy whatever N.  Sums go registers -> shuffles within the block's lanes, or (a block shared by
+// four waves) metric_src.h::block_sums -> plain stores of the five totals.  No atomics: every slot has one writer and every slot is written, the planes
 // outside the mask as 0.
 template <bool S16>
 __global__ __launch_bounds__(256) void xpsnr_kernel(const XpArgs s) {
@@ -166,25 +144,19 @@ __global__ __launch_bounds__(256) void xpsnr_kernel(const XpArgs s) {
             else xp_activity2<S16>(s.b[0], frame, R, p.crop, order, lane, lanes, acc[3], acc[4]);
         }
     }
-    const int width = lanes < 64 ? lanes : 64;
-#pragma unroll
-    for (int q = 0; q < 5; ++q)
-        for (int off = width >> 1; off > 0; off >>= 1) acc[q] += __shfl_down(acc[q], off, width);
     unsigned long long* out = s.sums + ((long)frame * nblk + kb) * 5;
-    if (lanes <= 64) {
+    if (lanes <= 64) {                                          // (the same for the whole thread block)
+#pragma unroll
+        for (int q = 0; q < 5; ++q)
+            for (int off = lanes >> 1; off > 0; off >>= 1) acc[q] += __shfl_down(acc[q], off, lanes);
         if (kb < nblk && lane == 0) {
 #pragma unroll
             for (int q = 0; q < 5; ++q) out[q] = acc[q];
         }
         return;
     }
-    const int t = threadIdx.x;
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < 5; ++q) red[t >> 6][q] = acc[q];
-    }
-    __syncthreads();
-    if (kb < nblk && t < 5) out[t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
+    const unsigned long long v = block_sums(acc, red);
+    if (kb < nblk && threadIdx.x < 5) out[threadIdx.x] = v;
 }
 
 template <bool S16>
@@ -212,33 +184,22 @@ extern "C" int pnp_xpsnr_grid(int h, int w, int crop_border, int* rows, int* col
 
 extern "C" int pnp_xpsnr_sums_yuv420(const pnp_yuv420_planes* a, const pnp_yuv420_planes* b, int plane_mask, unsigned long long* sums,
                                      int frames, int h, int w, int crop_border, int fps, void* stream) {
-    if (!planes_args_ok(a, b, sums, frames, h, w, crop_border) || plane_mask < 1 || plane_mask > 7 || fps < 1) return PNP_ERR_BAD_ARG;
+    if (!planes_args_ok(a, b, sums, frames, h, w, crop_border) || !plane_mask_ok(plane_mask) || fps < 1) return PNP_ERR_BAD_ARG;
     XpArgs s;
     s.plan = pnp_xp_plan(h, w, crop_border);
     if (!s.plan.ok) return PNP_ERR_BAD_ARG;
-    const ChromaSrc ac = chroma_src(*a, h, w), bc = chroma_src(*b, h, w);
-    for (int k = 0; k < 3; ++k) s.a[k] = s.b[k] = XpSrc{};
-    s.a[0].p8 = luma_src(*a, h, w);
-    s.b[0].p8 = luma_src(*b, h, w);
-    for (int cr = 0; cr < 2; ++cr) {
-        s.a[1 + cr].p8 = ac.c[cr];
-        s.b[1 + cr].p8 = bc.c[cr];
-        s.a[1 + cr].sel = ac.paired && cr != ac.cr_first;          // the plane one byte behind the pair's first
-        s.b[1 + cr].sel = bc.paired && cr != bc.cr_first;
-    }
+    clip_planes(*a, h, w, PNP_YUV_FORMAT_420, s.a);
+    clip_planes(*b, h, w, PNP_YUV_FORMAT_420, s.b);
     return launch<false>(s, plane_mask, fps, sums, frames, (hipStream_t)stream);
 }
 
 extern "C" int pnp_xpsnr_sums_yuv420p16(const pnp_yuv420_planes16* a, const pnp_yuv420_planes16* b, int plane_mask, unsigned long long* sums,
                                         int frames, int h, int w, int crop_border, int fps, void* stream) {
-    if (!planes16_args_ok(a, b, sums, frames, h, w, crop_border) || plane_mask < 1 || plane_mask > 7 || fps < 1) return PNP_ERR_BAD_ARG;
+    if (!planes16_args_ok(a, b, sums, frames, h, w, crop_border) || !plane_mask_ok(plane_mask) || fps < 1) return PNP_ERR_BAD_ARG;
     XpArgs s;
     s.plan = pnp_xp_plan(h, w, crop_border);
     if (!s.plan.ok) return PNP_ERR_BAD_ARG;
-    for (int k = 0; k < 3; ++k) {
-        s.a[k] = s.b[k] = XpSrc{};
-        s.a[k].p16 = plane16(*a, k);
-        s.b[k].p16 = plane16(*b, k);
-    }
+    clip_planes(*a, s.a);
+    clip_planes(*b, s.b);
     return launch<true>(s, plane_mask, fps, sums, frames, (hipStream_t)stream);
 }

@@ -1018,6 +1018,24 @@ def _yuv_entry(name, frames):
     return name + ('p16' if isinstance(frames, _YUV16_CLASSES) else '')
 
 
+def _yuv_each_clip(name, frames, clips, t, call):
+    """The plane metrics' call loop: the C entry `name` for the frames' sample size, called once per clip of `clips` (descriptor pairs
+    or triples; nothing is called for clips of no frames) on the frames' device: call(entry, i, *descriptors by reference) -> status.
+    A generator: it yields i after clip i's call was checked, for callers that read a per-clip buffer before the next call."""
+    entry = getattr(_native.lib(), _yuv_entry(name, frames))
+    with torch.cuda.device(frames.y.device):
+        for i, descs in enumerate(clips):
+            if t:
+                _native.check(call(entry, i, *(ctypes.byref(d) for d in descs)), _yuv_entry(name, frames))
+                yield i
+
+
+def _yuv_all_clips(*args):
+    """_yuv_each_clip for callers whose calls write into one tensor of all clips"""
+    for _ in _yuv_each_clip(*args):
+        pass
+
+
 def _yuv_views_format(buf, h, w, fmt, order, tail=()):
     """yuv420_views / yuv420p16_views / yuv_views: a packed buffer (..., h + 2 (h / sy) / sx, pitch) -> views of the format's frame
     class; order 'nv12' | 'nv21' | 'i420' (the plane order); tail () -> the class of a uint8 buffer, (bit_depth, msb_aligned) -> the
@@ -1374,14 +1392,9 @@ def _plane_geometry(fmt, h, w, crop):
 
 def _psnr_sse_yuv(a, b, crop_border, any_format):
     pairs, lead, t, h, w, crop = _yuv_metric_pair(a, b, crop_border, any_format=any_format)
-    entry = 'pnp_psnr_sse_yuvp16' if isinstance(a, _YUV16_CLASSES) else 'pnp_psnr_sse_yuv'
     fmt = _native.YUV_FORMAT[yuv_format(a)]
-    dev = a.y.device
-    with torch.cuda.device(dev):
-        sse = torch.empty((len(pairs), t, 3), dtype=torch.int64, device=dev)
-        for i, (da, db) in enumerate(pairs):
-            if t:
-                _native.check(getattr(_native.lib(), entry)(ctypes.byref(da), ctypes.byref(db), _ptr(sse[i]), t, h, w, crop, fmt, _stream()), entry)
+    sse = torch.empty((len(pairs), t, 3), dtype=torch.int64, device=a.y.device)
+    _yuv_all_clips('pnp_psnr_sse_yuv', a, pairs, t, lambda entry, i, da, db: entry(da, db, _ptr(sse[i]), t, h, w, crop, fmt, _stream()))
     return sse.cpu().reshape(lead + (3,))
 
 
@@ -1409,21 +1422,16 @@ def _ssim_yuv(a, b, crop_border, planes, any_format):
     nb = {p: int(L.pnp_ssim_blocks_yuv(h, w, crop, _PLANE_BITS[p], fmt)) for p in order}
     if any(v < 1 for v in nb.values()):
         raise ValueError('a cropped plane is smaller than the 11x11 SSIM window')
-    dev = a.y.device
     res = torch.empty((len(pairs), t, len(planes)), dtype=torch.float64)
-    entry = 'pnp_ssim_partials_yuvp16' if isinstance(a, _YUV16_CLASSES) else 'pnp_ssim_partials_yuv'
-    with torch.cuda.device(dev):
-        for i, (da, db) in enumerate(pairs):
-            if not t:
-                continue
-            part = torch.empty(t * sum(nb.values()), dtype=torch.float64, device=dev)
-            _native.check(getattr(L, entry)(ctypes.byref(da), ctypes.byref(db), mask, _ptr(part), t, h, w, crop, fmt, _stream()), entry)
-            off = 0
-            for p in order:
-                rows, cols, cy, cx = geo[p]
-                n = (rows - 2 * cy - 10) * (cols - 2 * cx - 10)
-                res[i, :, planes.index(p)] = (part[off:off + t * nb[p]].reshape(t, nb[p]).sum(dim=1) / n).cpu()
-                off += t * nb[p]
+    part = torch.empty(t * sum(nb.values()), dtype=torch.float64, device=a.y.device)
+    for i in _yuv_each_clip('pnp_ssim_partials_yuv', a, pairs, t,
+                            lambda entry, i, da, db: entry(da, db, mask, _ptr(part), t, h, w, crop, fmt, _stream())):
+        off = 0
+        for p in order:
+            rows, cols, cy, cx = geo[p]
+            n = (rows - 2 * cy - 10) * (cols - 2 * cx - 10)
+            res[i, :, planes.index(p)] = (part[off:off + t * nb[p]].reshape(t, nb[p]).sum(dim=1) / n).cpu()
+            off += t * nb[p]
     return res.reshape(lead + (len(planes),))
 
 
@@ -1489,22 +1497,18 @@ def msssim_yuv420(a, b, crop_border=0, planes='y', scales=False):
     dev = a.y.device
     res = torch.empty((len(pairs), t, len(planes)), dtype=torch.float64)
     sc = torch.empty((len(pairs), t, len(planes), 5, 2), dtype=torch.float64)
-    entry = 'pnp_msssim_partials_yuv420p16' if isinstance(a, Yuv420Frames16) else 'pnp_msssim_partials_yuv420'
-    with torch.cuda.device(dev):
-        for i, (da, db) in enumerate(pairs):
-            if not t:
-                continue
-            part = torch.empty(t * sum(sum(plans[p][0]) for p in order) * 2, dtype=torch.float64, device=dev)
-            ws = torch.empty(int(L.pnp_msssim_workspace_bytes(t, len(order), h, w, crop)) // 4, dtype=torch.float32, device=dev)
-            _native.check(getattr(L, entry)(ctypes.byref(da), ctypes.byref(db), mask, _ptr(part), _ptr(ws), t, h, w, crop, _stream()), entry)
-            off = 0
-            for p in order:
-                blocks, sizes = plans[p]
-                n = t * sum(blocks) * 2
-                s = _msssim_scales(part[off:off + n].reshape(t, sum(blocks), 2), blocks, sizes)
-                sc[i, :, planes.index(p)] = s
-                res[i, :, planes.index(p)] = _msssim_value(s)
-                off += n
+    part = torch.empty(t * sum(sum(plans[p][0]) for p in order) * 2, dtype=torch.float64, device=dev)
+    ws = torch.empty(int(L.pnp_msssim_workspace_bytes(t, len(order), h, w, crop)) // 4, dtype=torch.float32, device=dev)
+    for i in _yuv_each_clip('pnp_msssim_partials_yuv420', a, pairs, t,
+                            lambda entry, i, da, db: entry(da, db, mask, _ptr(part), _ptr(ws), t, h, w, crop, _stream())):
+        off = 0
+        for p in order:
+            blocks, sizes = plans[p]
+            n = t * sum(blocks) * 2
+            s = _msssim_scales(part[off:off + n].reshape(t, sum(blocks), 2), blocks, sizes)
+            sc[i, :, planes.index(p)] = s
+            res[i, :, planes.index(p)] = _msssim_value(s)
+            off += n
     res = res.reshape(lead + (len(planes),))
     return (res, sc.reshape(lead + (len(planes), 5, 2))) if scales else res
 
@@ -1529,13 +1533,8 @@ def xpsnr_sums_yuv420(a, b, crop_border=0, planes='y', fps=30):
     _native.check(L.pnp_xpsnr_grid(h, w, crop, ctypes.byref(rows), ctypes.byref(cols)), 'pnp_xpsnr_grid')
     nblk = rows.value * cols.value
     mask = sum(_PLANE_BITS[p] for p in planes)
-    entry = 'pnp_xpsnr_sums_yuv420p16' if isinstance(a, Yuv420Frames16) else 'pnp_xpsnr_sums_yuv420'
-    dev = a.y.device
-    with torch.cuda.device(dev):
-        sums = torch.empty((len(pairs), t, nblk, 5), dtype=torch.int64, device=dev)
-        for i, (da, db) in enumerate(pairs):
-            if t:
-                _native.check(getattr(L, entry)(ctypes.byref(da), ctypes.byref(db), mask, _ptr(sums[i]), t, h, w, crop, fps, _stream()), entry)
+    sums = torch.empty((len(pairs), t, nblk, 5), dtype=torch.int64, device=a.y.device)
+    _yuv_all_clips('pnp_xpsnr_sums_yuv420', a, pairs, t, lambda entry, i, da, db: entry(da, db, mask, _ptr(sums[i]), t, h, w, crop, fps, _stream()))
     return sums.cpu().reshape(lead + (nblk, 5))
 
 
@@ -1656,14 +1655,9 @@ def psnrb_sums_yuv420(a, b, crop_border=0, planes='y', block=8):
         rows, cols, c = (h, w, crop) if p == 'y' else (h // 2, w // 2, crop // 2)
         metrics.psnrb_counts(rows, cols, c, metrics.psnrb_block(block, p != 'y'))
     mask = sum(_PLANE_BITS[p] for p in planes)
-    entry = 'pnp_psnrb_sums_yuv420p16' if isinstance(a, Yuv420Frames16) else 'pnp_psnrb_sums_yuv420'
-    dev = a.y.device
-    with torch.cuda.device(dev):
-        sums = torch.empty((len(pairs), t, 3, 5), dtype=torch.int64, device=dev)
-        for i, (da, db) in enumerate(pairs):
-            if t:
-                _native.check(getattr(_native.lib(), entry)(ctypes.byref(da), None if b is None else ctypes.byref(db), mask, _ptr(sums[i]), t, h,
-                                                            w, crop, int(block), _stream()), entry)
+    sums = torch.empty((len(pairs), t, 3, 5), dtype=torch.int64, device=a.y.device)
+    _yuv_all_clips('pnp_psnrb_sums_yuv420', a, pairs, t,
+                   lambda entry, i, da, db: entry(da, None if b is None else db, mask, _ptr(sums[i]), t, h, w, crop, int(block), _stream()))
     return sums.cpu().reshape(lead + (3, 5))
 
 
@@ -1767,17 +1761,13 @@ def gain_sums_yuv(a, l, g, crop_border=0, planes='y', block=64, par=None):
     par = _gain_par(par, lead, h, w, dev)
     rows, cols = metrics.gain_grid(h, w, block)
     mask = sum(_PLANE_BITS[p] for p in planes)
-    entry = 'pnp_gain_sums_yuvp16' if isinstance(a, _YUV16_CLASSES) else 'pnp_gain_sums_yuv'
     fmt = _native.YUV_FORMAT[yuv_format(a)]
-    with torch.cuda.device(dev):
-        grid = torch.empty((len(pairs), t, 3, rows, cols, 2), dtype=torch.int64, device=dev)
-        cls = None if par is None else torch.empty((len(pairs), t, 8, 3), dtype=torch.int64, device=dev)
-        par_clips = None if par is None else par.reshape((len(pairs), t, 3, h, w))
-        for i, ((da, dg), (dl, _)) in enumerate(zip(pairs, pairs_l)):
-            if t:
-                _native.check(getattr(_native.lib(), entry)(ctypes.byref(da), ctypes.byref(dl), ctypes.byref(dg), mask,
-                                                            None if par is None else _ptr(par_clips[i]), _ptr(grid[i]),
-                                                            None if cls is None else _ptr(cls[i]), t, h, w, crop, block, fmt, _stream()), entry)
+    grid = torch.empty((len(pairs), t, 3, rows, cols, 2), dtype=torch.int64, device=dev)
+    cls = None if par is None else torch.empty((len(pairs), t, 8, 3), dtype=torch.int64, device=dev)
+    par_clips = None if par is None else par.reshape((len(pairs), t, 3, h, w))
+    _yuv_all_clips('pnp_gain_sums_yuv', a, [(da, dl, dg) for (da, dg), (dl, _) in zip(pairs, pairs_l)], t,
+                   lambda entry, i, da, dl, dg: entry(da, dl, dg, mask, None if par is None else _ptr(par_clips[i]), _ptr(grid[i]),
+                                                      None if cls is None else _ptr(cls[i]), t, h, w, crop, block, fmt, _stream()))
     idx = ['yuv'.index(p) for p in planes]
     grid = grid.cpu()[:, :, idx].reshape(lead + (len(planes), rows, cols, 2))
     return grid, (None if cls is None else cls.cpu().reshape(lead + (8, 3)))

@@ -11,7 +11,8 @@
 // 2. chroma_src(p, h, w, format) of 8-bit planes that are heap blocks of EXACTLY the bytes the reading rule allows (the last row ends
 //    with its last sample; ASan's red zone sits right behind it), walked through pnp_plane_load4 with pnp_plane_runs of the plane's true
 //    rows, columns and per-axis crop, the way the PSNR kernel walks them: every sample inside the crop is fetched exactly once with its
-//    value, none outside it.
+//    value, none outside it.  clip_planes(p, h, w, format, ...) -- what the metric entries fill their kernel arguments with -- must name
+//    the same planes: every group is fetched again through its Cb and Cr sources and their `sel` and must be the same word.
 // 3. The pack launcher's choice of its form, through the host-only stand-in of the launcher (csrc/host_stub/yuv_stub.h, which records
 //    what the scheduler build would launch): tightly packed aligned planes of nv16 / yuv422p / nv24 / yuv444p and their 16-bit
 //    siblings must record the aligned form, the same planes 2 samples further on and a forced general launch must not, and a frame
@@ -134,6 +135,8 @@ long walk_case(int format, int step, bool paired, bool cr_first, int off, int ex
     p.y = plane_at[0];              // (never read here)
     const ChromaSrc s = chroma_src(p, h, w, format);
     if (s.paired != (paired ? 1 : 0) || (paired && s.cr_first != (cr_first ? 1 : 0))) fail("pairing", format, step, off, extra, crop, 0, 0);
+    PlaneSamp pl[3];
+    clip_planes(p, h, w, format, pl);
     const PlaneGeom g = plane_geom(h, w, crop, PNP_PLANE_CB, format);
     if (g.H != rows || g.W != cols) fail("geometry", format, step, off, extra, crop, g.H, g.W);
     const PnpPlaneRuns runs = pnp_plane_runs(g.H, g.W, g.cropy, g.cropx);
@@ -155,6 +158,10 @@ long walk_case(int format, int step, bool paired, bool cr_first, int off, int ex
                 pnp_plane_load4(s.c[1], 0, row, col, npix, o);
                 v[1] = o[0];
                 loads += 2;
+            }
+            for (int k = 0; k < 2; ++k) {       // the plane as a metric kernel reads it (metric_src.h::plane_load4's 8-bit arm)
+                pnp_plane_load4(pl[1 + k].p8, 0, row, col, npix, o);
+                if ((pl[1 + k].sel ? o[1] : o[0]) != v[k]) fail("clip_planes names another plane", format, step, off, extra, crop, row, col);
             }
             for (int k = 0; k < 2; ++k)
                 for (int j = 0; j < 4; ++j) {
